@@ -113,7 +113,14 @@ def parse(argv=None):
                     help="functional tests of the multi-rank path on one GPU: gloo + --single-device")
     ap.add_argument("--single-device", action="store_true",
                     help="all ranks use cuda:0 (testing only; RCCL refuses two ranks on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="frame workload: after the timed steps, write what the last timed step returned (rgb, "
+                         "weights.grad, tables.grad) as DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "frame":
+        ap.error("--dump-outputs: the frame workload only")
     training = args.workload.startswith("train")
     if args.steps is None:
         # frame: 200 steps = 0.64 s of back-to-back graph replays (the round-1 default of 20 was a 63 ms
@@ -272,6 +279,32 @@ def cpu_baseline(pipe, sample_rays):
                       f"neural textures fwd+bwd (oracle/neural_texture.py on torch-CPU, {torch.get_num_threads()} "
                       f"threads) + composite fwd+bwd (oracle/composite.py); {dt:.1f} s"}
     return base, parity
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float32) per array, DUMP_BYTES in all.  An array larger than an equal share of
+    that budget is written as DIR/<name>_sample.npy: its flattened entries at indices drawn without replacement from a
+    fixed seed and sorted, so that two builds run with the same arguments write the same entries.  DIR also gets a
+    .gitignore of `*` (as pytest's cache directory does): a dump inside a checkout leaves `git status` clean.
+    Returns {file name: shape written} for the result line."""
+    os.makedirs(path, exist_ok=True)
+    gi = os.path.join(path, ".gitignore")
+    if not os.path.exists(gi):
+        with open(gi, "w") as f:
+            f.write("*\n")
+    share = DUMP_BYTES // len(arrays)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 def synthetic_reel(n_views, res, device, seed=42):
@@ -791,14 +824,13 @@ def main():
 
     def step(record=False):
         if ostep is not None:
-            ostep.run(record=record)
-            return
+            return ostep.run(record=record)
         if dist is None:
-            pipe.step(record=record)
-            return
-        pipe.step(record=record, grad_ready=overlap.reduce_async)       # --dp-split-launches
+            return pipe.step(record=record)
+        rgb = pipe.step(record=record, grad_ready=overlap.reduce_async)       # --dp-split-launches
         pipe.timer.run("grad_allreduce", overlap.wait, record,
                        bytes=sum(p.numel() for p in params) * 4)
+        return rgb
 
     for _ in range(max(1, args.warmup)):
         step()
@@ -849,15 +881,14 @@ def main():
             pipe.rays_o.copy_(views[i % len(views)][0])
             pipe.rays_d.copy_(views[i % len(views)][1])
         if use_graph and ostep is not None:
-            ostep.run_split(pipe.replay_prefix, pipe.replay_mid, pipe.replay_tail)
-        elif use_graph:
-            pipe.replay()
-        else:
-            step()
+            return ostep.run_split(pipe.replay_prefix, pipe.replay_mid, pipe.replay_tail)
+        if use_graph:
+            return pipe.replay()
+        return step()
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        timed_step(i)
+        rgb = timed_step(i)
     if ostep is not None:
         ostep.finish()                 # the last step's reduction (inside the timed region)
     barrier()
@@ -866,6 +897,10 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    # before anything else runs on the pipeline: the last timed step's colours and (reduced) gradients
+    dumped = dump_outputs(args.dump_outputs, {"rgb": rgb, "weights_grad": pipe.bank.weights.grad,
+                                              "tables_grad": pipe.bank.tables.grad}) \
+        if args.dump_outputs and rank == 0 else None
 
     # the reduced gradients of the last step, checksummed on EVERY rank: after the all-reduce they are the same bits
     # everywhere, so the first multi-GPU run validates its own collectives (outside the timed region)
@@ -946,6 +981,8 @@ def main():
             "stage_roofline": {k: pipe.stage_roofline(v, HBM_PEAK_GBS, MFMA_F16_PEAK_TFLOPS)
                                for k, v in stages.items()},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if traffic_note:
             out["roofline"]["traffic_note"] = traffic_note
         if traffic_all:
