@@ -195,9 +195,8 @@ int vsa_trace_q_fb(const uint32_t* qnodes, const float* tris, const int32_t* mes
  * `chunk` trips at how many of its lanes are still walking, and once they are at most `lanes` the WHOLE wave finishes
  * those rays together: their pending subtrees go into a queue of (node, ray) entries, every lane takes one entry per
  * round and appends the children that survive.  The hits are bit for bit those of the plain walk (the closest hit is
- * a minimum over (t, face id); a stale bound only visits more).  Process-wide setting, defaults 16 / 24 / 4096
- * (environment VSA_TRACE_COOP="chunk,lanes", VSA_TRACE_COOP_WAVES); lanes = 0 switches it off.  Returns
- * VSA_ERR_ARG for chunk < 1, lanes outside 0..64 or max_waves < 0. */
+ * a minimum over (t, face id); a stale bound only visits more).  Process-wide setting, defaults 16 / 24 / 4096;
+ * lanes = 0 switches it off.  Returns VSA_ERR_ARG for chunk < 1, lanes outside 0..64 or max_waves < 0. */
 int vsa_trace_coop_config(int chunk, int lanes, long long max_waves);
 /* Measurement aid (bench.py's stage_roofline.trace; not on the product path): the walk of vsa_trace_q with
  * counters.  stats (device, 5 x u64, overwritten): lane-level node visits (one 32-byte node fetch each),
@@ -323,21 +322,14 @@ int vsa_nt_rebalance(const vsa_nt_plan* plan, void* stream);
 int vsa_nt_mark(const vsa_nt_plan* plan, const int32_t* hit_slot, const float* hit_uv,
                 const float* face_uvs, int nr_rays, float* tex_uv, uint8_t* marks, void* stream);
 
-/* Step 2: compact marks into slots.  slot_of [dom total] i32 (-1 = untouched),
- * texel_of_slot [slot_capacity] i32 (domain index), slot_xy [slot_capacity,2] f32
- * (normalised texel-centre coordinates = the network input of the slot),
- * seg_start [K*4+1] i32 (first slot of each (shell,degree); last = total),
- * block_scratch [dom total/4096 + 1] i32. */
-int vsa_nt_compact(const vsa_nt_plan* plan, const uint8_t* marks, int32_t* slot_of,
-                   int32_t* texel_of_slot, float* slot_xy, int32_t* seg_start,
-                   int32_t* block_scratch, void* stream);
-/* vsa_nt_compact for a frame loop: the same slots, seg_start and slot_xy, but slot_of is written only
- * where a texel is marked (entries of untouched texels keep whatever they held: nothing on the path
- * reads them - shading only looks up the corners it marked), the marks are CLEARED on the way (the
- * next vsa_nt_mark needs no fill), and texel_of_slot may be NULL.  At 800x800, K = 5 that is 112 MB
- * of -1 and a 28 MB fill less per frame.  The frame loop's invariant is "marks are zero between
- * frames": a vsa_nt_mark that is NOT followed by a successful vsa_nt_compact_frame (an error in
- * between, or the dense vsa_nt_compact above, which leaves the marks as they are) must be followed by
+/* Step 2 (per frame): compact marks into slots.  slot_of [dom total] i32, texel_of_slot [slot_capacity] i32
+ * (domain index; may be NULL), slot_xy [slot_capacity,2] f32 (normalised texel-centre coordinates = the network
+ * input of the slot), seg_start [K*4+1] i32 (first slot of each (shell,degree); last = total),
+ * block_scratch [dom total/4096 + 1] i32.  slot_of is written only where a texel is marked (entries of untouched
+ * texels keep whatever they held: nothing on the path reads them - shading only looks up the corners it marked),
+ * and the marks are CLEARED on the way (the next vsa_nt_mark needs no fill).  At 800x800, K = 5 that is 112 MB
+ * of -1 and a 28 MB fill less per frame.  The frame loop's invariant is "marks are zero between frames": a
+ * vsa_nt_mark that is NOT followed by a successful vsa_nt_compact_frame (an error in between) must be followed by
  * a fill of the marks before the next frame - stale marks inflate every later frame's slot counts. */
 int vsa_nt_compact_frame(const vsa_nt_plan* plan, uint8_t* marks, int32_t* slot_of,
                          int32_t* texel_of_slot, float* slot_xy, int32_t* seg_start,

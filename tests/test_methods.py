@@ -548,9 +548,10 @@ def test_baseline_config0_plumbing_case_matches_cpu_restatement():
 @pytest.mark.parametrize("cfg", [dict(), dict(is_inner_mesh_solid=True, rgb_normal_dep=True),
                                  dict(are_volsurfs_colors_indep=False, are_volsurfs_alphas_indep=False,
                                       rgb_pos_encoder_type="gridhash")])
-def test_legacy_grouped_shading_equals_the_per_shell_loop(cfg):
+def test_legacy_grouped_shading_matches_the_per_shell_loop(cfg):
     """methods._shade_legacy_grouped (all shells' hits prepared at once, one grouped MLP op per
-    model type) against the per-shell loop it replaces: identical forward, equal gradients."""
+    model type, its glue fused) against the per-shell loop it replaces: the same forward, loss and
+    gradients up to the fused glue's last-bit rounding."""
     from volsurfs_amd.camera import pinhole_rays
     from volsurfs_amd.mesh import nested_shells
     from volsurfs_amd.methods import VolSurfs
@@ -568,11 +569,10 @@ def test_legacy_grouped_shading_equals_the_per_shell_loop(cfg):
     o, d = pinhole_rays(40, 40, focal=70.0)
     gt = torch.rand(1600, 3, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     res = {}
-    glue0 = VolSurfs.legacy_fused_glue
     # "glue": the grouped path with its glue fused (hit preparation, sigmoid / decay / scatter, composite + L1 as one
-    # launch each — the default); True / False: the grouped path on torch expressions / the per-shell loop
-    for mode, grouped, glue, samples in (("glue", True, True, False), (True, True, False, True), (False, False, False, True)):
-        VolSurfs.legacy_grouped, VolSurfs.legacy_fused_glue = grouped, glue
+    # launch each); False: the per-shell loop
+    for mode, grouped, samples in (("glue", True, False), (False, False, True)):
+        VolSurfs.legacy_grouped = grouped
         try:
             assert m._legacy_groupable(o)
             for p in m.parameters():
@@ -581,28 +581,25 @@ def test_legacy_grouped_shading_equals_the_per_shell_loop(cfg):
             losses["loss"].backward()
             rt = m.render_rays(o, d, return_samples=False)["renders"]["ray_traced"]
         finally:
-            VolSurfs.legacy_grouped, VolSurfs.legacy_fused_glue = True, glue0
+            VolSurfs.legacy_grouped = True
         res[mode] = ({k: v.detach().clone() for k, v in rt.items() if v is not None},
                      [None if p.grad is None else p.grad.clone() for p in m.parameters()],
                      losses["loss"].item())
-    for k in res[True][0]:
-        assert torch.equal(res[True][0][k], res[False][0][k]), k
+    for k in res["glue"][0]:
         # the fused glue takes the same steps in fp32; expf / the norm may round the last bit differently — and a last
         # fp32 bit of a per-shell colour can flip its fp16 cast in the composite (the reference composites in fp16):
         # one fp16 ulp (9.8e-4 below 2) on a handful of values, 2e-6 everywhere else
         diff = (res["glue"][0][k].float() - res[False][0][k].float()).abs()
         assert diff.max().item() <= 1e-3 and (diff > 2e-6).float().mean().item() <= 2e-3, k
-    assert res[True][2] == res[False][2]
     assert abs(res["glue"][2] - res[False][2]) <= 2e-6 * abs(res[False][2])
-    for mode, tol in ((True, 1e-5), ("glue", 5e-5)):
-        n_with_grad = 0
-        for a, b in zip(res[mode][1], res[False][1]):
-            assert (a is None) == (b is None)
-            if a is not None:
-                n_with_grad += 1
-                s_ = b.abs().max().item()
-                assert (a - b).abs().max().item() <= tol * s_ + 1e-12
-        assert n_with_grad >= 6
+    n_with_grad = 0
+    for a, b in zip(res["glue"][1], res[False][1]):
+        assert (a is None) == (b is None)
+        if a is not None:
+            n_with_grad += 1
+            s_ = b.abs().max().item()
+            assert (a - b).abs().max().item() <= 5e-5 * s_ + 1e-12
+    assert n_with_grad >= 6
 
 
 @pytest.mark.gpu

@@ -1,6 +1,8 @@
 """Traversal of a TRAINING batch (34 000 random rays of 100 views, K = 5 subdiv-6 shells) with narrow waves: ms per launch
 for rays-per-wave 64 (plain vsa_trace_q_fb) / 32 / 16 / 8 / 4 (vsa_trace_q_narrow), hits compared bit for bit.
-usage: python tools/trace_narrow_ab.py [rays]"""
+With "chunk,lanes" the cooperative finish is set to that (RayTracer.coop_config; lanes 0 = off) and the 64-ray row
+measures it.
+usage: python tools/trace_narrow_ab.py [rays] [chunk,lanes]"""
 import os
 import sys
 
@@ -12,6 +14,8 @@ from volsurfs_amd.mesh import nested_shells                    # noqa: E402
 from volsurfs_amd.raytrace import RayTracer                    # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 34000
+if len(sys.argv) > 2:
+    RayTracer.coop_config(*map(int, sys.argv[2].split(",")))
 dev = torch.device("cuda:0")
 tr = RayTracer(nested_shells(K=5, subdiv=6, device=dev))
 reel = bench.synthetic_reel(100, 800, dev, seed=42)

@@ -87,10 +87,6 @@ def declared_prototypes():
     return out
 
 
-# "0": no argtypes (rounds 1-5: every argument converted by _conv alone)
-USE_ARGTYPES = os.environ.get("VSA_CTYPES_ARGTYPES", "1") != "0"
-
-
 def lib():
     """The loaded library (ctypes.CDLL).  Raises if it is not built."""
     global _lib
@@ -104,7 +100,7 @@ def lib():
         # not share devices / streams).
         import torch  # noqa: F401
         _lib = ctypes.CDLL(LIB_PATH)
-        protos = declared_prototypes() if USE_ARGTYPES else {}
+        protos = declared_prototypes()
         for name in declared_symbols():
             fn = getattr(_lib, name)  # AttributeError if the .so lacks a declared symbol
             fn.restype = ctypes.c_int

@@ -15,16 +15,8 @@
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifndef VSA_ADAM_NT
-#define VSA_ADAM_NT 1
-#endif
-#if VSA_ADAM_NT
 #define ADAM_LD(ptr) __builtin_nontemporal_load(ptr)
 #define ADAM_ST(val, ptr) __builtin_nontemporal_store(val, ptr)
-#else
-#define ADAM_LD(ptr) (*(ptr))
-#define ADAM_ST(val, ptr) (*(ptr) = (val))
-#endif
 constexpr int ADAM_BLOCK = 256;
 constexpr int ADAM_VEC = 4;                                  // one dwordx4 per array per lane
 constexpr int ADAM_CHUNK = ADAM_BLOCK * ADAM_VEC * 4;        // 4096 elements per workgroup

@@ -34,12 +34,6 @@ struct Lds {
 // among them) the slab is one contiguous run: whole tiles go HBM -> LDS by LDS-DMA
 // (global_load_lds_dwordx4: 1 KiB per wave-instruction, no registers, no index arithmetic), ragged
 // tiles by 16-B register copies.
-#ifndef VSA_COMP_DMA
-#define VSA_COMP_DMA 1
-#endif
-#ifndef VSA_COMP_NT
-#define VSA_COMP_NT 0     /* aux of the LDS-DMA loads: 2 = nt */
-#endif
 template <int W, int S>
 __device__ __forceinline__ void slab_load(const float* __restrict__ g, float* __restrict__ s,
                                           int rows_valid) {
@@ -47,14 +41,14 @@ __device__ __forceinline__ void slab_load(const float* __restrict__ g, float* __
   const int nvec = total >> 2;
   const float4* g4 = reinterpret_cast<const float4*>(g);
   if constexpr (W == S) {
-    if (VSA_COMP_DMA && rows_valid == TILE && (TILE * W) % 4 == 0) {
+    if (rows_valid == TILE && (TILE * W) % 4 == 0) {
       typedef __attribute__((address_space(3))) void* lds_vp;
       typedef __attribute__((address_space(1))) const void* glb_vp;
       const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
       constexpr int NV = TILE * W / 4, NC = (NV + 63) / 64;        // 64 x 16 B = 1 KiB per wave-instruction
       for (int c = wave; c < NC; c += TILE / 64)
         if (c * 64 + lane < NV)
-          __builtin_amdgcn_global_load_lds((glb_vp)(g4 + c * 64 + lane), (lds_vp)(s + c * 256), 16, 0, VSA_COMP_NT);
+          __builtin_amdgcn_global_load_lds((glb_vp)(g4 + c * 64 + lane), (lds_vp)(s + c * 256), 16, 0, 0);
       return;
     }
     float4* s4 = reinterpret_cast<float4*>(s);

@@ -12,16 +12,9 @@
 // (sample, level), 2^D float2 gathers, D-linear weights formed in the oracle's order.
 #include "common.h"
 #include <cstdint>
-#include <cstdlib>
 
 namespace {
 
-#ifndef GRID_FWD_PAIRS
-#define GRID_FWD_PAIRS 1
-#endif
-#ifndef GRID_FWD_LV
-#define GRID_FWD_LV 2     /* levels per thread: 1 / 2 / 4 = 1.63 / 1.47 / 1.59 ms per 2.1 M-sample batch (bench.py --workload dtu) */
-#endif
 constexpr unsigned GRID_PRIMES[3] = {1u, 2654435761u, 805459861u};
 
 struct GridLevel {
@@ -108,7 +101,6 @@ __global__ __launch_bounds__(256) void grid_encode_fwd_kernel(vsa_grid_plan plan
   const GridLevel g = grid_level(plan, l);
   const GridCell<D> cell = grid_cell<D>(g, x + b * D);
   float f0 = 0.f, f1 = 0.f;
-#if GRID_FWD_PAIRS
   // The kernel is bound by the rate of divergent 8-byte gathers (~1 address per clock and CU).  On
   // a hashed level the x coordinate enters the index with prime 1, so for an EVEN x the two
   // x-neighbours of a corner pair differ in index bit 0 only: one aligned 16-byte load fetches both
@@ -143,18 +135,6 @@ __global__ __launch_bounds__(256) void grid_encode_fwd_kernel(vsa_grid_plan plan
     f0 = f0 + w1 * v1.x;
     f1 = f1 + w1 * v1.y;
   }
-#else
-#pragma unroll
-  for (int corner = 0; corner < (1 << D); ++corner) {
-    unsigned c[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) c[d] = cell.c[d] + ((corner >> d) & 1);
-    const float w = corner_weight<D>(cell, corner);
-    const float2 v = tables[g.offset + grid_index<D>(g, c)];
-    f0 = f0 + w * v.x;
-    f1 = f1 + w * v.y;
-  }
-#endif
   res[2 * lv] = f0, res[2 * lv + 1] = f1;
   }
   // out row = [2 L features | the D inputs when append_x] (GridHashEncoder's concat_points written
@@ -715,21 +695,19 @@ extern "C" int vsa_grid_encode_fwd_ld(const vsa_grid_plan* plan, const float* ta
   if (nr_points < 0 || out_stride < 2 * plan->n_levels + (append_x ? plan->n_dims : 0)) return VSA_ERR_ARG;
   if (nr_points == 0) return VSA_OK;
   if (!tables || !x || !out) return VSA_ERR_ARG;
-  // levels per thread: 4 (32-byte stores) / 2 where the level count divides and the rows are 16-byte groups
-  static const int lv_env = getenv("VSA_GRID_FWD_LV") ? atoi(getenv("VSA_GRID_FWD_LV")) : GRID_FWD_LV;
+  // levels per thread: 2 where the level count divides and the rows are 16-byte groups (1 / 2 / 4 levels per
+  // thread = 1.63 / 1.47 / 1.59 ms per 2.1 M-sample batch, bench.py --workload dtu)
   const bool wide = (out_stride & 3) == 0 && ((uintptr_t)out & 15) == 0;
-  const int lv = wide && lv_env >= 4 && plan->n_levels % 4 == 0 ? 4 : wide && lv_env >= 2 && plan->n_levels % 2 == 0 ? 2 : 1;
+  const int lv = wide && plan->n_levels % 2 == 0 ? 2 : 1;
   dim3 grid(vsa_div_up(nr_points, 256), plan->n_levels / lv);
 #define GRID_FWD_LAUNCH(DD, LL)                                                                                  \
   hipLaunchKernelGGL((grid_encode_fwd_kernel<DD, LL>), grid, dim3(256), 0, (hipStream_t)stream, *plan,          \
                      reinterpret_cast<const float2*>(tables), x, nr_points, out, out_stride, append_x)
   if (plan->n_dims == 2) {
-    if (lv == 4) GRID_FWD_LAUNCH(2, 4);
-    else if (lv == 2) GRID_FWD_LAUNCH(2, 2);
+    if (lv == 2) GRID_FWD_LAUNCH(2, 2);
     else GRID_FWD_LAUNCH(2, 1);
   } else {
-    if (lv == 4) GRID_FWD_LAUNCH(3, 4);
-    else if (lv == 2) GRID_FWD_LAUNCH(3, 2);
+    if (lv == 2) GRID_FWD_LAUNCH(3, 2);
     else GRID_FWD_LAUNCH(3, 1);
   }
 #undef GRID_FWD_LAUNCH

@@ -32,12 +32,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int MLP_MAXB = 4;               // layer widths up to 128 (4 blocks of 32)
 constexpr int MLP_BLOCK = 256;            // 4 waves = 4 tiles of 32 points
 constexpr int MLP_TILE = 32;
-#ifndef MLP_XPF
-#define MLP_XPF 1
-#endif
-#ifndef MLP_ZPF
-#define MLP_ZPF 1
-#endif
 
 __device__ __forceinline__ int rho(int s, int h) { return 8 * (s >> 2) + 4 * h + (s & 3); }
 __host__ __device__ __forceinline__ int blocks_of(int w) { return (w + 31) / 32; }
@@ -135,31 +129,13 @@ __device__ __forceinline__ const float* meta_bias(const LayerMeta& m, int l) {
 
 // packed_fwd[l][(m * inb + b) * 1024 + mlp_frag_pos(s, lane)] = W_l[32 m + (lane & 31)][32 b + rho(s, lane >> 5)]
 // packed_bwd[l][(b * outb + m) * 1024 + mlp_frag_pos(s, lane)] = W_l[32 m + rho(s, lane >> 5)][32 b + (lane & 31)]
-// mlp_frag_pos: with MLP_FRAG_B128 = 1 a lane's four consecutive k-steps are one 16-byte run
-// ([s / 4][lane][s % 4]), so ONE ds_read_b128 (lanes 16 B apart: conflict-free) feeds four MFMAs instead
-// of a 4-byte ds_read per v_mfma_f32_32x32x2_f32 (1199 -> 271 narrow reads in the ISA).  Measured on
-// tools/bench_bg.py (one box, two runs each): fwd 881 / 873 us, dgrad 1189-1212 / 1186-1216 us - no
-// difference, so the issue stalls of profiles/NOTEBOOK.md A9.5 are not the fragment reads; the k-step-major layout
-// of rounds 1-2 stays the default.
-#ifndef MLP_FRAG_B128
-#define MLP_FRAG_B128 0
-#endif
-__host__ __device__ inline int mlp_frag_pos(int s, int lane) {
-  return MLP_FRAG_B128 ? ((s >> 2) * 64 + lane) * 4 + (s & 3) : s * 64 + lane;
-}
+// mlp_frag_pos: k-step-major ([s][lane]).  A [s / 4][lane][s % 4] layout read by one ds_read_b128 per four MFMAs
+// measured the same (profiles/NOTEBOOK.md A9.5: the issue stalls are not the fragment reads).
+__host__ __device__ inline int mlp_frag_pos(int s, int lane) { return s * 64 + lane; }
 // the 16 fragments of one 32x32 block pair for this lane
 __device__ __forceinline__ void mlp_load_frags(const float* blk, int lane, float w[16]) {
-#if MLP_FRAG_B128
-  const float4* f4 = reinterpret_cast<const float4*>(blk) + lane;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float4 v = f4[q * 64];
-    w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-  }
-#else
 #pragma unroll
   for (int s = 0; s < 16; ++s) w[s] = blk[s * 64 + lane];
-#endif
 }
 __global__ void mlp_pack_kernel(vsa_mlp_plan plan, MlpGroups gp, long long packed_stride,
                                 float* __restrict__ packed_fwd, float* __restrict__ packed_bwd) {
@@ -189,19 +165,6 @@ __global__ void mlp_pack_kernel(vsa_mlp_plan plan, MlpGroups gp, long long packe
       packed_bwd[dst] = (row < out && col < in) ? W[(long long)row * in + col] : 0.f;
     }
   }
-}
-
-// exact GELU (torch.nn.GELU default) = z Phi(z); Phi to 6.6e-8 absolute in ~13 instructions (gelu_fast.h; the device
-// library's erff: ~45 — the forward spent as long in its GELUs as in its matrix instructions)
-#ifndef MLP_GELU_ERFF
-#define MLP_GELU_ERFF 0
-#endif
-__device__ __forceinline__ float gelu_f(float z) {
-#if MLP_GELU_ERFF
-  return 0.5f * z * (1.0f + erff(z * 0.70710678118654752440f));
-#else
-  return gelu_fast(z);
-#endif
 }
 
 // per-lane bias / saved-activation helpers: lane (p, h) owns rows 32 m + 8 g + 4 h + i of block m
@@ -245,7 +208,7 @@ __global__ __launch_bounds__(MLP_BLOCK, 2) void mlp_fwd_kernel(
   const int rounds = (ntiles + per_round - 1) / per_round;
   // the input rows of round rd + 1 are requested before round rd's layers (up to 96 wide; at 128
   // the second set of 64 registers does not fit)
-  constexpr bool XPF = MLP_XPF && NB <= 3;
+  constexpr bool XPF = NB <= 3;
   float xn[XPF ? NB : 1][16];
   auto load_x = [&](int rd, float dst[][16]) {
     const int tile = rd * per_round + blockIdx.x * 4 + wave;
@@ -350,8 +313,10 @@ __global__ __launch_bounds__(MLP_BLOCK, 2) void mlp_fwd_kernel(
               // hidden widths are multiples of 32: aligned 16-byte rows
               if (z_ws && valid)
                 *reinterpret_cast<float4*>(z_ws + z_off + pt * out + n0) = make_float4(v[0], v[1], v[2], v[3]);
+              // exact GELU (torch.nn.GELU default) = z Phi(z); Phi to 6.6e-8 absolute in ~13 instructions (gelu_fast.h;
+              // the device library's erff: ~45 — the forward spent as long in its GELUs as in its matrix instructions)
 #pragma unroll
-              for (int i = 0; i < 4; ++i) act[m][4 * g + i] = gelu_f(v[i]);
+              for (int i = 0; i < 4; ++i) act[m][4 * g + i] = gelu_fast(v[i]);
               // the activations the weight gradients will contract with: stored here, where the
               // kernel has time to spare (it is bound by its MFMAs and the GELU), instead of by
               // mlp_dgrad, which is bound by its traffic (1.50 -> 1.21 ms without these stores)
@@ -433,7 +398,7 @@ __global__ __launch_bounds__(MLP_BLOCK, 2) void mlp_dgrad_kernel(
       // the saved pre-activations this layer's epilogue needs are requested BEFORE its MFMAs: the
       // loads do not depend on them, and with 8 waves per CU nothing else hides their latency
       // (not at 128 wide: dz, da and a third 64-register block do not fit the 256 registers)
-      constexpr bool ZPF = MLP_ZPF && NB <= 3;
+      constexpr bool ZPF = NB <= 3;
       float4 zq[ZPF ? NB : 1][4];
       if (l > 0) z_off -= (long long)M * in;
       if (ZPF && l > 0) {
@@ -492,13 +457,8 @@ __global__ __launch_bounds__(MLP_BLOCK, 2) void mlp_dgrad_kernel(
               float d4[4];
 #pragma unroll
               for (int i = 0; i < 4; ++i) {
-#if MLP_GELU_ERFF
-                const float cdf = 0.5f * (1.0f + erff(zz[i] * 0.70710678118654752440f));
-                const float pdf = 0.39894228040143267794f * __expf(-0.5f * zz[i] * zz[i]);
-#else
                 float cdf, pdf;
                 gelu_cdf_pdf(zz[i], cdf, pdf);
-#endif
                 d4[i] = da[b][4 * g + i] * (cdf + zz[i] * pdf);
                 dz[b][4 * g + i] = d4[i];
               }
@@ -752,12 +712,6 @@ size_t max_layer_bytes(const vsa_mlp_plan& p) {
 #ifndef MLP_WG_SMALL_WGS
 #define MLP_WG_SMALL_WGS 4
 #endif
-#ifndef MLP_WG_SMALL_PF
-#define MLP_WG_SMALL_PF 1
-#endif
-#ifndef MLP_WG_COST
-#define MLP_WG_COST 1
-#endif
 struct WgradShape {
   int nb, q, wgs;
 };
@@ -837,13 +791,8 @@ WgradLayers wgrad_layers(const vsa_mlp_plan& p, int total_wgs) {
   WgradLayers wl;
   int cost[VSA_MLP_MAX_LAYERS], sum = 0;
   for (int l = 0; l < p.n_layers; ++l) {
-#if MLP_WG_COST == 0
-    // a wave issues ceil(pairs / 4) MFMAs per point pair
-    cost[l] = (blocks_of(p.dims[l]) * blocks_of(p.dims[l + 1]) + 3) / 4;
-#else
     // the loop waits for its tile loads, not for its MFMAs: bytes per point
     cost[l] = blocks_of(p.dims[l]) + blocks_of(p.dims[l + 1]);
-#endif
     sum += cost[l];
   }
   int begin = 0;
@@ -864,14 +813,12 @@ WgradLayers wgrad_layers(const vsa_mlp_plan& p, int total_wgs) {
 
 // The fused backward (mlp_f32_fused.h) serves a network when its transposed weights stay resident in LDS beside the
 // staging rows (<= 160 KiB), its layers are at most 96 wide and its block pairs fit five accumulators per wave.
-// MLP_BWD_FUSED=0 in the environment: the two-kernel backward of rounds 1-5 (A/B switch).
 constexpr size_t MLP_FUSED_LDS_MAX = 160 * 1024 - 512;
 // a row-major matrix whose rows can be read / written as 16-byte groups
 bool rows_aligned(const void* ptr, int stride) { return stride % 4 == 0 && (reinterpret_cast<size_t>(ptr) & 15) == 0; }
 
 bool bwd_is_fused(const vsa_mlp_plan& p) {
-  static const bool off = [] { const char* e = getenv("MLP_BWD_FUSED"); return e && e[0] == '0'; }();
-  if (off || p.n_layers < 2) return false;
+  if (p.n_layers < 2) return false;
   const size_t all = (size_t)pack_offsets(p).fwd[p.n_layers] * sizeof(float);
   for (int l = 1; l < p.n_layers; ++l)
     if (p.dims[l] > 64) return false;          // hidden layers: two 32-blocks (the z registers of the data waves)
@@ -1106,8 +1053,8 @@ extern "C" int vsa_mlp_bwd_grouped(const vsa_mlp_plan* plans, int nr_groups, con
   hipLaunchKernelGGL((mlp_wgrad_kernel<NB_, Q_, PF_, WGS_>), dim3(wl.wg_begin[L], nr_groups), dim3(MLP_BLOCK), \
                      wg_lds, st, *plan, wl, gp, hidden, partial_stride, x, x_stride, dy, dy_stride, dz_ws, a_ws, \
                      partial_ws)
-  if (ws.nb == 2) VSA_WGRAD_LAUNCH(2, 1, MLP_WG_SMALL_PF, MLP_WG_SMALL_WGS);
-  else if (ws.nb == 3) VSA_WGRAD_LAUNCH(3, 2, MLP_WG_SMALL_PF, MLP_WG_SMALL_WGS);
+  if (ws.nb == 2) VSA_WGRAD_LAUNCH(2, 1, 1, MLP_WG_SMALL_WGS);
+  else if (ws.nb == 3) VSA_WGRAD_LAUNCH(3, 2, 1, MLP_WG_SMALL_WGS);
   else VSA_WGRAD_LAUNCH(4, 4, 1, 3);
 #undef VSA_WGRAD_LAUNCH
   hipLaunchKernelGGL(mlp_reduce_kernel, dim3(68, L, nr_groups), dim3(256), 0, st, *plan, wl, partial_stride,

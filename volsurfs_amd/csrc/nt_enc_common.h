@@ -36,9 +36,6 @@ struct CellRef {
   f32x2 w01, w23;   // corner weights (x0y0, x1y0), (x0y1, x1y1)
 };
 
-#ifndef NT_ENC_FRACT
-#define NT_ENC_FRACT 1
-#endif
 // floor and fraction of a positive coordinate in two instructions instead of three:
 // v_cvt_flr_i32_f32 = (int)floor(p), v_fract_f32 = p - floor(p) (the subtraction is exact in
 // fp32, so this is the same value as the oracle's p - floorf(p))
@@ -66,20 +63,11 @@ __device__ __forceinline__ int enc_round_i(float x) {
 __device__ __forceinline__ CellRef cell_ref(const LevelGeom& g, float x, float y) {
   const f32x2 xy = {x, y};
   const f32x2 p = xy * g.scale + 0.5f;
-#if NT_ENC_FRACT
   const f32x2 f = {enc_fract(p.x), enc_fract(p.y)};
   const f32x2 q = 1.0f - f;
   CellRef c;
   c.cx = (unsigned)enc_floor_i(p.x);
   c.cy = (unsigned)enc_floor_i(p.y);
-#else
-  const f32x2 fl = {floorf(p.x), floorf(p.y)};
-  const f32x2 f = p - fl;
-  const f32x2 q = 1.0f - f;
-  CellRef c;
-  c.cx = (unsigned)(int)fl.x;
-  c.cy = (unsigned)(int)fl.y;
-#endif
   const f32x2 ax = {q.x, f.x};
   c.w01 = ax * q.y;
   c.w23 = ax * f.y;
@@ -95,20 +83,11 @@ struct CellRefS {
 
 __device__ __forceinline__ CellRefS cell_ref_s(const LevelGeom& g, float x, float y) {
   const float px = x * g.scale + 0.5f, py = y * g.scale + 0.5f;
-#if NT_ENC_FRACT
   const float fx = enc_fract(px), fy = enc_fract(py);
   const float gx = 1.0f - fx, gy = 1.0f - fy;
   CellRefS c;
   c.cx = (unsigned)enc_floor_i(px);
   c.cy = (unsigned)enc_floor_i(py);
-#else
-  const float flx = floorf(px), fly = floorf(py);
-  const float fx = px - flx, fy = py - fly;
-  const float gx = 1.0f - fx, gy = 1.0f - fy;
-  CellRefS c;
-  c.cx = (unsigned)(int)flx;
-  c.cy = (unsigned)(int)fly;
-#endif
   c.w[0] = gx * gy;
   c.w[1] = fx * gy;
   c.w[2] = gx * fy;
@@ -116,9 +95,6 @@ __device__ __forceinline__ CellRefS cell_ref_s(const LevelGeom& g, float x, floa
   return c;
 }
 
-#ifndef NT_ENC_MIX
-#define NT_ENC_MIX 1
-#endif
 // fp32 product of one half of a packed f16 pair and an fp32 value (see nt_mlp.hip mul_mix)
 template <int HI>
 __device__ __forceinline__ float enc_mul_mix(unsigned h2, float f) {
@@ -165,17 +141,10 @@ __device__ __forceinline__ CellCorners cell_corners(const LevelGeom& g, float x,
 }
 
 // The feature of one level at one texel: bilinear blend of the cell's four table entries
-// (packed f16x2 words e[], corner weights w[] in fp32).
-// NT_ENC_ACC_F16 = 1 (default): tiny-cuda-nn's published kernel_grid —
+// (packed f16x2 words e[], corner weights w[] in fp32), as tiny-cuda-nn's published kernel_grid —
 // `result = fma((T)weight, grid_val(corner), result)` with T = __half over the corners in index
 // order — i.e. four packed half FMAs (v_pk_fma_f16: one rounding each) on the weight rounded to
 // half; oracle/tcnn_like.py hashgrid_forward(accumulate="f16").  4 conversions + 4 FMAs.
-// NT_ENC_ACC_F16 = 0: the fp32 sum rounded once that rounds 1-2 restated (accumulate="f32"):
-// 8 mixed-precision multiplies + 8 adds + 1 pack.
-#ifndef NT_ENC_ACC_F16
-#define NT_ENC_ACC_F16 1
-#endif
-#if NT_ENC_ACC_F16
 // The blend in two steps, for callers that blend SEVERAL tables with one set of corner weights (the
 // colour and the alpha texture of a (shell, degree) pair): the four weights rounded to half once ...
 __device__ __forceinline__ void enc_weights_h(const float w[4], half2_t wh[4]) {
@@ -192,10 +161,8 @@ __device__ __forceinline__ unsigned enc_blend_h(const unsigned e[4], const half2
   for (int k = 0; k < 4; ++k) acc = __builtin_elementwise_fma(wh[k], __builtin_bit_cast(half2_t, e[k]), acc);
   return __builtin_bit_cast(unsigned, acc);
 }
-#endif
 
 __device__ __forceinline__ unsigned enc_blend(const unsigned e[4], const float w[4]) {
-#if NT_ENC_ACC_F16
   half2_t acc = {(_Float16)0.f, (_Float16)0.f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -206,21 +173,6 @@ __device__ __forceinline__ unsigned enc_blend(const unsigned e[4], const float w
     acc = __builtin_elementwise_fma(w2, __builtin_bit_cast(half2_t, e[k]), acc);
   }
   return __builtin_bit_cast(unsigned, acc);
-#else
-  float f0 = 0.f, f1 = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    // w * (float)entry in ONE instruction per feature (v_fma_mix_f32 with a zero addend: the
-    // f16 -> f32 conversion is exact, so the product is the same single rounding as
-    // convert-then-multiply)
-    f0 = f0 + enc_mul_mix<0>(e[k], w[k]);
-    f1 = f1 + enc_mul_mix<1>(e[k], w[k]);
-  }
-  half2_t r;
-  r.x = (_Float16)f0;
-  r.y = (_Float16)f1;
-  return __builtin_bit_cast(unsigned, r);
-#endif
 }
 
 }  // namespace

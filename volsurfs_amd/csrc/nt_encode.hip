@@ -50,18 +50,6 @@ constexpr int LDS_ENTRIES = 32768;    // 4-byte entries of LDS a workgroup may u
 #ifndef NT_ENC_DIAG_FWD
 #define NT_ENC_DIAG_FWD 0
 #endif
-#ifndef NT_ENC_FWD_NOREUSE
-#define NT_ENC_FWD_NOREUSE 0
-#endif
-#ifndef NT_ENC_PREFETCH_FWD
-#define NT_ENC_PREFETCH_FWD 0     /* stretches of texel centres in flight per lane (0: loaded at their use) */
-#endif
-#ifndef NT_ENC_ONE_LAUNCH
-#define NT_ENC_ONE_LAUNCH 1      /* dense + hashed levels of a direction in one launch */
-#endif
-#ifndef NT_ENC_PAIR_DENSE
-#define NT_ENC_PAIR_DENSE 1      /* dense levels: colour + alpha texture of a (shell, degree) in ONE piece (shared cell / weights) */
-#endif
 constexpr int ENC_PAIR_OFF = 15360;   // entries: the second table of a pair sits at a FIXED LDS offset (61 440 B: an
                                       // immediate of the gathers); the largest dense level has 15 136 entries
 template <bool HASHED>
@@ -75,8 +63,7 @@ __device__ __forceinline__ void nt_encode_fwd_body(
   NT_SPAN_MARK(HASHED ? 1 : 0, 0);
   NT_BAL_BEGIN();
   // dense levels: pieces are (shell, degree) pairs (nt_for_each_piece, paired) — both tables in LDS
-  const bool pair_mode = !HASHED && NT_ENC_PAIR_DENSE && NT_ENC_ACC_F16 && !NT_ENC_PREFETCH_FWD &&
-                         plan.nr_shells * 2 * VSA_NT_MAX_DEG <= 64;
+  const bool pair_mode = !HASHED && plan.nr_shells * 2 * VSA_NT_MAX_DEG <= 64;
   // per-piece overheads and unit weights: fitted from per-workgroup timings (tools/fit_cost.py):
   // a piece costs 87 (hashed: a 128 KiB table to stage) / 27 (dense) units of 256 slots, and a
   // unit of a level finer than the texture (no reuse of the previous slot's cell) 0.92 of one
@@ -134,31 +121,8 @@ __device__ __forceinline__ void nt_encode_fwd_body(
     auto run = [&](auto reuse_tag, auto pair_tag) {
       constexpr bool REUSE = decltype(reuse_tag)::value;
       constexpr bool PAIR = decltype(pair_tag)::value;
-#if NT_ENC_PREFETCH_FWD
-      // NT_ENC_PREFETCH_FWD stretches of texel centres are in flight per lane, requested AFTER the
-      // stores of the stretch that is being finished: the wait at the head of a trip then never
-      // includes those stores (past the end: the last stretch again, unused)
-      constexpr int PD = NT_ENC_PREFETCH_FWD;
-      const int s_max = (last - 1) & ~(ENC_UNROLL_FWD - 1);
-      float4 xyn[PD][ENC_UNROLL_FWD / 2];
-      auto request = [&](int s, float4 (&dst)[ENC_UNROLL_FWD / 2]) {
-        const float4* xp = reinterpret_cast<const float4*>(slot_xy + (s < s_max ? s : s_max));
-#pragma unroll
-        for (int i = 0; i < ENC_UNROLL_FWD / 2; ++i) dst[i] = xp[i];
-      };
-#pragma unroll
-      for (int d = 0; d < PD; ++d) request(a_first + threadIdx.x * ENC_UNROLL_FWD + d * ENC_BLOCK * ENC_UNROLL_FWD, xyn[d]);
-#endif
       for (int s0 = a_first + threadIdx.x * ENC_UNROLL_FWD; s0 < last; s0 += ENC_BLOCK * ENC_UNROLL_FWD) {
         float4 xyv[ENC_UNROLL_FWD / 2];
-#if NT_ENC_PREFETCH_FWD
-#pragma unroll
-        for (int i = 0; i < ENC_UNROLL_FWD / 2; ++i) xyv[i] = xyn[0][i];
-#pragma unroll
-        for (int d = 0; d + 1 < PD; ++d)
-#pragma unroll
-          for (int i = 0; i < ENC_UNROLL_FWD / 2; ++i) xyn[d][i] = xyn[d + 1][i];
-#else
 #if NT_ENC_DIAG_FWD & 1   /* timing-only: texel centres from a 64 KiB window (L2-resident) */
         const float4* xp = reinterpret_cast<const float4*>(slot_xy + (s0 & 0x1fff));
 #else
@@ -166,7 +130,6 @@ __device__ __forceinline__ void nt_encode_fwd_body(
 #endif
 #pragma unroll
         for (int i = 0; i < ENC_UNROLL_FWD / 2; ++i) xyv[i] = xp[i];
-#endif
         CellRefS cr[ENC_UNROLL_FWD];
         bool fresh[ENC_UNROLL_FWD];
 #pragma unroll
@@ -204,7 +167,6 @@ __device__ __forceinline__ void nt_encode_fwd_body(
           unsigned ew[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) ew[k] = __builtin_bit_cast(unsigned, v[u][k]);
-#if NT_ENC_ACC_F16
           if constexpr (PAIR) {
             half2_t wh[4];
             enc_weights_h(cr[u].w, wh);
@@ -213,7 +175,6 @@ __device__ __forceinline__ void nt_encode_fwd_body(
             for (int k = 0; k < 4; ++k) ew[k] = __builtin_bit_cast(unsigned, v2[u][k]);
             outw2[u] = enc_blend_h(ew, wh);
           } else
-#endif
           {
             outw[u] = enc_blend(ew, cr[u].w);
           }
@@ -249,12 +210,9 @@ __device__ __forceinline__ void nt_encode_fwd_body(
               if constexpr (PAIR) op2[u] = outw2[u];
             }
         }
-#if NT_ENC_PREFETCH_FWD
-        request(s0 + PD * ENC_BLOCK * ENC_UNROLL_FWD, xyn[PD - 1]);
-#endif
       }
     };
-    const bool reuse = !NT_ENC_FWD_NOREUSE && g.scale < (float)plan.tex_res[tex % VSA_NT_MAX_DEG];
+    const bool reuse = g.scale < (float)plan.tex_res[tex % VSA_NT_MAX_DEG];
     if (!HASHED && tex2 >= 0) {
       if (reuse) run(std::true_type{}, std::true_type{});
       else run(std::false_type{}, std::true_type{});
@@ -313,14 +271,8 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_both_kernel(
 #ifndef NT_ENC_DIAG
 #define NT_ENC_DIAG 0
 #endif
-#ifndef NT_ENC_FLUSH_ATOMIC
-#define NT_ENC_FLUSH_ATOMIC 1     /* every flush through no-return float atomics: no read-modify-write round trip (r4: bwd 0.626 -> 0.607 ms) */
-#endif
 #ifndef NT_ENC_FLUSH_BATCH
-#define NT_ENC_FLUSH_BATCH 8     /* table entries per thread whose read-modify-write is in flight together (0: one at a time) */
-#endif
-#ifndef NT_ENC_PREFETCH
-#define NT_ENC_PREFETCH 1
+#define NT_ENC_FLUSH_BATCH 8     /* table entries per thread whose flush is in flight together */
 #endif
 #if NT_ENC_DIAG & 64   /* timing-only: the scatter's LDS atomics compiled out (values kept alive) */
 #define ENC_LDS_ADD(ptr, val) asm volatile("" ::"v"(ptr), "v"(val))
@@ -330,7 +282,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_both_kernel(
 template <bool HASHED, int NF, bool MERGE>
 __device__ __forceinline__ void enc_bwd_piece(
     const vsa_nt_plan& plan, int* s_g, int level, int feat, int tex, int first, int last,
-    bool single, bool store, const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
+    bool store, const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
     float dscale_inv, const float2* __restrict__ slot_xy, float* __restrict__ grad_tables) {
   const int nl = plan.n_levels;
   const long long n_entries = plan.level_offset[plan.n_levels];
@@ -377,11 +329,10 @@ __device__ __forceinline__ void enc_bwd_piece(
   // their four corner contributions are summed in registers and added once.  The sums
   // are integers, so the result is independent of this grouping.
   const int a_first = first & ~(ENC_UNROLL - 1);
-#if NT_ENC_PREFETCH
-  // NT_ENC_PREFETCH stretches of texel centres and gradients are in flight per lane (past the
-  // end: the last stretch's again, unused); the loop has no other vector-memory operation, so
-  // the wait at the head of a trip is for exactly the oldest request
-  constexpr int PD = NT_ENC_PREFETCH;
+  // PD stretches of texel centres and gradients are in flight per lane (past the end: the last
+  // stretch's again, unused); the loop has no other vector-memory operation, so the wait at the
+  // head of a trip is for exactly the oldest request
+  constexpr int PD = 1;
   const int s_max = (last - 1) & ~(ENC_UNROLL - 1);
   float4 xyn[PD][ENC_UNROLL / 2];
   uint4 dn[PD][ENC_UNROLL / 4];
@@ -405,11 +356,9 @@ __device__ __forceinline__ void enc_bwd_piece(
 #pragma unroll
   for (int d = 0; d < PD; ++d)
     request(a_first + threadIdx.x * ENC_UNROLL + d * ENC_BLOCK * ENC_UNROLL, xyn[d], dn[d]);
-#endif
   for (int s0 = a_first + threadIdx.x * ENC_UNROLL; s0 < last; s0 += ENC_BLOCK * ENC_UNROLL) {
     float4 xyv[ENC_UNROLL / 2];
     uint4 dv[ENC_UNROLL / 4];
-#if NT_ENC_PREFETCH
 #pragma unroll
     for (int i = 0; i < ENC_UNROLL / 2; ++i) xyv[i] = xyn[0][i];
 #pragma unroll
@@ -422,14 +371,6 @@ __device__ __forceinline__ void enc_bwd_piece(
       for (int i = 0; i < ENC_UNROLL / 4; ++i) dn[d][i] = dn[d + 1][i];
     }
     request(s0 + PD * ENC_BLOCK * ENC_UNROLL, xyn[PD - 1], dn[PD - 1]);
-#else
-    const float4* xp = reinterpret_cast<const float4*>(slot_xy + s0);
-    const uint4* dp = reinterpret_cast<const uint4*>(dFw + nt_feat_in_plane(nl, s0));
-#pragma unroll
-    for (int i = 0; i < ENC_UNROLL / 2; ++i) xyv[i] = xp[i];
-#pragma unroll
-    for (int i = 0; i < ENC_UNROLL / 4; ++i) dv[i] = dp[i];
-#endif
     const unsigned dws[ENC_UNROLL] = {dv[0].x, dv[0].y, dv[0].z, dv[0].w,
                                       dv[1].x, dv[1].y, dv[1].z, dv[1].w};
     unsigned cur_idx[4] = {0, 0, 0, 0};
@@ -446,15 +387,10 @@ __device__ __forceinline__ void enc_bwd_piece(
       bool nz = false;
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
-#if NT_ENC_MIX
         // conversion and scaling in one instruction (enc_mul_mix); NF = 2: the two halves of the
         // word, NF = 1: the word shifted so that feature `feat` is the low half
         gv[f] = NF == 2 ? (f ? enc_mul_mix<1>(dws[u], S[f]) : enc_mul_mix<0>(dws[u], S[f]))
                         : enc_mul_mix<0>(dws[u] >> (16 * feat), S[f]);
-#else
-        const unsigned short hb = (unsigned short)(dws[u] >> (16 * (feat + f)));
-        gv[f] = (float)__builtin_bit_cast(_Float16, hb) * S[f];
-#endif
         nz |= gv[f] != 0.f;
       }
       if (slot >= first && slot < last && nz) {
@@ -463,13 +399,8 @@ __device__ __forceinline__ void enc_bwd_piece(
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
           const f32x2 p01 = cr.w01 * gv[f], p23 = cr.w23 * gv[f];
-#if NT_ENC_FRACT
           v[f][0] = enc_round_i(p01.x), v[f][1] = enc_round_i(p01.y);
           v[f][2] = enc_round_i(p23.x), v[f][3] = enc_round_i(p23.y);
-#else
-          v[f][0] = __float2int_rn(p01.x), v[f][1] = __float2int_rn(p01.y);
-          v[f][2] = __float2int_rn(p23.x), v[f][3] = __float2int_rn(p23.y);
-#endif
         }
         if (!MERGE) {   // cells are finer than texels: every slot has its own cell
           unsigned idx[4];
@@ -506,7 +437,6 @@ __device__ __forceinline__ void enc_bwd_piece(
         for (int k = 0; k < 4; ++k) ENC_LDS_ADD(&my_g[f * plane + cur_idx[k]], acc[f][k]);
     }
   }
-#if NT_ENC_PREFETCH
   // retire the last (unused) request here: left pending, its landing registers made the
   // compiler put an s_waitcnt vmcnt(0) in front of every register it reuses in the flush
   // below — i.e. in front of every flush atomic, which then waited for the previous one
@@ -519,13 +449,11 @@ __device__ __forceinline__ void enc_bwd_piece(
     for (int i = 0; i < ENC_UNROLL / 4; ++i)
       asm volatile("" ::"v"(dn[d][i].x), "v"(dn[d][i].y), "v"(dn[d][i].z), "v"(dn[d][i].w));
   }
-#endif
   __syncthreads();
 #if NT_ENC_DIAG & 1
   return;
 #endif
   float* gt = grad_tables + ((long long)nt_param_tex(plan, tex) * n_entries + plan.level_offset[level]) * 2 + feat;
-#if NT_ENC_FLUSH_BATCH
   // FB entries per thread and trip: their table values are all requested before the first one is
   // waited for.  (One entry at a time — LDS read, test, global load, add, store, with a branch in
   // between — is a serial global round trip per entry: 32 of them per thread and 128 KiB plane,
@@ -567,24 +495,6 @@ __device__ __forceinline__ void enc_bwd_piece(
         }
       }
     }
-  } else if (single) {        // sole writer of this (texture, level, feature) plane: plain read-modify-write
-    for (int i0 = threadIdx.x; i0 < (int)g.size; i0 += ENC_BLOCK * FB) {
-      int vi[FB][NF];
-      float old[FB][NF];
-      plane_sums(i0, vi);
-#pragma unroll
-      for (int b = 0; b < FB; ++b)
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          old[b][f] = 0.f;
-          if (vi[b][f] != 0) old[b][f] = gt[2 * (long long)(i0 + b * ENC_BLOCK) + f];
-        }
-#pragma unroll
-      for (int b = 0; b < FB; ++b)
-#pragma unroll
-        for (int f = 0; f < NF; ++f)
-          if (vi[b][f] != 0) gt[2 * (long long)(i0 + b * ENC_BLOCK) + f] = old[b][f] + (float)vi[b][f] * S_inv[f];
-    }
   } else {
     for (int i0 = threadIdx.x; i0 < (int)g.size; i0 += ENC_BLOCK * FB) {
       int vi[FB][NF];
@@ -596,24 +506,6 @@ __device__ __forceinline__ void enc_bwd_piece(
           if (vi[b][f] != 0) atomicAdd(&gt[2 * (long long)(i0 + b * ENC_BLOCK) + f], (float)vi[b][f] * S_inv[f]);
     }
   }
-#else
-  for (int i = threadIdx.x; i < (int)g.size; i += ENC_BLOCK) {
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      int vi = 0;
-      for (int cpy = 0; cpy < copies; ++cpy) vi += s_g[f * plane + cpy * g.size + i];
-      if (vi == 0) continue;
-      const float v = (float)vi * S_inv[f];
-      if (store) {
-        gt[2 * (long long)i + f] = v;
-      } else if (single) {
-        gt[2 * (long long)i + f] += v;  // sole writer of this (texture, level, feature) plane
-      } else {
-        atomicAdd(&gt[2 * (long long)i + f], v);
-      }
-    }
-  }
-#endif
 }
 
 // Planes of a launch over levels [level0, level0 + n_levels): a dense level whose two
@@ -647,15 +539,8 @@ __device__ __forceinline__ void nt_encode_bwd_body(
       ++level;
       both = enc_both_features(plan, level, HASHED);
     }
-#if NT_ENC_FLUSH_ATOMIC   /* every flush through no-return float atomics: fire and forget, where the sole-writer form
-                            waits for a batch of table entries to come back before it can add and store them.
-                            A sole writer adds exactly once per entry, so its result is the same old + v either way */
-    const bool single = false;
-#else
-    const bool single = first == seg_begin && last == seg_end &&
-                        !((((tex / VSA_NT_MAX_DEG) & 1) ? plan.shared_alpha : plan.shared_rgb) != 0);
-#endif
-    // ... unless the caller vouches for a zero gradient buffer: then a sole writer's plane is simply stored
+    // every flush goes through no-return float atomics (fire and forget, no read-modify-write round trip) unless
+    // the caller vouches for a zero gradient buffer: then a sole writer's plane is simply stored
     // (a plane that K shells share — plan.shared_rgb / shared_alpha — has K writers whoever walks the segment)
     const bool shared_plane = (((tex / VSA_NT_MAX_DEG) & 1) ? plan.shared_alpha : plan.shared_rgb) != 0;
     const bool store = plan.grads_zeroed != 0 && first == seg_begin && last == seg_end && !shared_plane;
@@ -663,13 +548,13 @@ __device__ __forceinline__ void nt_encode_bwd_body(
     // in-register merging of same-cell slots cannot fire and its bookkeeping is skipped
     const bool merge = plan.level_scale[level] < (float)plan.tex_res[tex % VSA_NT_MAX_DEG];
     if (both)
-      enc_bwd_piece<HASHED, 2, true>(plan, s_g, level, 0, tex, first, last, single, store, dfeatures,
+      enc_bwd_piece<HASHED, 2, true>(plan, s_g, level, 0, tex, first, last, store, dfeatures,
                                      dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
     else if (merge)
-      enc_bwd_piece<HASHED, 1, true>(plan, s_g, level, r, tex, first, last, single, store, dfeatures,
+      enc_bwd_piece<HASHED, 1, true>(plan, s_g, level, r, tex, first, last, store, dfeatures,
                                      dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
     else
-      enc_bwd_piece<HASHED, 1, false>(plan, s_g, level, r, tex, first, last, single, store, dfeatures,
+      enc_bwd_piece<HASHED, 1, false>(plan, s_g, level, r, tex, first, last, store, dfeatures,
                                       dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
   }, tex_begin, tex_end, unit_weight,
      // a launch over a sub-range of the textures (the sliced backward of parallel.py) keeps equal shares
@@ -839,7 +724,7 @@ extern "C" int vsa_nt_encode_fwd(const vsa_nt_plan* plan, const void* tables_h,
   half2_t* out = reinterpret_cast<half2_t*>(features);
   int nr_cus = 0;
   if ((rc = vsa_cu_count(&nr_cus))) return rc;
-  if (NT_ENC_ONE_LAUNCH && lh > 0 && lh < plan->n_levels) {
+  if (lh > 0 && lh < plan->n_levels) {
     hipLaunchKernelGGL(nt_encode_fwd_both_kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
                        (hipStream_t)stream, *plan, lh, tab, xy, seg_start, out);
     VSA_RETURN_LAUNCH_STATUS();
@@ -891,7 +776,7 @@ extern "C" int vsa_nt_encode_bwd_range(const vsa_nt_plan* plan, const void* dfea
   const float2* xy = reinterpret_cast<const float2*>(slot_xy);
   int nr_cus = 0;
   if ((rc = vsa_cu_count(&nr_cus))) return rc;
-  if (NT_ENC_ONE_LAUNCH && lh > 0 && lh < plan->n_levels) {
+  if (lh > 0 && lh < plan->n_levels) {
     int n_planes = 0;
     for (int l = 0; l < lh; ++l) n_planes += enc_both_features(*plan, l, false) ? 1 : 2;
     hipLaunchKernelGGL(nt_encode_bwd_both_kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,

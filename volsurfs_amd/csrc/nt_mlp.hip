@@ -181,21 +181,6 @@ __device__ __forceinline__ void prefetch_features(const vsa_nt_plan& plan,
 // consumer: 1 or 2 k-steps of dH2); each instance owns its accumulators and its epilogue.
 // Round-2 stamps (NT_STAMP, tools/wg_timeline.py; cycles per tile, producer | consumer work):
 // 5050 | 3880 before, 2740 | 3460 now — see profiles/NOTEBOOK.md A9.1 for what moved and what it cost.
-#ifndef NT_PC_DW3_CONSUMER
-#define NT_PC_DW3_CONSUMER 0    /* dW3: 0 producer, 1 consumer (from the finished images), 2 split by 32-column block */
-#endif
-#ifndef NT_PC_BATCH
-#define NT_PC_BATCH 1           /* consumer: operands fetched in batches a stage ahead of their MFMAs */
-#endif
-#ifndef NT_PC_DW3_LATE
-#define NT_PC_DW3_LATE 1        /* the producer's dW3 blocks one trip late, from the set written before the last barrier */
-#endif
-#ifndef NT_PC_DABS_MOD
-#define NT_PC_DABS_MOD 0
-#endif
-#ifndef NT_PC_PRIO
-#define NT_PC_PRIO 2          /* issue priority: 0 consumer raised, 1 producer raised, 2 none, 3 producer at 3 */
-#endif
 constexpr int PC_BLOCK = 512;
 constexpr int PC_PAIRS = 4;
 #ifndef NT_PC_S64
@@ -250,7 +235,7 @@ __device__ __forceinline__ half8_t read_tr_s(const _Float16* img, int col_base, 
 
 #ifdef NT_STAMP
 __device__ unsigned long long g_dbg[16384 * 8];   // per-workgroup timeline of the last pc launch
-__device__ unsigned long long g_dbg_stage[16384 * 8];   // consumer wave 4 / producer wave 0: cycles per stage (NT_PC_BATCH build)
+__device__ unsigned long long g_dbg_stage[16384 * 8];   // consumer wave 4 / producer wave 0: cycles per stage
 __device__ unsigned long long g_dbg_role[16384 * 4];   // {producer work, wait, consumer work, wait} cycles of wave 0 / 4
 #endif
 #ifdef NT_STAMP   // diagnostic build only (tools: make EXTRA=-DNT_STAMP): per-role cycles per tile
@@ -345,11 +330,6 @@ __device__ __forceinline__ void pc_run(
 #endif
 
   if (producer) {
-#if NT_PC_PRIO == 1
-    __builtin_amdgcn_s_setprio(1);
-#elif NT_PC_PRIO == 3
-    __builtin_amdgcn_s_setprio(3);
-#endif
 #ifdef NT_STAMP
     unsigned long long tw_ = 0, tb_ = 0, q0, q1, q2;
 #endif
@@ -362,7 +342,6 @@ __device__ __forceinline__ void pc_run(
       constexpr int NG = decltype(ng_tag)::value;
       // (accumulators and epilogue live inside the instance: values merging across the instances
       // made the register allocator copy whole accumulator sets around inside the loops)
-      constexpr int PM0 = 0, PM1 = NT_PC_DW3_CONSUMER == 0 ? 2 : NT_PC_DW3_CONSUMER == 2 ? 1 : 0;   // producer's dW3 blocks
       float16_t gW3[2] = {float16_t{0}, float16_t{0}};
       // gradient rows of one slot (raw f16: converting here would wait for the prefetch).  No
       // branches around the quads this lane has no use for — slots past the end, rows beyond the
@@ -395,24 +374,20 @@ __device__ __forceinline__ void pc_run(
         load_grows(s0, gr_next);
       }
       auto dw3_from = [&](const _Float16* img_dout, const _Float16* img_h2) {
-        if constexpr (PM1 > PM0) {
 #pragma unroll
-          for (int sx = 0; sx < 2; ++sx) {
-            const half8_t a3 = read_tr_s<S32>(img_dout, 0, sx, lane);
+        for (int sx = 0; sx < 2; ++sx) {
+          const half8_t a3 = read_tr_s<S32>(img_dout, 0, sx, lane);
 #pragma unroll
-            for (int m = PM0; m < PM1; ++m)
-              gW3[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3, read_tr_s<S64>(img_h2, 32 * m, sx, lane), gW3[m], 0, 0, 0);
-          }
+          for (int m = 0; m < 2; ++m)
+            gW3[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3, read_tr_s<S64>(img_h2, 32 * m, sx, lane), gW3[m], 0, 0, 0);
         }
       };
       auto trip = [&](const int it) {
         STAMP(q0);
         {
-#if NT_PC_DW3_LATE
           // dW3 of the PREVIOUS tile, from the set written before the last barrier (the consumer
           // reads the same set meanwhile): no wait on this trip's own LDS stores
           if (it > 0) dw3_from(pair + ((it - 1) & 1) * SET_HALFS + SET_DOUT, pair + ((it - 1) & 1) * SET_HALFS + SET_H2);
-#endif
           const int slot = wk.first + (pr + it * PC_PAIRS) * 32 + p;
           _Float16* set = pair + (it & 1) * SET_HALFS;
           _Float16* const img_dout_w = set + SET_DOUT;
@@ -534,10 +509,6 @@ __device__ __forceinline__ void pc_run(
             for (int g = 0; g < (NG > 2 ? 4 : 2); ++g)
               *reinterpret_cast<uint2v_*>(row + 8 * g) = g < NG ? uint2v_{dq[2 * (g < NG ? g : 0)], dq[2 * (g < NG ? g : 0) + 1]} : uint2v_{0u, 0u};
           }
-#if !NT_PC_DW3_LATE
-          // ---- dW3 += dOut . H2^T  (transposed reads of this wave's own, just-written images)
-          dw3_from(img_dout_w, img_h2_w);
-#endif
         }
         STAMP(q1);
         pc_barrier();
@@ -547,9 +518,7 @@ __device__ __forceinline__ void pc_run(
 #endif
       };
       for (int it = 0; it < iters; ++it) trip(it);
-#if NT_PC_DW3_LATE
       if (iters > 0) dw3_from(pair + ((iters - 1) & 1) * SET_HALFS + SET_DOUT, pair + ((iters - 1) & 1) * SET_HALFS + SET_H2);
-#endif
       pc_barrier();     // the consumer's last tile
 #ifdef NT_STAMP
       STAMP(ph2);
@@ -557,14 +526,14 @@ __device__ __forceinline__ void pc_run(
 #endif
       // weight-gradient partials of this pair into its own 32 KiB of the (now free) image area
       __syncthreads();
-      if constexpr (PM1 > PM0) {
+      {
         // one lane-dependent base, the (register, tile) part of the index as an immediate offset
         float* const b3_ = s_part + W3_OFF + 4 * h * 64 + p;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const int r0 = (reg & 3) + 8 * (reg >> 2);
 #pragma unroll
-          for (int m = PM0; m < PM1; ++m) b3_[r0 * 64 + 32 * m] = gW3[m][reg];
+          for (int m = 0; m < 2; ++m) b3_[r0 * 64 + 32 * m] = gW3[m][reg];
         }
       }
     };
@@ -573,11 +542,6 @@ __device__ __forceinline__ void pc_run(
     else if (ti.channels <= 24) run_producer(std::integral_constant<int, 3>{});
     else run_producer(std::integral_constant<int, 4>{});
   } else {
-    // the consumer is the later-dispatched wave of its SIMD (the arbitration loser at equal
-    // priority): raise it once, statically (measured against the other assignments, profiles/NOTEBOOK.md A9.1)
-#if NT_PC_PRIO == 0
-    __builtin_amdgcn_s_setprio(1);
-#endif
 #ifdef NT_STAMP
     unsigned long long tw_ = 0, tb_ = 0, q0, q1, q2;
     unsigned long long st_[5] = {0, 0, 0, 0, 0};
@@ -592,8 +556,6 @@ __device__ __forceinline__ void pc_run(
       gW2[i][1] = float16_t{0};
     }
     float16_t dabs = {0};   // per-lane sum |dF| per feature row (hash-grad fixed-point bound)
-    constexpr int CM0 = NT_PC_DW3_CONSUMER == 2 ? 1 : 0, CM1 = NT_PC_DW3_CONSUMER ? 2 : 0;   // consumer's dW3 blocks
-    float16_t gW3[2] = {float16_t{0}, float16_t{0}};
     for (int it = 0; it <= iters; ++it) {
       STAMP(q0);
       if (it > 0) {
@@ -601,7 +563,6 @@ __device__ __forceinline__ void pc_run(
         const int slot = wk.first + (pr + t * PC_PAIRS) * 32 + p;
         const bool valid = slot < wk.last;
         const _Float16* set = pair + (t & 1) * SET_HALFS;
-#if NT_PC_BATCH
         // Operands are fetched a stage ahead of the matrix instructions that use them, in batches,
         // and the data-gradient chain runs while the private image's store -> transposed-read
         // round trips are in flight (issued in the order written: each MFMA of the plain version
@@ -679,21 +640,6 @@ __device__ __forceinline__ void pc_run(
               for (int mj = 0; mj < 2; ++mj)
                 gW2[m][mj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2[sx][m], b1[sx][mj], gW2[m][mj], 0, 0, 0);
         }
-        if constexpr (CM1 > CM0) {
-          // ---- dW3 += dOut . H2^T: operands from the finished images, independent of the chain
-          half8_t a3[2], b3t[2][2];
-#pragma unroll
-          for (int sx = 0; sx < 2; ++sx) {
-            a3[sx] = read_tr_s<S32>(set + SET_DOUT, 0, sx, lane);
-#pragma unroll
-            for (int m = CM0; m < CM1; ++m) b3t[sx][m] = read_tr_s<S64>(set + SET_H2, 32 * m, sx, lane);
-          }
-#pragma unroll
-          for (int sx = 0; sx < 2; ++sx)
-#pragma unroll
-            for (int m = CM0; m < CM1; ++m)
-              gW3[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3[sx], b3t[sx][m], gW3[m], 0, 0, 0);
-        }
         NT_FENCE();
         CSTAMP(c3_);
         // ---- stage 4: dH1 image (dW2's reads of the private image are done), dX = W1^T dH1 meanwhile
@@ -730,87 +676,9 @@ __device__ __forceinline__ void pc_run(
 #endif
 #undef CSTAMP
 #undef NT_FENCE
-#else
-        // ---- dH2 = W3^T dOut (B operand: this point's dOut row, natural channel order)
-        half8_t dh2[4];
-        {
-          const half8_t d0 = *reinterpret_cast<const half8_t*>(set + SET_DOUT + p * S32 + 8 * h);
-          half8_t d1 = {0, 0, 0, 0, 0, 0, 0, 0};     // channels 16..31: only degree-3 colour textures have them
-          if constexpr (KS3 == 2) d1 = *reinterpret_cast<const half8_t*>(set + SET_DOUT + p * S32 + 16 + 8 * h);
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            float16_t a = {0};
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(s_frag[(32 + m * 2 + 0) * 64 + lane], d0, a, 0, 0, 0);
-            if constexpr (KS3 == 2)
-              a = __builtin_amdgcn_mfma_f32_32x32x16_f16(s_frag[(32 + m * 2 + 1) * 64 + lane], d1, a, 0, 0, 0);
-            half8_t h0, h1;
-            load_frags_s<S64>(set + SET_H2, 32 * m, h0, h1, p, h);
-            mask_pack(a, h0, h1, dh2[2 * m], dh2[2 * m + 1]);
-          }
-        }
-        // ---- dW3 += dOut . H2^T: operands from the finished images, independent of the chain
-        if constexpr (CM1 > CM0) {
-#pragma unroll
-          for (int sx = 0; sx < 2; ++sx) {
-            const half8_t a3 = read_tr_s<S32>(set + SET_DOUT, 0, sx, lane);
-#pragma unroll
-            for (int m = CM0; m < CM1; ++m)
-              gW3[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3, read_tr_s<S64>(set + SET_H2, 32 * m, sx, lane), gW3[m], 0, 0, 0);
-          }
-        }
-        // ---- dW2 += dH2 . H1^T
-        store_frags_s<S64>(priv, 0, dh2[0], dh2[1], p, h);
-        store_frags_s<S64>(priv, 32, dh2[2], dh2[3], p, h);
-#pragma unroll
-        for (int sx = 0; sx < 2; ++sx) {
-          const half8_t b1[2] = {read_tr_s<S64>(set + SET_H1, 0, sx, lane), read_tr_s<S64>(set + SET_H1, 32, sx, lane)};
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            const half8_t a2 = read_tr_s<S64>(priv, 32 * m, sx, lane);
-#pragma unroll
-            for (int mj = 0; mj < 2; ++mj)
-              gW2[m][mj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, b1[mj], gW2[m][mj], 0, 0, 0);
-          }
-        }
-        // ---- dH1 = W2^T dH2, masked
-        half8_t dh1[4];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          float16_t a = {0};
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            a = __builtin_amdgcn_mfma_f32_32x32x16_f16(s_frag[(20 + m * 4 + q) * 64 + lane], dh2[q], a, 0, 0, 0);
-          half8_t h0, h1;
-          load_frags_s<S64>(set + SET_H1, 32 * m, h0, h1, p, h);
-          mask_pack(a, h0, h1, dh1[2 * m], dh1[2 * m + 1]);
-        }
-        // ---- dW1 += dH1 . X^T   (the private image is reused: dW2's reads are done)
-        store_frags_s<S64>(priv, 0, dh1[0], dh1[1], p, h);
-        store_frags_s<S64>(priv, 32, dh1[2], dh1[3], p, h);
-#pragma unroll
-        for (int sx = 0; sx < 2; ++sx) {
-          const half8_t bxx = read_tr_s<S32>(set + SET_X, 0, sx, lane);
-#pragma unroll
-          for (int m = 0; m < 2; ++m)
-            gW1[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(read_tr_s<S64>(priv, 32 * m, sx, lane), bxx, gW1[m], 0, 0, 0);
-        }
-        // ---- dX = W1^T dH1 -> dF, in place over the features
-        float16_t dx = {0};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          dx = __builtin_amdgcn_mfma_f32_32x32x16_f16(s_frag[(28 + q) * 64 + lane], dh1[q], dx, 0, 0, 0);
-#endif
         if (valid) {
 #pragma unroll
-#if NT_PC_DABS_MOD   /* |x| as a source modifier of the add: 16 instructions instead of 16 and + 8 packed adds */
-          for (int reg = 0; reg < 16; ++reg) {
-            float a = dabs[reg];
-            asm("v_add_f32 %0, %0, |%1|" : "+v"(a) : "v"(dx[reg]));
-            dabs[reg] = a;
-          }
-#else
           for (int reg = 0; reg < 16; ++reg) dabs[reg] += fabsf(dx[reg]);
-#endif
           unsigned* base = features + nt_feat_plane_base(plan, ti.type, 2 * h) +
                            nt_feat_in_plane(plan.n_levels, slot);
 #pragma unroll
@@ -847,14 +715,6 @@ __device__ __forceinline__ void pc_run(
       for (int reg = 0; reg < 16; ++reg) d_[reg * PC_DABS_STRIDE] = dabs[reg];
       float* const b1_ = s_part + W1_OFF + 4 * h * 32 + p;
       float* const b2_ = s_part + W2_OFF + 4 * h * 64 + p;
-      if constexpr (CM1 > CM0) {
-        float* const b3_ = s_part + W3_OFF + 4 * h * 64 + p;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-#pragma unroll
-          for (int m = CM0; m < CM1; ++m) b3_[((reg & 3) + 8 * (reg >> 2)) * 64 + 32 * m] = gW3[m][reg];
-        }
-      }
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int r0 = (reg & 3) + 8 * (reg >> 2);

@@ -15,41 +15,25 @@
 #include "nt_common.h"
 
 // Launch geometry of the two shading kernels: a workgroup = (one shell, one tile of consecutive rays).
-// NT_SHADE_MAP 2 (default): 1-D grid, XCD-aware — workgroups are dealt to the 8 XCDs round-robin by their linear
-//   id, so (tile t, shell s) gets id = ((t / 8) * K + s) * 8 + t % 8: the K workgroups of one tile run on ONE XCD,
-//   back to back, and their K partial writes into the tile's [N,K,3] / [N,K] lines (12 and 4 bytes at a stride of
-//   12 K and 4 K) merge in that XCD's L2 before they leave it.
-// 1: grid (shell, tile) — the K workgroups close in time but on K different XCDs (each L2 then writes its partial
-//   line back by itself: at 1920x1080, K = 7 the launch wrote 0.98 GB for 0.30 GB of outputs);
-// 0: rounds 1-4's grid (tile, shell): every line written K times a whole pass over the frame apart (1.22 GB).
-#ifndef NT_SHADE_MAP
-#define NT_SHADE_MAP 2
-#endif
+// 1-D grid, XCD-aware — workgroups are dealt to the 8 XCDs round-robin by their linear id, so (tile t, shell s) gets
+// id = ((t / 8) * K + s) * 8 + t % 8: the K workgroups of one tile run on ONE XCD, back to back, and their K partial
+// writes into the tile's [N,K,3] / [N,K] lines (12 and 4 bytes at a stride of 12 K and 4 K) merge in that XCD's L2
+// before they leave it.  (A (shell, tile) grid put the K workgroups on K different XCDs, each L2 writing its partial
+// line back by itself: at 1920x1080, K = 7 the launch wrote 0.98 GB for 0.30 GB of outputs; a (tile, shell) grid
+// 1.22 GB.)
 struct ShadeIdx {
   long long tile;
   int shell;
   bool valid;
 };
 __device__ __forceinline__ ShadeIdx shade_idx(int K, int tiles) {
-#if NT_SHADE_MAP == 2
   const unsigned id = blockIdx.x, x = id & 7u, q = id >> 3;
   const unsigned s = q % (unsigned)K, tg = q / (unsigned)K;
   const long long t = (long long)tg * 8 + x;
   return {t, (int)s, t < tiles};
-#elif NT_SHADE_MAP == 1
-  return {(long long)blockIdx.y, (int)blockIdx.x, true};
-#else
-  return {(long long)blockIdx.x, (int)blockIdx.y, true};
-#endif
 }
 static inline dim3 shade_grid(int tiles, int shells) {
-#if NT_SHADE_MAP == 2
   return dim3((unsigned)(((tiles + 7) / 8) * 8 * shells));
-#elif NT_SHADE_MAP == 1
-  return dim3(shells, tiles);
-#else
-  return dim3(tiles, shells);
-#endif
 }
 
 namespace {
@@ -337,7 +321,7 @@ __global__ __launch_bounds__(SH_BLOCK, NT_SHADE_FWD_OCC) void nt_shade_fwd_kerne
   build_lut(plan, s_lut);
   __syncthreads();
   const int K = plan.nr_shells;
-  const ShadeIdx wi = shade_idx(K, (N + SH_BLOCK - 1) / SH_BLOCK);      // (shell, ray tile), XCD-aware: see NT_SHADE_MAP
+  const ShadeIdx wi = shade_idx(K, (N + SH_BLOCK - 1) / SH_BLOCK);      // (shell, ray tile), XCD-aware: see shade_idx
   const long long n = wi.tile * SH_BLOCK + threadIdx.x;
   const int s = wi.shell;
   if (!wi.valid) return;
@@ -413,9 +397,6 @@ __device__ __forceinline__ void atomic_pk_add_f16(const _Float16* base, unsigned
   asm volatile("global_atomic_pk_add_f16 %0, %1, %2" ::"v"(byte_off), "v"(__builtin_bit_cast(unsigned, v)), "s"(base) : "memory");
 }
 
-#ifndef NT_SHB_PREFETCH
-#define NT_SHB_PREFETCH 1
-#endif
 template <bool RECOMPUTE, bool FULL4, bool F16ROWS = false>
 #ifndef NT_SHADE_BWD_OCC
 #define NT_SHADE_BWD_OCC 4
@@ -539,7 +520,6 @@ __global__ __launch_bounds__(SHB_BLOCK, RECOMPUTE ? 2 : NT_SHADE_BWD_OCC) void n
   float2_t acc[4] = {float2_t(0.f), float2_t(0.f), float2_t(0.f), float2_t(0.f)};
   const unsigned lofs_b = 2u * (unsigned)lofs;
   unsigned long long rem = hits;
-#if NT_SHB_PREFETCH
   // the eight LDS values a lane needs of a hit are read one hit ahead of their use
   struct HitIn { float g0, g1, b0, b1, fx, fy; int r0, r1; };
   auto fetch = [&](int ht) {
@@ -550,38 +530,23 @@ __global__ __launch_bounds__(SHB_BLOCK, RECOMPUTE ? 2 : NT_SHADE_BWD_OCC) void n
     return r;
   };
   HitIn nx = fetch(wbase + (rem ? __ffsll((long long)rem) - 1 : 0));
-#endif
   while (rem) {
     const int hl = __ffsll((long long)rem) - 1;
     rem &= rem - 1;
-    const int ht = wbase + hl;
-#if NT_SHB_PREFETCH
     const HitIn cu = nx;
     nx = fetch(wbase + (rem ? __ffsll((long long)rem) - 1 : hl));
-    (void)ht;
-#endif
     if (band_on) {
       float2_t gg;
-#if NT_SHB_PREFETCH
       gg.x = cu.g0 * cu.b0;
       gg.y = on1 ? cu.g1 * cu.b1 : 0.f;
       const float fx = cu.fx, fy = cu.fy;
-#else
-      gg.x = s_graw[ht][ch0] * s_basis[ht][m0];
-      gg.y = on1 ? s_graw[ht][ch1] * s_basis[ht][m1] : 0.f;
-      const float fx = s_f[ht][2 * d], fy = s_f[ht][2 * d + 1];
-#endif
       // the lerp weights exactly as load_ctx forms them, then x span, then x g
       const float w[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
       int sl[4];
       float wl[4];
 #pragma unroll
       for (int y = 0; y < 2; ++y) {
-#if NT_SHB_PREFETCH
         const int ra = y ? cu.r1 : cu.r0, rb = ra + qd;              // the x0 and x1 corner rows (quads)
-#else
-        const int ra = s_row[ht][2 * d + y], rb = ra + qd;           // the x0 and x1 corner rows (quads)
-#endif
         const int la = ra >> 3, lbn = rb >> 3;                        // their lines (8 quads of 8 B)
         const bool ma = q == ((ra & 7) >> qsh), mb = q == ((rb & 7) >> qsh), one = la == lbn;
         sl[2 * y] = la;

@@ -167,85 +167,10 @@ __global__ __launch_bounds__(1024) void nt_scan_blocks_kernel(vsa_nt_plan plan,
   }
 }
 
-// pass C: slot_of[texel], texel_of_slot[slot], slot_xy[slot].  One thread per 4 texels
-// (1024 threads = one 4096-texel domain block): the marks come in as one dword and
-// slot_of goes out as one int4 per lane, i.e. every wave instruction moves a contiguous
-// 256 B / 1 KiB (16 texels per thread made each store touch 64 lines at 16 B).
-// SPARSE (vsa_nt_compact_frame): slot_of is only written where a texel is marked (nothing reads the
-// slot of an untouched texel: 112 MB of -1 per 800x800 frame otherwise), the marks are cleared on the
-// way (the next frame needs no 28 MB fill), texel_of_slot is optional.
-template <bool SPARSE>
-__global__ __launch_bounds__(1024) void nt_assign_kernel(vsa_nt_plan plan,
-                                                         unsigned* __restrict__ marks,
-                                                         const int* __restrict__ block_prefix,
-                                                         int4* __restrict__ slot_of,
-                                                         int* __restrict__ texel_of_slot,
-                                                         float2* __restrict__ slot_xy,
-                                                         long long slot_capacity) {
-  __shared__ int s_w[16];
-  // an untouched block (a training batch touches a few per cent of the 28 M texels; the back of every
-  // shell is never seen): no marks to clear, no slot to write
-  if (SPARSE && block_prefix[blockIdx.x + 1] == block_prefix[blockIdx.x]) return;
-  // the (shell, degree) domain this block lies in (domains are block aligned)
-  const long long blk0 = (long long)blockIdx.x * NT_DOM_BLOCK;
-  int sd = 0;
-  const int nseg = plan.nr_shells * VSA_NT_MAX_DEG;
-  while (sd + 1 < nseg && plan.dom_off[sd + 1] <= blk0) ++sd;
-  const int R = plan.tex_res[sd % VSA_NT_MAX_DEG], W = R + 2;
-  const float Rf = (float)R, inv_R = 1.0f / Rf;
-  const bool pow2 = (R & (R - 1)) == 0;
-  const long long dom0 = plan.dom_off[sd];
-  const long long vec = (long long)blockIdx.x * 1024 + threadIdx.x;   // 4-texel group
-  const unsigned word = marks[vec] & 0x01010101u;
-  const int c = __popc(word);
-  // exclusive scan across the 1024 threads (PMC had this kernel 59 % VALU-busy: the wave scan as six
-  // ds_bpermute steps and a generic 32-bit division per thread; now a DPP scan and a float-reciprocal
-  // quotient, exact below 2^24, with one correction step)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int incl = nt_wave_incl_scan(c);
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  // the waves in front of this one: a 16-lane scan of the wave totals (up to 15 dependent LDS reads and adds before)
-  const int wtot = nt_wave_incl_scan(lane < 16 ? s_w[lane] : 0);
-  const int before = wave ? __builtin_amdgcn_readlane(wtot, (wave - 1) & 15) : 0;
-  int slot = block_prefix[blockIdx.x] + incl - c + before;
-  int out[4];
-  const int local0 = (int)(vec * 4 - dom0);
-  int iy, ix;
-  if (local0 < (1 << 24)) {      // (R + 2)^2 <= 2^24 up to R = 4094: exact in fp32, off by at most one row
-    iy = (int)((float)local0 * (1.0f / (float)W));
-    ix = local0 - iy * W;
-    if (ix < 0) --iy, ix += W;
-    else if (ix >= W) ++iy, ix -= W;
-  } else {
-    iy = local0 / W;
-    ix = local0 - iy * W;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bool m = (word >> (8 * i)) & 1u;
-    out[i] = m ? slot : -1;
-    if (m) {
-      if (slot < slot_capacity) {
-        if (!SPARSE || texel_of_slot) texel_of_slot[slot] = (int)(vec * 4 + i);
-        // texel centre, normalised exactly like normalize_uv_coord(corner) in the reference.  A power-of-two R
-        // (every shipped configuration): the quotient is an exact scaling, i.e. the same bits as a product with
-        // 1 / R — two IEEE divisions per marked texel were most of this kernel's vector work
-        const float cx = (float)(ix - 1) + 0.5f, cy = (float)(iy - 1) + 0.5f;
-        slot_xy[slot] = pow2 ? make_float2(cx * inv_R, cy * inv_R) : make_float2(cx / Rf, cy / Rf);
-      }
-      ++slot;
-    }
-    if (++ix == W) {
-      ix = 0;
-      ++iy;
-    }
-  }
-  if (!SPARSE || word) slot_of[vec] = make_int4(out[0], out[1], out[2], out[3]);
-  if (SPARSE && word) marks[vec] = 0;
-}
-
-// The SPARSE pass C with ONE WAVE per 4096-texel block (vsa_nt_compact_frame): a block is one dependent chain —
+// pass C: slot_of[texel], texel_of_slot[slot] (optional), slot_xy[slot].  slot_of is only written where a texel is
+// marked (nothing reads the slot of an untouched texel: 112 MB of -1 per 800x800 frame otherwise), and the marks are
+// cleared on the way (the next frame needs no 28 MB fill).
+// ONE WAVE per 4096-texel block: a block is one dependent chain —
 // prefix + marks in, scan, slots out — and with a 1024-thread workgroup per block only 2 chains per CU are in
 // flight: 48 us for the 6.8 k blocks of a training batch (~115 marks per block), 3.6 us per block on a CU, all of
 // it round trips (rocprofv3, profiles/r06/train_graph_timeline.txt; several blocks per workgroup one after the
@@ -287,7 +212,7 @@ __global__ __launch_bounds__(256) void nt_assign_wave_kernel(vsa_nt_plan plan, u
     const long long vec = vec0 + 64 * k;
     const int local0 = (int)(vec * 4 - dom0);
     int iy, ix;
-    if (local0 < (1 << 24)) {      // exact in fp32, off by at most one row (as nt_assign_kernel)
+    if (local0 < (1 << 24)) {      // (R + 2)^2 <= 2^24 up to R = 4094: exact in fp32, off by at most one row
       iy = (int)((float)local0 * inv_W);
       ix = local0 - iy * W;
       if (ix < 0) --iy, ix += W;
@@ -304,6 +229,9 @@ __global__ __launch_bounds__(256) void nt_assign_wave_kernel(vsa_nt_plan plan, u
       if (m) {
         if (slot < slot_capacity) {
           if (texel_of_slot) texel_of_slot[slot] = (int)(vec * 4 + i);
+          // texel centre, normalised exactly like normalize_uv_coord(corner) in the reference.  A power-of-two R
+          // (every shipped configuration): the quotient is an exact scaling, i.e. the same bits as a product with
+          // 1 / R, without two IEEE divisions per marked texel
           const float cx = (float)(ix - 1) + 0.5f, cy = (float)(iy - 1) + 0.5f;
           slot_xy[slot] = pow2 ? make_float2(cx * inv_R, cy * inv_R) : make_float2(cx / Rf, cy / Rf);
         }
@@ -360,40 +288,22 @@ extern "C" int vsa_nt_mark(const vsa_nt_plan* plan, const int32_t* hit_slot, con
   VSA_RETURN_LAUNCH_STATUS();
 }
 
-static int nt_compact(const vsa_nt_plan* plan, uint8_t* marks, int32_t* slot_of, int32_t* texel_of_slot,
-                      float* slot_xy, int32_t* seg_start, int32_t* block_scratch, bool sparse, void* stream) {
+extern "C" int vsa_nt_compact_frame(const vsa_nt_plan* plan, uint8_t* marks, int32_t* slot_of,
+                                    int32_t* texel_of_slot, float* slot_xy, int32_t* seg_start,
+                                    int32_t* block_scratch, void* stream) {
   int rc = plan_check(plan);
   if (rc) return rc;
-  if (!marks || !slot_of || (!texel_of_slot && !sparse) || !slot_xy || !seg_start || !block_scratch)
-    return VSA_ERR_ARG;
+  if (!marks || !slot_of || !slot_xy || !seg_start || !block_scratch) return VSA_ERR_ARG;
   const long long total = plan->dom_off[plan->nr_shells * VSA_NT_MAX_DEG];
   const int nr_blocks = (int)(total / NT_DOM_BLOCK);
   if (nr_blocks == 0) return VSA_OK;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(nt_count_kernel, dim3(nr_blocks), dim3(256), 0, st,
                      reinterpret_cast<const uint4*>(marks), block_scratch);
-  hipLaunchKernelGGL(nt_scan_blocks_kernel, dim3(sparse && plan->balance ? 1 + NT_BAL_KERNELS : 1), dim3(1024), 0, st,
+  hipLaunchKernelGGL(nt_scan_blocks_kernel, dim3(plan->balance ? 1 + NT_BAL_KERNELS : 1), dim3(1024), 0, st,
                      *plan, block_scratch, nr_blocks, seg_start);
-  if (sparse)
-    hipLaunchKernelGGL(nt_assign_wave_kernel, dim3(vsa_div_up(nr_blocks, 4)), dim3(256), 0, st, *plan,
-                       reinterpret_cast<unsigned*>(marks), block_scratch, reinterpret_cast<int4*>(slot_of),
-                       texel_of_slot, reinterpret_cast<float2*>(slot_xy), (long long)plan->slot_capacity, nr_blocks);
-  else
-    hipLaunchKernelGGL(nt_assign_kernel<false>, dim3(nr_blocks), dim3(1024), 0, st, *plan,
-                       reinterpret_cast<unsigned*>(marks), block_scratch, reinterpret_cast<int4*>(slot_of),
-                       texel_of_slot, reinterpret_cast<float2*>(slot_xy), (long long)plan->slot_capacity);
+  hipLaunchKernelGGL(nt_assign_wave_kernel, dim3(vsa_div_up(nr_blocks, 4)), dim3(256), 0, st, *plan,
+                     reinterpret_cast<unsigned*>(marks), block_scratch, reinterpret_cast<int4*>(slot_of),
+                     texel_of_slot, reinterpret_cast<float2*>(slot_xy), (long long)plan->slot_capacity, nr_blocks);
   VSA_RETURN_LAUNCH_STATUS();
-}
-
-extern "C" int vsa_nt_compact(const vsa_nt_plan* plan, const uint8_t* marks, int32_t* slot_of,
-                              int32_t* texel_of_slot, float* slot_xy, int32_t* seg_start,
-                              int32_t* block_scratch, void* stream) {
-  return nt_compact(plan, const_cast<uint8_t*>(marks), slot_of, texel_of_slot, slot_xy, seg_start, block_scratch,
-                    false, stream);
-}
-
-extern "C" int vsa_nt_compact_frame(const vsa_nt_plan* plan, uint8_t* marks, int32_t* slot_of,
-                                    int32_t* texel_of_slot, float* slot_xy, int32_t* seg_start,
-                                    int32_t* block_scratch, void* stream) {
-  return nt_compact(plan, marks, slot_of, texel_of_slot, slot_xy, seg_start, block_scratch, true, stream);
 }

@@ -906,13 +906,7 @@ struct TraceCoopConfig {
   long long max_waves;
 };
 static TraceCoopConfig& trace_coop_config() {
-  static TraceCoopConfig cfg = [] {
-    TraceCoopConfig c{TRACE_COOP_CHUNK, TRACE_COOP_LANES, TRACE_COOP_WAVES};
-    if (const char* e = getenv("VSA_TRACE_COOP")) sscanf(e, "%d,%d", &c.chunk, &c.lanes);
-    if (const char* e = getenv("VSA_TRACE_COOP_WAVES")) c.max_waves = atoll(e);
-    if (c.chunk < 1 || c.lanes < 0 || c.lanes > TRACE_BLOCK || c.max_waves < 0) c = TraceCoopConfig{TRACE_COOP_CHUNK, TRACE_COOP_LANES, TRACE_COOP_WAVES};
-    return c;
-  }();
+  static TraceCoopConfig cfg{TRACE_COOP_CHUNK, TRACE_COOP_LANES, TRACE_COOP_WAVES};
   return cfg;
 }
 extern "C" int vsa_trace_coop_config(int chunk, int lanes, long long max_waves) {

@@ -273,10 +273,6 @@ class VolSurfs(torch.nn.Module):
             self.optimizer.gather_masters()      # sharded Adam: fp32 masters are per-slice until gathered
 
     legacy_grouped = True     # class-wide switch: False = the per-shell loop (tests compare the two)
-    legacy_fused_step = __import__("os").environ.get("VSA_LEGACY_FUSED_STEP", "1") != "0"   # trainer: no autograd at all
-    legacy_two_streams = __import__("os").environ.get("VSA_LEGACY_TWO_STREAMS", "1") != "0"  # ... colour / alpha chains side by side
-    legacy_fused_glue = __import__("os").environ.get("VSA_LEGACY_FUSED_GLUE", "1") != "0"   # grouped path: hit preparation,
-    # sigmoid / decay / scatter and (forward()) composite + L1 as one launch each instead of torch expressions
 
     def _legacy_groupable(self, x_probe):
         """The grouped path covers the configuration BASELINE configs[2] trains: every model an `RGB`
@@ -304,9 +300,6 @@ class VolSurfs(torch.nn.Module):
         from .models import fused_mlp_grouped
         N, K = rays_o.shape[0], self.nr_meshes
         dev = rays_o.device
-
-        def dense_zeros():
-            return torch.zeros(N, K, 3, device=dev), torch.zeros(N, K, device=dev), torch.zeros(N, K, 3, device=dev)
         if ahead is not None:          # compacted when the traversal was queued (trace_ahead)
             counts = ahead.counts()
             M = int(sum(counts))
@@ -316,28 +309,20 @@ class VolSurfs(torch.nn.Module):
             counts = torch.bincount(shell_of, minlength=K).tolist()
             M = int(sum(counts))
         if M == 0:
-            return dense_zeros()
+            return torch.zeros(N, K, 3, device=dev), torch.zeros(N, K, device=dev), torch.zeros(N, K, 3, device=dev)
         begin = [0]
         for c in counts:
             begin.append(begin[-1] + c)
-        fused_glue = VolSurfs.legacy_fused_glue
-        if fused_glue:
-            # the hits' points, directions and face normals in one launch (18 torch launches otherwise)
-            # (torch.nonzero lays its [n, 2] result out column by column: the two columns are contiguous as they are)
-            shell_of, ray_of = shell_of.contiguous(), ray_of.contiguous()
-            pts, d, nrm = (torch.empty(M, 3, device=dev) for _ in range(3))
-            _lib.call("vsa_legacy_hit_prep", rays_o, rays_d, hit_t, hit_slot, self.raytracer.tris, shell_of, ray_of, M, N,
-                      pts, d, nrm, _lib.stream_ptr())
-        else:
-            slots = hit_slot[shell_of, ray_of].long()
-            tri = self.raytracer.tris[slots]
-            nrm = torch.nn.functional.normalize(torch.cross(tri[:, 4:7], tri[:, 8:11], dim=1), dim=1)
-            d = rays_d[ray_of]
-            pts = rays_o[ray_of] + hit_t[shell_of, ray_of][:, None] * d
+        # the hits' points, directions and face normals in one launch (18 torch launches otherwise)
+        # (torch.nonzero lays its [n, 2] result out column by column: the two columns are contiguous as they are)
+        shell_of, ray_of = shell_of.contiguous(), ray_of.contiguous()
+        pts, d, nrm = (torch.empty(M, 3, device=dev) for _ in range(3))
+        _lib.call("vsa_legacy_hit_prep", rays_o, rays_d, hit_t, hit_slot, self.raytracer.tris, shell_of, ray_of, M, N,
+                  pts, d, nrm, _lib.stream_ptr())
 
         def evaluate(typ, indep, first_shell):
-            """sigmoid(MLP(cat(pos enc, dir enc, normals))) for the hits of shells >= first_shell (fused glue: the
-            MLP's output; the sigmoid is taken in _LegacyShadeOut)."""
+            """MLP(cat(pos enc, dir enc, normals)) for the hits of shells >= first_shell (the sigmoid is taken in
+            _LegacyShadeOut)."""
             a0 = begin[first_shell]
             if a0 == M:
                 return None
@@ -364,7 +349,7 @@ class VolSurfs(torch.nn.Module):
                 n_enc = enc.shape[1]
                 tape[typ] = lambda gy: enc_bwd(mlp_bwd(gy)[:, :n_enc])
                 return y
-            if VolSurfs.legacy_grouped_encode and len(mods) > 1 and permuto_hash_encoders_groupable(pos_encs, pts):
+            if len(mods) > 1 and permuto_hash_encoders_groupable(pos_encs, pts):
                 # one autograd node for all shells' position encodings (encodings._PermutoEncodeGrouped)
                 parts = [permuto_hash_encode_grouped(pos_encs, pts[a0:], sizes, iter_nr=iter_nr)]
             else:
@@ -380,64 +365,42 @@ class VolSurfs(torch.nn.Module):
                     parts.append(m0.dir_encoder(d[a0:], iter_nr=iter_nr))
             if m0.normal_dep:
                 parts.append(nrm[a0:])
-            y = fused_mlp_grouped([mod.mlp for mod in mods], torch.cat(parts, 1), sizes)
-            return y if fused_glue else torch.sigmoid(y)
+            return fused_mlp_grouped([mod.mlp for mod in mods], torch.cat(parts, 1), sizes)
         first = 1 if self.solid_inner else 0
         has_alpha = any(k.split("_")[0] == "alpha" for k in self.models)
-        if fused_glue:
-            two = tape is not None and has_alpha and VolSurfs.legacy_two_streams
-            if two:
-                # the colour and the alpha models are independent chains of small launches (49 k rows in ten groups
-                # fill the chip only in part): the alpha chain on a side stream beside the colour chain
-                side = getattr(self, "_alpha_stream", None)
-                if side is None:
-                    side = self._alpha_stream = torch.cuda.Stream(device=dev)
-                main = torch.cuda.current_stream()
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    y_alpha = evaluate("alpha", self.alphas_indep, first)
-                y_rgb = evaluate("rgb", self.colors_indep, 0)
-                main.wait_stream(side)
-                if y_alpha is not None:
-                    y_alpha.record_stream(main)
-                tape["side"] = side
-            else:
-                y_rgb = evaluate("rgb", self.colors_indep, 0)
-                y_alpha = evaluate("alpha", self.alphas_indep, first) if has_alpha else None
-            if tape is not None:
-                from .encodings import ManualCtx
-                ctx = ManualCtx()
-                out = _LegacyShadeOut.forward(ctx, y_rgb, y_alpha, shell_of, ray_of, d, nrm, N, K, begin[first],
-                                              bool(self.with_alpha_decay))
-                tape["out"] = lambda g_rgb, g_alpha: _LegacyShadeOut.backward(ctx, g_rgb, g_alpha, None)[:2]
-                return out
-            return _LegacyShadeOut.apply(y_rgb, y_alpha, shell_of, ray_of, d, nrm, N, K, begin[first],
-                                         bool(self.with_alpha_decay))
-        surfs_rgb, surfs_alpha, surfs_normals = dense_zeros()
-        pred = evaluate("rgb", self.colors_indep, 0)
-        surfs_rgb = surfs_rgb.index_put((ray_of, shell_of), pred[:, :3])
-        alpha = torch.ones(M, device=dev)
-        if has_alpha:
-            pa = evaluate("alpha", self.alphas_indep, first)
-            if pa is not None:
-                av = pa[:, 0]
-                if self.with_alpha_decay:
-                    with torch.no_grad():
-                        dot = torch.sum(-d[begin[first]:] * nrm[begin[first]:], dim=1).clamp(0.0, 1.0)
-                        decay = torch.sigmoid(10.0 * dot) * 2.0 - 1.0
-                    av = av * decay
-                alpha = torch.cat([alpha[:begin[first]], av]) if begin[first] else av
-        surfs_alpha = surfs_alpha.index_put((ray_of, shell_of), alpha)
-        surfs_normals = surfs_normals.index_put((ray_of, shell_of), nrm)
-        return surfs_rgb, surfs_alpha, surfs_normals
+        if tape is not None and has_alpha:
+            # the colour and the alpha models are independent chains of small launches (49 k rows in ten groups
+            # fill the chip only in part): the alpha chain on a side stream beside the colour chain
+            side = getattr(self, "_alpha_stream", None)
+            if side is None:
+                side = self._alpha_stream = torch.cuda.Stream(device=dev)
+            main = torch.cuda.current_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                y_alpha = evaluate("alpha", self.alphas_indep, first)
+            y_rgb = evaluate("rgb", self.colors_indep, 0)
+            main.wait_stream(side)
+            if y_alpha is not None:
+                y_alpha.record_stream(main)
+            tape["side"] = side
+        else:
+            y_rgb = evaluate("rgb", self.colors_indep, 0)
+            y_alpha = evaluate("alpha", self.alphas_indep, first) if has_alpha else None
+        if tape is not None:
+            from .encodings import ManualCtx
+            ctx = ManualCtx()
+            out = _LegacyShadeOut.forward(ctx, y_rgb, y_alpha, shell_of, ray_of, d, nrm, N, K, begin[first],
+                                          bool(self.with_alpha_decay))
+            tape["out"] = lambda g_rgb, g_alpha: _LegacyShadeOut.backward(ctx, g_rgb, g_alpha, None)[:2]
+            return out
+        return _LegacyShadeOut.apply(y_rgb, y_alpha, shell_of, ray_of, d, nrm, N, K, begin[first],
+                                     bool(self.with_alpha_decay))
 
     def supports_fused_legacy_step(self, rays_o, gt_mask=None, is_training_masked=False):
         """The legacy branch's training step without autograd (fused_legacy_forward / _backward): the configuration
         the grouped launches cover (BASELINE configs[2]), constant background, unmasked L1, every model's encoder a
         groupable permutohedral one."""
-        if (self.using_neural_textures or not (VolSurfs.legacy_fused_glue and VolSurfs.legacy_grouped
-                                               and VolSurfs.legacy_grouped_encode and VolSurfs.legacy_fused_step)
-                or self.bg_color is None or (is_training_masked and gt_mask is not None)
+        if (self.using_neural_textures or not VolSurfs.legacy_grouped or self.bg_color is None or (is_training_masked and gt_mask is not None)
                 or rays_o.shape[0] > self.max_rays or not self._legacy_groupable(rays_o)):
             return False
         from .encodings import permuto_hash_encoders_groupable
@@ -538,9 +501,7 @@ class VolSurfs(torch.nn.Module):
             surfs_normals = surfs_normals.index_put((rows, col), nrm)
         return surfs_rgb, surfs_alpha, surfs_normals
 
-    legacy_grouped_encode = __import__("os").environ.get("VSA_GROUPED_ENCODE", "1") != "0"   # A/B switch
     look_ahead = True      # trainer.train_step_from_reel queues the next batch's traversal a step ahead (legacy models)
-    look_ahead_stream = __import__("os").environ.get("VSA_LOOK_AHEAD_STREAM", "1") != "0"   # ... on a side stream
 
     class _TraceAhead:
         """The traversal and hit compaction of a batch, queued ahead of time (trace_ahead)."""
@@ -557,7 +518,7 @@ class VolSurfs(torch.nn.Module):
             self._joined = False
 
         def join(self):
-            """Built on a side stream (trace_ahead with look_ahead_stream): the consumer's stream waits for it once,
+            """Built on a side stream (trace_ahead): the consumer's stream waits for it once,
             and the allocator is told that the context's arrays are now in use there."""
             if self._joined:
                 return
@@ -594,13 +555,6 @@ class VolSurfs(torch.nn.Module):
         no parameter, so the order does not matter).  No sync in here: `nonzero_static` over the
         whole [K, N] mask, padded."""
         rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
-        if not VolSurfs.look_ahead_stream:
-            hit = self.raytracer.trace_all(rays_o, rays_d)
-            mask = hit[1] >= 0
-            idx = torch.nonzero_static(mask, size=mask.numel(), fill_value=0)
-            ctx = VolSurfs._TraceAhead(rays_o, rays_d, hit, idx, mask.sum(1))
-            ctx._joined = True
-            return ctx
         # on a side stream: the traversal of a training batch is one long latency chain on a nearly empty chip
         # (profiles/NOTEBOOK.md round 5) — beside this batch's backward pass it costs the step nothing
         side = getattr(self, "_ahead_stream", None)
@@ -778,7 +732,7 @@ class VolSurfs(torch.nn.Module):
         the caller has no use for them."""
         self._warmup_scheduler(is_first_iter)                                   # :774-783
         want_samples = return_samples and (ahead is None or self.using_neural_textures)
-        if (VolSurfs.legacy_fused_glue and VolSurfs.legacy_grouped and not self.using_neural_textures and not want_samples
+        if (VolSurfs.legacy_grouped and not self.using_neural_textures and not want_samples
                 and self.bg_color is not None and not (is_training_masked and gt_mask is not None)
                 and rays_o.shape[0] <= self.max_rays and self._legacy_groupable(rays_o)):
             # the legacy training step with its glue fused (BASELINE configs[2]): traversal (or the look-ahead

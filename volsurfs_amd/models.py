@@ -203,8 +203,6 @@ def _direct_grads(params):
 
 
 MLP_MAX_GROUPS = 8
-_NO_CACHE = __import__("os").environ.get("VSA_NO_DESC_CACHE", "0") == "1"     # A/B switch
-
 
 class _FusedMLPGrouped(torch.autograd.Function):
     """G MLPs of ONE architecture (the per-shell models of the legacy appearance branch) applied to
@@ -236,7 +234,7 @@ class _FusedMLPGrouped(torch.autograd.Function):
         key = (tuple(map(id, params)), nl, has_bias)
         ptrs = tuple(p_.data_ptr() for p_ in params)
         hit = _FusedMLPGrouped._desc_cache.get(key)
-        if hit is None or hit[0] != ptrs or _NO_CACHE:
+        if hit is None or hit[0] != ptrs:
             per = nl * (2 if has_bias else 1)
             groups = []
             for g in range(G):
@@ -321,7 +319,7 @@ class _FusedMLPGrouped(torch.autograd.Function):
         # gradient pointer tables: kept while the target buffers stay where they are (persistent .grad)
         tptrs = tuple(t.data_ptr() for t in targets)
         got = grad_cache.get(direct is not None)
-        if got is None or got[0] != tptrs or _NO_CACHE:
+        if got is None or got[0] != tptrs:
             per = nl * (2 if has_bias else 1)
             tables = []
             for g0 in range(0, G, MLP_MAX_GROUPS):

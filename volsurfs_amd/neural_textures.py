@@ -32,7 +32,6 @@ WEIGHTS_PER_TEX = 8192
 # work split of the persistent kernels corrected by the previous frame's measured workgroup times
 # (vsa_nt_rebalance; same results); "0" = the fitted cost model alone
 REBALANCE = os.environ.get("VSA_NT_REBALANCE", "1") != "0"
-_DENSE_COMPACT = os.environ.get("VSA_NT_DENSE_COMPACT", "0") == "1"    # A/B switch: rounds 1-2's fill + dense slot_of
 FUSED_FORWARD = {"0": False, "1": True}.get(os.environ.get("VSA_NT_FUSED", "auto"), "auto")
 
 class Plan(ctypes.Structure):
@@ -230,21 +229,15 @@ class NeuralTextureBank(torch.nn.Module):
             raise _lib.VolsurfsHipError("this bank holds baked textures: use tex_uv_only + shade")
         st = _lib.stream_ptr()
         tex_uv = torch.empty(K, N, 2, device=hit_slot.device)
-        if self.plan.balance and _DENSE_COMPACT:     # (vsa_nt_compact_frame rebalances inside its scan launch)
-            _lib.call("vsa_nt_rebalance", ctypes.byref(self.plan), st)
         # Invariant: the marks are zero between frames — allocated so, and vsa_nt_compact_frame clears
         # what it reads.  `_marks_dirty` is set while a mark has not been followed by a compaction that
-        # returned OK (an exception between the two, a failed launch, the dense vsa_nt_compact, which
-        # does not clear): stale marks would silently inflate every later frame's slot counts.
-        if _DENSE_COMPACT or getattr(self, "_marks_dirty", False):
+        # returned OK (an exception between the two, a failed launch): stale marks would silently
+        # inflate every later frame's slot counts.
+        if getattr(self, "_marks_dirty", False):
             self.marks.zero_()
         self._marks_dirty = True
         _lib.call("vsa_nt_mark", ctypes.byref(self.plan), hit_slot, hit_uv, face_uvs, N, tex_uv,
                   self.marks, st)
-        if _DENSE_COMPACT:
-            _lib.call("vsa_nt_compact", ctypes.byref(self.plan), self.marks, self.slot_of,
-                      self.texel_of_slot, self.slot_xy, self.seg_start, self.block_scratch, st)
-            return tex_uv                  # (marks stay dirty: the next frame zeroes them)
         _lib.call("vsa_nt_compact_frame", ctypes.byref(self.plan), self.marks, self.slot_of,
                   self.texel_of_slot if want_texel_of_slot else None, self.slot_xy, self.seg_start,
                   self.block_scratch, st)
@@ -275,10 +268,9 @@ class NeuralTextureBank(torch.nn.Module):
                                                 "(max_rays >= NeuralTextureBank.full_capacity_rays)")
                 off = int(self.plan.dom_off[s * MAX_DEG + d])
                 self.marks[off:off + W * W].view(W, W).fill_(1)   # interior + the one-texel apron
-        _lib.call("vsa_nt_compact", ctypes.byref(self.plan), self.marks, self.slot_of,
+        _lib.call("vsa_nt_compact_frame", ctypes.byref(self.plan), self.marks, self.slot_of,
                   self.texel_of_slot, self.slot_xy, self.seg_start, self.block_scratch,
                   _lib.stream_ptr())
-        self.marks.zero_()
         self.evaluate(need_features=False)
         self.baked = True
         return self

@@ -12,7 +12,6 @@ iteration.  Gradients therefore live in persistent buffers (`p.grad` is allocate
 set to None): `zero_grad()` is free after a `step()`.
 """
 import ctypes
-import os
 import weakref
 
 import torch
@@ -24,9 +23,6 @@ class AdamTensor(ctypes.Structure):
     """Mirror of `vsa_adam_tensor` (include/volsurfs_hip.h)."""
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
                 ("exp_avg_sq", ctypes.c_void_p), ("param_f16", ctypes.c_void_p), ("n", ctypes.c_int64)]
-
-
-_NO_CACHE = __import__("os").environ.get("VSA_NO_DESC_CACHE", "0") == "1"     # A/B switch
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -65,7 +61,7 @@ class FusedAdam(torch.optim.Optimizer):
         # sit where they sat; the full pointer-level check below runs every 64th step and whenever one of these differs.  (Four data_ptr() calls
         # per parameter and step were 0.2 ms of host time with the 90 tensors of BASELINE configs[2].)
         cur = self._plans.get(gi)
-        if cur is not None and not _NO_CACHE:
+        if cur is not None:
             self._plan_age[gi] = self._plan_age.get(gi, 0) + 1
             if self._plan_age[gi] % 64:
                 state = self.state
@@ -144,7 +140,7 @@ class FusedAdam(torch.optim.Optimizer):
     def _dirty_hook(self, _param):
         self._grads_clean = False
 
-    shared_workgroups = int(os.environ.get("VSA_ADAM_SHARED_WGS", "512"))   # step(stream=...): grid of the side-stream launch
+    shared_workgroups = 512   # step(stream=...): grid of the side-stream launch
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0, stream=None):

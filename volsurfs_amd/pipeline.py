@@ -89,10 +89,9 @@ class KShellPipeline:
         self.tracer = RayTracer(meshes) if tracer is None else tracer
         self.rays_o, self.rays_d, self.gt = rays_o, rays_d, gt_rgb
         self.nr_rays = rays_o.shape[0]
-        import os
         self.image_hw = None
         if image_hw is not None and image_hw[0] % 8 == 0 and image_hw[1] % 8 == 0 and \
-                image_hw[0] * image_hw[1] == self.nr_rays and os.environ.get("VSA_TILE_ORDER", "1") != "0":
+                image_hw[0] * image_hw[1] == self.nr_rays:
             self.image_hw = (int(image_hw[0]), int(image_hw[1]))
             self._o_t, self._d_t, self._gt_t = (torch.empty_like(x) for x in (rays_o, rays_d, gt_rgb))
             self._rgb_out = torch.empty_like(gt_rgb)

@@ -16,7 +16,7 @@ from . import _lib
 
 
 class RayTracer:
-    def __init__(self, tensor_meshes, leaf_size=None, node_format=None):
+    def __init__(self, tensor_meshes, leaf_size=4, node_format=None):
         """node_format: "q16" (default; binary 32-byte quantised nodes, vsa_trace_q / vsa_trace_q_fb) or
         "f32" (binary 64-byte fp32 nodes, vsa_trace); also selected by VSA_TRACE_NODES.  Both give
         identical hits; the quantised format assumes ray origins within ~60 mesh extents of the mesh
@@ -32,8 +32,6 @@ class RayTracer:
         if not 1 <= self.nr_meshes <= 16:
             raise _lib.VolsurfsHipError("RayTracer supports 1..16 meshes")
         L = _lib.lib()
-        if leaf_size is None:
-            leaf_size = int(os.environ.get("VSA_LEAF_SIZE", "4"))
         self._bvh, self._layout = [], []            # builder handles (kept for refit) and (node_base, nr_nodes, tri_base, nr_tris)
         self.mesh_tri_offset, self.mesh_nr_tris = [], []
         self.max_depth = 0
@@ -185,7 +183,7 @@ class RayTracer:
     # Measured on MI355X (tools/trace_narrow_ab.py, profiles/r06/trace_narrow_ab.txt): 34 000 random rays x 5 shells
     # 0.108 ms -> 0.132 (worse), 8 000 rays 0.080 -> 0.069 at 8 per wave: off by default, the hits do not depend on it
     NARROW_BELOW = int(os.environ.get("VSA_TRACE_NARROW_BELOW", "0"))
-    NARROW_RPW = int(os.environ.get("VSA_TRACE_RPW", "16"))
+    NARROW_RPW = 16
 
     @staticmethod
     def coop_config(chunk=16, lanes=24, max_waves=4096):
