@@ -138,6 +138,32 @@ int vsa_bvh_export_q(const vsa_bvh* bvh, uint32_t* qnodes_out, float* tris_out, 
 int vsa_bvh_refit(vsa_bvh* bvh, const float* verts, int nr_verts);
 int vsa_bvh_destroy(vsa_bvh* bvh);
 
+/* The same build on the GPU from the meshes' DEVICE arrays (csrc/bvh_device.hip): a Karras LBVH on 30-bit Morton
+ * codes of the triangle centroids, leaves of <= leaf_size (1..8) triangles, emitted in the layouts of vsa_bvh_export
+ * and vsa_bvh_export_q.  Replaces the host copy + vsa_bvh_build of raytracelib.RayTracer(tensor_meshes)
+ * (volsurfs_py/methods/volsurfs.py:128) where the shells already live on the device.  Closest hits through it are
+ * bit-identical to the host tree's (the boxes only prune); its SAH cost is higher.  The handle owns its device
+ * buffers (a copy of verts and faces among them) until vsa_bvh_dev_destroy.
+ * vsa_bvh_dev_build   verts [nv,3] f32, faces [nf,3] i32: DEVICE pointers; enqueued on `stream`, no sync.
+ *   VSA_ERR_ARG on null pointers or nr_verts / nr_faces <= 0 (before any HIP call).
+ * vsa_bvh_dev_sizes   synchronises the build; node / triangle counts and depth as vsa_bvh_sizes.
+ *   VSA_ERR_ARG when a face indexes outside the vertices, VSA_ERR_UNSUPPORTED when max_depth >= 48 (the
+ *   traversal's stack; use the host builder).  Call it once before the first export.
+ * vsa_bvh_dev_export  nodes_out [nr_nodes,16] f32, qnodes_out [nr_nodes,8] u32, tris_out [nr_tris,12] f32: DEVICE;
+ *   frame_out [6] [host] (vsa_trace_q takes host frames).  node_base / tri_base as vsa_bvh_export; synchronises
+ *   `stream` to hand back the frame.
+ * vsa_bvh_dev_refit   the vertices moved (same faces, same nr_verts, DEVICE pointer): triangle boxes, child boxes
+ *   and the q16 frame are recomputed on `stream`; leaf order (every triangle slot) is unchanged.  Re-export
+ *   afterwards.  Replaces re-running RayTracer(tensor_meshes) (volsurfs.py:82-128) when only positions changed. */
+typedef struct vsa_bvh_dev vsa_bvh_dev;
+int vsa_bvh_dev_build(const float* verts, const int32_t* faces, int nr_verts, int nr_faces, int leaf_size,
+                      void* stream, vsa_bvh_dev** out_bvh);
+int vsa_bvh_dev_sizes(const vsa_bvh_dev* bvh, int* nr_nodes, int* nr_tris, int* max_depth);
+int vsa_bvh_dev_export(const vsa_bvh_dev* bvh, float* nodes_out, uint32_t* qnodes_out, float* tris_out,
+                       int node_base, int tri_base, float* frame_out, void* stream);
+int vsa_bvh_dev_refit(vsa_bvh_dev* bvh, const float* verts, int nr_verts, void* stream);
+int vsa_bvh_dev_destroy(vsa_bvh_dev* bvh);
+
 /* vsa_trace: closest hit of every ray against each of nr_meshes BVHs in ONE
  * launch (grid.y = mesh).  mesh_roots [host, nr_meshes] = root node index of
  * each mesh in `nodes`; max_depth = deepest tree (must be < 48).

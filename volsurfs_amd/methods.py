@@ -126,8 +126,9 @@ class VolSurfs(torch.nn.Module):
                  are_volsurfs_colors_indep=True, are_volsurfs_alphas_indep=True, bb_sides=2.0,
                  lr_milestones=(100000, 150000, 180000, 190000), nr_warmup_iters=3000,
                  using_neural_textures_anchor=False, using_neural_textures_lerp=True,
-                 using_sh_quantization=True, using_sh_squeezing=True):
-        """using_neural_textures_anchor / _lerp, using_sh_quantization, using_sh_squeezing: the reference's
+                 using_sh_quantization=True, using_sh_squeezing=True, bvh_builder="host"):
+        """bvh_builder: RayTracer(builder=...): "host" (binned SAH on the CPU) or "device" (LBVH on the GPU; the same hits).
+        using_neural_textures_anchor / _lerp, using_sh_quantization, using_sh_squeezing: the reference's
         hyper-parameters of the same names (config/volsurfs/base_5.cfg:16-19 -> volsurfs.py:149-153); every
         combination the reference accepts is built, the ones it exits on raise in NeuralTextureBank.
         are_volsurfs_colors_indep / are_volsurfs_alphas_indep = 0 (volsurfs.py:159-165, 200-206): ONE colour / alpha
@@ -138,7 +139,7 @@ class VolSurfs(torch.nn.Module):
         self.tensor_meshes = tensor_meshes
         self.nr_meshes = len(tensor_meshes)
         dev = tensor_meshes[0].vertices.device
-        self.raytracer = RayTracer(tensor_meshes)                      # volsurfs.py:128
+        self.raytracer = RayTracer(tensor_meshes, builder=bvh_builder)  # volsurfs.py:128
         fu = []
         for m, off, n in zip(tensor_meshes, self.raytracer.mesh_tri_offset, self.raytracer.mesh_nr_tris):
             ids = self.raytracer.slot_face_id[off:off + n].long()

@@ -76,17 +76,18 @@ class KShellPipeline:
     dtype_desc = "f16 (hash features, MLP on MFMA, composite: as the reference), f32 accumulate and I/O"
 
     def __init__(self, meshes, rays_o, rays_d, gt_rgb, bg_color=(1.0, 1.0, 1.0), seed=42,
-                 init="tcnn", image_hw=None, tracer=None):
+                 init="tcnn", image_hw=None, tracer=None, bvh_builder="host"):
         """image_hw = (H, W): the rays are the row-major pixels of one full frame; every step
         then first re-orders them (and the ground truth) into 8x8-pixel tiles, so that a wave
         of any per-ray kernel covers a square patch, and returns the colours in the caller's
         order (vsa_tile_order; both passes are inside the step).
         tracer: a RayTracer already built over `meshes` (another pipeline's: the BVH of a 1.3 M-triangle
-        shell takes seconds to build) instead of building one."""
+        shell takes seconds to build on the host) instead of building one.
+        bvh_builder: RayTracer(builder=...) of the tracer built here: "host" or "device" (the same hits)."""
         from .neural_textures import NeuralTextureBank
         self.meshes = meshes
         self.K = len(meshes)
-        self.tracer = RayTracer(meshes) if tracer is None else tracer
+        self.tracer = RayTracer(meshes, builder=bvh_builder) if tracer is None else tracer
         self.rays_o, self.rays_d, self.gt = rays_o, rays_d, gt_rgb
         self.nr_rays = rays_o.shape[0]
         self.image_hw = None

@@ -16,12 +16,21 @@ from . import _lib
 
 
 class RayTracer:
-    def __init__(self, tensor_meshes, leaf_size=4, node_format=None):
-        """node_format: "q16" (default; binary 32-byte quantised nodes, vsa_trace_q / vsa_trace_q_fb) or
+    BUILDERS = ("host", "device")
+
+    def __init__(self, tensor_meshes, leaf_size=4, node_format=None, builder="host"):
+        """builder: "host" (default; binned-SAH trees built on the CPU from host copies of the meshes,
+        csrc/bvh_build.cpp) or "device" (Karras LBVH built on the GPU from the meshes' device tensors,
+        csrc/bvh_device.hip: no host copy, milliseconds instead of seconds, a higher SAH cost).  Both give
+        bit-identical hits.
+        node_format: "q16" (default; binary 32-byte quantised nodes, vsa_trace_q / vsa_trace_q_fb) or
         "f32" (binary 64-byte fp32 nodes, vsa_trace); also selected by VSA_TRACE_NODES.  Both give
         identical hits; the quantised format assumes ray origins within ~60 mesh extents of the mesh
         (include/volsurfs_hip.h).  (The 4-wide nodes, the budgeted three-pass walk and the persistent-lane
         kernel of round 3 — bit-exact, measured slower: profiles/NOTEBOOK.md A9.4 — left the library in round 5.)"""
+        if builder not in self.BUILDERS:
+            raise _lib.VolsurfsHipError(f"unknown builder {builder!r} (expected one of {self.BUILDERS})")
+        self.builder = builder
         self.node_format = node_format or os.environ.get("VSA_TRACE_NODES", "q16")
         if self.node_format not in ("q16", "f32"):
             raise _lib.VolsurfsHipError(f"unknown node_format {self.node_format}")
@@ -35,6 +44,9 @@ class RayTracer:
         self._bvh, self._layout = [], []            # builder handles (kept for refit) and (node_base, nr_nodes, tri_base, nr_tris)
         self.mesh_tri_offset, self.mesh_nr_tris = [], []
         self.max_depth = 0
+        if builder == "device":
+            self._build_on_device(tensor_meshes, leaf_size)
+            return
         node_base = tri_base = 0
         # The K shells' trees are independent host builds (binned SAH, csrc/bvh_build.cpp, one thread each): built side by
         # side on a thread pool — ctypes drops the GIL inside the call — 7 x 1.31 M triangles (configs[4]) take the time of one
@@ -80,6 +92,74 @@ class RayTracer:
         self.roots = [lay[0] for lay in self._layout]
         self._roots = (ctypes.c_int32 * self.nr_meshes)(*self.roots)
 
+    def _build_on_device(self, tensor_meshes, leaf_size):
+        """The K trees built on the GPU (vsa_bvh_dev_build) one after another on the current stream from the
+        meshes' device tensors, one synchronisation per shell to read its sizes, then exported straight into
+        the concatenated device arrays."""
+        L = _lib.lib()
+        dev = tensor_meshes[0].vertices.device
+        if dev.type != "cuda":
+            raise _lib.VolsurfsHipError('builder="device" needs the meshes on the GPU')
+        st = _lib.stream_ptr()
+        inputs = []             # (alive until the sizes calls have synchronised the builds that read them)
+        try:
+            for m in tensor_meshes:
+                v = m.vertices.detach().to(dev, torch.float32).contiguous()
+                f = m.faces.detach().to(dev, torch.int32).contiguous()
+                inputs.append((v, f))
+                h = ctypes.c_void_p()
+                rc = L.vsa_bvh_dev_build(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, st,
+                                         ctypes.byref(h))
+                if rc != 0:
+                    raise _lib.VolsurfsHipError(f"vsa_bvh_dev_build failed with status {rc}")
+                self._bvh.append(h)
+            node_base = tri_base = 0
+            for h in self._bvh:
+                nn, nt, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+                rc = L.vsa_bvh_dev_sizes(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
+                if rc == -2 and md.value >= 48:
+                    raise _lib.VolsurfsHipError(
+                        f'builder="device": tree depth {md.value} >= 48, deeper than the traversal stack; '
+                        'build this mesh with builder="host"')
+                if rc != 0:
+                    raise _lib.VolsurfsHipError(f"vsa_bvh_dev_sizes failed with status {rc}")
+                self._layout.append((node_base, nn.value, tri_base, nt.value))
+                self.mesh_tri_offset.append(tri_base)
+                self.mesh_nr_tris.append(nt.value)
+                self.max_depth = max(self.max_depth, md.value)
+                node_base += nn.value
+                tri_base += nt.value
+        except Exception:
+            self._destroy()
+            raise
+        self.device = dev
+        self.nodes = torch.empty(node_base, 16, dtype=torch.float32, device=dev)
+        self.qnodes = torch.empty(node_base, 8, dtype=torch.int32, device=dev)
+        self.tris = torch.empty(tri_base, 12, dtype=torch.float32, device=dev)
+        self._export_device()
+        self.slot_face_id = self.tris[:, 3].contiguous().view(torch.int32)
+        self.roots = [lay[0] for lay in self._layout]
+        self._roots = (ctypes.c_int32 * self.nr_meshes)(*self.roots)
+
+    def _export_device(self):
+        """Both node formats and the triangles of the device-built trees, written in place into self.nodes /
+        self.qnodes / self.tris; the K quantisation frames into self._frames (host)."""
+        L = _lib.lib()
+        frames = (ctypes.c_float * (6 * self.nr_meshes))()
+        st = _lib.stream_ptr()
+        for i, (h, (nb, nn, tb, nt)) in enumerate(zip(self._bvh, self._layout)):
+            rc = L.vsa_bvh_dev_export(h, self.nodes[nb].data_ptr(), self.qnodes[nb].data_ptr(), self.tris[tb].data_ptr(),
+                                      nb, tb, ctypes.addressof(frames) + 24 * i, st)
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_dev_export failed with status {rc}")
+        self._frames = frames
+
+    def _destroy(self):
+        L = _lib.lib()
+        for h in self._bvh:
+            (L.vsa_bvh_dev_destroy if self.builder == "device" else L.vsa_bvh_destroy)(h)
+        self._bvh = []
+
     def _export(self):
         """Concatenated fp32 nodes [*,16], quantised nodes [*,8] u32, triangles [*,12] and the K
         quantisation frames [K*6] of the builder handles."""
@@ -110,6 +190,16 @@ class RayTracer:
         if len(tensor_meshes) != self.nr_meshes:
             raise _lib.VolsurfsHipError("refit needs the meshes the tracer was built on")
         L = _lib.lib()
+        if self.builder == "device":
+            st = _lib.stream_ptr()
+            for h, m in zip(self._bvh, tensor_meshes):
+                v = m.vertices.detach().to(self.device, torch.float32).contiguous()
+                rc = L.vsa_bvh_dev_refit(h, v.data_ptr(), v.shape[0], st)
+                if rc != 0:
+                    raise _lib.VolsurfsHipError(f"vsa_bvh_dev_refit failed with status {rc} (vertex count changed?)")
+            self._export_device()
+            self._fb = None
+            return self
         for h, m in zip(self._bvh, tensor_meshes):
             v = np.ascontiguousarray(m.vertices.detach().cpu().numpy(), np.float32)
             rc = L.vsa_bvh_refit(h, v.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(v.shape[0]))
@@ -125,9 +215,8 @@ class RayTracer:
 
     def __del__(self):
         try:
-            L = _lib.lib()
-            for h in getattr(self, "_bvh", []):
-                L.vsa_bvh_destroy(h)
+            if getattr(self, "_bvh", None):
+                self._destroy()
         except Exception:
             pass
         self._bvh = []
@@ -206,6 +295,29 @@ class RayTracer:
                   self.max_depth, rays_o, rays_d, N, float(t_min), st, _lib.stream_ptr())
         v = st.cpu().tolist()
         return dict(zip(("lane_visits", "tri_tests", "wave_trips", "waves", "max_wave_trips"), v))
+
+    def sah_cost(self):
+        """Per-mesh SAH cost of the trees, from the fp32 nodes (measurement; copies them to the host):
+        1 (the root's visit) + sum over every child box of area / root area x (1 for an inner node, its triangle
+        count for a leaf).  Lower is a better tree for the same geometry."""
+        nodes = self.nodes.cpu().numpy()
+        out = []
+        for nb, nn, _, _ in self._layout:
+            nd = nodes[nb:nb + nn, :12].astype(np.float64)                             # (12:16 are int bits)
+            ref = nodes[nb:nb + nn, 12:14].copy().view(np.int32)
+            cnt = nodes[nb:nb + nn, 14:16].copy().view(np.int32)
+            w = np.where(ref >= 0, 1.0, cnt.astype(np.float64))                     # empty child: cnt 0
+            area = np.zeros((nn, 2))
+            for c in range(2):
+                ext = np.clip(nd[:, 6 * c + 3:6 * c + 6] - nd[:, 6 * c:6 * c + 3], 0.0, None)
+                area[:, c] = 2.0 * (ext[:, 0] * ext[:, 1] + ext[:, 1] * ext[:, 2] + ext[:, 2] * ext[:, 0])
+            live = w[0] > 0
+            lo = nd[0, [0, 6]][live].min(), nd[0, [1, 7]][live].min(), nd[0, [2, 8]][live].min()
+            hi = nd[0, [3, 9]][live].max(), nd[0, [4, 10]][live].max(), nd[0, [5, 11]][live].max()
+            e = np.subtract(hi, lo)
+            root_area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0])
+            out.append(1.0 + float((area * w).sum()) / root_area)
+        return out
 
     def feedback_header(self):
         """{tag, n0, n1, n2} of the half the LAST cost-feedback launch wrote (tests, diagnostics)."""

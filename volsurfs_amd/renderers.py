@@ -107,9 +107,10 @@ def _load_texture(path, sh_range):
 
 class MeshRenderer(BaseRenderer):
     def __init__(self, scene_path=None, t_near=1e-3, t_far=100, profiler=None, tensor_mesh=None,
-                 texture=None, sh_range=15.0):
+                 texture=None, sh_range=15.0, bvh_builder="host"):
         """scene_path: a directory with scene.json = {"meshes": [{"mesh_path": ..., "textures":
-        [{"texture_path": ...}]}]} (mesh_renderer.py:27-45); or pass tensor_mesh + texture."""
+        [{"texture_path": ...}]}]} (mesh_renderer.py:27-45); or pass tensor_mesh + texture.
+        bvh_builder: RayTracer(builder=...): "host" or "device" (the same hits)."""
         super().__init__(profiler=profiler)
         if scene_path is not None:
             with open(os.path.join(scene_path, "scene.json")) as f:
@@ -122,7 +123,7 @@ class MeshRenderer(BaseRenderer):
         self.tensor_texture = TensorTexture(texture, lerp=True)
         if self.tensor_texture.texture.shape[-1] not in (4, 16, 36, 64):
             raise ValueError("texture channels must be 4 * (deg + 1)^2, deg 0..3")
-        self.raytracer = RayTracer([tensor_mesh])
+        self.raytracer = RayTracer([tensor_mesh], builder=bvh_builder)
         self.t_near, self.t_far = t_near, t_far
         self.active_render_mode, self.active_shader = "ray_traced", "rgb"
         self.default_bg_color = (255, 255, 255)
