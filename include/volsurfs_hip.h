@@ -163,6 +163,15 @@ int vsa_bvh_dev_export(const vsa_bvh_dev* bvh, float* nodes_out, uint32_t* qnode
                        int node_base, int tri_base, float* frame_out, void* stream);
 int vsa_bvh_dev_refit(vsa_bvh_dev* bvh, const float* verts, int nr_verts, void* stream);
 int vsa_bvh_dev_destroy(vsa_bvh_dev* bvh);
+/* vsa_bvh_dev_build_ploc: the same handle, built by PLOC clustering (Meister & Bittner 2018; csrc/bvh_ploc.hip)
+ * over the same Morton-sorted triangles: each cluster merges with the neighbour within `radius` positions of the
+ * Morton-ordered cluster array (1..32; RayTracer's default is in DESIGN §12) whose union box has the smallest
+ * surface area, until one cluster is left.  Its SAH cost lies between the LBVH's and the host tree's; the build
+ * synchronises `stream` a few times (it reads the live cluster count once per batch of iterations).
+ * vsa_bvh_dev_sizes / _export / _refit / _destroy serve it unchanged; refit keeps its topology and slots.
+ *   VSA_ERR_ARG on null pointers, nr_verts / nr_faces <= 0 or radius outside 1..32 (before any HIP call). */
+int vsa_bvh_dev_build_ploc(const float* verts, const int32_t* faces, int nr_verts, int nr_faces, int leaf_size,
+                           int radius, void* stream, vsa_bvh_dev** out_bvh);
 
 /* vsa_trace: closest hit of every ray against each of nr_meshes BVHs in ONE
  * launch (grid.y = mesh).  mesh_roots [host, nr_meshes] = root node index of

@@ -10,13 +10,15 @@
 //   4. stable radix sort of (code, face id) — equal codes stay in face-id order: the build is deterministic;
 //   5. the n - 1 internal nodes from the common-prefix lengths of neighbouring keys (duplicates split by
 //      index), with the sorted range each covers and parent links;
+//      vsa_bvh_dev_build_ploc puts PLOC clustering (csrc/bvh_ploc.hip) in its place: the same form (root 0, ranges,
+//      parent links), leaf order = the PLOC tree's left-to-right order instead of the sorted order;
 //   6. bottom-up: one thread per leaf climbs with one arrival counter per node, the second arrival
 //      continues; it writes its un-padded box and its subtree's kept-internal-node count into the parent's
 //      child slot.  Min / max do not depend on arrival order: the boxes are the same bits every build;
 //   7. pre-order numbering of the kept internal nodes (a subtree of > leaf_size triangles; smaller ones
 //      collapse into one leaf, the host rule `n <= leaf_size`), and the tree depth;
 //   8. export: fp32 64-B nodes, q16 32-B nodes on the union of the root's child boxes, and the triangle
-//      records in leaf (= sorted) order.
+//      records in leaf order.
 // Refit re-runs 1, 2 and 6 on moved vertices; slots and topology stay.
 // Every closest hit is a minimum over (t, face id) and the boxes only prune, so hits through this tree are
 // bit-identical to the host tree's and to brute force (tests/test_bvh_device.py).
@@ -26,7 +28,9 @@
 
 #include <cmath>
 #include <cstdint>
+#include <utility>
 
+#include "bvh_ploc.h"
 #include "common.h"
 
 namespace {
@@ -508,9 +512,12 @@ int bottom_up_and_frame(vsa_bvh_dev* h) {
 
 }  // namespace
 
-extern "C" int vsa_bvh_dev_build(const float* verts, const int32_t* faces, int nr_verts, int nr_faces, int leaf_size,
-                                 void* stream, vsa_bvh_dev** out_bvh) {
-  if (!verts || !faces || !out_bvh || nr_verts <= 0 || nr_faces <= 0) return VSA_ERR_ARG;
+namespace {
+
+// The whole build; radius 0: the Karras hierarchy (step 5), radius >= 1: PLOC clustering at that radius
+// (csrc/bvh_ploc.hip) in its place.  Arguments checked by the callers.
+int build_handle(const float* verts, const int32_t* faces, int nr_verts, int nr_faces, int leaf_size, int radius,
+                 void* stream, vsa_bvh_dev** out_bvh) {
   if (nr_faces >= (1 << 27)) return VSA_ERR_UNSUPPORTED;     // q16 leaf code: first triangle << 4
   if (leaf_size < 1) leaf_size = 4;
   if (leaf_size > 8) leaf_size = 8;
@@ -561,12 +568,18 @@ extern "C" int vsa_bvh_dev_build(const float* verts, const int32_t* faces, int n
                                     30, h->stream);
     if (e == hipSuccess && n > 1) e = hipMemsetAsync(h->parent_leaf, 0xff, sizeof(int32_t) * (size_t)n, h->stream);
     if (e == hipSuccess && n > 1) e = hipMemsetAsync(h->parent_int, 0xff, sizeof(int32_t) * (size_t)ni, h->stream);
-    if (e == hipSuccess && n > 1) {
+    if (e == hipSuccess && n > 1 && radius == 0) {
       hipLaunchKernelGGL(bvh_dev_hierarchy, dim3(vsa_div_up(ni, BVHD_BLOCK)), dim3(BVHD_BLOCK), 0, h->stream, h->keys, n,
                          h->child, h->range, h->parent_int, h->parent_leaf);
       e = hipGetLastError();
     }
     rc = e == hipSuccess ? VSA_OK : (int)e;
+    if (rc == VSA_OK && n > 1 && radius > 0) {
+      // the PLOC tree's leaf order replaces the sorted order: written to vals_in (consumed by the sort), then swapped
+      rc = bvh_ploc_topology(h->tbox, h->order, n, radius, h->stream, h->vals_in, h->child, h->range, h->parent_int,
+                             h->parent_leaf, h->info + INFO_ERR, ERR_WALK);
+      std::swap(h->order, h->vals_in);
+    }
   }
   if (rc == VSA_OK) rc = bottom_up_and_frame(h);
   if (rc == VSA_OK && n > leaf_size) {
@@ -583,6 +596,21 @@ extern "C" int vsa_bvh_dev_build(const float* verts, const int32_t* faces, int n
   }
   *out_bvh = h;
   return VSA_OK;
+}
+
+}  // namespace
+
+extern "C" int vsa_bvh_dev_build(const float* verts, const int32_t* faces, int nr_verts, int nr_faces, int leaf_size,
+                                 void* stream, vsa_bvh_dev** out_bvh) {
+  if (!verts || !faces || !out_bvh || nr_verts <= 0 || nr_faces <= 0) return VSA_ERR_ARG;
+  return build_handle(verts, faces, nr_verts, nr_faces, leaf_size, 0, stream, out_bvh);
+}
+
+extern "C" int vsa_bvh_dev_build_ploc(const float* verts, const int32_t* faces, int nr_verts, int nr_faces,
+                                      int leaf_size, int radius, void* stream, vsa_bvh_dev** out_bvh) {
+  if (!verts || !faces || !out_bvh || nr_verts <= 0 || nr_faces <= 0) return VSA_ERR_ARG;
+  if (radius < 1 || radius > BVH_PLOC_MAX_RADIUS) return VSA_ERR_ARG;
+  return build_handle(verts, faces, nr_verts, nr_faces, leaf_size, radius, stream, out_bvh);
 }
 
 extern "C" int vsa_bvh_dev_sizes(const vsa_bvh_dev* bvh, int* nr_nodes, int* nr_tris, int* max_depth) {

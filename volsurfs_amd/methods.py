@@ -127,7 +127,8 @@ class VolSurfs(torch.nn.Module):
                  lr_milestones=(100000, 150000, 180000, 190000), nr_warmup_iters=3000,
                  using_neural_textures_anchor=False, using_neural_textures_lerp=True,
                  using_sh_quantization=True, using_sh_squeezing=True, bvh_builder="host"):
-        """bvh_builder: RayTracer(builder=...): "host" (binned SAH on the CPU) or "device" (LBVH on the GPU; the same hits).
+        """bvh_builder: RayTracer(builder=...): "host" (binned SAH on the CPU), "device" (LBVH on the GPU) or "ploc" (PLOC
+        on the GPU, close to the host tree's quality); the same hits.
         using_neural_textures_anchor / _lerp, using_sh_quantization, using_sh_squeezing: the reference's
         hyper-parameters of the same names (config/volsurfs/base_5.cfg:16-19 -> volsurfs.py:149-153); every
         combination the reference accepts is built, the ones it exits on raise in NeuralTextureBank.

@@ -83,7 +83,7 @@ class KShellPipeline:
         order (vsa_tile_order; both passes are inside the step).
         tracer: a RayTracer already built over `meshes` (another pipeline's: the BVH of a 1.3 M-triangle
         shell takes seconds to build on the host) instead of building one.
-        bvh_builder: RayTracer(builder=...) of the tracer built here: "host" or "device" (the same hits)."""
+        bvh_builder: RayTracer(builder=...) of the tracer built here: "host", "device" or "ploc" (the same hits)."""
         from .neural_textures import NeuralTextureBank
         self.meshes = meshes
         self.K = len(meshes)

@@ -16,12 +16,16 @@ from . import _lib
 
 
 class RayTracer:
-    BUILDERS = ("host", "device")
+    BUILDERS = ("host", "device", "ploc")
+    DEVICE_BUILDERS = ("device", "ploc")
+    PLOC_RADIUS = 8                                 # builder="ploc"'s default search radius
 
-    def __init__(self, tensor_meshes, leaf_size=4, node_format=None, builder="host"):
+    def __init__(self, tensor_meshes, leaf_size=4, node_format=None, builder="host", ploc_radius=None):
         """builder: "host" (default; binned-SAH trees built on the CPU from host copies of the meshes,
-        csrc/bvh_build.cpp) or "device" (Karras LBVH built on the GPU from the meshes' device tensors,
-        csrc/bvh_device.hip: no host copy, milliseconds instead of seconds, a higher SAH cost).  Both give
+        csrc/bvh_build.cpp), "device" (Karras LBVH built on the GPU from the meshes' device tensors,
+        csrc/bvh_device.hip: no host copy, milliseconds instead of seconds, a higher SAH cost) or "ploc" (PLOC
+        clustering on the GPU from the device tensors, csrc/bvh_ploc.hip: no host copy, milliseconds, close to
+        the host tree's SAH cost; ploc_radius = its search radius 1..32, default PLOC_RADIUS).  All three give
         bit-identical hits.
         node_format: "q16" (default; binary 32-byte quantised nodes, vsa_trace_q / vsa_trace_q_fb) or
         "f32" (binary 64-byte fp32 nodes, vsa_trace); also selected by VSA_TRACE_NODES.  Both give
@@ -44,8 +48,8 @@ class RayTracer:
         self._bvh, self._layout = [], []            # builder handles (kept for refit) and (node_base, nr_nodes, tri_base, nr_tris)
         self.mesh_tri_offset, self.mesh_nr_tris = [], []
         self.max_depth = 0
-        if builder == "device":
-            self._build_on_device(tensor_meshes, leaf_size)
+        if builder in self.DEVICE_BUILDERS:
+            self._build_on_device(tensor_meshes, leaf_size, self.PLOC_RADIUS if ploc_radius is None else ploc_radius)
             return
         node_base = tri_base = 0
         # The K shells' trees are independent host builds (binned SAH, csrc/bvh_build.cpp, one thread each): built side by
@@ -92,14 +96,14 @@ class RayTracer:
         self.roots = [lay[0] for lay in self._layout]
         self._roots = (ctypes.c_int32 * self.nr_meshes)(*self.roots)
 
-    def _build_on_device(self, tensor_meshes, leaf_size):
-        """The K trees built on the GPU (vsa_bvh_dev_build) one after another on the current stream from the
-        meshes' device tensors, one synchronisation per shell to read its sizes, then exported straight into
-        the concatenated device arrays."""
+    def _build_on_device(self, tensor_meshes, leaf_size, radius):
+        """The K trees built on the GPU (vsa_bvh_dev_build, or vsa_bvh_dev_build_ploc at `radius`) one after another
+        on the current stream from the meshes' device tensors, one synchronisation per shell to read its sizes, then
+        exported straight into the concatenated device arrays."""
         L = _lib.lib()
         dev = tensor_meshes[0].vertices.device
         if dev.type != "cuda":
-            raise _lib.VolsurfsHipError('builder="device" needs the meshes on the GPU')
+            raise _lib.VolsurfsHipError(f'builder="{self.builder}" needs the meshes on the GPU')
         st = _lib.stream_ptr()
         inputs = []             # (alive until the sizes calls have synchronised the builds that read them)
         try:
@@ -108,10 +112,16 @@ class RayTracer:
                 f = m.faces.detach().to(dev, torch.int32).contiguous()
                 inputs.append((v, f))
                 h = ctypes.c_void_p()
-                rc = L.vsa_bvh_dev_build(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, st,
-                                         ctypes.byref(h))
+                if self.builder == "ploc":
+                    name = "vsa_bvh_dev_build_ploc"
+                    rc = L.vsa_bvh_dev_build_ploc(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, radius,
+                                                  st, ctypes.byref(h))
+                else:
+                    name = "vsa_bvh_dev_build"
+                    rc = L.vsa_bvh_dev_build(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, st,
+                                             ctypes.byref(h))
                 if rc != 0:
-                    raise _lib.VolsurfsHipError(f"vsa_bvh_dev_build failed with status {rc}")
+                    raise _lib.VolsurfsHipError(f"{name} failed with status {rc}")
                 self._bvh.append(h)
             node_base = tri_base = 0
             for h in self._bvh:
@@ -119,7 +129,7 @@ class RayTracer:
                 rc = L.vsa_bvh_dev_sizes(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
                 if rc == -2 and md.value >= 48:
                     raise _lib.VolsurfsHipError(
-                        f'builder="device": tree depth {md.value} >= 48, deeper than the traversal stack; '
+                        f'builder="{self.builder}": tree depth {md.value} >= 48, deeper than the traversal stack; '
                         'build this mesh with builder="host"')
                 if rc != 0:
                     raise _lib.VolsurfsHipError(f"vsa_bvh_dev_sizes failed with status {rc}")
@@ -157,7 +167,7 @@ class RayTracer:
     def _destroy(self):
         L = _lib.lib()
         for h in self._bvh:
-            (L.vsa_bvh_dev_destroy if self.builder == "device" else L.vsa_bvh_destroy)(h)
+            (L.vsa_bvh_dev_destroy if self.builder in self.DEVICE_BUILDERS else L.vsa_bvh_destroy)(h)
         self._bvh = []
 
     def _export(self):
@@ -190,7 +200,7 @@ class RayTracer:
         if len(tensor_meshes) != self.nr_meshes:
             raise _lib.VolsurfsHipError("refit needs the meshes the tracer was built on")
         L = _lib.lib()
-        if self.builder == "device":
+        if self.builder in self.DEVICE_BUILDERS:
             st = _lib.stream_ptr()
             for h, m in zip(self._bvh, tensor_meshes):
                 v = m.vertices.detach().to(self.device, torch.float32).contiguous()

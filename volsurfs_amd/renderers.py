@@ -110,7 +110,7 @@ class MeshRenderer(BaseRenderer):
                  texture=None, sh_range=15.0, bvh_builder="host"):
         """scene_path: a directory with scene.json = {"meshes": [{"mesh_path": ..., "textures":
         [{"texture_path": ...}]}]} (mesh_renderer.py:27-45); or pass tensor_mesh + texture.
-        bvh_builder: RayTracer(builder=...): "host" or "device" (the same hits)."""
+        bvh_builder: RayTracer(builder=...): "host", "device" or "ploc" (the same hits)."""
         super().__init__(profiler=profiler)
         if scene_path is not None:
             with open(os.path.join(scene_path, "scene.json")) as f:
