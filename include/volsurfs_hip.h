@@ -1034,6 +1034,30 @@ int vsa_sample_fg_occupied(const float* rays_o, const float* rays_d, const float
                            float* samples_3d, float* samples_dirs, float* samples_z,
                            int32_t* ray_start_end_idx, int nr_rays, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Held-out-view evaluation (csrc/image_metrics.hip): per-image PSNR and SSIM of B image pairs of one size, piq
+ * 0.8.0's `psnr(x, y, data_range=1.)` and `ssim(x, y, data_range=1.)` with their defaults as the reference calls
+ * them (volsurfs_py/utils/evaluation.py:167-168; piq is unpinned here, the definitions are restated in DESIGN §13).
+ *   pred, gt      [B,H,W,3] HWC RGB, contiguous, 16-byte aligned; each fp32 (flag 0, values in [0,1]) or uint8
+ *                 (flag 1, read as u8 / 255).
+ *   pool          SSIM's average-pooling factor f >= 1 (piq: max(1, round(min(H, W) / 256)); 1 = downsample off);
+ *                 the pooled image (H / f) x (W / f) must be at least 11 x 11.
+ *   quantize_pred 1: the 8-bit rule trunc(clamp(x, 0, 1) * 255) / 255 on an fp32 pred as it is loaded (the PNG
+ *                 round trip of rendering.py:15-33 without a PNG); ignored for a uint8 pred.
+ *   workspace     vsa_image_metrics_workspace_bytes(...) bytes of device memory, 8-byte aligned; no state is kept
+ *                 in it between calls.
+ *   psnr_out, ssim_out  [B] f64: -10 log10(mse + 1e-8) over the 3 H W values; the mean SSIM map over channels
+ *                 and pixels.  Every sum runs in a fixed order: the same bits every call and for every B.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer, B / H / W < 1, pool < 1, a pooled size under 11, a dtype or
+ * quantize flag other than 0 / 1, an unaligned pointer, a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED:
+ * a pooled row run of pred + gt that does not fit the kernel's staging area (pool above 18 for two fp32 inputs).
+ * The workspace query returns the byte count or one of those two codes.
+ */
+long long vsa_image_metrics_workspace_bytes(int B, int H, int W, int pool, int pred_u8, int gt_u8);
+int vsa_image_metrics(const void* pred, int pred_u8, const void* gt, int gt_u8, int B, int H, int W, int pool,
+                      int quantize_pred, void* workspace, long long workspace_bytes, double* psnr_out,
+                      double* ssim_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
