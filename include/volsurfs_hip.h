@@ -1058,6 +1058,49 @@ int vsa_image_metrics(const void* pred, int pred_u8, const void* gt, int gt_u8, 
                       int quantize_pred, void* workspace, long long workspace_bytes, double* psnr_out,
                       double* ssim_out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Marching cubes (csrc/isosurface.hip): the K level sets of one grid, the mesh extraction of the reference's baker
+ * (volsurfs_py/baker.py:324-452, utils/mesh_extraction.py:224-373, which runs skimage on the host once per level).
+ *   grid          [nx, ny, nz] f32, C-contiguous: value (i, j, k) = f(x_i, y_j, z_k) (indexing "ij"), finite (the
+ *                 caller checks: NaN has no inside / outside); grid point (i, j, k) sits at origin + (i, j, k) * spacing.
+ *   levels        [host] K f32, 1 <= K <= 16, any order; inside_above 0 / 1.
+ * Rules (the output is a function of the grid and the levels only; tests/test_isosurface.py restates them in numpy):
+ *   inside        a grid point is inside when value < level (strict), or value > level when inside_above.
+ *   vertices      one per crossed grid edge (endpoints differ in inside status), shared by every cell around the
+ *                 edge.  With a the edge's lower-index endpoint and b the other, t = (level - f_a) / (f_b - f_a) in
+ *                 fp32 (IEEE division, no contraction); along the edge's axis origin + (idx_a + t) * spacing, the
+ *                 other two coordinates origin + idx * spacing.  Order: by owning point a in C order, then by axis
+ *                 x, y, z.
+ *   faces         [F, 3] i32 vertex ids local to the level; order: by cell (i, j, k) in C order, then by table order.
+ *                 The table (vsa_mc_table, volsurfs_amd/isosurface.py:build_mc_table) resolves every ambiguous face
+ *                 by one rule, so closed surfaces come out watertight; (v1 - v0) x (v2 - v0) points out of the inside
+ *                 region (towards increasing value for an SDF: mesh.icosphere's winding).  Zero-area faces (a grid
+ *                 value exactly at the level) are kept.
+ * Two passes:
+ *   vsa_isosurface_count  per-row counts, a device scan into per-row offsets and the per-level totals in the
+ *                 workspace, then the 2K totals (V_0, F_0, V_1, F_1, ...) copied to [host] `totals`: the call
+ *                 synchronises `stream` once.  VSA_ERR_UNSUPPORTED when a level's V or F reaches 2^31.
+ *   vsa_isosurface_emit   with the same grid, levels, flag and workspace right after the count: writes verts[L]
+ *                 [V_L, 3] f32 and faces[L] [F_L, 3] i32 ([host] arrays of K device pointers; NULL allowed for an
+ *                 empty array), never past the V_L / F_L of `totals`; origin, spacing [host] 3 f32, spacing > 0.
+ *   workspace     vsa_isosurface_workspace_bytes(nx, ny, nz, K) bytes: 12 bytes per row (nx * ny) and level plus the
+ *                 scan's temporary storage -- O(K nx ny), never O(nx ny nz).
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer, a dimension < 2, K outside 1..16, inside_above other than 0 / 1,
+ * a spacing <= 0 (or NaN), a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED: nx * ny >= 2^31 rows or
+ * nz >= 2^31 / 5.  The workspace query returns the byte count or one of those codes.
+ */
+long long vsa_isosurface_workspace_bytes(long long nx, long long ny, long long nz, int nr_levels);
+int vsa_isosurface_count(const float* grid, long long nx, long long ny, long long nz, const float* levels,
+                         int nr_levels, int inside_above, void* workspace, long long workspace_bytes,
+                         long long* totals, void* stream);
+int vsa_isosurface_emit(const float* grid, long long nx, long long ny, long long nz, const float* levels,
+                        int nr_levels, int inside_above, const float* origin, const float* spacing, void* workspace,
+                        long long workspace_bytes, const long long* totals, float* const* verts,
+                        int32_t* const* faces, void* stream);
+/* The marching-cubes triangle table compiled into the library: out [host] 256 x 16 int8 (case c: bit b set when
+ * cube corner b = dx | dy << 1 | dz << 2 is inside; up to five triangles of edge ids, -1 padded). */
+int vsa_mc_table(int8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,12 @@ class BoundingBox:
         return self.half
 
     @torch.no_grad()
+    def check_points_inside(self, points):
+        """[P, 3] -> [P] bool: |p|_inf <= side / 2 (closed).  The reference calls this on its mvdatasets class
+        (utils/mesh_extraction.py:356), which is absent: the boundary's semantics are unpinned, this is ours."""
+        return points.abs().amax(-1) <= self.half
+
+    @torch.no_grad()
     def intersect(self, rays_o, rays_d):
         return _intersect(0, self.half, rays_o, rays_d)
 
@@ -45,6 +51,12 @@ class BoundingSphere:
 
     def get_radius(self):
         return self.radius
+
+    @torch.no_grad()
+    def check_points_inside(self, points):
+        """[P, 3] -> [P] bool: ||p|| <= radius (closed).  The reference's class lives in the absent mvdatasets
+        (utils/mesh_extraction.py:356): the boundary's semantics are unpinned, this is ours."""
+        return torch.linalg.vector_norm(points, dim=-1) <= self.radius
 
     @torch.no_grad()
     def intersect(self, rays_o, rays_d):
