@@ -1101,6 +1101,68 @@ int vsa_isosurface_emit(const float* grid, long long nx, long long ny, long long
  * cube corner b = dx | dy << 1 | dz << 2 is inside; up to five triangles of edge ids, -1 padded). */
 int vsa_mc_table(int8_t* out);
 
+/* ------------------------------------------------------------------------
+ * Mesh simplification (csrc/simplify.hip): parallel Garland-Heckbert quadric edge collapse, in rounds, down to a
+ * face count -- the baker's `--simplify_meshes` step (pymeshlab's quadric edge-collapse decimation in the reference,
+ * volsurfs_py/baker.py:682-724, utils/mesh_extraction.py:492-537).
+ *   verts [V, 3] f32 and faces [F, 3] i32 on the device: finite, indices in [0, V), no index twice in one face (the
+ *   caller checks).  V, F >= 1.  target_faces >= 0: the caller's int(F * ratio).
+ * Rules (the output is a function of the input mesh and the target only; tests/test_simplify.py restates them in
+ * numpy and the kernels are held to it bit for bit; every float operation below is IEEE fp64 unless said, in the
+ * order written, with no contraction):
+ *   quadrics      face f's plane quadric: n = (p1 - p0) x (p2 - p0), u = n / |n|, d = -(u.p0), Q_f = (|n| / 2) *
+ *                 (u, d)(u, d)^T (zero for |n| = 0), stored as the upper triangle xx xy xz xd yy yz yd zz zd dd, each
+ *                 entry w * (p_i * p_j).  A boundary edge (one face) c: pi -> pj of face f adds to both its endpoints
+ *                 the plane through the edge along n: m = (pj - pi) x n, u = m / |m|, weight 10 |pj - pi|^2 (zero for
+ *                 |m| = 0).  Q_v = the sum over the faces at v in ascending face index of Q_f, then the penalties of
+ *                 f's boundary edges at v in corner order c = 0, 1, 2 (a sorted (vertex, face) list, no float
+ *                 atomics).  Computed once from the input; a collapse of b into a sets Q_a := Q_a + Q_b.
+ *   edges         per round, the unique undirected edges of the current faces; id = rank in (min, max) order; the
+ *                 edge's face count from the faces.  Boundary vertex: on an edge with one face; frozen: on an edge
+ *                 with more than two.  Edge (a, b) has a < b; b collapses into a.
+ *   placement     Q = Q_a + Q_b.  Exactly one endpoint on a boundary: that endpoint.  Otherwise the 3x3 system
+ *                 [xx xy xz; xy yy yz; xz yz zz] x = -(xd, yd, zd) by cofactors (c00 = yy zz - yz yz, c01 = xz yz -
+ *                 xy zz, c02 = xy yz - xz yy, c11 = xx zz - xz xz, c12 = xy xz - xx yz, c22 = xx yy - xy xy, det =
+ *                 xx c00 + xy c01 + xz c02, x = (c00 r0 + c01 r1 + c02 r2) / det, ...) when det > 1e-10 tr^3 (tr = xx +
+ *                 yy + zz); else the cheapest of a, b and fp32((a + b) * 0.5), ties in that order.  The position is
+ *                 rounded to fp32 and the cost evaluated there: t_i = row i of Q . (x, y, z, 1), cost = t0 x + t1 y +
+ *                 t2 z + t3.
+ *   candidate     an edge is one when all hold: neither endpoint frozen; no pinching (an edge with two faces between
+ *                 two boundary vertices); a finite position and a non-NaN cost; the link condition (the number of
+ *                 distinct common neighbours of a and b equals the edge's face count); no flip (every face at a or b
+ *                 without both, with the moved vertex at the new position: dot(n_before, n_after) > 0, a face with
+ *                 n_before = 0 exempt); no duplicated face (no face at a without b equals, as a vertex set, a face at
+ *                 b without a with b renamed a -- this also keeps a closed component from shrinking below a
+ *                 tetrahedron).
+ *   key           (fp32 bits of max(cost, 0) rounded up) << 32 | edge id; UINT64_MAX for a non-candidate.
+ *   winners       m1(v) = min key over the edges at v; m2(v) = min m1 over the vertices of the faces at v (64-bit
+ *                 atomicMin: a minimum does not depend on arrival order).  (a, b) wins when key == m2(a) == m2(b).
+ *                 Two winners share no face and no vertex, and no winner's endpoint lies in another's ring; the global
+ *                 minimum always wins.
+ *   target        a round accepts winners in ascending key order while the faces still to remove (F - target) are
+ *                 positive; each removes the faces that contain both its endpoints.  The loop ends when F <= target
+ *                 or a round has no candidate (`stalled`).  So F_out <= target unless stalled, and F_out >= target - 1
+ *                 when every accepted edge has at most two faces.
+ *   collapse      b is replaced by a in place in every face (winding kept); faces with both are dropped; surviving
+ *                 faces keep ascending input order.
+ *   output        out_verts: the vertices referenced by a surviving face, in ascending input index; out_faces: the
+ *                 surviving faces in ascending input face index, renumbered.  out_verts [V, 3] f32 and out_faces
+ *                 [F, 3] i32 are sized for the input; the first V_out / F_out rows are written.
+ *   stats         [host] 5 long long: rounds (rounds that collapsed), collapses, stalled (0 / 1), V_out, F_out.
+ *   stage_ms      [host] 6 floats or NULL: device ms of init, edges, cost, select, collapse, compact (events, with one
+ *                 stream synchronisation per stage; NULL: none).
+ * The host reads one small counter pair per round (W, faces removed), and one more in the last round; the call
+ * synchronises `stream` before it returns.
+ *   workspace     vsa_simplify_workspace_bytes(V, F): 120 bytes per vertex and 156 per face plus rocPRIM's temporary
+ *                 storage (its radix sorts of 3F keys) -- O(V + F).
+ * VSA_ERR_ARG: a NULL pointer, V or F < 1, target < 0, a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED:
+ * V >= 2^31 or 3 F + 3 >= 2^31.  The workspace query returns the byte count or one of those codes.
+ */
+long long vsa_simplify_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                 long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
+                 int32_t* out_faces, long long* stats, float* stage_ms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

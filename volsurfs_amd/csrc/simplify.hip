@@ -1,0 +1,887 @@
+// Quadric edge-collapse simplification of one triangle mesh (vsa_simplify*; rules in include/volsurfs_hip.h,
+// DESIGN §15).
+//
+// Rounds on one stream.  Each round:
+//   edges:    the 3F (min, max) keys of the current faces, packed into s + s bits (s = bits of V - 1), radix-sorted;
+//             head flags + an exclusive scan give every unique edge its id (its rank) and `ehead[id]`, the first
+//             sorted slot of the edge, so its face count is ehead[id + 1] - ehead[id].  Vertex flags (boundary,
+//             frozen) come from the counts by an atomic OR.  The (vertex, face) list is radix-sorted into a CSR
+//             (vstart / vend over the sorted slots): the ring of faces of every vertex.
+//   cost:     one lane per edge: placement, cost and the validity rules over the rings of both endpoints -> the
+//             64-bit key (cost bits << 32 | edge id) or UINT64_MAX.
+//   select:   m1 (64-bit atomicMin over edges), m2 (64-bit atomicMin over faces), the winners' flags, a scan, the
+//             winners' keys compacted in edge-id order, and {W, faces they remove} read by the host.  Only when the
+//             winners would remove more than the faces still to remove are their keys sorted and a scan of their
+//             face counts decides the accepted prefix.
+//   collapse: one lane per accepted winner: b's ring rewritten to a (faces with both dropped), a moved, Q_a += Q_b.
+//   compact:  surviving faces scanned and scattered in order into the other face buffer.
+// Winners share no vertex and no face (see the header), so the lanes of one round never touch the same data.  Every
+// float sum has a fixed order (no float atomics); integer atomics only form minima, ORs and counts.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <cstdint>
+
+#include "common.h"
+
+#define SMP_BLOCK 256
+#define SMP_BOUNDARY 1u
+#define SMP_FROZEN 2u
+#define SMP_DET_REL 1e-10
+#define SMP_BOUNDARY_WEIGHT 10.0
+#define SMP_NONE 0xFFFFFFFFFFFFFFFFull
+
+// device counters
+#define CTR_E 0
+#define CTR_W 1
+#define CTR_R 2
+#define CTR_F 3
+#define CTR_ACC 4
+#define CTR_V 5
+#define CTR_N 8
+
+typedef unsigned long long u64;
+
+// ------------------------------------------------------------------------------------------------ fp64 geometry
+
+// Plane quadric w * p p^T of p = (u, d), upper triangle in the order xx xy xz xd yy yz yd zz zd dd.
+__device__ __forceinline__ void smp_plane(double w, double ux, double uy, double uz, double d, double* q) {
+  const double p[4] = {ux, uy, uz, d};
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = i; j < 4; ++j) q[k++] = w * (p[i] * p[j]);
+}
+
+__device__ __forceinline__ void smp_load(const float* P, int v, double* p) {
+  p[0] = (double)P[3 * (long long)v];
+  p[1] = (double)P[3 * (long long)v + 1];
+  p[2] = (double)P[3 * (long long)v + 2];
+}
+
+// n = (p1 - p0) x (p2 - p0) in fp64.
+__device__ __forceinline__ void smp_normal(const double* p0, const double* p1, const double* p2, double* n) {
+  const double e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
+  const double e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
+  n[0] = e1y * e2z - e1z * e2y;
+  n[1] = e1z * e2x - e1x * e2z;
+  n[2] = e1x * e2y - e1y * e2x;
+}
+
+// Area-weighted plane quadric of a face: (|n| / 2) * (u, -u.p0)(u, -u.p0)^T with u = n / |n|; zero for |n| = 0.
+__device__ void smp_face_quadric(const double* p0, const double* n, double* q) {
+  const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  if (!(len > 0.0)) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) q[k] = 0.0;
+    return;
+  }
+  const double ux = n[0] / len, uy = n[1] / len, uz = n[2] / len;
+  const double d = -(ux * p0[0] + uy * p0[1] + uz * p0[2]);
+  smp_plane(0.5 * len, ux, uy, uz, d, q);
+}
+
+// Boundary penalty of the edge pi -> pj of a face with normal n: the plane through the edge along n, weighted by
+// SMP_BOUNDARY_WEIGHT * |pj - pi|^2; zero when (pj - pi) x n = 0.
+__device__ void smp_boundary_quadric(const double* pi, const double* pj, const double* n, double* q) {
+  const double ex = pj[0] - pi[0], ey = pj[1] - pi[1], ez = pj[2] - pi[2];
+  const double mx = ey * n[2] - ez * n[1], my = ez * n[0] - ex * n[2], mz = ex * n[1] - ey * n[0];
+  const double len = sqrt(mx * mx + my * my + mz * mz);
+  if (!(len > 0.0)) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) q[k] = 0.0;
+    return;
+  }
+  const double ux = mx / len, uy = my / len, uz = mz / len;
+  const double d = -(ux * pi[0] + uy * pi[1] + uz * pi[2]);
+  smp_plane(SMP_BOUNDARY_WEIGHT * (ex * ex + ey * ey + ez * ez), ux, uy, uz, d, q);
+}
+
+// (x, y, z, 1) Q (x, y, z, 1)^T at an fp32 position.
+__device__ __forceinline__ double smp_eval(const double* q, const float* p) {
+  const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+  const double t0 = q[0] * x + q[1] * y + q[2] * z + q[3];
+  const double t1 = q[1] * x + q[4] * y + q[5] * z + q[6];
+  const double t2 = q[2] * x + q[5] * y + q[7] * z + q[8];
+  const double t3 = q[3] * x + q[6] * y + q[8] * z + q[9];
+  return t0 * x + t1 * y + t2 * z + t3;
+}
+
+// Placement of the vertex that replaces edge (a, b) and its cost (header rules).
+__device__ void smp_place(const double* __restrict__ Q, const float* __restrict__ P, const unsigned* __restrict__ vflag,
+                          int a, int b, float* p, double* cost) {
+  double q[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) q[k] = Q[10 * (long long)a + k] + Q[10 * (long long)b + k];
+  float pa[3], pb[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    pa[c] = P[3 * (long long)a + c];
+    pb[c] = P[3 * (long long)b + c];
+  }
+  const bool ba = vflag[a] & SMP_BOUNDARY, bb = vflag[b] & SMP_BOUNDARY;
+  if (ba != bb) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = ba ? pa[c] : pb[c];
+    *cost = smp_eval(q, p);
+    return;
+  }
+  const double A = q[0], B = q[1], C = q[2], D = q[4], E = q[5], F = q[7];
+  const double r0 = -q[3], r1 = -q[6], r2 = -q[8];
+  const double c00 = D * F - E * E, c01 = C * E - B * F, c02 = B * E - C * D;
+  const double c11 = A * F - C * C, c12 = B * C - A * E, c22 = A * D - B * B;
+  const double det = A * c00 + B * c01 + C * c02;
+  const double tr = A + D + F;
+  if (det > SMP_DET_REL * (tr * tr * tr)) {
+    p[0] = (float)((c00 * r0 + c01 * r1 + c02 * r2) / det);
+    p[1] = (float)((c01 * r0 + c11 * r1 + c12 * r2) / det);
+    p[2] = (float)((c02 * r0 + c12 * r1 + c22 * r2) / det);
+    *cost = smp_eval(q, p);
+    return;
+  }
+  float pm[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) pm[c] = (float)(((double)pa[c] + (double)pb[c]) * 0.5);
+  const double ca = smp_eval(q, pa), cb = smp_eval(q, pb), cm = smp_eval(q, pm);
+  double best = ca;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) p[c] = pa[c];
+  if (cb < best) {
+    best = cb;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = pb[c];
+  }
+  if (cm < best) {
+    best = cm;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = pm[c];
+  }
+  *cost = best;
+}
+
+// ------------------------------------------------------------------------------------------------ edges and rings
+
+__device__ __forceinline__ u64 smp_pack(int x, int y, int s) {
+  const int lo = x < y ? x : y, hi = x < y ? y : x;
+  return (u64)(unsigned)lo << s | (u64)(unsigned)hi;
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_edge_keys(const int32_t* __restrict__ faces, long long n3, int s,
+                                                          u64* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  const long long f = i / 3;
+  const int c = (int)(i - 3 * f);
+  keys[i] = smp_pack(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
+  if (vals) vals[i] = (uint32_t)i;
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_heads(const u64* __restrict__ sorted, long long n3,
+                                                      int32_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  flags[i] = i == 0 || sorted[i] != sorted[i - 1];
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_edge_index(const int32_t* __restrict__ flags,
+                                                           const int32_t* __restrict__ rank, long long n3,
+                                                           int32_t* __restrict__ ehead, long long* __restrict__ ctr) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  if (flags[i]) ehead[rank[i]] = (int32_t)i;
+  if (i == n3 - 1) {
+    const int E = rank[i] + flags[i];
+    ehead[E] = (int32_t)n3;
+    ctr[CTR_E] = E;
+  }
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_vertex_flags(const u64* __restrict__ sorted,
+                                                             const int32_t* __restrict__ ehead, long long n3, int s,
+                                                             const long long* __restrict__ ctr,
+                                                             unsigned* __restrict__ vflag) {
+  const long long e = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (e >= ctr[CTR_E]) return;
+  const int cnt = ehead[e + 1] - ehead[e];
+  if (cnt == 2) return;
+  const u64 k = sorted[ehead[e]];
+  const int a = (int)(k >> s), b = (int)(k & ((1ull << s) - 1));
+  const unsigned fl = cnt == 1 ? SMP_BOUNDARY : SMP_FROZEN;
+  atomicOr(vflag + a, fl);
+  atomicOr(vflag + b, fl);
+}
+
+// Init only: the face count of the edge at every face slot 3 f + c.
+__global__ __launch_bounds__(SMP_BLOCK) void smp_slot_counts(const int32_t* __restrict__ flags,
+                                                            const int32_t* __restrict__ rank,
+                                                            const uint32_t* __restrict__ slot,
+                                                            const int32_t* __restrict__ ehead, long long n3,
+                                                            int32_t* __restrict__ slot_cnt) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  const int e = rank[i] + flags[i] - 1;
+  slot_cnt[slot[i]] = ehead[e + 1] - ehead[e];
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_vf_pairs(const int32_t* __restrict__ faces, long long n3,
+                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  keys[i] = (uint32_t)faces[i];
+  vals[i] = (uint32_t)(i / 3);
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_vf_ranges(const uint32_t* __restrict__ k, long long n3,
+                                                          int32_t* __restrict__ vstart, int32_t* __restrict__ vend) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  if (i == 0 || k[i] != k[i - 1]) vstart[k[i]] = (int32_t)i;
+  if (i == n3 - 1 || k[i] != k[i + 1]) vend[k[i]] = (int32_t)(i + 1);
+}
+
+// Init: Q_v = sum over the faces at v in ascending face order of (face quadric, then the penalties of the face's
+// boundary edges at v in corner order).
+__global__ __launch_bounds__(SMP_BLOCK) void smp_quadrics(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                                                         const uint32_t* __restrict__ vff,
+                                                         const int32_t* __restrict__ vstart,
+                                                         const int32_t* __restrict__ vend,
+                                                         const int32_t* __restrict__ slot_cnt, long long V,
+                                                         double* __restrict__ Q) {
+  const long long v = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (v >= V) return;
+  double acc[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+  for (int j = vstart[v]; j < vend[v]; ++j) {
+    const long long f = vff[j];
+    int id[3];
+    double p[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      id[c] = faces[3 * f + c];
+      smp_load(P, id[c], p[c]);
+    }
+    double n[3], q[10];
+    smp_normal(p[0], p[1], p[2], n);
+    smp_face_quadric(p[0], n, q);
+#pragma unroll
+    for (int k = 0; k < 10; ++k) acc[k] += q[k];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int c1 = c == 2 ? 0 : c + 1;
+      if ((id[c] == v || id[c1] == v) && slot_cnt[3 * f + c] == 1) {
+        smp_boundary_quadric(p[c], p[c1], n, q);
+#pragma unroll
+        for (int k = 0; k < 10; ++k) acc[k] += q[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) Q[10 * v + k] = acc[k];
+}
+
+// ------------------------------------------------------------------------------------------------ cost
+
+__device__ __forceinline__ bool smp_has(const int32_t* __restrict__ faces, long long f, int x) {
+  return faces[3 * f] == x || faces[3 * f + 1] == x || faces[3 * f + 2] == x;
+}
+
+__device__ __forceinline__ void smp_sort3(int* t) {
+  int x;
+  if (t[0] > t[1]) { x = t[0]; t[0] = t[1]; t[1] = x; }
+  if (t[1] > t[2]) { x = t[1]; t[1] = t[2]; t[2] = x; }
+  if (t[0] > t[1]) { x = t[0]; t[0] = t[1]; t[1] = x; }
+}
+
+// Faces of the ring of `m` (a or b) that survive the collapse: no flip allowed; returns false on a flip.
+__device__ bool smp_no_flip(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                            const uint32_t* __restrict__ vff, int j0, int j1, int m, int other, const float* p) {
+  for (int j = j0; j < j1; ++j) {
+    const long long f = vff[j];
+    int id[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) id[c] = faces[3 * f + c];
+    if (id[0] == other || id[1] == other || id[2] == other) continue;
+    double po[3][3], pn[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      smp_load(P, id[c], po[c]);
+#pragma unroll
+      for (int x = 0; x < 3; ++x) pn[c][x] = id[c] == m ? (double)p[x] : po[c][x];
+    }
+    double nb[3], na[3];
+    smp_normal(po[0], po[1], po[2], nb);
+    smp_normal(pn[0], pn[1], pn[2], na);
+    if (nb[0] == 0.0 && nb[1] == 0.0 && nb[2] == 0.0) continue;
+    if (!(nb[0] * na[0] + nb[1] * na[1] + nb[2] * na[2] > 0.0)) return false;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_cost(const float* __restrict__ P, const double* __restrict__ Q,
+                                                     const unsigned* __restrict__ vflag,
+                                                     const int32_t* __restrict__ faces, const u64* __restrict__ sorted,
+                                                     const int32_t* __restrict__ ehead,
+                                                     const uint32_t* __restrict__ vff,
+                                                     const int32_t* __restrict__ vstart,
+                                                     const int32_t* __restrict__ vend, long long n3, int s,
+                                                     const long long* __restrict__ ctr, u64* __restrict__ ekey) {
+  const long long e = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (e >= ctr[CTR_E]) return;
+  const int cnt = ehead[e + 1] - ehead[e];
+  const u64 hk = sorted[ehead[e]];
+  const int a = (int)(hk >> s), b = (int)(hk & ((1ull << s) - 1));
+  const unsigned fa = vflag[a], fb = vflag[b];
+  u64 key = SMP_NONE;
+  // frozen endpoints; no pinching (an interior edge between two boundary vertices)
+  if (((fa | fb) & SMP_FROZEN) || (cnt > 1 && (fa & fb & SMP_BOUNDARY))) {
+    ekey[e] = key;
+    return;
+  }
+  float p[3];
+  double cost;
+  smp_place(Q, P, vflag, a, b, p, &cost);
+  bool ok = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && !isnan(cost);
+  const int sa = vstart[a], ea = vend[a], sb = vstart[b], eb = vend[b];
+  // link condition: distinct common neighbours == face count
+  if (ok) {
+    int common = 0;
+    for (int j = sa; j < ea; ++j) {
+      const long long f = vff[j];
+      for (int c = 0; c < 3; ++c) {
+        const int x = faces[3 * f + c];
+        if (x == a || x == b) continue;
+        bool seen = false;
+        for (int j2 = sa; j2 < j && !seen; ++j2) seen = smp_has(faces, vff[j2], x);
+        if (seen) continue;
+        bool adj = false;
+        for (int j3 = sb; j3 < eb && !adj; ++j3) adj = smp_has(faces, vff[j3], x);
+        common += adj;
+      }
+    }
+    ok = common == cnt;
+  }
+  // no flips around a or b
+  if (ok) ok = smp_no_flip(P, faces, vff, sa, ea, a, b, p) && smp_no_flip(P, faces, vff, sb, eb, b, a, p);
+  // no duplicated face: a surviving face at a against a surviving face at b (b -> a)
+  if (ok) {
+    for (int j = sa; j < ea && ok; ++j) {
+      const long long f = vff[j];
+      int t[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
+      if (t[0] == b || t[1] == b || t[2] == b) continue;
+      smp_sort3(t);
+      for (int j2 = sb; j2 < eb; ++j2) {
+        const long long g = vff[j2];
+        int u[3] = {faces[3 * g], faces[3 * g + 1], faces[3 * g + 2]};
+        if (u[0] == a || u[1] == a || u[2] == a) continue;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) u[c] = u[c] == b ? a : u[c];
+        smp_sort3(u);
+        if (t[0] == u[0] && t[1] == u[1] && t[2] == u[2]) {
+          ok = false;
+          break;
+        }
+      }
+    }
+  }
+  if (ok) {
+    const double c = cost < 0.0 ? 0.0 : cost;
+    const float cf = (float)c;
+    unsigned bits = __float_as_uint(cf);
+    if ((double)cf < c) bits += 1u;          // rounded up
+    key = (u64)bits << 32 | (u64)e;
+  }
+  ekey[e] = key;
+}
+
+// ------------------------------------------------------------------------------------------------ select
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_m1(const u64* __restrict__ ekey, const u64* __restrict__ sorted,
+                                                   const int32_t* __restrict__ ehead, int s,
+                                                   const long long* __restrict__ ctr, u64* __restrict__ m1) {
+  const long long e = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (e >= ctr[CTR_E]) return;
+  const u64 key = ekey[e];
+  if (key == SMP_NONE) return;
+  const u64 hk = sorted[ehead[e]];
+  atomicMin(m1 + (hk >> s), key);
+  atomicMin(m1 + (hk & ((1ull << s) - 1)), key);
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_m2(const int32_t* __restrict__ faces, long long F,
+                                                   const u64* __restrict__ m1, u64* __restrict__ m2) {
+  const long long f = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+  u64 m = m1[i0];
+  m = m1[i1] < m ? m1[i1] : m;
+  m = m1[i2] < m ? m1[i2] : m;
+  if (m == SMP_NONE) return;
+  atomicMin(m2 + i0, m);
+  atomicMin(m2 + i1, m);
+  atomicMin(m2 + i2, m);
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_win_flags(const u64* __restrict__ ekey, const u64* __restrict__ sorted,
+                                                          const int32_t* __restrict__ ehead, long long n3, int s,
+                                                          const u64* __restrict__ m2, long long* __restrict__ ctr,
+                                                          int32_t* __restrict__ flags) {
+  const long long e = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (e >= n3) return;
+  int win = 0;
+  if (e < ctr[CTR_E]) {
+    const u64 key = ekey[e];
+    if (key != SMP_NONE) {
+      const u64 hk = sorted[ehead[e]];
+      win = key == m2[hk >> s] && key == m2[hk & ((1ull << s) - 1)];
+      if (win) atomicAdd((unsigned long long*)(ctr + CTR_R), (unsigned long long)(ehead[e + 1] - ehead[e]));
+    }
+  }
+  flags[e] = win;
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_win_compact(const u64* __restrict__ ekey,
+                                                            const int32_t* __restrict__ flags,
+                                                            const int32_t* __restrict__ rank, long long n3,
+                                                            u64* __restrict__ wkeys, long long* __restrict__ ctr) {
+  const long long e = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (e >= n3) return;
+  if (flags[e]) wkeys[rank[e]] = ekey[e];
+  if (e == n3 - 1) ctr[CTR_W] = rank[e] + flags[e];
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_win_counts(const u64* __restrict__ wkeys, long long W,
+                                                           const int32_t* __restrict__ ehead,
+                                                           int32_t* __restrict__ cnt) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= W) return;
+  const long long e = (long long)(wkeys[i] & 0xFFFFFFFFull);
+  cnt[i] = ehead[e + 1] - ehead[e];
+}
+
+// ------------------------------------------------------------------------------------------------ collapse, compact
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_collapse(const u64* __restrict__ wkeys, long long W,
+                                                         const int32_t* __restrict__ pre, long long need,
+                                                         const u64* __restrict__ sorted,
+                                                         const int32_t* __restrict__ ehead, int s,
+                                                         const unsigned* __restrict__ vflag,
+                                                         const uint32_t* __restrict__ vff,
+                                                         const int32_t* __restrict__ vstart,
+                                                         const int32_t* __restrict__ vend, float* P, double* Q,
+                                                         int32_t* faces, long long* __restrict__ ctr) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= W) return;
+  if (pre && pre[i] >= need) return;
+  if (pre) atomicAdd((unsigned long long*)(ctr + CTR_ACC), 1ull);
+  const long long e = (long long)(wkeys[i] & 0xFFFFFFFFull);
+  const u64 hk = sorted[ehead[e]];
+  const int a = (int)(hk >> s), b = (int)(hk & ((1ull << s) - 1));
+  float p[3];
+  double cost;
+  smp_place(Q, P, vflag, a, b, p, &cost);
+  for (int j = vstart[b]; j < vend[b]; ++j) {
+    const long long f = vff[j];
+    if (smp_has(faces, f, a)) {
+      faces[3 * f] = -1;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (faces[3 * f + c] == b) faces[3 * f + c] = a;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) Q[10 * (long long)a + k] = Q[10 * (long long)a + k] + Q[10 * (long long)b + k];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) P[3 * (long long)a + c] = p[c];
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_face_alive(const int32_t* __restrict__ faces, long long F,
+                                                           int32_t* __restrict__ flags) {
+  const long long f = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  flags[f] = faces[3 * f] >= 0;
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_face_scatter(const int32_t* __restrict__ faces, long long F,
+                                                             const int32_t* __restrict__ flags,
+                                                             const int32_t* __restrict__ rank,
+                                                             int32_t* __restrict__ out, long long* __restrict__ ctr) {
+  const long long f = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  if (flags[f]) {
+    const long long o = rank[f];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * o + c] = faces[3 * f + c];
+  }
+  if (f == F - 1) ctr[CTR_F] = rank[f] + flags[f];
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_mark_used(const int32_t* __restrict__ faces, long long n3,
+                                                          int32_t* __restrict__ used) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  used[faces[i]] = 1;
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_out_verts(const float* __restrict__ P, long long V,
+                                                          const int32_t* __restrict__ used,
+                                                          const int32_t* __restrict__ vnew, float* __restrict__ out,
+                                                          long long* __restrict__ ctr) {
+  const long long v = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (v >= V) return;
+  if (used[v]) {
+    const long long o = vnew[v];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * o + c] = P[3 * v + c];
+  }
+  if (v == V - 1) ctr[CTR_V] = vnew[v] + used[v];
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void smp_out_faces(const int32_t* __restrict__ faces, long long n3,
+                                                          const int32_t* __restrict__ vnew,
+                                                          int32_t* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  out[i] = vnew[faces[i]];
+}
+
+// ------------------------------------------------------------------------------------------------ host
+
+static size_t smp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct SmpLayout {
+  size_t pos, Q, vflag, vstart, vend, m1, m2, fa, fb, A, B, flags, rank, ehead, ekey, vfk, vff, ctr, tmp, tmp_bytes,
+      total;
+};
+
+static int smp_check(long long V, long long F) {
+  if (V < 1 || F < 1) return VSA_ERR_ARG;
+  if (V > 0x7FFFFFFFll || F > 0x7FFFFFFFll / 3 - 1) return VSA_ERR_UNSUPPORTED;
+  return VSA_OK;
+}
+
+static int smp_layout(long long V, long long F, SmpLayout* l) {
+  const size_t v = (size_t)V, n3 = 3 * (size_t)F;
+  size_t t = 0, need = 0;
+  // rocPRIM temporary storage: the largest of every sort and scan below
+  VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (const uint32_t*)nullptr,
+                                        (uint32_t*)nullptr, n3, 0, 64, (hipStream_t)0));
+  need = t > need ? t : need;
+  VSA_HIP_TRY(rocprim::radix_sort_keys(nullptr, t, (const u64*)nullptr, (u64*)nullptr, n3, 0, 64, (hipStream_t)0));
+  need = t > need ? t : need;
+  VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0, 32, (hipStream_t)0));
+  need = t > need ? t : need;
+  VSA_HIP_TRY(rocprim::exclusive_scan(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, 0, n3 > v ? n3 : v,
+                                      rocprim::plus<int32_t>(), (hipStream_t)0));
+  need = t > need ? t : need;
+  size_t o = 0;
+#define SMP_AT(field, bytes) \
+  l->field = o;              \
+  o += smp_align(bytes)
+  SMP_AT(pos, 12 * v);
+  SMP_AT(Q, 80 * v);
+  SMP_AT(vflag, 4 * v);
+  SMP_AT(vstart, 4 * v);
+  SMP_AT(vend, 4 * v);
+  SMP_AT(m1, 8 * v);
+  SMP_AT(m2, 8 * v);
+  SMP_AT(fa, 4 * n3);
+  SMP_AT(fb, 4 * n3);
+  SMP_AT(A, 8 * n3);
+  SMP_AT(B, 8 * n3);
+  SMP_AT(flags, 4 * (n3 > v ? n3 : v));
+  SMP_AT(rank, 4 * (n3 > v ? n3 : v));
+  SMP_AT(ehead, 4 * (n3 + 1));
+  SMP_AT(ekey, 8 * n3);
+  SMP_AT(vfk, 4 * n3);
+  SMP_AT(vff, 4 * n3);
+  SMP_AT(ctr, 8 * CTR_N);
+  SMP_AT(tmp, need ? need : 16);
+#undef SMP_AT
+  l->tmp_bytes = need ? need : 16;
+  l->total = o;
+  return VSA_OK;
+}
+
+extern "C" long long vsa_simplify_workspace_bytes(long long nr_verts, long long nr_faces) {
+  const int rc = smp_check(nr_verts, nr_faces);
+  if (rc != VSA_OK) return rc;
+  SmpLayout l;
+  const int rl = smp_layout(nr_verts, nr_faces, &l);
+  if (rl != VSA_OK) return rl;
+  return (long long)l.total;
+}
+
+namespace {
+
+struct Smp {
+  hipStream_t st;
+  char* ws;
+  SmpLayout l;
+  long long V, F;
+  int s;
+  float* P;
+  double* Q;
+  unsigned* vflag;
+  int32_t *vstart, *vend, *fcur, *fnext, *flags, *rank, *ehead;
+  u64 *m1, *m2, *A, *B, *ekey;
+  uint32_t *vfk, *vff;
+  long long* ctr;
+  hipEvent_t ev[2];
+  float* stage_ms;
+};
+
+dim3 grid_of(long long n) { return dim3((unsigned)vsa_div_up(n > 0 ? n : 1, SMP_BLOCK)); }
+
+int smp_scan(Smp& m, const int32_t* in, int32_t* out, long long n) {
+  size_t bytes = m.l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::exclusive_scan(m.ws + m.l.tmp, bytes, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), m.st));
+  return VSA_OK;
+}
+
+// Stage timing (only when stage_ms is given): stage_open() opens a stage, stage_close(k) adds its device time to
+// stage_ms[k].
+int stage_open(Smp& m) {
+  if (m.stage_ms) VSA_HIP_TRY(hipEventRecord(m.ev[0], m.st));
+  return VSA_OK;
+}
+
+int stage_close(Smp& m, int k) {
+  if (!m.stage_ms) return VSA_OK;
+  float ms = 0.f;
+  VSA_HIP_TRY(hipEventRecord(m.ev[1], m.st));
+  VSA_HIP_TRY(hipEventSynchronize(m.ev[1]));
+  VSA_HIP_TRY(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
+  m.stage_ms[k] += ms;
+  return VSA_OK;
+}
+
+// Unique edges of the F current faces (sorted keys in B, ids via flags / rank, ehead, E on the device); with
+// `slots`, the sorted slot of every key lands in vff and the edge's face count at every face slot in slot_cnt.
+int build_edges(Smp& m, bool slots, int32_t* slot_cnt) {
+  const long long n3 = 3 * m.F;
+  size_t bytes = m.l.tmp_bytes;
+  uint32_t* vin = slots ? m.vfk : nullptr;
+  hipLaunchKernelGGL(smp_edge_keys, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.s, m.A, vin);
+  VSA_HIP_TRY(hipGetLastError());
+  if (slots)
+    VSA_HIP_TRY(rocprim::radix_sort_pairs(m.ws + m.l.tmp, bytes, m.A, m.B, vin, m.vff, (size_t)n3, 0, 2 * m.s, m.st));
+  else
+    VSA_HIP_TRY(rocprim::radix_sort_keys(m.ws + m.l.tmp, bytes, m.A, m.B, (size_t)n3, 0, 2 * m.s, m.st));
+  hipLaunchKernelGGL(smp_heads, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.B, n3, m.flags);
+  VSA_HIP_TRY(hipGetLastError());
+  int rc = smp_scan(m, m.flags, m.rank, n3);
+  if (rc != VSA_OK) return rc;
+  hipLaunchKernelGGL(smp_edge_index, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.flags, m.rank, n3, m.ehead, m.ctr);
+  VSA_HIP_TRY(hipGetLastError());
+  if (slots) {
+    hipLaunchKernelGGL(smp_slot_counts, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.flags, m.rank, m.vff, m.ehead, n3,
+                       slot_cnt);
+    VSA_HIP_TRY(hipGetLastError());
+  }
+  return VSA_OK;
+}
+
+// The (vertex, face) list sorted by vertex (stable: ascending face within a vertex) -> vff, vstart / vend.
+int build_rings(Smp& m) {
+  const long long n3 = 3 * m.F;
+  uint32_t* kin = reinterpret_cast<uint32_t*>(m.A);
+  uint32_t* vin = kin + n3;
+  size_t bytes = m.l.tmp_bytes;
+  hipLaunchKernelGGL(smp_vf_pairs, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, kin, vin);
+  VSA_HIP_TRY(hipGetLastError());
+  VSA_HIP_TRY(rocprim::radix_sort_pairs(m.ws + m.l.tmp, bytes, kin, m.vfk, vin, m.vff, (size_t)n3, 0, m.s, m.st));
+  VSA_HIP_TRY(hipMemsetAsync(m.vstart, 0, 4 * (size_t)m.V, m.st));
+  VSA_HIP_TRY(hipMemsetAsync(m.vend, 0, 4 * (size_t)m.V, m.st));
+  hipLaunchKernelGGL(smp_vf_ranges, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.vfk, n3, m.vstart, m.vend);
+  VSA_HIP_TRY(hipGetLastError());
+  return VSA_OK;
+}
+
+#define SMP_TRY(expr)              \
+  do {                             \
+    const int r__ = (expr);        \
+    if (r__ != VSA_OK) return r__; \
+  } while (0)
+
+int run(Smp& m, const float* verts, const int32_t* faces, long long target, float* out_verts, int32_t* out_faces,
+        long long* stats) {
+  const long long V = m.V;
+  long long rounds = 0, collapses = 0, stalled = 0;
+  SMP_TRY(stage_open(m));
+  VSA_HIP_TRY(hipMemcpyAsync(m.P, verts, 12 * (size_t)V, hipMemcpyDeviceToDevice, m.st));
+  VSA_HIP_TRY(hipMemcpyAsync(m.fcur, faces, 12 * (size_t)m.F, hipMemcpyDeviceToDevice, m.st));
+  VSA_HIP_TRY(hipMemsetAsync(m.ctr, 0, 8 * CTR_N, m.st));
+  int32_t* slot_cnt = reinterpret_cast<int32_t*>(m.ekey);
+  SMP_TRY(build_edges(m, true, slot_cnt));
+  SMP_TRY(build_rings(m));
+  hipLaunchKernelGGL(smp_quadrics, grid_of(V), dim3(SMP_BLOCK), 0, m.st, m.P, m.fcur, m.vff, m.vstart, m.vend,
+                     slot_cnt, V, m.Q);
+  VSA_HIP_TRY(hipGetLastError());
+  SMP_TRY(stage_close(m, 0));
+  while (m.F > target) {
+    const long long n3 = 3 * m.F;
+    // edges
+    SMP_TRY(stage_open(m));
+    SMP_TRY(build_edges(m, false, nullptr));
+    VSA_HIP_TRY(hipMemsetAsync(m.vflag, 0, 4 * (size_t)V, m.st));
+    hipLaunchKernelGGL(smp_vertex_flags, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.B, m.ehead, n3, m.s, m.ctr, m.vflag);
+    VSA_HIP_TRY(hipGetLastError());
+    SMP_TRY(build_rings(m));
+    SMP_TRY(stage_close(m, 1));
+    // cost
+    SMP_TRY(stage_open(m));
+    hipLaunchKernelGGL(smp_cost, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.P, m.Q, m.vflag, m.fcur, m.B, m.ehead, m.vff,
+                       m.vstart, m.vend, n3, m.s, m.ctr, m.ekey);
+    VSA_HIP_TRY(hipGetLastError());
+    SMP_TRY(stage_close(m, 2));
+    // select
+    SMP_TRY(stage_open(m));
+    VSA_HIP_TRY(hipMemsetAsync(m.m1, 0xFF, 8 * (size_t)V, m.st));
+    VSA_HIP_TRY(hipMemsetAsync(m.m2, 0xFF, 8 * (size_t)V, m.st));
+    VSA_HIP_TRY(hipMemsetAsync(m.ctr + CTR_R, 0, 8, m.st));
+    hipLaunchKernelGGL(smp_m1, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.B, m.ehead, m.s, m.ctr, m.m1);
+    VSA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(smp_m2, grid_of(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.m1, m.m2);
+    VSA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(smp_win_flags, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.B, m.ehead, n3, m.s, m.m2,
+                       m.ctr, m.flags);
+    VSA_HIP_TRY(hipGetLastError());
+    SMP_TRY(smp_scan(m, m.flags, m.rank, n3));
+    u64* wkeys = m.A;
+    u64* wsorted = m.A + m.F;   // winners share no face: W <= F
+    hipLaunchKernelGGL(smp_win_compact, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.flags, m.rank, n3, wkeys,
+                       m.ctr);
+    VSA_HIP_TRY(hipGetLastError());
+    long long wr[2];
+    VSA_HIP_TRY(hipMemcpyAsync(wr, m.ctr + CTR_W, sizeof(wr), hipMemcpyDeviceToHost, m.st));
+    VSA_HIP_TRY(hipStreamSynchronize(m.st));
+    const long long W = wr[0], R = wr[1], need = m.F - target;
+    if (W < 0 || W > m.F) return VSA_ERR_UNSUPPORTED;
+    if (W == 0) {
+      SMP_TRY(stage_close(m, 3));
+      stalled = 1;
+      break;
+    }
+    const u64* list = wkeys;
+    const int32_t* pre = nullptr;
+    if (R > need) {
+      size_t bytes = m.l.tmp_bytes;
+      VSA_HIP_TRY(rocprim::radix_sort_keys(m.ws + m.l.tmp, bytes, wkeys, wsorted, (size_t)W, 0, 64, m.st));
+      hipLaunchKernelGGL(smp_win_counts, grid_of(W), dim3(SMP_BLOCK), 0, m.st, wsorted, W, m.ehead, m.flags);
+      VSA_HIP_TRY(hipGetLastError());
+      SMP_TRY(smp_scan(m, m.flags, m.rank, W));
+      list = wsorted;
+      pre = m.rank;
+    }
+    SMP_TRY(stage_close(m, 3));
+    // collapse
+    SMP_TRY(stage_open(m));
+    hipLaunchKernelGGL(smp_collapse, grid_of(W), dim3(SMP_BLOCK), 0, m.st, list, W, pre, need, m.B, m.ehead, m.s,
+                       m.vflag, m.vff, m.vstart, m.vend, m.P, m.Q, m.fcur, m.ctr);
+    VSA_HIP_TRY(hipGetLastError());
+    SMP_TRY(stage_close(m, 4));
+    // compact
+    SMP_TRY(stage_open(m));
+    hipLaunchKernelGGL(smp_face_alive, grid_of(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags);
+    VSA_HIP_TRY(hipGetLastError());
+    SMP_TRY(smp_scan(m, m.flags, m.rank, m.F));
+    hipLaunchKernelGGL(smp_face_scatter, grid_of(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags, m.rank, m.fnext,
+                       m.ctr);
+    VSA_HIP_TRY(hipGetLastError());
+    int32_t* t = m.fcur;
+    m.fcur = m.fnext;
+    m.fnext = t;
+    ++rounds;
+    if (pre) {
+      // the last round: read the faces left and the accepted collapses back (F <= target now)
+      long long fa[2];
+      VSA_HIP_TRY(hipMemcpyAsync(fa, m.ctr + CTR_F, sizeof(fa), hipMemcpyDeviceToHost, m.st));
+      VSA_HIP_TRY(hipStreamSynchronize(m.st));
+      if (fa[0] < 0 || fa[0] > target || fa[1] < 1 || fa[1] > W) return VSA_ERR_UNSUPPORTED;
+      collapses += fa[1];
+      m.F = fa[0];
+    } else {
+      collapses += W;
+      m.F -= R;
+    }
+    SMP_TRY(stage_close(m, 5));
+  }
+  // output: the referenced vertices in ascending index, faces in order
+  SMP_TRY(stage_open(m));
+  const long long n3 = 3 * m.F;
+  VSA_HIP_TRY(hipMemsetAsync(m.flags, 0, 4 * (size_t)V, m.st));
+  hipLaunchKernelGGL(smp_mark_used, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.flags);
+  VSA_HIP_TRY(hipGetLastError());
+  SMP_TRY(smp_scan(m, m.flags, m.rank, V));
+  hipLaunchKernelGGL(smp_out_verts, grid_of(V), dim3(SMP_BLOCK), 0, m.st, m.P, V, m.flags, m.rank, out_verts, m.ctr);
+  VSA_HIP_TRY(hipGetLastError());
+  if (n3 > 0) {
+    hipLaunchKernelGGL(smp_out_faces, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.rank, out_faces);
+    VSA_HIP_TRY(hipGetLastError());
+  }
+  long long vout = 0;
+  VSA_HIP_TRY(hipMemcpyAsync(&vout, m.ctr + CTR_V, sizeof(vout), hipMemcpyDeviceToHost, m.st));
+  VSA_HIP_TRY(hipStreamSynchronize(m.st));
+  SMP_TRY(stage_close(m, 5));
+  stats[0] = rounds;
+  stats[1] = collapses;
+  stats[2] = stalled;
+  stats[3] = vout;
+  stats[4] = m.F;
+  return VSA_OK;
+}
+
+}  // namespace
+
+extern "C" int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                            long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
+                            int32_t* out_faces, long long* stats, float* stage_ms, void* stream) {
+  if (!verts || !faces || !workspace || !out_verts || !out_faces || !stats || target_faces < 0) return VSA_ERR_ARG;
+  int rc = smp_check(nr_verts, nr_faces);
+  if (rc != VSA_OK) return rc;
+  Smp m;
+  rc = smp_layout(nr_verts, nr_faces, &m.l);
+  if (rc != VSA_OK) return rc;
+  if (workspace_bytes < (long long)m.l.total) return VSA_ERR_ARG;
+  m.st = (hipStream_t)stream;
+  m.ws = static_cast<char*>(workspace);
+  m.V = nr_verts;
+  m.F = nr_faces;
+  m.s = 1;
+  while ((1ll << m.s) < nr_verts) ++m.s;
+  m.P = reinterpret_cast<float*>(m.ws + m.l.pos);
+  m.Q = reinterpret_cast<double*>(m.ws + m.l.Q);
+  m.vflag = reinterpret_cast<unsigned*>(m.ws + m.l.vflag);
+  m.vstart = reinterpret_cast<int32_t*>(m.ws + m.l.vstart);
+  m.vend = reinterpret_cast<int32_t*>(m.ws + m.l.vend);
+  m.m1 = reinterpret_cast<u64*>(m.ws + m.l.m1);
+  m.m2 = reinterpret_cast<u64*>(m.ws + m.l.m2);
+  m.fcur = reinterpret_cast<int32_t*>(m.ws + m.l.fa);
+  m.fnext = reinterpret_cast<int32_t*>(m.ws + m.l.fb);
+  m.A = reinterpret_cast<u64*>(m.ws + m.l.A);
+  m.B = reinterpret_cast<u64*>(m.ws + m.l.B);
+  m.flags = reinterpret_cast<int32_t*>(m.ws + m.l.flags);
+  m.rank = reinterpret_cast<int32_t*>(m.ws + m.l.rank);
+  m.ehead = reinterpret_cast<int32_t*>(m.ws + m.l.ehead);
+  m.ekey = reinterpret_cast<u64*>(m.ws + m.l.ekey);
+  m.vfk = reinterpret_cast<uint32_t*>(m.ws + m.l.vfk);
+  m.vff = reinterpret_cast<uint32_t*>(m.ws + m.l.vff);
+  m.ctr = reinterpret_cast<long long*>(m.ws + m.l.ctr);
+  m.stage_ms = stage_ms;
+  if (stage_ms) {
+    for (int k = 0; k < 6; ++k) stage_ms[k] = 0.f;
+    VSA_HIP_TRY(hipEventCreate(&m.ev[0]));
+    VSA_HIP_TRY(hipEventCreate(&m.ev[1]));
+  }
+  rc = run(m, verts, faces, target_faces, out_verts, out_faces, stats);
+  if (stage_ms) {
+    (void)hipEventDestroy(m.ev[0]);
+    (void)hipEventDestroy(m.ev[1]);
+  }
+  return rc;
+}
