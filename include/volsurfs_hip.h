@@ -1163,6 +1163,80 @@ int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, l
                  long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
                  int32_t* out_faces, long long* stats, float* stage_ms, void* stream);
 
+/* ------------------------------------------------------------------------
+ * UV atlas (csrc/atlas.hip): box-projection charts of one uv-less, consistently wound triangle mesh, packed into one
+ * square atlas -- the baker's `--compute_meshes_xatlas` step (xatlas in the reference, volsurfs_py/baker.py:727-776,
+ * utils/texture_extraction.py::compute_o3d_mesh_atlas).
+ *   verts [V, 3] f32 and faces [F, 3] i32 on the device: finite, indices in [0, V), no index twice in one face (the
+ *   caller checks).  V, F >= 1.  resolution R in [8, 16384] (the atlas is R x R texels); padding p >= 0, 2p < R.
+ * Rules (the output is a function of the mesh, R and p only; tests/test_atlas.py::restate restates them in numpy and
+ * the kernels are held to it bit for bit; fp32 unless said, in the order written, with no contraction):
+ *   label         n_f = (p1 - p0) x (p2 - p0) (e1 = p1 - p0, e2 = p2 - p0, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z,
+ *                 e1x e2y - e1y e2x)).  N_v = 0 + the n_f of the faces at v in ascending face index (a sorted
+ *                 (vertex, face) list); s_f = (N_a + N_b) + N_c.  Directions d = +x, -x, +y, -y, +z, -z (labels 0..5);
+ *                 the candidate is the argmax of s_f . d (a component or its negation), ties to the earlier direction.
+ *                 It is kept when n_f . d >= 0.5 |n_f|, evaluated in fp64 as c >= 0 and 4 (c c) >= (nx nx + ny ny) +
+ *                 nz nz (c = n_f . d); otherwise the label is the argmax of n_f . d.  n_f = 0: label 0.  So a face keeps
+ *                 at least half its area in projection and never flips.
+ *   charts        faces f < g join when they share an undirected edge that has exactly two face corners, traverse it
+ *                 in opposite directions, have the same label and the same split code, and the code is not 0.  A chart
+ *                 is a connected component of the joins; its id is its minimum face index (union-find hooks the larger
+ *                 root under the smaller), and charts are numbered 0 .. C-1 in ascending id.
+ *   projection    by label: +x -> (u, v) = (y, z), -x -> (z, y), +y -> (z, x), -y -> (x, z), +z -> (x, y), -z -> (y, x)
+ *                 (coordinates picked: exact; a face's projected signed area is >= 0).  Chart box: min / max of the
+ *                 corners' u and v over its faces (as ordered float bits: -0 < +0).  w = umax - umin, h = vmax - vmin;
+ *                 a chart with h > w is rotated by 90 degrees: local (x, y) = (vmax - v, u - umin), else (u - umin,
+ *                 v - vmin); extents (ew, eh) = (h, w) rotated, else (w, h).
+ *   pack          at density s (texels per unit), side(e) = ceil(e * s) + 2p, or R + 1 when ceil(e * s) > R; a chart's
+ *                 rectangle is side(ew) x side(eh).  Rectangles sorted by (height desc, width desc, chart) are laid on
+ *                 next-fit shelves of width R: a shelf starts at y = the heights of the shelves before it, takes
+ *                 rectangles while their widths sum to <= R (a rectangle wider than R does not fit), and its height is
+ *                 its first rectangle's.  The pack fits when the shelves' heights sum to <= R.  s = 0 fits when p = 0
+ *                 or ceil(C / floor(R / 2p)) 2p <= R (else VSA_ERR_ATLAS_FULL); then s is the fp32 whose bit pattern
+ *                 ends a bisection over bits lo = 0 (fits), hi = 0x7F800000 (never tried): mid = lo + (hi - lo) / 2
+ *                 while hi - lo > 1, lo = mid when it fits, else hi = mid.
+ *   uv            a corner of a face of chart c at offset (ox, oy): ((x * s + (float)(ox + p)) / R, (y * s +
+ *                 (float)(oy + p)) / R), in [0, 1].  Chart contents lie p texels inside their rectangles, so two
+ *                 charts' contents are at least 2p texels apart.
+ *   raster        corners snapped in fp64: X = rint(clamp(u, 0, 1) * 256 R), Y likewise (int64, 1/256 texel, ties to
+ *                 even).  Texel (i, j) (i along u, j along v; index j R + i) has centre (256 i + 128, 256 j + 128); it
+ *                 is covered by a face with A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) > 0 when for every edge a -> b
+ *                 (0 -> 1, 1 -> 2, 2 -> 0), e = dx (py - ay) - dy (px - ax) > 0, or e = 0 on a top-left edge (dy < 0, or
+ *                 dy = 0 and dx < 0).  Faces with A <= 0 cover nothing.  A shared edge's points count once.
+ *   overlap       after a pack, per-texel coverage counts of all faces; a chart holding a texel counted twice overlaps
+ *                 itself (packed rectangles are disjoint).  Every face of such a chart: code 0 (one chart per face)
+ *                 when its code is >= 2^24 (depth cap 24); else code = 2 code + side, side = 1 when (c0 + c1) + c2 >
+ *                 1.5 (lo + hi) in fp64, with c_k the corners' coordinates along the chart box's longer side (u when
+ *                 w >= h) and [lo, hi] the box on it.  Codes start at 1.  Charts are rebuilt and packed again, until
+ *                 no chart overlaps itself.  VSA_ERR_UNSUPPORTED when a split changes no face's code (the next round
+ *                 would repeat this one) or when round 100 (split rounds + 1) still finds an overlapping chart.
+ *   output        out_faces_uvs [F, 3, 2] f32; out_chart [F] i32 (chart number); [host] scale: s; [host] stats 4 long
+ *                 long: charts C, split rounds, covered texels (count >= 1), and on VSA_ERR_ATLAS_FULL the smallest
+ *                 resolution at which C charts fit at s = 0 (else 0).
+ *   stage_ms      [host] 5 floats or NULL: device ms of label, charts, pack, emit, raster (the overlap passes and the
+ *                 split included) (events, one stream synchronisation per stage; NULL: none).
+ * The host reads the chart count once per round, one fit flag per bisection step (31), the tile total and the number
+ * of overlapping charts; the call synchronises `stream` before it returns.
+ *   workspace     vsa_atlas_workspace_bytes(V, F, R): 20 bytes per vertex, 216 per face and 4 R^2 plus rocPRIM's
+ *                 temporary storage (radix sorts of 3F keys) -- O(V + F + R^2).
+ * VSA_ERR_ARG: a NULL pointer, V or F < 1, R outside [8, 16384], p < 0 or 2p >= R, a workspace smaller than asked for.
+ * VSA_ERR_UNSUPPORTED: V >= 2^31 or 3 F + 3 >= 2^31 (and from the queries, a failed rocPRIM size query: no device).
+ * VSA_ERR_ATLAS_FULL: C charts do not fit even at s = 0.  The
+ * workspace query returns the byte count or one of those codes.
+ *
+ * vsa_atlas_rasterize: the raster rule above on any faces_uvs [F, 3, 2] f32 (device): out_face_id [R, R] i32 (the lowest
+ * covering face, -1 when none) and out_count [R, R] i32 (covering faces), row j = v.  Workspace
+ * vsa_atlas_rasterize_workspace_bytes(F) (16 bytes per face plus a scan's storage).  Synchronises `stream`.
+ */
+#define VSA_ERR_ATLAS_FULL (-3)
+long long vsa_atlas_workspace_bytes(long long nr_verts, long long nr_faces, int resolution);
+int vsa_atlas(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, int resolution,
+              int padding, void* workspace, long long workspace_bytes, float* out_faces_uvs, int32_t* out_chart,
+              long long* stats, float* scale, float* stage_ms, void* stream);
+long long vsa_atlas_rasterize_workspace_bytes(long long nr_faces);
+int vsa_atlas_rasterize(const float* faces_uvs, long long nr_faces, int resolution, void* workspace,
+                        long long workspace_bytes, int32_t* out_face_id, int32_t* out_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,206 @@
+"""UV atlases of extracted shells on the device: the baker's `--compute_meshes_xatlas` step (volsurfs_py/baker.py:727-776,
+utils/texture_extraction.py::compute_o3d_mesh_atlas, xatlas with padding 3 in the reference) as box-projection charts
+packed into one square atlas in HIP (csrc/atlas.hip, rules in include/volsurfs_hip.h and DESIGN §16).
+
+* `compute_atlas` — one uv-less, consistently wound TensorMesh (what `marching_cubes` / `simplify_mesh` return) with
+  per-corner UVs; vertices and faces unchanged; output bits depend on the mesh, the resolution and the padding only.
+* `rasterize_atlas` — which face covers each texel of an atlas, and how many do.
+* `compute_meshes_atlas` — every `<level>.ply` of a directory (what `simplify.simplify_meshes` writes) into
+  `<level>.obj` with UVs plus `atlas/<level>.png` (the reference's `meshes_simplified_uvs/`), the neural-texture
+  branch's input.
+"""
+import ctypes
+import os
+
+import torch
+
+from . import _lib
+from .mesh import TensorMesh, load_ply, save_obj
+
+STAGES = ("label", "charts", "pack", "emit", "raster")
+ERR_ATLAS_FULL = -3
+
+
+def workspace_bytes(nr_verts, nr_faces, resolution):
+    """Device workspace of one atlas of a mesh with `nr_verts` vertices and `nr_faces` faces at `resolution`^2."""
+    n = _lib.lib().vsa_atlas_workspace_bytes(int(nr_verts), int(nr_faces), int(resolution))
+    if n < 0:
+        raise _lib.VolsurfsHipError(f"vsa_atlas_workspace_bytes failed with status {n}")
+    return int(n)
+
+
+def min_resolution(charts, padding):
+    """Smallest resolution at which `charts` rectangles of (2 padding)^2 texels (every chart at zero size) fit on
+    next-fit shelves."""
+    side = 2 * int(padding)
+    r = max(side, 1)
+    while True:
+        per = r // side if side else charts
+        if per > 0 and -(-charts // per) * side <= r:
+            return r
+        r += 1
+
+
+def full_message(charts, resolution, padding, smallest):
+    return (f"compute_atlas: {charts} charts do not fit a {resolution} x {resolution} atlas with padding {padding} "
+            f"even at zero size; the smallest resolution that holds them is {smallest}")
+
+
+def _check(mesh, resolution, padding):
+    resolution, padding = int(resolution), int(padding)
+    if not 8 <= resolution <= 16384:
+        raise ValueError(f"compute_atlas: resolution must lie in [8, 16384], got {resolution}")
+    if padding < 0 or 2 * padding >= resolution:
+        raise ValueError(f"compute_atlas: padding must satisfy 0 <= 2 * padding < resolution, got {padding}")
+    V, F = mesh.vertices, mesh.faces
+    if not (V.is_cuda and F.is_cuda):
+        raise ValueError(f"compute_atlas: the mesh must be on cuda, got {V.device} / {F.device}")
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError(f"compute_atlas: expected vertices [V, 3] and faces [F, 3], got {tuple(V.shape)} / "
+                         f"{tuple(F.shape)}")
+    V = V.to(torch.float32).contiguous()
+    F = F.to(torch.int32).contiguous()
+    if F.shape[0] == 0:
+        return V, F, resolution, padding
+    if not bool(torch.isfinite(V).all()):
+        raise _lib.VolsurfsHipError("compute_atlas: the vertices hold NaN or inf")
+    lo, hi = torch.aminmax(F)
+    if int(lo) < 0 or int(hi) >= V.shape[0]:
+        raise _lib.VolsurfsHipError(f"compute_atlas: face indices out of range [0, {V.shape[0]}): "
+                                    f"min {int(lo)}, max {int(hi)}")
+    if bool(((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 2] == F[:, 0])).any()):
+        raise _lib.VolsurfsHipError("compute_atlas: a face names one vertex twice")
+    return V, F, resolution, padding
+
+
+@torch.no_grad()
+def _atlas(V, F, R, p, stage_ms=None):
+    """The C-ABI call: (faces_uvs [F, 3, 2], chart [F], stats dict)."""
+    nv, nf = int(V.shape[0]), int(F.shape[0])
+    ws = torch.empty(workspace_bytes(nv, nf, R), dtype=torch.uint8, device=V.device)
+    uv = torch.empty(nf, 3, 2, device=V.device)
+    chart = torch.empty(nf, dtype=torch.int32, device=V.device)
+    stats = (ctypes.c_longlong * 4)()
+    scale = ctypes.c_float(0.0)
+    ms = (ctypes.c_float * len(STAGES))() if stage_ms is not None else None
+    rc = _lib.lib().vsa_atlas(V.data_ptr(), nv, F.data_ptr(), nf, R, p, ws.data_ptr(), ws.numel(), uv.data_ptr(),
+                              chart.data_ptr(), ctypes.addressof(stats), ctypes.addressof(scale),
+                              ctypes.addressof(ms) if ms is not None else None, _lib.stream_ptr().value)
+    if rc == ERR_ATLAS_FULL:
+        raise _lib.VolsurfsHipError(full_message(int(stats[0]), R, p, int(stats[3])))
+    if rc != 0:
+        raise _lib.VolsurfsHipError(f"vsa_atlas failed with status {rc}")
+    if ms is not None:
+        stage_ms.update({k: float(ms[i]) for i, k in enumerate(STAGES)})
+    charts, splits, covered = int(stats[0]), int(stats[1]), int(stats[2])
+    st = {"charts": charts, "split_rounds": splits, "scale": float(scale.value), "covered": covered,
+          "utilization": covered / float(R * R), "resolution": R, "padding": p}
+    return uv, chart, st
+
+
+def compute_atlas(mesh, resolution=1024, padding=4, return_stats=False, return_charts=False, stage_ms=None):
+    """Per-corner UVs for a uv-less, consistently wound cuda TensorMesh by box projection: faces grouped
+    by normal direction into connected charts, each projected along its direction (at least half of every face's area
+    survives, no face flips), charts that overlap themselves split, and all packed by shelves into one
+    `resolution`^2 atlas at the largest texel density the bisection finds.  Returns a TensorMesh with the same
+    vertices and faces and `has_uvs = True`; with `return_stats` also {charts, split_rounds, scale (texels per unit),
+    covered, utilization (covered texels / resolution^2), resolution, padding}; with `return_charts` also the chart
+    number per face.
+
+    Padding: chart contents sit `padding` texels inside their rectangles, so two charts are at least 2 * padding
+    texels apart at `resolution`.  The default 4 at 1024 keeps them 2 texels apart at 256, the coarsest default
+    `textures_res` of the neural textures, so a bilinear lookup (which reads a 2 x 2 texel footprint) at every level
+    of the texture pyramid never mixes two charts.  The reference's xatlas call uses 3.
+
+    Raises VolsurfsHipError (naming the chart count and the smallest resolution that would hold them) when the charts
+    do not fit even at zero size."""
+    V, F, R, p = _check(mesh, resolution, padding)
+    if F.shape[0] == 0:
+        uv = torch.zeros(0, 3, 2, device=V.device)
+        chart = torch.zeros(0, dtype=torch.int32, device=V.device)
+        st = {"charts": 0, "split_rounds": 0, "scale": 0.0, "covered": 0, "utilization": 0.0, "resolution": R,
+              "padding": p}
+    else:
+        uv, chart, st = _atlas(V, F, R, p, stage_ms)
+    out = TensorMesh(V, F, uv, device=V.device)
+    out.has_uvs = True
+    res = (out,)
+    if return_stats:
+        res += (st,)
+    if return_charts:
+        res += (chart,)
+    return res[0] if len(res) == 1 else res
+
+
+@torch.no_grad()
+def rasterize_atlas(mesh, resolution):
+    """(face_id [R, R] i32, count [R, R] i32) of a cuda mesh's faces_uvs: row j holds texel centres v = (j + 0.5) / R,
+    column i u = (i + 0.5) / R; face_id is the lowest face covering the texel (-1: none), count the number of faces
+    covering it (header rule: 1/256-texel snapping, top-left fill, faces of zero or negative UV area cover nothing)."""
+    R = int(resolution)
+    if not 8 <= R <= 16384:
+        raise ValueError(f"rasterize_atlas: resolution must lie in [8, 16384], got {R}")
+    uv = mesh.get_faces_uvs() if isinstance(mesh, TensorMesh) else mesh
+    if uv is None or not uv.is_cuda or uv.dim() != 3 or tuple(uv.shape[1:]) != (3, 2):
+        raise ValueError("rasterize_atlas: expected cuda faces_uvs [F, 3, 2]")
+    uv = uv.to(torch.float32).contiguous()
+    face_id = torch.full((R, R), -1, dtype=torch.int32, device=uv.device)
+    count = torch.zeros((R, R), dtype=torch.int32, device=uv.device)
+    nf = int(uv.shape[0])
+    if nf == 0:
+        return face_id, count
+    if not bool(torch.isfinite(uv).all()):
+        raise _lib.VolsurfsHipError("rasterize_atlas: the UVs hold NaN or inf")
+    n = _lib.lib().vsa_atlas_rasterize_workspace_bytes(nf)
+    if n < 0:
+        raise _lib.VolsurfsHipError(f"vsa_atlas_rasterize_workspace_bytes failed with status {n}")
+    ws = torch.empty(int(n), dtype=torch.uint8, device=uv.device)
+    _lib.call("vsa_atlas_rasterize", uv, nf, R, ws, ws.numel(), face_id, count, _lib.stream_ptr())
+    return face_id, count
+
+
+def chart_image(charts, face_id):
+    """[R, R, 3] uint8: one colour per chart (a fixed hash of the chart number), black where no face covers the
+    texel; row 0 is the top of the atlas (v = 1), as image files and OBJ texture coordinates expect."""
+    c = charts.to(torch.int64)[face_id.clamp(min=0).to(torch.int64)]
+    h = (c + 1) * 2654435761
+    rgb = torch.stack([(h >> 8) & 255, (h >> 16) & 255, (h >> 24) & 255], -1)
+    rgb = (rgb % 192 + 64).to(torch.uint8)
+    rgb[face_id < 0] = 0
+    return torch.flip(rgb, [0])
+
+
+def _level_files(meshes_dir):
+    names = [n for n in os.listdir(meshes_dir) if n.endswith(".ply") or n.endswith(".obj")]
+    names.sort(key=lambda x: float(x[:-4]))
+    if not names:
+        raise FileNotFoundError(f"no <level>.ply / <level>.obj meshes in {meshes_dir}")
+    return names
+
+
+def compute_meshes_atlas(meshes_dir, out_dir, resolution=1024, padding=4, device="cuda"):
+    """The baker's `--compute_meshes_xatlas` (baker.py:727-776): every `<level>.ply` of `meshes_dir` (the reference's
+    `meshes_simplified/`) atlased on its own and written to `out_dir` (its `meshes_simplified_uvs/`) as `<level>.obj`
+    with per-corner UVs, plus `atlas/<level>.png`, one colour per chart.  Returns the .obj paths, inner to outer;
+    `VolSurfs.from_meshes_path(out_dir, ..., using_neural_textures=True)` trains on them."""
+    from .evaluation import _save_png
+    from .mesh import load_mesh
+    names = _level_files(meshes_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for n in names:
+        src = os.path.join(meshes_dir, n)
+        m = load_ply(src, device=device) if n.endswith(".ply") else load_mesh(src, device=device)
+        if m.faces.shape[0] == 0:
+            raise ValueError(f"{n}: no faces to atlas")
+        out, charts = compute_atlas(m, resolution, padding, return_charts=True)
+        stem = n[:-4]
+        path = os.path.join(out_dir, stem + ".obj")
+        save_obj(path, out)
+        face_id, _ = rasterize_atlas(out, resolution)
+        _save_png(chart_image(charts, face_id), os.path.join(out_dir, "atlas", stem + ".png"))
+        paths.append(path)
+    return paths
+
+
+__all__ = ["compute_atlas", "rasterize_atlas", "compute_meshes_atlas", "chart_image", "workspace_bytes", "STAGES"]

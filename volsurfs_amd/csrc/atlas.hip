@@ -1,0 +1,1016 @@
+// UV atlas of one consistently wound triangle mesh by box projection (vsa_atlas*; rules in include/volsurfs_hip.h,
+// DESIGN §16).
+//
+// One stream.  Once per call:
+//   label:   fp32 face normals; the (vertex, face) list radix-sorted by vertex (ascending face within a vertex) gives
+//            the per-vertex normal sums in a fixed order; one lane per face picks the face's direction label.  The 3F
+//            (min, max) edge keys are radix-sorted with their slots: an edge with exactly two slots, traversed in
+//            opposite directions by two faces of one label, is a join pair; pairs are compacted by a scan.
+// Then rounds, until no chart overlaps itself:
+//   charts:  union-find over the join pairs whose faces carry the same split code (CAS hooks of the larger root under
+//            the smaller, so a root is its component's minimum face index whatever the order); roots flagged and
+//            scanned into chart indices; chart boxes by 32-bit atomic min / max of ordered float bits.
+//   pack:    a bisection over the fp32 bit pattern of the texel density s.  A step: rectangle keys per chart, a radix
+//            sort, a scan of the sorted widths, and one lane walking the next-fit shelves (a binary search over the
+//            width prefix per shelf: about sqrt(charts) shelves); the host reads the fit flag.  The last walk writes
+//            the shelves, and one lane per sorted rectangle finds its shelf and offset.
+//   emit:    one lane per face writes its three corners' UVs.
+//   raster:  faces snapped to 1/256 texel; a scan of every face's 8x8-tile count gives (face, tile) work items, one lane
+//            per item tests its 64 texel centres with int64 edge functions (top-left rule) and counts them; a second
+//            pass over the same items flags the charts with a texel counted twice.  Flagged charts are split by a bit
+//            of their faces' split codes and the round repeats.
+// No float is summed by atomics: the normal sums have a fixed order, and integer atomics form minima, maxima, unions,
+// flags and counts.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include <cstdint>
+
+#include "common.h"
+
+#define ATL_BLOCK 256
+#define ATL_TILE 8
+#define ATL_SNAP 256
+#define ATL_DEPTH_CAP 24
+#define ATL_MIN_RES 8
+#define ATL_MAX_RES 16384
+#define ATL_MAX_ROUNDS 100   // rounds of chart building and packing; measured at most 20
+
+// device counters
+#define ACT_J 0
+#define ACT_C 1
+#define ACT_FIT 2
+#define ACT_NSH 3
+#define ACT_OVL 4
+#define ACT_COV 5
+#define ACT_PROG 6
+#define ACT_N 8
+
+typedef unsigned long long u64;
+
+// Projection axes per label (+x, -x, +y, -y, +z, -z): +x -> (y, z), -x -> (z, y), +y -> (z, x), -y -> (x, z),
+// +z -> (x, y), -z -> (y, x).
+__constant__ int atl_ax_u[6] = {1, 2, 2, 0, 0, 1};
+__constant__ int atl_ax_v[6] = {2, 1, 0, 2, 1, 0};
+
+__device__ __forceinline__ unsigned atl_ord(float x) {
+  const unsigned b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ float atl_unord(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+// ------------------------------------------------------------------------------------------------ label
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_normals(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                                                        long long F, float* __restrict__ fn) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const long long a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+  const float e1x = P[3 * b] - P[3 * a], e1y = P[3 * b + 1] - P[3 * a + 1], e1z = P[3 * b + 2] - P[3 * a + 2];
+  const float e2x = P[3 * c] - P[3 * a], e2y = P[3 * c + 1] - P[3 * a + 1], e2z = P[3 * c + 2] - P[3 * a + 2];
+  fn[3 * f] = e1y * e2z - e1z * e2y;
+  fn[3 * f + 1] = e1z * e2x - e1x * e2z;
+  fn[3 * f + 2] = e1x * e2y - e1y * e2x;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_vf_pairs(const int32_t* __restrict__ faces, long long n3,
+                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  keys[i] = (uint32_t)faces[i];
+  vals[i] = (uint32_t)(i / 3);
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_vf_ranges(const uint32_t* __restrict__ k, long long n3,
+                                                          int32_t* __restrict__ vstart, int32_t* __restrict__ vend) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  if (i == 0 || k[i] != k[i - 1]) vstart[k[i]] = (int32_t)i;
+  if (i == n3 - 1 || k[i] != k[i + 1]) vend[k[i]] = (int32_t)(i + 1);
+}
+
+// N_v: the fp32 sum of n_f over the faces at v, in ascending face index, from 0.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_vertex_sums(const float* __restrict__ fn,
+                                                            const uint32_t* __restrict__ vff,
+                                                            const int32_t* __restrict__ vstart,
+                                                            const int32_t* __restrict__ vend, long long V,
+                                                            float* __restrict__ nv) {
+  const long long v = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (v >= V) return;
+  float x = 0.f, y = 0.f, z = 0.f;
+  for (int j = vstart[v]; j < vend[v]; ++j) {
+    const long long f = vff[j];
+    x = x + fn[3 * f];
+    y = y + fn[3 * f + 1];
+    z = z + fn[3 * f + 2];
+  }
+  nv[3 * v] = x;
+  nv[3 * v + 1] = y;
+  nv[3 * v + 2] = z;
+}
+
+// argmax of (x, -x, y, -y, z, -z), ties to the earlier direction.
+__device__ __forceinline__ int atl_argmax6(float x, float y, float z) {
+  const float d[6] = {x, -x, y, -y, z, -z};
+  int best = 0;
+#pragma unroll
+  for (int k = 1; k < 6; ++k)
+    if (d[k] > d[best]) best = k;
+  return best;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_labels(const int32_t* __restrict__ faces, long long F,
+                                                       const float* __restrict__ fn, const float* __restrict__ nv,
+                                                       int32_t* __restrict__ label, uint32_t* __restrict__ code) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const float nx = fn[3 * f], ny = fn[3 * f + 1], nz = fn[3 * f + 2];
+  code[f] = 1u;
+  if (nx == 0.f && ny == 0.f && nz == 0.f) {
+    label[f] = 0;
+    return;
+  }
+  const long long a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+  const float sx = (nv[3 * a] + nv[3 * b]) + nv[3 * c];
+  const float sy = (nv[3 * a + 1] + nv[3 * b + 1]) + nv[3 * c + 1];
+  const float sz = (nv[3 * a + 2] + nv[3 * b + 2]) + nv[3 * c + 2];
+  const int cand = atl_argmax6(sx, sy, sz);
+  const float comp[3] = {nx, ny, nz};
+  const double dn = (double)(cand & 1 ? -comp[cand >> 1] : comp[cand >> 1]);
+  const double nn = ((double)nx * (double)nx + (double)ny * (double)ny) + (double)nz * (double)nz;
+  label[f] = (dn >= 0.0 && 4.0 * (dn * dn) >= nn) ? cand : atl_argmax6(nx, ny, nz);
+}
+
+__device__ __forceinline__ u64 atl_pack(int x, int y, int s) {
+  const int lo = x < y ? x : y, hi = x < y ? y : x;
+  return (u64)(unsigned)lo << s | (u64)(unsigned)hi;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_edge_keys(const int32_t* __restrict__ faces, long long n3, int s,
+                                                          u64* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  const long long f = i / 3;
+  const int c = (int)(i - 3 * f);
+  keys[i] = atl_pack(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
+  vals[i] = (uint32_t)i;
+}
+
+// Join flag at the first sorted slot of an edge with exactly two slots, opposite directions and one label.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_join_flags(const u64* __restrict__ sorted,
+                                                           const uint32_t* __restrict__ slot,
+                                                           const int32_t* __restrict__ faces,
+                                                           const int32_t* __restrict__ label, long long n3,
+                                                           int32_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  int ok = 0;
+  if ((i == 0 || sorted[i - 1] != sorted[i]) && i + 1 < n3 && sorted[i + 1] == sorted[i] &&
+      (i + 2 == n3 || sorted[i + 2] != sorted[i])) {
+    const long long s0 = slot[i], s1 = slot[i + 1];
+    const long long f0 = s0 / 3, f1 = s1 / 3;
+    const int c0 = (int)(s0 - 3 * f0), c1 = (int)(s1 - 3 * f1);
+    ok = faces[3 * f0 + c0] == faces[3 * f1 + (c1 == 2 ? 0 : c1 + 1)] && label[f0] == label[f1];
+  }
+  flags[i] = ok;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_join_compact(const uint32_t* __restrict__ slot,
+                                                             const int32_t* __restrict__ flags,
+                                                             const int32_t* __restrict__ rank, long long n3,
+                                                             int2* __restrict__ pairs, long long* __restrict__ ctr) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= n3) return;
+  if (flags[i]) pairs[rank[i]] = make_int2((int)(slot[i] / 3), (int)(slot[i + 1] / 3));
+  if (i == n3 - 1) ctr[ACT_J] = rank[i] + flags[i];
+}
+
+// ------------------------------------------------------------------------------------------------ charts
+
+__device__ __forceinline__ int atl_find(int* par, int x) {
+  while (true) {
+    const int p = __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p == x) return x;
+    const int g = __hip_atomic_load(par + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (g != p) __hip_atomic_store(par + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // halving: an ancestor
+    x = p;
+  }
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_iota(int32_t* __restrict__ par, long long F) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f < F) par[f] = (int32_t)f;
+}
+
+// Every parent is <= its child, so the root of a component is its minimum face index.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_hook(const int2* __restrict__ pairs, const long long* __restrict__ ctr,
+                                                     const uint32_t* __restrict__ code, int32_t* par) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= ctr[ACT_J]) return;
+  const int2 pr = pairs[i];
+  const uint32_t k = code[pr.x];
+  if (k == 0u || k != code[pr.y]) return;
+  int a = pr.x, b = pr.y;
+  while (true) {
+    a = atl_find(par, a);
+    b = atl_find(par, b);
+    if (a == b) return;
+    if (a > b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    if (atomicCAS(par + b, b, a) == b) return;
+  }
+}
+
+// Root of x by a walk that only reads: `par` is left as the hooks built it while other lanes walk it, so every lane
+// sees the same final forest and finds the same root.
+__device__ __forceinline__ int atl_root(const int32_t* __restrict__ par, int x) {
+  int p = par[x];
+  while (p != x) {
+    x = p;
+    p = par[x];
+  }
+  return x;
+}
+
+// root[f] = the root of f (a separate array: no lane writes to a node another lane walks).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_compress(const int32_t* __restrict__ par, long long F,
+                                                         int32_t* __restrict__ root, int32_t* __restrict__ flags) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const int r = atl_root(par, (int)f);
+  root[f] = r;
+  flags[f] = r == f;
+}
+
+// cidx[f] = the chart number of f's root, in place over root[f] (each lane reads and writes its own entry only).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_chart_index(const int32_t* __restrict__ flags,
+                                                            const int32_t* __restrict__ rank, long long F,
+                                                            int32_t* __restrict__ cidx, long long* __restrict__ ctr) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  cidx[f] = rank[cidx[f]];
+  if (f == F - 1) ctr[ACT_C] = rank[f] + flags[f];
+}
+
+// Chart box: [umin, umax, vmin, vmax] as ordered bits; minima start at 0xFFFFFFFF, maxima at 0.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_box_init(unsigned* __restrict__ box, long long n) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i < n) box[i] = (i & 1) ? 0u : 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_boxes(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                                                      long long F, const int32_t* __restrict__ label,
+                                                      const int32_t* __restrict__ cidx, unsigned* __restrict__ box) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const int l = label[f], au = atl_ax_u[l], av = atl_ax_v[l];
+  unsigned umin = 0xFFFFFFFFu, umax = 0u, vmin = 0xFFFFFFFFu, vmax = 0u;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const long long v = faces[3 * f + c];
+    const unsigned ku = atl_ord(P[3 * v + au]), kv = atl_ord(P[3 * v + av]);
+    umin = ku < umin ? ku : umin;
+    umax = ku > umax ? ku : umax;
+    vmin = kv < vmin ? kv : vmin;
+    vmax = kv > vmax ? kv : vmax;
+  }
+  unsigned* b = box + 4 * (long long)cidx[f];
+  atomicMin(b, umin);
+  atomicMax(b + 1, umax);
+  atomicMin(b + 2, vmin);
+  atomicMax(b + 3, vmax);
+}
+
+// ------------------------------------------------------------------------------------------------ pack
+
+// (width, height) extents of chart c after its rotation; rot = height > width before it.
+__device__ __forceinline__ void atl_extent(const unsigned* __restrict__ box, long long c, float* ew, float* eh,
+                                           bool* rot) {
+  const float w = atl_unord(box[4 * c + 1]) - atl_unord(box[4 * c]);
+  const float h = atl_unord(box[4 * c + 3]) - atl_unord(box[4 * c + 2]);
+  *rot = h > w;
+  *ew = *rot ? h : w;
+  *eh = *rot ? w : h;
+}
+
+// ceil(fl(e * s)) + 2p texels, or R + 1 when ceil(fl(e * s)) > R (inf included).
+__device__ __forceinline__ int atl_side(float e, float s, int R, int p) {
+  const float t = ceilf(e * s);
+  return t <= (float)R ? (int)t + 2 * p : R + 1;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_rect_keys(const unsigned* __restrict__ box, long long C, float s,
+                                                          int R, int p, u64* __restrict__ keys) {
+  const long long c = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (c >= C) return;
+  float ew, eh;
+  bool rot;
+  atl_extent(box, c, &ew, &eh, &rot);
+  const int W = atl_side(ew, s, R, p), H = atl_side(eh, s, R, p);
+  keys[c] = (u64)(0xFFFFu - (unsigned)H) << 48 | (u64)(0xFFFFu - (unsigned)W) << 32 | (u64)c;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_rect_widths(const u64* __restrict__ sorted, long long C,
+                                                            long long* __restrict__ wid) {
+  const long long k = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (k >= C) return;
+  wid[k] = (long long)(0xFFFFu - (unsigned)((sorted[k] >> 32) & 0xFFFFu));
+}
+
+// One lane: next-fit shelves over the sorted rectangles.  pre[k] = sum of the first k widths (pre[0] = 0).  A shelf
+// starting at i takes rectangles i .. j - 1, j the largest index with pre[j] - pre[i] <= R; its height is rectangle
+// i's.  emit: shelf starts and y offsets written.
+__global__ void atl_shelf_walk(const u64* __restrict__ sorted, const long long* __restrict__ pre, long long C, int R,
+                               int emit, int32_t* __restrict__ sh_start, int32_t* __restrict__ sh_y,
+                               long long* __restrict__ ctr) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  long long i = 0, y = 0, nsh = 0;
+  int fit = 1;
+  while (i < C) {
+    const long long lim = pre[i] + R;
+    long long lo = i, hi = C;   // largest j in [i, C] with pre[j] <= lim
+    while (lo < hi) {
+      const long long mid = lo + (hi - lo + 1) / 2;
+      if (pre[mid] <= lim) lo = mid;
+      else hi = mid - 1;
+    }
+    if (lo == i) {
+      fit = 0;
+      break;
+    }
+    if (emit) {
+      sh_start[nsh] = (int32_t)i;
+      sh_y[nsh] = (int32_t)y;
+    }
+    ++nsh;
+    y += (long long)(0xFFFFu - (unsigned)(sorted[i] >> 48));
+    if (y > R) {
+      fit = 0;
+      break;
+    }
+    i = lo;
+  }
+  ctr[ACT_FIT] = fit;
+  ctr[ACT_NSH] = nsh;
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_offsets(const u64* __restrict__ sorted,
+                                                        const long long* __restrict__ pre, long long C,
+                                                        const int32_t* __restrict__ sh_start,
+                                                        const int32_t* __restrict__ sh_y,
+                                                        const long long* __restrict__ ctr, int2* __restrict__ off) {
+  const long long k = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (k >= C) return;
+  long long lo = 0, hi = ctr[ACT_NSH] - 1;   // the last shelf starting at or before k
+  while (lo < hi) {
+    const long long mid = lo + (hi - lo + 1) / 2;
+    if (sh_start[mid] <= k) lo = mid;
+    else hi = mid - 1;
+  }
+  off[sorted[k] & 0xFFFFFFFFull] = make_int2((int)(pre[k] - pre[sh_start[lo]]), sh_y[lo]);
+}
+
+// ------------------------------------------------------------------------------------------------ emit
+
+// uv = (local * s + (offset + p)) / R in fp32; local = (u - umin, v - vmin), or (vmax - v, u - umin) when rotated.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_emit(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                                                     long long F, const int32_t* __restrict__ label,
+                                                     const int32_t* __restrict__ cidx,
+                                                     const unsigned* __restrict__ box, const int2* __restrict__ off,
+                                                     float s, int R, int p, float* __restrict__ uv) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const int l = label[f], au = atl_ax_u[l], av = atl_ax_v[l];
+  const long long c = cidx[f];
+  const float umin = atl_unord(box[4 * c]), umax = atl_unord(box[4 * c + 1]);
+  const float vmin = atl_unord(box[4 * c + 2]), vmax = atl_unord(box[4 * c + 3]);
+  const bool rot = (vmax - vmin) > (umax - umin);
+  const int2 o = off[c];
+  const float ox = (float)(o.x + p), oy = (float)(o.y + p), r = (float)R;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const long long v = faces[3 * f + k];
+    const float u = P[3 * v + au], w = P[3 * v + av];
+    const float lx = rot ? vmax - w : u - umin;
+    const float ly = rot ? u - umin : w - vmin;
+    uv[6 * f + 2 * k] = (lx * s + ox) / r;
+    uv[6 * f + 2 * k + 1] = (ly * s + oy) / r;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ raster
+
+struct AtlTri {
+  long long x[3], y[3];
+  int i0, i1, j0, j1;   // texel box (inclusive); empty when i0 > i1 or j0 > j1
+};
+
+__device__ __forceinline__ long long atl_floordiv(long long a, long long b) {
+  return a >= 0 ? a / b : -((-a + b - 1) / b);
+}
+
+// Snapped corners (rint(clamp(uv, 0, 1) * 256 R), fp64) and the texel box; a face whose snapped signed area is <= 0
+// gets an empty box.
+__device__ void atl_tri(const float* __restrict__ uv, long long f, int R, AtlTri* t) {
+  const double q = (double)ATL_SNAP * (double)R;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float u = fminf(fmaxf(uv[6 * f + 2 * k], 0.f), 1.f), v = fminf(fmaxf(uv[6 * f + 2 * k + 1], 0.f), 1.f);
+    t->x[k] = (long long)rint((double)u * q);
+    t->y[k] = (long long)rint((double)v * q);
+  }
+  const long long a2 = (t->x[1] - t->x[0]) * (t->y[2] - t->y[0]) - (t->y[1] - t->y[0]) * (t->x[2] - t->x[0]);
+  const long long xl = min(t->x[0], min(t->x[1], t->x[2])), xh = max(t->x[0], max(t->x[1], t->x[2]));
+  const long long yl = min(t->y[0], min(t->y[1], t->y[2])), yh = max(t->y[0], max(t->y[1], t->y[2]));
+  const long long h = ATL_SNAP / 2;
+  long long i0 = -atl_floordiv(-(xl - h), ATL_SNAP), i1 = atl_floordiv(xh - h, ATL_SNAP);
+  long long j0 = -atl_floordiv(-(yl - h), ATL_SNAP), j1 = atl_floordiv(yh - h, ATL_SNAP);
+  i0 = i0 < 0 ? 0 : i0;
+  j0 = j0 < 0 ? 0 : j0;
+  i1 = i1 > R - 1 ? R - 1 : i1;
+  j1 = j1 > R - 1 ? R - 1 : j1;
+  if (a2 <= 0) i1 = i0 - 1;
+  t->i0 = (int)i0;
+  t->i1 = (int)i1;
+  t->j0 = (int)j0;
+  t->j1 = (int)j1;
+}
+
+__device__ __forceinline__ bool atl_edge_in(long long ax, long long ay, long long bx, long long by, long long px,
+                                            long long py) {
+  const long long dx = bx - ax, dy = by - ay;
+  const long long e = dx * (py - ay) - dy * (px - ax);
+  return e > 0 || (e == 0 && (dy < 0 || (dy == 0 && dx < 0)));
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_tile_counts(const float* __restrict__ uv, long long F, int R,
+                                                            long long* __restrict__ ntile) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  AtlTri t;
+  atl_tri(uv, f, R, &t);
+  ntile[f] = (t.i0 > t.i1 || t.j0 > t.j1)
+                 ? 0
+                 : (long long)(t.i1 / ATL_TILE - t.i0 / ATL_TILE + 1) * (t.j1 / ATL_TILE - t.j0 / ATL_TILE + 1);
+}
+
+// mode 0: count[j R + i] += 1 and face_id[j R + i] = min(face) (unsigned: empty stays -1) for every covered texel;
+// mode 1: flag[cidx[f]] = 1 where a covered texel's count is >= 2.  toff[f] = tiles before face f (toff[F] = total).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_raster(const float* __restrict__ uv, long long F, int R,
+                                                       const long long* __restrict__ toff, long long total, int mode,
+                                                       int32_t* __restrict__ count, uint32_t* __restrict__ face_id,
+                                                       const int32_t* __restrict__ cidx, int32_t* __restrict__ flag) {
+  for (long long it = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x; it < total;
+       it += (long long)gridDim.x * ATL_BLOCK) {
+    long long lo = 0, hi = F - 1;   // the last face with toff[f] <= it
+    while (lo < hi) {
+      const long long mid = lo + (hi - lo + 1) / 2;
+      if (toff[mid] <= it) lo = mid;
+      else hi = mid - 1;
+    }
+    const long long f = lo;
+    AtlTri t;
+    atl_tri(uv, f, R, &t);
+    const long long k = it - toff[f];
+    const int ntx = t.i1 / ATL_TILE - t.i0 / ATL_TILE + 1;
+    const int tx = t.i0 / ATL_TILE + (int)(k % ntx), ty = t.j0 / ATL_TILE + (int)(k / ntx);
+    const int ia = max(tx * ATL_TILE, t.i0), ib = min(tx * ATL_TILE + ATL_TILE - 1, t.i1);
+    const int ja = max(ty * ATL_TILE, t.j0), jb = min(ty * ATL_TILE + ATL_TILE - 1, t.j1);
+    bool hit2 = false;
+    for (int j = ja; j <= jb; ++j) {
+      const long long py = (long long)j * ATL_SNAP + ATL_SNAP / 2;
+      for (int i = ia; i <= ib; ++i) {
+        const long long px = (long long)i * ATL_SNAP + ATL_SNAP / 2;
+        if (!atl_edge_in(t.x[0], t.y[0], t.x[1], t.y[1], px, py) ||
+            !atl_edge_in(t.x[1], t.y[1], t.x[2], t.y[2], px, py) ||
+            !atl_edge_in(t.x[2], t.y[2], t.x[0], t.y[0], px, py))
+          continue;
+        const long long o = (long long)j * R + i;
+        if (mode == 0) {
+          atomicAdd(count + o, 1);
+          if (face_id) atomicMin(face_id + o, (uint32_t)f);
+        } else {
+          hit2 |= count[o] >= 2;
+        }
+      }
+    }
+    if (hit2) flag[cidx[f]] = 1;
+  }
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_covered(const int32_t* __restrict__ count, long long n,
+                                                        long long* __restrict__ ctr) {
+  __shared__ int part[ATL_BLOCK / VSA_WAVE];
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  int c = i < n && count[i] > 0;
+#pragma unroll
+  for (int d = VSA_WAVE / 2; d > 0; d >>= 1) c += __shfl_down(c, d, VSA_WAVE);
+  if ((threadIdx.x & (VSA_WAVE - 1)) == 0) part[threadIdx.x / VSA_WAVE] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < ATL_BLOCK / VSA_WAVE; ++w) s += part[w];
+    if (s) atomicAdd((unsigned long long*)(ctr + ACT_COV), (unsigned long long)s);
+  }
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_count_flags(const int32_t* __restrict__ flag, long long C,
+                                                            long long* __restrict__ ctr) {
+  const long long c = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (c < C && flag[c]) atomicAdd((unsigned long long*)(ctr + ACT_OVL), 1ull);
+}
+
+// A face of a flagged chart: code 0 (one chart per face) at the depth cap, else code = 2 code + side, side = 1 when
+// the sum of its corners' coordinates along the box's longer side (u on a tie) exceeds 3 x the side's midpoint (fp64).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_split(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                                                      long long F, const int32_t* __restrict__ label,
+                                                      const int32_t* __restrict__ cidx,
+                                                      const unsigned* __restrict__ box,
+                                                      const int32_t* __restrict__ flag, uint32_t* __restrict__ code,
+                                                      long long* __restrict__ ctr) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  bool changed = false;
+  if (f < F) {
+    const long long c = cidx[f];
+    const uint32_t k = code[f];
+    if (flag[c] && k != 0u) {
+      changed = true;
+      if (k >= (1u << ATL_DEPTH_CAP)) {
+        code[f] = 0u;
+      } else {
+        const float umin = atl_unord(box[4 * c]), umax = atl_unord(box[4 * c + 1]);
+        const float vmin = atl_unord(box[4 * c + 2]), vmax = atl_unord(box[4 * c + 3]);
+        const bool along_u = (umax - umin) >= (vmax - vmin);
+        const int ax = along_u ? atl_ax_u[label[f]] : atl_ax_v[label[f]];
+        const double lo = along_u ? umin : vmin, hi = along_u ? umax : vmax;
+        const double sum = ((double)P[3 * (long long)faces[3 * f] + ax] +
+                            (double)P[3 * (long long)faces[3 * f + 1] + ax]) +
+                           (double)P[3 * (long long)faces[3 * f + 2] + ax];
+        code[f] = 2u * k + (sum > 1.5 * (lo + hi) ? 1u : 0u);
+      }
+    }
+  }
+  // faces whose code changed (one atomic per wave): 0 means the next round would repeat this one
+  const u64 m = __ballot(changed);
+  if ((threadIdx.x & (VSA_WAVE - 1)) == 0 && m)
+    atomicAdd((unsigned long long*)(ctr + ACT_PROG), (unsigned long long)__popcll(m));
+}
+
+// ------------------------------------------------------------------------------------------------ host
+
+static size_t atl_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct AtlLayout {
+  size_t fn, nv, vstart, vend, label, code, par, cidx, flags, rank, A, B, va, vb, pairs, box, off, flag, pre, wid,
+      sh_start, sh_y, toff, ntile, count, ctr, tmp, tmp_bytes, total;
+};
+
+static int atl_check(long long V, long long F, int R) {
+  if (V < 1 || F < 1 || R < ATL_MIN_RES || R > ATL_MAX_RES) return VSA_ERR_ARG;
+  if (V > 0x7FFFFFFFll || F > 0x7FFFFFFFll / 3 - 1) return VSA_ERR_UNSUPPORTED;
+  return VSA_OK;
+}
+
+// rocPRIM temporary storage for every sort and scan of a mesh of V vertices and F faces (F only: rasterize).
+static int atl_tmp_bytes(long long V, long long F, size_t* out) {
+  const size_t n3 = 3 * (size_t)F, f = (size_t)F;
+  size_t t = 0, need = 16;
+  VSA_HIP_TRY(rocprim::inclusive_scan(nullptr, t, (const long long*)nullptr, (long long*)nullptr, f,
+                                      rocprim::plus<long long>(), (hipStream_t)0));
+  need = t > need ? t : need;
+  if (V > 0) {
+    VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (const uint32_t*)nullptr,
+                                          (uint32_t*)nullptr, n3, 0, 64, (hipStream_t)0));
+    need = t > need ? t : need;
+    VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                          (const uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0, 32, (hipStream_t)0));
+    need = t > need ? t : need;
+    VSA_HIP_TRY(rocprim::radix_sort_keys(nullptr, t, (const u64*)nullptr, (u64*)nullptr, f, 0, 64, (hipStream_t)0));
+    need = t > need ? t : need;
+    VSA_HIP_TRY(rocprim::exclusive_scan(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, 0, n3,
+                                        rocprim::plus<int32_t>(), (hipStream_t)0));
+    need = t > need ? t : need;
+  }
+  *out = need;
+  return VSA_OK;
+}
+
+// V = 0: the rasterize-only layout (toff, ntile, count unused, ctr, tmp).
+static int atl_layout(long long V, long long F, int R, AtlLayout* l) {
+  const size_t v = (size_t)V, f = (size_t)F, n3 = 3 * f, rr = (size_t)R * (size_t)R;
+  size_t need = 0;
+  const int rc = atl_tmp_bytes(V, F, &need);
+  if (rc != VSA_OK) return rc;
+  size_t o = 0;
+  const bool full = V > 0;
+#define ATL_AT(field, bytes) \
+  l->field = o;              \
+  o += atl_align(bytes)
+  ATL_AT(toff, 8 * (f + 1));
+  ATL_AT(ntile, 8 * f);
+  ATL_AT(ctr, 8 * ACT_N);
+  ATL_AT(fn, full ? 12 * f : 0);
+  ATL_AT(nv, 12 * v);
+  ATL_AT(vstart, 4 * v);
+  ATL_AT(vend, 4 * v);
+  ATL_AT(label, full ? 4 * f : 0);
+  ATL_AT(code, full ? 4 * f : 0);
+  ATL_AT(par, full ? 4 * f : 0);
+  ATL_AT(cidx, full ? 4 * f : 0);
+  ATL_AT(flags, full ? 4 * n3 : 0);
+  ATL_AT(rank, full ? 4 * n3 : 0);
+  ATL_AT(A, full ? 8 * n3 : 0);
+  ATL_AT(B, full ? 8 * n3 : 0);
+  ATL_AT(va, full ? 4 * n3 : 0);
+  ATL_AT(vb, full ? 4 * n3 : 0);
+  ATL_AT(pairs, full ? 8 * n3 : 0);
+  ATL_AT(box, full ? 16 * f : 0);
+  ATL_AT(off, full ? 8 * f : 0);
+  ATL_AT(flag, full ? 4 * f : 0);
+  ATL_AT(pre, full ? 8 * (f + 1) : 0);
+  ATL_AT(wid, full ? 8 * f : 0);
+  ATL_AT(sh_start, full ? 4 * f : 0);
+  ATL_AT(sh_y, full ? 4 * f : 0);
+  ATL_AT(count, full ? 4 * rr : 0);
+  ATL_AT(tmp, need);
+#undef ATL_AT
+  l->tmp_bytes = need;
+  l->total = o;
+  return VSA_OK;
+}
+
+extern "C" long long vsa_atlas_workspace_bytes(long long nr_verts, long long nr_faces, int resolution) {
+  const int rc = atl_check(nr_verts, nr_faces, resolution);
+  if (rc != VSA_OK) return rc;
+  AtlLayout l;
+  const int rl = atl_layout(nr_verts, nr_faces, resolution, &l);
+  if (rl != VSA_OK) return rl > 0 ? VSA_ERR_UNSUPPORTED : rl;   // a HIP status of rocPRIM's size query
+  return (long long)l.total;
+}
+
+extern "C" long long vsa_atlas_rasterize_workspace_bytes(long long nr_faces) {
+  if (nr_faces < 1) return VSA_ERR_ARG;
+  if (nr_faces > 0x7FFFFFFFll) return VSA_ERR_UNSUPPORTED;
+  AtlLayout l;
+  const int rl = atl_layout(0, nr_faces, ATL_MIN_RES, &l);
+  if (rl != VSA_OK) return rl > 0 ? VSA_ERR_UNSUPPORTED : rl;
+  return (long long)l.total;
+}
+
+namespace {
+
+#define ATL_TRY(expr)              \
+  do {                             \
+    const int r__ = (expr);        \
+    if (r__ != VSA_OK) return r__; \
+  } while (0)
+
+dim3 agrid(long long n) { return dim3((unsigned)vsa_div_up(n > 0 ? n : 1, ATL_BLOCK)); }
+
+template <typename T>
+T* at(char* ws, size_t o) {
+  return reinterpret_cast<T*>(ws + o);
+}
+
+struct Atl {
+  hipStream_t st;
+  char* ws;
+  AtlLayout l;
+  long long V, F, C;
+  int R, p, s_bits;
+  const float* P;
+  const int32_t* faces;
+  long long* ctr;
+  hipEvent_t ev[2];
+  float* stage_ms;
+};
+
+int stage_open(Atl& m) {
+  if (m.stage_ms) VSA_HIP_TRY(hipEventRecord(m.ev[0], m.st));
+  return VSA_OK;
+}
+
+int stage_close(Atl& m, int k) {
+  if (!m.stage_ms) return VSA_OK;
+  float ms = 0.f;
+  VSA_HIP_TRY(hipEventRecord(m.ev[1], m.st));
+  VSA_HIP_TRY(hipEventSynchronize(m.ev[1]));
+  VSA_HIP_TRY(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
+  m.stage_ms[k] += ms;
+  return VSA_OK;
+}
+
+int read_ctr(Atl& m, int k, long long* out) {
+  VSA_HIP_TRY(hipMemcpyAsync(out, m.ctr + k, sizeof(long long), hipMemcpyDeviceToHost, m.st));
+  VSA_HIP_TRY(hipStreamSynchronize(m.st));
+  return VSA_OK;
+}
+
+// Rasterization of F faces' UVs: tile counts, their scan and the item passes (mode 0 counts, then mode 1 flags when
+// `flag` is given).  count / face_id must be zeroed / 0xFF-filled by the caller.
+int raster(hipStream_t st, char* ws, const AtlLayout& l, const float* uv, long long F, int R, int32_t* count,
+           uint32_t* face_id, const int32_t* cidx, int32_t* flag) {
+  long long* toff = at<long long>(ws, l.toff);
+  long long* ntile = at<long long>(ws, l.ntile);
+  hipLaunchKernelGGL(atl_tile_counts, agrid(F), dim3(ATL_BLOCK), 0, st, uv, F, R, ntile);
+  VSA_HIP_TRY(hipGetLastError());
+  VSA_HIP_TRY(hipMemsetAsync(toff, 0, 8, st));
+  size_t bytes = l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::inclusive_scan(ws + l.tmp, bytes, ntile, toff + 1, (size_t)F, rocprim::plus<long long>(), st));
+  long long total = 0;
+  VSA_HIP_TRY(hipMemcpyAsync(&total, toff + F, sizeof(total), hipMemcpyDeviceToHost, st));
+  VSA_HIP_TRY(hipStreamSynchronize(st));
+  if (total < 0) return VSA_ERR_UNSUPPORTED;
+  if (total == 0) return VSA_OK;
+  const long long blocks = (total + ATL_BLOCK - 1) / ATL_BLOCK;
+  const dim3 g((unsigned)(blocks < 65536 ? blocks : 65536));
+  hipLaunchKernelGGL(atl_raster, g, dim3(ATL_BLOCK), 0, st, uv, F, R, toff, total, 0, count, face_id, cidx, flag);
+  VSA_HIP_TRY(hipGetLastError());
+  if (flag) {
+    hipLaunchKernelGGL(atl_raster, g, dim3(ATL_BLOCK), 0, st, uv, F, R, toff, total, 1, count, face_id, cidx, flag);
+    VSA_HIP_TRY(hipGetLastError());
+  }
+  return VSA_OK;
+}
+
+int label_stage(Atl& m) {
+  const long long F = m.F, V = m.V, n3 = 3 * F;
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  float* fn = at<float>(ws, l.fn);
+  size_t bytes = l.tmp_bytes;
+  hipLaunchKernelGGL(atl_normals, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, fn);
+  VSA_HIP_TRY(hipGetLastError());
+  uint32_t* kin = at<uint32_t>(ws, l.A);
+  uint32_t* kout = at<uint32_t>(ws, l.B);
+  uint32_t* vin = at<uint32_t>(ws, l.va);
+  uint32_t* vff = at<uint32_t>(ws, l.vb);
+  hipLaunchKernelGGL(atl_vf_pairs, agrid(n3), dim3(ATL_BLOCK), 0, m.st, m.faces, n3, kin, vin);
+  VSA_HIP_TRY(hipGetLastError());
+  VSA_HIP_TRY(rocprim::radix_sort_pairs(ws + l.tmp, bytes, kin, kout, vin, vff, (size_t)n3, 0, m.s_bits, m.st));
+  int32_t* vstart = at<int32_t>(ws, l.vstart);
+  int32_t* vend = at<int32_t>(ws, l.vend);
+  VSA_HIP_TRY(hipMemsetAsync(vstart, 0, 4 * (size_t)V, m.st));
+  VSA_HIP_TRY(hipMemsetAsync(vend, 0, 4 * (size_t)V, m.st));
+  hipLaunchKernelGGL(atl_vf_ranges, agrid(n3), dim3(ATL_BLOCK), 0, m.st, kout, n3, vstart, vend);
+  VSA_HIP_TRY(hipGetLastError());
+  float* nv = at<float>(ws, l.nv);
+  hipLaunchKernelGGL(atl_vertex_sums, agrid(V), dim3(ATL_BLOCK), 0, m.st, fn, vff, vstart, vend, V, nv);
+  VSA_HIP_TRY(hipGetLastError());
+  int32_t* label = at<int32_t>(ws, l.label);
+  hipLaunchKernelGGL(atl_labels, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.faces, F, fn, nv, label,
+                     at<uint32_t>(ws, l.code));
+  VSA_HIP_TRY(hipGetLastError());
+  // edges -> join pairs
+  u64* ek = at<u64>(ws, l.A);
+  u64* es = at<u64>(ws, l.B);
+  uint32_t* slot = at<uint32_t>(ws, l.vb);
+  hipLaunchKernelGGL(atl_edge_keys, agrid(n3), dim3(ATL_BLOCK), 0, m.st, m.faces, n3, m.s_bits, ek, vin);
+  VSA_HIP_TRY(hipGetLastError());
+  bytes = l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::radix_sort_pairs(ws + l.tmp, bytes, ek, es, vin, slot, (size_t)n3, 0, 2 * m.s_bits, m.st));
+  int32_t* flags = at<int32_t>(ws, l.flags);
+  int32_t* rank = at<int32_t>(ws, l.rank);
+  hipLaunchKernelGGL(atl_join_flags, agrid(n3), dim3(ATL_BLOCK), 0, m.st, es, slot, m.faces, label, n3, flags);
+  VSA_HIP_TRY(hipGetLastError());
+  bytes = l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, flags, rank, 0, (size_t)n3, rocprim::plus<int32_t>(), m.st));
+  hipLaunchKernelGGL(atl_join_compact, agrid(n3), dim3(ATL_BLOCK), 0, m.st, slot, flags, rank, n3,
+                     at<int2>(ws, l.pairs), m.ctr);
+  VSA_HIP_TRY(hipGetLastError());
+  return VSA_OK;
+}
+
+int chart_stage(Atl& m) {
+  const long long F = m.F;
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  int32_t* par = at<int32_t>(ws, l.par);
+  int32_t* flags = at<int32_t>(ws, l.flags);
+  int32_t* rank = at<int32_t>(ws, l.rank);
+  hipLaunchKernelGGL(atl_iota, agrid(F), dim3(ATL_BLOCK), 0, m.st, par, F);
+  VSA_HIP_TRY(hipGetLastError());
+  // J <= 3F / 2: the grid covers every pair, the kernel reads J on the device
+  hipLaunchKernelGGL(atl_hook, agrid(3 * F / 2 + 1), dim3(ATL_BLOCK), 0, m.st, at<int2>(ws, l.pairs), m.ctr,
+                     at<uint32_t>(ws, l.code), par);
+  VSA_HIP_TRY(hipGetLastError());
+  int32_t* cidx = at<int32_t>(ws, l.cidx);
+  hipLaunchKernelGGL(atl_compress, agrid(F), dim3(ATL_BLOCK), 0, m.st, par, F, cidx, flags);
+  VSA_HIP_TRY(hipGetLastError());
+  size_t bytes = l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, flags, rank, 0, (size_t)F, rocprim::plus<int32_t>(), m.st));
+  hipLaunchKernelGGL(atl_chart_index, agrid(F), dim3(ATL_BLOCK), 0, m.st, flags, rank, F, cidx, m.ctr);
+  VSA_HIP_TRY(hipGetLastError());
+  ATL_TRY(read_ctr(m, ACT_C, &m.C));
+  if (m.C < 1 || m.C > F) return VSA_ERR_UNSUPPORTED;
+  unsigned* box = at<unsigned>(ws, l.box);
+  hipLaunchKernelGGL(atl_box_init, agrid(4 * m.C), dim3(ATL_BLOCK), 0, m.st, box, 4 * m.C);
+  VSA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(atl_boxes, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
+                     box);
+  VSA_HIP_TRY(hipGetLastError());
+  return VSA_OK;
+}
+
+// One shelf walk at density bits `sb`; returns the fit flag in *fit.
+int pack_step(Atl& m, uint32_t sb, int emit, long long* fit) {
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  const long long C = m.C;
+  float s;
+  memcpy(&s, &sb, 4);
+  u64* keys = at<u64>(ws, l.A);
+  u64* sorted = at<u64>(ws, l.B);
+  long long* wid = at<long long>(ws, l.wid);
+  long long* pre = at<long long>(ws, l.pre);
+  hipLaunchKernelGGL(atl_rect_keys, agrid(C), dim3(ATL_BLOCK), 0, m.st, at<unsigned>(ws, l.box), C, s, m.R, m.p, keys);
+  VSA_HIP_TRY(hipGetLastError());
+  size_t bytes = l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::radix_sort_keys(ws + l.tmp, bytes, keys, sorted, (size_t)C, 0, 64, m.st));
+  hipLaunchKernelGGL(atl_rect_widths, agrid(C), dim3(ATL_BLOCK), 0, m.st, sorted, C, wid);
+  VSA_HIP_TRY(hipGetLastError());
+  VSA_HIP_TRY(hipMemsetAsync(pre, 0, 8, m.st));
+  bytes = l.tmp_bytes;
+  VSA_HIP_TRY(rocprim::inclusive_scan(ws + l.tmp, bytes, wid, pre + 1, (size_t)C, rocprim::plus<long long>(), m.st));
+  hipLaunchKernelGGL(atl_shelf_walk, dim3(1), dim3(1), 0, m.st, sorted, pre, C, m.R, emit,
+                     at<int32_t>(ws, l.sh_start), at<int32_t>(ws, l.sh_y), m.ctr);
+  VSA_HIP_TRY(hipGetLastError());
+  return read_ctr(m, ACT_FIT, fit);
+}
+
+// Smallest resolution at which C charts of (2p)^2 texels fit by next-fit shelves.
+long long min_resolution(long long C, int p) {
+  const long long side = 2ll * p;
+  for (long long r = side;; ++r) {
+    const long long per = r / side;
+    if (per > 0 && ((C + per - 1) / per) * side <= r) return r;
+  }
+}
+
+int pack_stage(Atl& m, uint32_t* s_out, long long* minres) {
+  const long long C = m.C;
+  if (m.p > 0) {
+    const long long side = 2ll * m.p, per = m.R / side;
+    if (per == 0 || ((C + per - 1) / per) * side > m.R) {
+      *minres = min_resolution(C, m.p);
+      return VSA_ERR_ATLAS_FULL;
+    }
+  }
+  uint32_t lo = 0u, hi = 0x7F800000u;   // fits(lo); hi (+inf) is never tried
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    long long fit = 0;
+    ATL_TRY(pack_step(m, mid, 0, &fit));
+    if (fit) lo = mid;
+    else hi = mid;
+  }
+  long long fit = 0;
+  ATL_TRY(pack_step(m, lo, 1, &fit));
+  if (!fit) return VSA_ERR_UNSUPPORTED;
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  hipLaunchKernelGGL(atl_offsets, agrid(C), dim3(ATL_BLOCK), 0, m.st, at<u64>(ws, l.B), at<long long>(ws, l.pre), C,
+                     at<int32_t>(ws, l.sh_start), at<int32_t>(ws, l.sh_y), m.ctr, at<int2>(ws, l.off));
+  VSA_HIP_TRY(hipGetLastError());
+  *s_out = lo;
+  return VSA_OK;
+}
+
+int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  const long long F = m.F;
+  VSA_HIP_TRY(hipMemsetAsync(m.ctr, 0, 8 * ACT_N, m.st));
+  ATL_TRY(stage_open(m));
+  ATL_TRY(label_stage(m));
+  ATL_TRY(stage_close(m, 0));
+  int32_t* count = at<int32_t>(ws, l.count);
+  int32_t* flag = at<int32_t>(ws, l.flag);
+  int32_t* cidx = at<int32_t>(ws, l.cidx);
+  long long splits = 0;
+  uint32_t sb = 0;
+  while (true) {
+    ATL_TRY(stage_open(m));
+    ATL_TRY(chart_stage(m));
+    ATL_TRY(stage_close(m, 1));
+    ATL_TRY(stage_open(m));
+    long long minres = 0;
+    const int rc = pack_stage(m, &sb, &minres);
+    if (rc == VSA_ERR_ATLAS_FULL) {
+      stats[0] = m.C;
+      stats[1] = splits;
+      stats[2] = 0;
+      stats[3] = minres;
+    }
+    if (rc != VSA_OK) return rc;
+    ATL_TRY(stage_close(m, 2));
+    ATL_TRY(stage_open(m));
+    float s;
+    memcpy(&s, &sb, 4);
+    hipLaunchKernelGGL(atl_emit, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
+                       at<unsigned>(ws, l.box), at<int2>(ws, l.off), s, m.R, m.p, uv);
+    VSA_HIP_TRY(hipGetLastError());
+    ATL_TRY(stage_close(m, 3));
+    ATL_TRY(stage_open(m));
+    VSA_HIP_TRY(hipMemsetAsync(count, 0, 4 * (size_t)m.R * (size_t)m.R, m.st));
+    VSA_HIP_TRY(hipMemsetAsync(flag, 0, 4 * (size_t)m.C, m.st));
+    VSA_HIP_TRY(hipMemsetAsync(m.ctr + ACT_OVL, 0, 16, m.st));
+    ATL_TRY(raster(m.st, ws, l, uv, F, m.R, count, nullptr, cidx, flag));
+    hipLaunchKernelGGL(atl_count_flags, agrid(m.C), dim3(ATL_BLOCK), 0, m.st, flag, m.C, m.ctr);
+    VSA_HIP_TRY(hipGetLastError());
+    long long ovl = 0;
+    ATL_TRY(read_ctr(m, ACT_OVL, &ovl));
+    if (ovl == 0) {
+      const long long rr = (long long)m.R * m.R;
+      hipLaunchKernelGGL(atl_covered, agrid(rr), dim3(ATL_BLOCK), 0, m.st, count, rr, m.ctr);
+      VSA_HIP_TRY(hipGetLastError());
+      VSA_HIP_TRY(hipMemcpyAsync(out_chart, cidx, 4 * (size_t)F, hipMemcpyDeviceToDevice, m.st));
+      long long cov = 0;
+      ATL_TRY(read_ctr(m, ACT_COV, &cov));
+      ATL_TRY(stage_close(m, 4));
+      stats[0] = m.C;
+      stats[1] = splits;
+      stats[2] = cov;
+      stats[3] = 0;
+      memcpy(scale, &sb, 4);
+      return VSA_OK;
+    }
+    // a texel counted twice across two charts, or one-face charts flagged, would repeat the round unchanged
+    if (splits + 1 >= ATL_MAX_ROUNDS) return VSA_ERR_UNSUPPORTED;
+    VSA_HIP_TRY(hipMemsetAsync(m.ctr + ACT_PROG, 0, 8, m.st));
+    hipLaunchKernelGGL(atl_split, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
+                       at<unsigned>(ws, l.box), flag, at<uint32_t>(ws, l.code), m.ctr);
+    VSA_HIP_TRY(hipGetLastError());
+    long long changed = 0;
+    ATL_TRY(read_ctr(m, ACT_PROG, &changed));
+    if (changed == 0) return VSA_ERR_UNSUPPORTED;
+    ATL_TRY(stage_close(m, 4));
+    ++splits;
+  }
+}
+
+}  // namespace
+
+extern "C" int vsa_atlas(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                         int resolution, int padding, void* workspace, long long workspace_bytes, float* out_faces_uvs,
+                         int32_t* out_chart, long long* stats, float* scale, float* stage_ms, void* stream) {
+  if (!verts || !faces || !workspace || !out_faces_uvs || !out_chart || !stats || !scale) return VSA_ERR_ARG;
+  int rc = atl_check(nr_verts, nr_faces, resolution);
+  if (rc != VSA_OK) return rc;
+  if (padding < 0 || 2 * padding >= resolution) return VSA_ERR_ARG;
+  Atl m;
+  rc = atl_layout(nr_verts, nr_faces, resolution, &m.l);
+  if (rc != VSA_OK) return rc;
+  if (workspace_bytes < (long long)m.l.total) return VSA_ERR_ARG;
+  m.st = (hipStream_t)stream;
+  m.ws = static_cast<char*>(workspace);
+  m.V = nr_verts;
+  m.F = nr_faces;
+  m.C = 0;
+  m.R = resolution;
+  m.p = padding;
+  m.P = verts;
+  m.faces = faces;
+  m.s_bits = 1;
+  while ((1ll << m.s_bits) < nr_verts) ++m.s_bits;
+  m.ctr = at<long long>(m.ws, m.l.ctr);
+  m.stage_ms = stage_ms;
+  if (stage_ms) {
+    for (int k = 0; k < 5; ++k) stage_ms[k] = 0.f;
+    VSA_HIP_TRY(hipEventCreate(&m.ev[0]));
+    VSA_HIP_TRY(hipEventCreate(&m.ev[1]));
+  }
+  rc = run(m, out_faces_uvs, out_chart, stats, scale);
+  if (stage_ms) {
+    (void)hipEventDestroy(m.ev[0]);
+    (void)hipEventDestroy(m.ev[1]);
+  }
+  return rc;
+}
+
+extern "C" int vsa_atlas_rasterize(const float* faces_uvs, long long nr_faces, int resolution, void* workspace,
+                                   long long workspace_bytes, int32_t* out_face_id, int32_t* out_count, void* stream) {
+  if (!faces_uvs || !workspace || !out_face_id || !out_count) return VSA_ERR_ARG;
+  if (nr_faces < 1 || resolution < ATL_MIN_RES || resolution > ATL_MAX_RES) return VSA_ERR_ARG;
+  if (nr_faces > 0x7FFFFFFFll) return VSA_ERR_UNSUPPORTED;
+  AtlLayout l;
+  int rc = atl_layout(0, nr_faces, resolution, &l);
+  if (rc != VSA_OK) return rc;
+  if (workspace_bytes < (long long)l.total) return VSA_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t rr = (size_t)resolution * (size_t)resolution;
+  VSA_HIP_TRY(hipMemsetAsync(out_count, 0, 4 * rr, st));
+  VSA_HIP_TRY(hipMemsetAsync(out_face_id, 0xFF, 4 * rr, st));
+  rc = raster(st, static_cast<char*>(workspace), l, faces_uvs, nr_faces, resolution, out_count,
+              reinterpret_cast<uint32_t*>(out_face_id), nullptr, nullptr);
+  if (rc != VSA_OK) return rc;
+  VSA_HIP_TRY(hipStreamSynchronize(st));
+  return VSA_OK;
+}
