@@ -436,6 +436,33 @@ int vsa_nt_shade_bwd(const vsa_nt_plan* plan, const int32_t* hit_slot, const flo
                      const float* g_surfs_alpha, float grad_scale, uint16_t* grad_rows,
                      const float* act_in, void* stream);
 
+/* Texture export / import (csrc/texture_io.hip): the baked 8-bit texel rows <-> the RGBA8 images of the baker's
+ * `--extract_textures` (volsurfs_py/baker.py:778-1009), one image per (shell, degree d, coefficient i).
+ *   planes      u8, contiguous [R_d, R_d, 4] images ordered (shell, degree, coefficient): image (s, d, i) starts at
+ *               byte s * S + sum_{d' < d} (2d'+1) 4 R_d'^2 + i * 4 R_d^2, S = sum_{d < rgb_degrees} (2d+1) 4 R_d^2;
+ *               vsa_nt_planes_bytes(plan) = nr_shells * S (or a VSA_ERR_* code).
+ *   orientation pixel (row r, column c) of image (s, d, i) holds texel (iy, ix) = (c, R-1-r) of the network's grid
+ *               (the bake grid's axis 0 = u_pix flipped by np.flipud, axis 1 = v_pix), i.e. the texel a hit at uv
+ *               reads under anchor addressing when r = floor(v R), c = floor(u R).  Only the R x R interior.
+ *   bytes       R, G, B = the texel row's rgb elements channel * (2d+1) + i, A = its alpha element i; A = 255 on a
+ *               shell without an alpha model (nt_shell_has_alpha: the solid inner shell, every shell when the alpha
+ *               model is shared as well).  The stored 8-bit values unchanged.
+ * vsa_nt_export_planes reads the rows through slot_of / seg_start / row_base of a baked bank (every texel marked,
+ * then vsa_nt_compact_frame).  vsa_nt_import_planes is the inverse into a bank whose slots were set up the same way:
+ * interior rows get the image bytes (padding zero; alpha elements zero without an alpha model), and the one-texel
+ * apron is CLAMPED TO THE EDGE: apron texel (iy, ix) gets the row of interior texel (clamp(iy, 0, R-1),
+ * clamp(ix, 0, R-1)) -- the border rule of renderers.TensorTexture and of a viewer sampling with CLAMP_TO_EDGE (the
+ * baked bank holds the network's values there instead; lerp reads them only for uv within half a texel of the
+ * border).  A texel whose slot lies outside its segment is skipped (export: written as zero bytes).
+ * planes and texels must be 16-byte aligned and planes_bytes = vsa_nt_planes_bytes(plan).
+ * VSA_ERR_ARG: NULL pointers, misalignment, a wrong planes_bytes, nr_shells or a resolution out of range.
+ * VSA_ERR_UNSUPPORTED: alpha_degrees != rgb_degrees or row_format != 0. */
+long long vsa_nt_planes_bytes(const vsa_nt_plan* plan);
+int vsa_nt_export_planes(const vsa_nt_plan* plan, const int32_t* slot_of, const int32_t* seg_start,
+                         const uint8_t* texels, uint8_t* planes, long long planes_bytes, void* stream);
+int vsa_nt_import_planes(const vsa_nt_plan* plan, const uint8_t* planes, long long planes_bytes,
+                         const int32_t* slot_of, const int32_t* seg_start, uint8_t* texels, void* stream);
+
 /* Backward of step 3: grad_tables (f32 [n_tex][level_offset[n]][2]) +=
  * transpose-interpolation of dfeatures (f16x2, same layout as features, holding
  * grad * grad_scale).  Accumulates (caller zeroes grad_tables per optimiser step; plan->grads_zeroed

@@ -79,7 +79,7 @@ class NeuralTextureBank(torch.nn.Module):
                  sh_range=(15.0, 15.0, 15.0, 15.0), textures_res=(2048, 1024, 512, 256),
                  inner_solid=False, with_alpha_decay=True, device="cuda", seed=42,
                  training=True, anchor=False, lerp=True, quantize_output=True, squeeze_output=True,
-                 grid=None, shared_rgb=False, shared_alpha=False):
+                 grid=None, shared_rgb=False, shared_alpha=False, parameters=True):
         """anchor / lerp / quantize_output / squeeze_output: NeuralTexture's switches
         (models/neural_texture.py:19-52; config keys using_neural_textures_anchor / _lerp,
         using_sh_quantization, using_sh_squeezing).  Built: lerp (the shipped configs) and anchor, each with 8-bit
@@ -92,7 +92,9 @@ class NeuralTextureBank(torch.nn.Module):
         means NO alpha model at all: the reference's loop stores models["alpha"] = None at i = 0 and leaves.
         grid: keyword arguments of grid_geometry() for a hash grid other than the reference's
         (16 levels always: the MLP reads 32 features); levels of more than 2^15 entries are refused
-        by the library (one level = one LDS plane)."""
+        by the library (one level = one LDS plane).
+        parameters=False: a bank that only holds texel rows written from outside (texture_export.load_scene):
+        no hash tables, MLP weights, feature planes or gradient rows; `tables` / `weights` are None."""
         super().__init__()
         if bool(anchor) == bool(lerp):
             raise ValueError("NeuralTexture is either anchor or lerp (neural_texture.py:47-51, 141-147)")
@@ -143,6 +145,11 @@ class NeuralTextureBank(torch.nn.Module):
         self.plan, self.dom_total, self.slot_capacity = p, off, cap
         self.tex_res = tuple(int(r) for r in textures_res)
 
+        self.has_parameters = bool(parameters)
+        if not parameters:
+            self.tables = self.weights = None
+            self._alloc(device, training=False)
+            return
         # ---- parameters (fp32 masters), tcnn-style init: U(-1e-4, 1e-4) tables,
         # Xavier-uniform weights
         g = torch.Generator().manual_seed(seed)
@@ -200,14 +207,18 @@ class NeuralTextureBank(torch.nn.Module):
         self.slot_xy = torch.zeros(cap, 2, device=dev)
         self.seg_start = torch.zeros(K * MAX_DEG + 1, dtype=i32, device=dev)
         self.block_scratch = torch.zeros(self.dom_total // DOM_BLOCK + 1, dtype=i32, device=dev)
+        texel_dtype = u8 if self.row_format == 0 else torch.float16
+        if not self.has_parameters:
+            self.features = self.tables_h = self.weights_h = self.grad_rows = None
+            self.texels = torch.zeros(self.row_quads_total * 4, dtype=texel_dtype, device=dev)
+            return
         # blocked layout [type][slot/256][level][slot%256][2]  (nt_common.h: nt_feat_index)
         self.features = torch.empty(2, cap // 256, 16, 256, 2, dtype=torch.float16, device=dev)
         self.tables_h = torch.empty(self.n_tex, self.n_entries, 2, dtype=torch.float16, device=dev)
         self.weights_h = torch.empty(self.n_tex, WEIGHTS_PER_TEX, dtype=torch.float16, device=dev)
         # per-degree row widths (include/volsurfs_hip.h: VSA_NT_ROW_QUADS), 4 elements per quad
         # texel rows: 4 elements per quad — bytes (8-bit quantised) or halves (row_format 1)
-        self.texels = torch.zeros(self.row_quads_total * 4, dtype=u8 if self.row_format == 0 else torch.float16,
-                                  device=dev)
+        self.texels = torch.zeros(self.row_quads_total * 4, dtype=texel_dtype, device=dev)
         self.grad_rows = torch.zeros(self.row_quads_total * 4, dtype=torch.float16, device=dev) if training else None
         self.refresh_half_params()
 
@@ -258,6 +269,15 @@ class NeuralTextureBank(torch.nn.Module):
         with max_rays >= full_capacity_rays(textures_res)."""
         if self.row_format != 0:
             raise _lib.VolsurfsHipError("baked textures are the 8-bit deploy format: using_sh_quantization=1 only")
+        self.compact_all()
+        self.evaluate(need_features=False)
+        self.baked = True
+        return self
+
+    @torch.no_grad()
+    def compact_all(self, want_texel_of_slot=True):
+        """Give EVERY texel of every (shell, degree) domain, interior and one-texel apron, a slot: all marks set,
+        then vsa_nt_compact_frame (the slot layout of a baked bank)."""
         self.marks.zero_()
         for s in range(self.K):
             for d in range(self.D):
@@ -269,11 +289,8 @@ class NeuralTextureBank(torch.nn.Module):
                 off = int(self.plan.dom_off[s * MAX_DEG + d])
                 self.marks[off:off + W * W].view(W, W).fill_(1)   # interior + the one-texel apron
         _lib.call("vsa_nt_compact_frame", ctypes.byref(self.plan), self.marks, self.slot_of,
-                  self.texel_of_slot, self.slot_xy, self.seg_start, self.block_scratch,
-                  _lib.stream_ptr())
-        self.evaluate(need_features=False)
-        self.baked = True
-        return self
+                  self.texel_of_slot if want_texel_of_slot else None, self.slot_xy, self.seg_start,
+                  self.block_scratch, _lib.stream_ptr())
 
     @torch.no_grad()
     def baked_textures(self):

@@ -12,7 +12,8 @@
   expanded to +-sh_range; the fetch uses the texel convention of NeuralTexture.forward
   (models/neural_texture.py:107-138), the one the textures were baked with.
 * VolsurfsRenderer — an empty stub in the reference (volsurfs_renderer.py:1-9); here the K-shell
-  deploy renderer on VolSurfs.render_baked()."""
+  deploy renderer on VolSurfs.render_baked(), or (`from_scene`) on an exported scene read back by
+  texture_export.load_scene."""
 import json
 import os
 from abc import ABC, abstractmethod
@@ -181,7 +182,7 @@ class MeshRenderer(BaseRenderer):
 
 class VolsurfsRenderer(BaseRenderer):
     """K nested shells from their baked textures (the deploy format): method = a
-    volsurfs_amd.methods.VolSurfs on which bake() has run."""
+    volsurfs_amd.methods.VolSurfs on which bake() has run, or a texture_export.BakedScene."""
 
     def __init__(self, method, profiler=None):
         super().__init__(profiler=profiler)
@@ -189,6 +190,13 @@ class VolsurfsRenderer(BaseRenderer):
             method.bake()
         self.method = method
         self.active_render_mode, self.active_shader = "ray_traced", "rgb"
+
+    @classmethod
+    def from_scene(cls, scene_path, device="cuda", bvh_builder="host", profiler=None):
+        """The renderer of a scene written by texture_export.extract_textures (scene.json, meshes/*.obj,
+        textures/*.png), loaded with texture_export.load_scene."""
+        from .texture_export import load_scene
+        return cls(load_scene(scene_path, device=device, bvh_builder=bvh_builder), profiler=profiler)
 
     @torch.no_grad()
     def render_rays(self, rays_o, rays_d, verbose=False) -> dict:
