@@ -803,6 +803,32 @@ int vsa_packed_composite_bwd(const int32_t* start_end, const float* density, con
                              const float* rgb, const float* g_pred_rgb, float* g_rgb,
                              float* g_density, float* scratch, int nr_rays, int bug_compat,
                              void* stream);
+/* NeRF's foreground render (volsurfs_py/methods/nerf.py render_fg_volumetric and the bg blend of
+ * render_rays) as one launch each way (csrc/nerf_render.hip states the summation orders).  Forward:
+ * alpha = 1 - exp(-density dt), T = cumprod((1 - alpha) + 1e-6), w = alpha T; rgb_fg [N,3] =
+ * integrate_with_weights_3d(rgb, w), weights_sum [N] = sum_over_rays(w), depth [N] =
+ * integrate_with_weights_1d(samples_z, w); with rgb_bg (NULL: none) rgb_out [N,3] = rgb_fg +
+ * (1 - weights_sum) rgb_bg, where rgb_bg is [N,3] (bg_per_ray = 1) or one colour [3] (0); weights
+ * [S] is optional.  Backward: g_rgb [N,3] (the gradient of rgb_out, or of rgb_fg without a
+ * background), g_weights_sum [N] or NULL -> g_density [S], g_rgb_samples [S,3], g_rgb_bg [N,3]
+ * (optional; needs rgb_bg and the forward's weights_sum); bug_compat as in
+ * vsa_packed_integrate_bwd; scratch: 2 S floats.  Bit-identical to the chain of the single ops
+ * above (cumprod, integrate_3d, sum_over_rays and their backward).  The per-sample arrays may be NULL
+ * when the pack has no samples. */
+int vsa_nerf_composite_fwd(const int32_t* start_end, const float* density, const float* dt,
+                           const float* samples_z, const float* rgb, const float* rgb_bg, int bg_per_ray,
+                           float* rgb_fg, float* rgb_out, float* weights_sum, float* depth, float* weights,
+                           int nr_rays, void* stream);
+int vsa_nerf_composite_bwd(const int32_t* start_end, const float* density, const float* dt,
+                           const float* rgb, const float* rgb_bg, int bg_per_ray, const float* weights_sum,
+                           const float* g_rgb, const float* g_weights_sum, float* g_density,
+                           float* g_rgb_samples, float* g_rgb_bg, float* scratch, int nr_rays,
+                           int bug_compat, void* stream);
+/* importance_sampling_nerf (volsurfs_py/utils/nerf_utils.py:61-82) from the uniform samples'
+ * densities [S] and dt [S] to cdf [S]: clamped alpha, the cumprod with +1e-6, w = alpha T,
+ * w / max(sum_over_rays(w), 1e-6), compute_cdf.  Bit-identical to that chain of single ops. */
+int vsa_nerf_coarse_cdf(const int32_t* start_end, const float* density, const float* dt, float* cdf,
+                        int nr_rays, void* stream);
 /* median_depth_over_rays (:372-416); fallback_compat=1 reproduces VolumeRenderingGPU.cuh:407. */
 int vsa_packed_median_depth(const int32_t* start_end, const float* samples_z,
                             const float* weights, float threshold, float* out, int nr_rays,

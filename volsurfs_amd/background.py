@@ -41,6 +41,11 @@ class BoundingBox:
         return points.abs().amax(-1) <= self.half
 
     @torch.no_grad()
+    def get_random_points_inside(self, nr_points, device="cuda"):
+        """[n, 3] points uniform in the box (the sparsity loss's samples, methods/nerf.py:462-464)."""
+        return (torch.rand(int(nr_points), 3, device=device) * 2.0 - 1.0) * self.half
+
+    @torch.no_grad()
     def intersect(self, rays_o, rays_d):
         return _intersect(0, self.half, rays_o, rays_d)
 
@@ -57,6 +62,13 @@ class BoundingSphere:
         """[P, 3] -> [P] bool: ||p|| <= radius (closed).  The reference's class lives in the absent mvdatasets
         (utils/mesh_extraction.py:356): the boundary's semantics are unpinned, this is ours."""
         return torch.linalg.vector_norm(points, dim=-1) <= self.radius
+
+    @torch.no_grad()
+    def get_random_points_inside(self, nr_points, device="cuda"):
+        """[n, 3] points uniform in the ball: a normalised Gaussian direction times radius * u^(1/3)."""
+        n = int(nr_points)
+        d = torch.nn.functional.normalize(torch.randn(n, 3, device=device), dim=-1)
+        return d * (self.radius * torch.rand(n, 1, device=device).pow(1.0 / 3.0))
 
     @torch.no_grad()
     def intersect(self, rays_o, rays_d):

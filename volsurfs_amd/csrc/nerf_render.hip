@@ -1,0 +1,295 @@
+// The two per-ray chains of the NeRF method (volsurfs_py/methods/nerf.py, utils/nerf_utils.py)
+// that the reference runs as long sequences of single ops on every ray of every iteration, fused
+// into one launch each.
+//
+// Layout as in packed.hip: a ray is owned by a 32-lane half-wave, lanes = consecutive samples
+// (coalesced rows), segmented scans / reductions by shuffles, chunks of 32 samples with a carried
+// running value for longer rays.  No atomics: every output element has exactly one writer, so the
+// output bits depend only on the inputs.  Every fp32 operation is the one the single-op chain
+// performs, in its order (the build has -ffp-contract=off): the scans and reductions below are the
+// ones of packed.hip's cumprod / cumsum / integrate / sum_over_rays / compute_cdf kernels, so the
+// results are bit-identical to that chain (tests/test_nerf_render.py).
+#include "common.h"
+
+namespace {
+
+constexpr int NR_BLOCK = 256;
+constexpr int SUB = 32;  // lanes per ray
+
+// the same shuffle scans / reduction as packed.hip (same partner order -> same bits)
+__device__ __forceinline__ float sub_scan_mul(float v, int l) {
+#pragma unroll
+  for (int off = 1; off < SUB; off <<= 1) {
+    const float u = __shfl_up(v, off, SUB);
+    if (l >= off) v *= u;
+  }
+  return v;
+}
+__device__ __forceinline__ float sub_scan_add(float v, int l) {
+#pragma unroll
+  for (int off = 1; off < SUB; off <<= 1) {
+    const float u = __shfl_up(v, off, SUB);
+    if (l >= off) v += u;
+  }
+  return v;
+}
+__device__ __forceinline__ float sub_reduce_add(float v) {
+#pragma unroll
+  for (int off = SUB / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, SUB);
+  return v;
+}
+
+#define NR_RAY_PROLOGUE()                                                        \
+  const int l = threadIdx.x & (SUB - 1);                                         \
+  const long long ray = ((long long)blockIdx.x * NR_BLOCK + threadIdx.x) / SUB;  \
+  if (ray >= N) return;                                                          \
+  const int i0 = start_end[2 * ray], i1 = start_end[2 * ray + 1];                \
+  const int n = i1 - i0;
+
+// One chunk step of T = cumprod((1 - alpha) + 1e-6) (exclusive, carried across chunks) for the
+// sample of lane l; returns T and advances `carry`.
+__device__ __forceinline__ float transmittance_step(float a1, bool in, int l, float& carry) {
+  const float incl = sub_scan_mul(in ? a1 : 1.0f, l);
+  float excl = __shfl_up(incl, 1, SUB);
+  if (l == 0) excl = 1.0f;
+  const float T = carry * excl;
+  carry *= __shfl(incl, SUB - 1, SUB);
+  return T;
+}
+
+// Forward.  Per ray, with w_i = alpha_i T_i:
+//   rgb_fg_d = sum_i w_i rgb_id   lane-strided partial sums over i = l, l + 32, .. then the
+//                                 xor butterfly (integrate_fwd_kernel<3>);
+//   depth    = sum_i w_i z_i      the same order (integrate_fwd_kernel<1>);
+//   wsum     = sum over chunks of the butterfly sum of the chunk (sum_over_rays_kernel<1>);
+//   rgb_d    = rgb_fg_d + (1 - wsum) bg_d.
+__global__ void nerf_composite_fwd_kernel(const int* __restrict__ start_end,
+                                          const float* __restrict__ density,
+                                          const float* __restrict__ dt,
+                                          const float* __restrict__ z,
+                                          const float* __restrict__ rgb,
+                                          const float* __restrict__ rgb_bg, int bg_stride,
+                                          float* __restrict__ rgb_fg, float* __restrict__ rgb_out,
+                                          float* __restrict__ wsum_out,
+                                          float* __restrict__ depth_out,
+                                          float* __restrict__ weights, int N) {
+  NR_RAY_PROLOGUE();
+  float acc[3] = {0.f, 0.f, 0.f};
+  float accz = 0.f, ws = 0.f;
+  float carry = 1.0f;
+  for (int c = 0; c < n; c += SUB) {
+    const int i = c + l;
+    const bool in = i < n;
+    const long long s = i0 + (in ? i : 0);
+    const float e = expf((-density[s]) * dt[s]);
+    const float alpha = 1.0f - e;
+    const float a1 = (1.0f - alpha) + 1e-6f;
+    const float T = transmittance_step(a1, in, l, carry);
+    const float w = alpha * T;
+    if (in) {
+      if (weights) weights[s] = w;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) acc[d] += w * rgb[s * 3 + d];
+      accz += w * z[s];
+    }
+    ws += sub_reduce_add(in ? w : 0.f);
+  }
+  float fg[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) fg[d] = sub_reduce_add(acc[d]);
+  const float depth = sub_reduce_add(accz);
+  if (l == 0) {
+    wsum_out[ray] = ws;
+    depth_out[ray] = depth;
+    const float bgT = 1.0f - ws;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      rgb_fg[ray * 3 + d] = fg[d];
+      if (rgb_out) rgb_out[ray * 3 + d] = rgb_bg ? fg[d] + bgT * rgb_bg[ray * bg_stride + d] : fg[d];
+    }
+  }
+}
+
+// Backward.  Per ray: g_d = g_rgb_d;  with a background
+//   g_bgT = (g_0 bg_0 + g_1 bg_1) + g_2 bg_2,  g_bg_d = g_d (1 - wsum),
+//   g_wsum = g_wsum_in + (-g_bgT)             (g_wsum_in = 0 without the mask term).
+// Per sample, forward sweep (T recomputed as in the forward kernel):
+//   g_w   = (g_0 rgb_0 + g_1 rgb_1) + g_2 rgb_c   (c = 1 under bug_compat, else 2: integrate_bwd_kernel<3>)
+//           + g_wsum                               (sum_over_rays_bwd_kernel: the per-ray gradient)
+//   g_rgb_sample_d = g_d w;  lv = (g_w alpha) T;  g_w T kept for the reversed sweep.
+// Reversed sweep: the suffix sums of lv in cumsum_kernel(inverse)'s order, the cumprod backward
+// (next suffix sum / max(a1, 1e-6), 0 for the ray's last sample), then
+//   g_alpha = g_w T + (-g_a1),  g_density = -(((-g_alpha) e) dt).
+// scratch: 2 floats per sample.
+__global__ void nerf_composite_bwd_kernel(const int* __restrict__ start_end,
+                                          const float* __restrict__ density,
+                                          const float* __restrict__ dt,
+                                          const float* __restrict__ rgb,
+                                          const float* __restrict__ rgb_bg, int bg_stride,
+                                          const float* __restrict__ wsum,
+                                          const float* __restrict__ g_rgb,
+                                          const float* __restrict__ g_wsum_in,
+                                          float* __restrict__ g_density,
+                                          float* __restrict__ g_rgb_samples,
+                                          float* __restrict__ g_rgb_bg,
+                                          float* __restrict__ scratch, int N, int bug_compat) {
+  NR_RAY_PROLOGUE();
+  float g[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) g[d] = g_rgb[ray * 3 + d];
+  float g_ws = g_wsum_in ? g_wsum_in[ray] : 0.0f;
+  if (rgb_bg) {
+    const float* b = rgb_bg + ray * bg_stride;
+    float g_bgT = g[0] * b[0];
+    g_bgT += g[1] * b[1];
+    g_bgT += g[2] * b[2];
+    g_ws = g_wsum_in ? g_ws + (-g_bgT) : -g_bgT;
+    if (g_rgb_bg && l == 0) {
+      const float bgT = 1.0f - wsum[ray];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) g_rgb_bg[ray * 3 + d] = g[d] * bgT;
+    }
+  }
+  if (n <= 0) return;
+  float carry = 1.0f;
+  for (int c = 0; c < n; c += SUB) {
+    const int i = c + l;
+    const bool in = i < n;
+    const long long s = i0 + (in ? i : 0);
+    const float e = expf((-density[s]) * dt[s]);
+    const float alpha = 1.0f - e;
+    const float a1 = (1.0f - alpha) + 1e-6f;
+    const float T = transmittance_step(a1, in, l, carry);
+    if (in) {
+      const float w = alpha * T;
+      float gw = 0.f;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        g_rgb_samples[s * 3 + d] = g[d] * w;
+        const int col = (bug_compat && d == 2) ? 1 : d;
+        gw += g[d] * rgb[s * 3 + col];
+      }
+      gw = gw + g_ws;
+      const float gT = gw * alpha;
+      scratch[2 * s] = gT * T;
+      scratch[2 * s + 1] = gw * T;
+    }
+  }
+  float csum = 0.0f;
+  for (int c = 0; c < n; c += SUB) {
+    const int i = c + l;
+    const bool in = i < n;
+    const long long s = in ? (long long)i1 - 1 - i : (long long)i0;
+    const float incl = sub_scan_add(in ? scratch[2 * s] : 0.0f, l);
+    const float cs = csum + incl;
+    float cs_next = __shfl_up(cs, 1, SUB);
+    if (l == 0) cs_next = csum;
+    csum += __shfl(incl, SUB - 1, SUB);
+    if (in) {
+      const float dts = dt[s];
+      const float e = expf((-density[s]) * dts);
+      const float alpha = 1.0f - e;
+      const float a1 = (1.0f - alpha) + 1e-6f;
+      float ga1 = 0.f;
+      if (i > 0) ga1 = cs_next / fmaxf(a1, 1e-6f);
+      const float g_alpha = scratch[2 * s + 1] + (-ga1);
+      const float gu = (-g_alpha) * e;
+      g_density[s] = -(gu * dts);
+    }
+  }
+}
+
+// The coarse pass of importance_sampling_nerf (utils/nerf_utils.py:61-82) from the uniform
+// samples' densities to the CDF:
+//   alpha = min(max(1 - exp(-density dt), 0), 1);  T = cumprod((1 - alpha) + 1e-6);  w = alpha T;
+//   wsum  = sum over chunks of the butterfly sum of the chunk (sum_over_rays_kernel<1>);
+//   w    /= max(wsum, 1e-6);
+//   cdf_i = carry + (incl_i - w_i) with incl the chunk's inclusive shuffle scan, and the last entry
+//           snapped to 1 when |wsum' - 1| < 1e-3 and |cdf_last - 1| > 1e-3 (compute_cdf_kernel).
+// Rays with fewer than 2 samples get a zero CDF (compute_cdf leaves them at zero).  The first
+// sweep parks w in `cdf` (each lane re-reads only what it wrote).
+__global__ void nerf_coarse_cdf_kernel(const int* __restrict__ start_end,
+                                       const float* __restrict__ density,
+                                       const float* __restrict__ dt, float* __restrict__ cdf,
+                                       int N) {
+  NR_RAY_PROLOGUE();
+  if (n < 2) {
+    if (n == 1 && l == 0) cdf[i0] = 0.0f;
+    return;
+  }
+  float carry = 1.0f, ws = 0.f;
+  for (int c = 0; c < n; c += SUB) {
+    const int i = c + l;
+    const bool in = i < n;
+    const long long s = i0 + (in ? i : 0);
+    const float e = expf((-density[s]) * dt[s]);
+    const float alpha = fminf(fmaxf(1.0f - e, 0.0f), 1.0f);
+    const float a1 = (1.0f - alpha) + 1e-6f;
+    const float T = transmittance_step(a1, in, l, carry);
+    const float w = alpha * T;
+    if (in) cdf[s] = w;
+    ws += sub_reduce_add(in ? w : 0.f);
+  }
+  const float wn = fmaxf(ws, 1e-6f);
+  float run = 0.0f, last_cdf = 0.0f;
+  for (int c = 0; c < n; c += SUB) {
+    const int i = c + l;
+    const float x = i < n ? cdf[i0 + i] / wn : 0.0f;
+    const float incl = sub_scan_add(x, l);
+    const float excl = run + (incl - x);
+    if (i < n) cdf[i0 + i] = excl;
+    if (i == n - 1) last_cdf = excl;
+    run += __shfl(incl, SUB - 1, SUB);
+  }
+  const int owner = (n - 1) & (SUB - 1);
+  if (l == owner && fabs((double)run - 1.0) < 1e-3 && fabs((double)last_cdf - 1.0) > 1e-3)
+    cdf[i1 - 1] = 1.0f;
+}
+
+inline dim3 nr_grid(int N) { return dim3(vsa_div_up((long long)N * SUB, NR_BLOCK)); }
+
+}  // namespace
+
+#define NR_CHECK(cond) \
+  if (!(cond)) return VSA_ERR_ARG
+#define NR_LAUNCH(kernel, N, ...)                                                          \
+  if ((N) == 0) return VSA_OK;                                                             \
+  hipLaunchKernelGGL(kernel, nr_grid(N), dim3(NR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); \
+  VSA_RETURN_LAUNCH_STATUS()
+
+extern "C" int vsa_nerf_composite_fwd(const int32_t* start_end, const float* density,
+                                      const float* dt, const float* samples_z, const float* rgb,
+                                      const float* rgb_bg, int bg_per_ray, float* rgb_fg,
+                                      float* rgb_out, float* weights_sum, float* depth,
+                                      float* weights, int nr_rays, void* stream) {
+  // the per-sample arrays are only read for rays with samples: NULL is fine for a pack without any
+  NR_CHECK(nr_rays >= 0);
+  if (nr_rays == 0) return VSA_OK;
+  NR_CHECK(start_end && rgb_fg && weights_sum && depth && (bg_per_ray == 0 || bg_per_ray == 1) &&
+           (!rgb_bg || rgb_out));
+  NR_LAUNCH(nerf_composite_fwd_kernel, nr_rays, start_end, density, dt, samples_z, rgb, rgb_bg,
+            bg_per_ray ? 3 : 0, rgb_fg, rgb_out, weights_sum, depth, weights, nr_rays);
+}
+
+extern "C" int vsa_nerf_composite_bwd(const int32_t* start_end, const float* density,
+                                      const float* dt, const float* rgb, const float* rgb_bg,
+                                      int bg_per_ray, const float* weights_sum, const float* g_rgb,
+                                      const float* g_weights_sum, float* g_density,
+                                      float* g_rgb_samples, float* g_rgb_bg, float* scratch,
+                                      int nr_rays, int bug_compat, void* stream) {
+  NR_CHECK(nr_rays >= 0);
+  if (nr_rays == 0) return VSA_OK;
+  NR_CHECK(start_end && g_rgb && (bg_per_ray == 0 || bg_per_ray == 1) &&
+           (!g_rgb_bg || (rgb_bg && weights_sum)));
+  NR_LAUNCH(nerf_composite_bwd_kernel, nr_rays, start_end, density, dt, rgb, rgb_bg,
+            bg_per_ray ? 3 : 0, weights_sum, g_rgb, g_weights_sum, g_density, g_rgb_samples,
+            g_rgb_bg, scratch, nr_rays, bug_compat);
+}
+
+extern "C" int vsa_nerf_coarse_cdf(const int32_t* start_end, const float* density, const float* dt,
+                                   float* cdf, int nr_rays, void* stream) {
+  NR_CHECK(nr_rays >= 0);
+  if (nr_rays == 0) return VSA_OK;
+  NR_CHECK(start_end);
+  NR_LAUNCH(nerf_coarse_cdf_kernel, nr_rays, start_end, density, dt, cdf, nr_rays);
+}

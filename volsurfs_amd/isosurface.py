@@ -248,13 +248,13 @@ def _lattice(n, r):
     return [-r] * 3, [2.0 * r / (n - 1)] * 3
 
 
-def _finish(grid, levels, n, bounding_primitive, threshold=None):
+def _finish(grid, levels, n, bounding_primitive, threshold=None, inside="below"):
     origin, spacing = _lattice(n, _radius(bounding_primitive))
     if threshold is not None:
         lo, hi = torch.aminmax(grid)
         if not float(lo) <= threshold <= float(hi):
             return [_empty_mesh(grid.device)]
-    meshes = marching_cubes(grid, levels, origin, spacing)
+    meshes = marching_cubes(grid, levels, origin, spacing, inside=inside)
     if bounding_primitive is not None:
         meshes = [filter_inside(m, bounding_primitive) for m in meshes]
     return meshes
@@ -295,6 +295,27 @@ def extract_level_sets(fn, nr_points_per_dim, nr_meshes, delta_surfs=0.0025, ext
     n = int(nr_points_per_dim)
     grid = sample_grid(fn, n, _radius(bounding_primitive), out_idx=out_idx, iter_nr=iter_nr)
     return _finish(grid, levels, n, bounding_primitive), levels
+
+
+NERF_DENSITY_SHIFT = 0.5      # mesh_extraction.py:473-483: level_set=0.5, threshold=<the baker's level>
+
+
+def extract_nerf_level_sets(method, nr_points_per_dim, nr_meshes=1, delta_surfs=0.0025, extract_level_set=0.0,
+                            iter_nr=None):
+    """The baker's `--extract_meshes` for the nerf method (baker.py:325-369, mesh_extraction.py:473-483): the density
+    field of `method.models["density"]` on the lattice of the method's bounding primitive, shifted by 0.5, cut at the
+    baker's levels (level_set_values) with the inside where the density is ABOVE the level, so that the faces wind
+    outward from the dense region; faces not wholly inside the bounding primitive are dropped.  One grid evaluation
+    and one marching-cubes call for all levels.  Returns (meshes, levels) in ascending level, which for a density
+    blob runs from the outer shell to the inner one (a higher density level lies inside a lower one)."""
+    levels = sorted(level_set_values(nr_meshes, delta_surfs, extract_level_set))
+    if len(levels) > MAX_LEVELS:
+        raise _lib.VolsurfsHipError(f"extract_nerf_level_sets: at most {MAX_LEVELS} levels, got {len(levels)}")
+    n = int(nr_points_per_dim)
+    bp = method.bounding_primitive
+    grid = sample_grid(method.models["density"], n, _radius(bp), iter_nr=iter_nr)
+    grid -= NERF_DENSITY_SHIFT
+    return _finish(grid, levels, n, bp, inside="above"), levels
 
 
 def save_level_sets(meshes, levels, out_dir):

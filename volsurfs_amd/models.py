@@ -669,3 +669,36 @@ class NerfHash(torch.nn.Module):
         points = ray_samples.view(-1, ray_samples.shape[-1])
         feat_and_density = self.mlp_feat_and_density(self._features(points, iter_nr))
         return self.softplus(feat_and_density[:, 0:1])
+
+
+class Density(torch.nn.Module):
+    """models/density.py:11-95: the NeRF method's density field.  Encoder from get_encoder(encoding_type,
+    nr_levels=24, ...), MLP(dims + [1 + geom_feat_size]) with a linear last layer, softplus on the first column;
+    returns (density [P,1], geom_feat [P,F] or None).  Same attribute names as the reference, so its state_dict
+    keys (pos_encoder.encoder.*, mlp.layers.*) are the reference's and a reference `density.pt` loads."""
+
+    def __init__(self, in_channels, mlp_layers_dims, encoding_type, out_channels=1, geom_feat_size=32,
+                 nr_iters_for_c2f=0, bb_sides=2.0, device="cuda"):
+        super().__init__()
+        self.in_channels = in_channels
+        self.mlp_layers_dims = copy.deepcopy(mlp_layers_dims)
+        self.out_channels = out_channels + geom_feat_size
+        self.encoding_type = encoding_type
+        self.bb_sides = _bb_sides(bb_sides, in_channels, device)
+        self.pos_encoder = get_encoder(encoding_type, input_dim=in_channels, nr_levels=24,
+                                       nr_iters_for_c2f=nr_iters_for_c2f, multires=6, bb_sides=self.bb_sides)
+        self.pos_encoder.compute_out_of_bounds = False       # (density.py:80-82 never reads it)
+        self.encoding_output_dims = self.pos_encoder.output_dim
+        self.mlp = MLP(self.encoding_output_dims, self.mlp_layers_dims + [self.out_channels],
+                       last_layer_linear=True).to(device)
+        self.softplus = torch.nn.Softplus()
+
+    def forward(self, points, iter_nr=None):
+        assert points.shape[1] == self.in_channels, "points should be N x in_channels"
+        feats = self.pos_encoder(points, iter_nr=iter_nr)
+        density_and_feat = self.mlp(feats[0] if isinstance(feats, tuple) else feats)
+        if self.out_channels != 1:
+            density, geom_feat = density_and_feat[:, 0:1], density_and_feat[:, 1:]
+        else:
+            density, geom_feat = density_and_feat, None
+        return self.softplus(density), geom_feat

@@ -1,0 +1,462 @@
+"""The NeRF method (volsurfs_py/methods/nerf.py, config/nerf/base.cfg, utils/nerf_utils.py): a density field and
+a radiance field trained from posed images by volume rendering, the first stage of the baker.  Its two per-ray
+chains run as fused HIP kernels (csrc/nerf_render.hip): the foreground composite with the background blend
+(`nerf_composite`) and the coarse pass of importance sampling (`nerf_coarse_cdf`); everything else is the
+project's existing HIP operators (permutohedral encoder, fused MLP, occupancy grid, packed samplers).
+`isosurface.extract_nerf_level_sets` meshes the trained density."""
+import os
+
+import torch
+
+from . import _lib
+from .background import BoundingSphere, intersect_bounding_primitive, render_contracted_bg
+from .models import RGB, ColorSH, Density, NerfHash
+from .trainer import loss_l1
+from .volsurfs import OccupancyGrid, RaySampler, VolumeRendering
+
+
+class NeRFHyperParams:
+    """params/hyper_params.py (HyperParams, HyperParamsNeRF) with config/nerf/base.cfg applied: the keys and values
+    a `nerf` run of the reference trains with.  Keyword arguments override single values."""
+
+    def __init__(self, **overrides):
+        # lr schedule
+        self.lr = 1e-3
+        self.nr_warmup_iters = 3000
+        self.lr_milestones = [100000, 150000, 180000, 190000]
+        self.training_end_iter = 200000
+        # rays
+        self.training_rays_batch_size = 512
+        self.is_nr_training_rays_dynamic = True
+        self.target_nr_of_training_samples = 512 * (64 + 16 + 16)
+        self.test_rays_batch_size = 16384
+        self.nr_training_rays_per_pixel = 1
+        self.nr_test_rays_per_pixel = 1
+        self.jitter_training_rays = True
+        self.jitter_test_rays = False
+        # masks
+        self.is_training_masked = False
+        self.is_testing_masked = False
+        self.mask_weight = 0.0
+        # density
+        self.geom_feat_size = 32
+        self.density_encoding_type = "permutohash"
+        self.density_mlp_layers_dims = [32, 32, 32]
+        self.density_nr_iters_for_c2f = 1000
+        # appearance
+        self.rgb_pos_encoder_type = "permutohash"
+        self.rgb_dir_encoder_type = "spherical_harmonics"
+        self.rgb_mlp_layers_dims = [128, 128, 64]
+        self.sh_degree = 3
+        self.appearance_predict_sh_coeffs = False
+        self.rgb_view_dep = True
+        self.rgb_normal_dep = False
+        self.rgb_geom_feat_dep = True
+        self.rgb_nr_iters_for_c2f = 0
+        # background
+        self.bg_pos_encoder_type = "permutohash"
+        self.bg_dir_encoder_type = "spherical_harmonics"
+        self.bg_nr_iters_for_c2f = 0
+        self.nr_samples_bg = 64
+        # sampling
+        self.use_occupancy_grid = True
+        self.do_importance_sampling = True
+        self.min_dist_between_samples = 1e-4
+        self.min_nr_samples_per_ray = 1
+        self.max_nr_samples_per_ray = 64
+        self.max_nr_imp_samples_per_ray = 32
+        # losses
+        self.sparsity_weight = 1e-4
+        for k, v in overrides.items():
+            if not hasattr(self, k):
+                raise KeyError(f"unknown hyper-parameter {k!r}")
+            setattr(self, k, v)
+        # hyper_params.py:173-178: the CDF of importance sampling needs 3 samples per ray
+        if self.do_importance_sampling and self.min_nr_samples_per_ray < 3:
+            self.min_nr_samples_per_ray = 3
+
+
+def init_occupancy_grid(bounding_primitive, res=256):
+    """utils/occupancy_grid.py:6-13."""
+    r = bounding_primitive.get_radius()
+    grid = OccupancyGrid(res, [r * 2, r * 2, r * 2])
+    if isinstance(bounding_primitive, BoundingSphere):
+        grid.init_sphere_roi(r, 0.0)
+    return grid
+
+
+# ---- fused per-ray chains (csrc/nerf_render.hip)
+class _NerfComposite(torch.autograd.Function):
+    """render_fg_volumetric's alpha / transmittance / weights / integrals and render_rays' background blend as one
+    launch each way (vsa_nerf_composite_fwd / _bwd).  Differentiable outputs: rgb (blended) and weights_sum; rgb_fg,
+    depth and weights are not (the reference integrates the depth without autograd; nerf.py's losses read only rgb
+    and weights_sum)."""
+
+    @staticmethod
+    def forward(ctx, pack, density, rgb, rgb_bg, want_weights):
+        density = _lib.check_f32(density.contiguous())
+        rgb = _lib.check_f32(rgb.contiguous())
+        S, N = rgb.shape[0], pack.get_nr_rays()
+        if density.numel() != S or pack.samples_dt.numel() != S or rgb.shape[1] != 3:
+            raise _lib.VolsurfsHipError("nerf composite: rgb [S,3], density [S,1], a pack with S samples and dt")
+        per_ray, bg_shape = 0, None
+        if rgb_bg is not None:
+            bg_shape = rgb_bg.shape
+            if rgb_bg.dim() == 2 and rgb_bg.shape == (N, 3) and N != 1:
+                per_ray = 1
+            elif rgb_bg.numel() == 3:
+                pass
+            else:
+                raise _lib.VolsurfsHipError(f"nerf composite: rgb_bg must be [N,3] or one colour, got {tuple(rgb_bg.shape)}")
+            rgb_bg = _lib.check_f32(rgb_bg.contiguous().view(-1, 3) if per_ray else rgb_bg.reshape(3).contiguous())
+        dev = rgb.device
+        rgb_fg = torch.empty(N, 3, device=dev)
+        rgb_out = torch.empty(N, 3, device=dev)
+        wsum = torch.empty(N, 1, device=dev)
+        depth = torch.empty(N, 1, device=dev)
+        weights = torch.empty(S, 1, device=dev) if want_weights else None
+        _lib.call("vsa_nerf_composite_fwd", pack.ray_start_end_idx, density, pack.samples_dt, pack.samples_z, rgb,
+                  rgb_bg, per_ray, rgb_fg, rgb_out, wsum, depth, weights, N, _lib.stream_ptr())
+        ctx.save_for_backward(density, rgb, rgb_bg, wsum)
+        ctx.pack, ctx.per_ray = pack, per_ray
+        ctx.bg_shape = bg_shape
+        ctx.set_materialize_grads(False)
+        nd = [rgb_fg, depth] + ([weights] if weights is not None else [])
+        ctx.mark_non_differentiable(*nd)
+        return rgb_out, rgb_fg, wsum, depth, weights
+
+    @staticmethod
+    def backward(ctx, g_rgb, _g_fg, g_wsum, _g_depth, _g_weights):
+        density, rgb, rgb_bg, wsum = ctx.saved_tensors
+        pack, ctx.pack = ctx.pack, None
+        N = pack.get_nr_rays()
+        if g_rgb is None:
+            g_rgb = torch.zeros(N, 3, device=rgb.device)
+        g_density, g_rgb_s = torch.empty_like(density), torch.empty_like(rgb)
+        need_bg = rgb_bg is not None and ctx.needs_input_grad[3]
+        g_bg = torch.empty(N, 3, device=rgb.device) if need_bg else None
+        scratch = torch.empty(2 * rgb.shape[0], device=rgb.device)
+        _lib.call("vsa_nerf_composite_bwd", pack.ray_start_end_idx, density, pack.samples_dt, rgb, rgb_bg,
+                  ctx.per_ray, wsum, g_rgb.contiguous(), None if g_wsum is None else g_wsum.contiguous(),
+                  g_density, g_rgb_s, g_bg, scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
+        if need_bg and not ctx.per_ray:
+            g_bg = g_bg.sum(0).view(ctx.bg_shape)
+        return None, g_density, g_rgb_s, g_bg, None
+
+
+def nerf_composite(pack, density, rgb, rgb_bg=None, return_weights=False):
+    """alpha = 1 - exp(-density dt), T = cumprod((1 - alpha) + 1e-6), w = alpha T (methods/nerf.py:266-287) on a
+    compacted pack with dt; rgb_bg [N,3], one colour or None (no blend: rgb = rgb_fg).  Returns a dict: rgb [N,3],
+    rgb_fg [N,3], weights_sum [N,1], bg_transmittance [N,1] = 1 - weights_sum, depth [N,1], weights [S,1] (or
+    None).  Bit-identical to the chain of CumprodOneMinusAlphaToTransmittanceFunc, IntegrateWithWeights3DFunc and
+    SumOverRaysFunc, forward and backward (tests/test_nerf_render.py)."""
+    rgb_out, rgb_fg, wsum, depth, weights = _NerfComposite.apply(pack, density.view(-1, 1), rgb, rgb_bg,
+                                                                 bool(return_weights))
+    return {"rgb": rgb_out, "rgb_fg": rgb_fg, "weights_sum": wsum, "bg_transmittance": 1 - wsum.detach(),
+            "depth": depth, "weights": weights}
+
+
+@torch.no_grad()
+def nerf_coarse_cdf(pack, density):
+    """importance_sampling_nerf (utils/nerf_utils.py:61-82) from the uniform pass's densities [S,1] to the CDF [S,1]
+    in one launch (vsa_nerf_coarse_cdf); bit-identical to the chain of single ops."""
+    density = _lib.check_f32(density.contiguous())
+    if density.numel() != pack.samples_dt.numel():
+        raise _lib.VolsurfsHipError("nerf_coarse_cdf: one density per sample")
+    cdf = torch.empty(density.numel(), 1, device=density.device)
+    _lib.call("vsa_nerf_coarse_cdf", pack.ray_start_end_idx, density, pack.samples_dt, cdf, pack.get_nr_rays(),
+              _lib.stream_ptr())
+    return cdf
+
+
+@torch.no_grad()
+def importance_sampling_nerf(density_fn, pack_uniform, iter_nr, nr_samples, jitter_samples=False):
+    """utils/nerf_utils.py:9-97: the density of the uniform samples (no autograd), the fused coarse CDF, then
+    VolumeRendering.importance_sample."""
+    if pack_uniform.is_empty():
+        raise _lib.VolsurfsHipError("ray_samples_packed_uniform should not be empty")
+    res = density_fn(points=pack_uniform.samples_3d, iter_nr=iter_nr)
+    density = res[0] if isinstance(res, tuple) else res
+    if density.shape[1] > 1:
+        density = density[:, 0:1]
+    pack_uniform.update_dt(False)
+    cdf = nerf_coarse_cdf(pack_uniform, density)
+    return VolumeRendering.importance_sample(pack_uniform, cdf, nr_samples, jitter_samples)
+
+
+def get_rays_samples_packed_nerf(rays_o, rays_d, t_near, t_far, density_fn, occupancy_grid=None, iter_nr=None,
+                                 min_dist_between_samples=1e-4, min_nr_samples_per_ray=1, max_nr_samples_per_ray=64,
+                                 max_nr_imp_samples_per_ray=32, jitter_samples=False, importance_sampling=True,
+                                 values_dim=1):
+    """utils/nerf_utils.py:100-190 -> (pack with dt, importance pack or None)."""
+    with torch.no_grad():
+        if occupancy_grid is not None:
+            pack = RaySampler.compute_samples_fg_in_grid_occupied_regions(
+                rays_o, rays_d, t_near, t_far, min_dist_between_samples, min_nr_samples_per_ray,
+                max_nr_samples_per_ray, jitter_samples, occupancy_grid.get_nr_voxels_per_dim(),
+                occupancy_grid.get_grid_extent(), occupancy_grid.get_grid_occupancy(), occupancy_grid.get_grid_roi(),
+                values_dim)
+        else:
+            pack = RaySampler.compute_samples_fg(rays_o, rays_d, t_near, t_far, min_dist_between_samples,
+                                                 min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples,
+                                                 values_dim)
+    imp = None
+    if not pack.is_empty():
+        if importance_sampling:
+            imp = importance_sampling_nerf(density_fn, pack, iter_nr, max_nr_imp_samples_per_ray, jitter_samples)
+            pack = VolumeRendering.combine_ray_samples_packets(pack, imp, min_dist_between_samples)
+        pack.update_dt(False)
+    return pack, imp
+
+
+class NeRF:
+    """methods/nerf.py:29-507.  models = {"density": Density, "rgb": RGB or ColorSH, "bg": NerfHash or None (with a
+    constant bg_color [3])}; the occupancy grid of init_occupancy_grid (256^3, a sphere ROI for a BoundingSphere).
+    Trains through trainer.train_step / train (the autograd path): `method(rays_o, rays_d, gt_rgb, gt_mask, iter_nr)`
+    returns (losses, info, foreground samples) — the sample count drives the dynamic ray count."""
+
+    method_name = "nerf"
+    OCCUPANCY_EVERY = 50                   # update_method_state (nerf.py:414-421)
+    OCCUPANCY_RANDOM_VOXELS = 256 * 256 * 4
+    OCCUPANCY_DECAY = 0.8
+    OCCUPANCY_THRESH = 1e-4
+    SPARSITY_FROM_ITER = 5000              # the sparsity term is on for iter_nr > 5000 (nerf.py:467)
+    SPARSITY_NR_POINTS = 1024
+
+    def __init__(self, train, hyper_params, load_checkpoints_path, save_checkpoints_path, bounding_primitive,
+                 bg_color=None, start_iter_nr=0):
+        hp = hyper_params
+        self.hyper_params = hp
+        self.load_checkpoints_path, self.save_checkpoints_path = load_checkpoints_path, save_checkpoints_path
+        self.bounding_primitive = bounding_primitive
+        self.bg_color = None if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32).cuda().view(1, 3)
+        self.optimizer = self.lr_scheduler = self.scheduler_lr_decay = None
+        self.is_training = bool(train)
+        self.occupancy_grid = init_occupancy_grid(bounding_primitive) if hp.use_occupancy_grid else None
+        bb = bounding_primitive.get_radius() * 2.0
+        self.models = {}
+        self.models["density"] = Density(in_channels=3, out_channels=1, geom_feat_size=hp.geom_feat_size,
+                                         mlp_layers_dims=hp.density_mlp_layers_dims,
+                                         encoding_type=hp.density_encoding_type,
+                                         nr_iters_for_c2f=hp.density_nr_iters_for_c2f, bb_sides=bb)
+        if hp.appearance_predict_sh_coeffs:
+            assert hp.rgb_view_dep, "SH coeffs only implemented for view dependent color"
+            self.models["rgb"] = ColorSH(in_channels=3, out_channels=3, mlp_layers_dims=hp.rgb_mlp_layers_dims,
+                                         pos_encoder_type=hp.rgb_pos_encoder_type, sh_deg=hp.sh_degree,
+                                         normal_dep=hp.rgb_normal_dep, geom_feat_dep=hp.rgb_geom_feat_dep,
+                                         in_geom_feat_size=hp.geom_feat_size,
+                                         nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
+        else:
+            self.models["rgb"] = RGB(in_channels=3, out_channels=3, mlp_layers_dims=hp.rgb_mlp_layers_dims,
+                                     pos_encoder_type=hp.rgb_pos_encoder_type, dir_encoder_type=hp.rgb_dir_encoder_type,
+                                     sh_deg=hp.sh_degree, pos_dep=True, view_dep=hp.rgb_view_dep,
+                                     normal_dep=hp.rgb_normal_dep, geom_feat_dep=hp.rgb_geom_feat_dep,
+                                     in_geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f,
+                                     use_lipshitz_mlp=False, bb_sides=bb)
+        self.models["bg"] = NerfHash(in_channels=3, pos_encoder_type=hp.bg_pos_encoder_type,
+                                     dir_encoder_type=hp.bg_dir_encoder_type,
+                                     nr_iters_for_c2f=hp.bg_nr_iters_for_c2f) if self.bg_color is None else None
+        if start_iter_nr > 0:
+            self.load(start_iter_nr)
+        if train:
+            self.init_optim()
+        self.update_method_state(iter_nr=start_iter_nr)
+        self.update_occupancy_grid(iter_nr=start_iter_nr, decay=0.0, random_voxels=False, jitter_samples=False)
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    def parameters(self):
+        return [p for m in self.models.values() if m is not None for p in m.parameters()]
+
+    # ---- optimisation (base_method.py:60-94, nerf.py:143-192)
+    def collect_opt_params(self):
+        groups = [{"params": list(self.models["density"].parameters()), "lr": self.hyper_params.lr,
+                   "name": "model_density"},
+                  {"params": list(self.models["rgb"].parameters()), "lr": self.hyper_params.lr, "name": "model_rgb"}]
+        if self.models["bg"] is not None:
+            groups.append({"params": list(self.models["bg"].parameters()), "lr": self.hyper_params.lr,
+                           "name": "model_bg"})
+        return groups
+
+    def init_optim(self, opt_params=None):
+        from .optim import FusedAdam
+        from .schedulers import MultiStepLR
+        self.optimizer = FusedAdam(opt_params or self.collect_opt_params(), lr=self.hyper_params.lr,
+                                   betas=(0.9, 0.99), eps=1e-15, weight_decay=0.0)
+        self.scheduler_lr_decay = MultiStepLR(self.optimizer, milestones=self.hyper_params.lr_milestones, gamma=0.3)
+        return self.optimizer
+
+    def optim_step(self, overlap=False):
+        self.optimizer.step()
+
+    def _warmup_scheduler(self, is_first_iter):
+        if is_first_iter and self.scheduler_lr_decay is not None:           # nerf.py:437-443
+            from .schedulers import GradualWarmupScheduler
+            if self.hyper_params.nr_warmup_iters > 0:
+                self.lr_scheduler = GradualWarmupScheduler(self.optimizer, multiplier=1,
+                                                           total_epoch=self.hyper_params.nr_warmup_iters,
+                                                           after_scheduler=self.scheduler_lr_decay)
+            else:
+                self.lr_scheduler = self.scheduler_lr_decay
+
+    # ---- occupancy grid (nerf.py:194-255, 414-421)
+    @torch.no_grad()
+    def update_occupancy_grid(self, iter_nr, decay=OCCUPANCY_DECAY, random_voxels=True, jitter_samples=True):
+        g = self.occupancy_grid
+        if g is None:
+            return
+        if random_voxels:
+            pts, idx = g.get_random_grid_samples_in_roi(self.OCCUPANCY_RANDOM_VOXELS, jitter_samples)
+        else:
+            pts, idx = g.get_grid_samples(jitter_samples)
+        dens = [self.models["density"](b, iter_nr=iter_nr)[0] for b in torch.split(pts, 256 * 256 * 100, dim=0)]
+        dens = torch.cat(dens, 0) if len(dens) > 1 else dens[0]
+        g.update_grid_values(idx, dens, decay)
+        g.update_grid_occupancy_with_density_values(idx, self.OCCUPANCY_THRESH, False)
+
+    def update_method_state(self, iter_nr):
+        if self.is_training and self.hyper_params.use_occupancy_grid and iter_nr % self.OCCUPANCY_EVERY == 0:
+            self.update_occupancy_grid(iter_nr=iter_nr)
+
+    # ---- rendering (nerf.py:257-412)
+    def render_fg_volumetric(self, pack, iter_nr=None, override=None, rgb_bg=None):
+        """-> (renders dict, samples_3d, None).  `rgb_bg` folds render_rays' blend into the same launch."""
+        N = pack.get_nr_rays()
+        dev = pack.ray_o.device
+        if pack.is_empty():
+            zeros = lambda c: torch.zeros(N, c, device=dev)
+            r = {"rgb_fg": zeros(3), "depth": zeros(1), "weights_sum": zeros(1),
+                 "bg_transmittance": torch.ones(N, 1, device=dev), "nr_samples": torch.zeros(N, 1, dtype=torch.int32, device=dev)}
+            r["rgb"] = r["rgb_fg"] if rgb_bg is None else r["rgb_fg"] + r["bg_transmittance"] * rgb_bg
+            return r, None, None
+        samples_3d = pack.samples_3d
+        density, geom_feat = self.models["density"](points=samples_3d, iter_nr=iter_nr)
+        dirs = pack.samples_dirs
+        view_dir = (override or {}).get("view_dir")
+        if view_dir is not None:
+            dirs = torch.as_tensor(view_dir, dtype=torch.float32, device=dev).view(1, 3).expand(dirs.shape[0], 3).contiguous()
+        rgb = self.models["rgb"](points=samples_3d, samples_dirs=dirs, iter_nr=iter_nr, geom_feat=geom_feat)
+        c = nerf_composite(pack, density, rgb, rgb_bg)
+        r = {"rgb": c["rgb"], "rgb_fg": c["rgb_fg"], "depth": c["depth"], "weights_sum": c["weights_sum"],
+             "bg_transmittance": c["bg_transmittance"],
+             "nr_samples": pack.get_nr_samples_per_ray().view(-1, 1).int()}
+        return r, samples_3d, None
+
+    def render_rays(self, rays_o, rays_d, iter_nr=None, override=None, **kwargs):
+        """The reference's dict: {"renders": {"volumetric": {rgb, rgb_fg, rgb_bg, depth, weights_sum,
+        bg_transmittance, nr_samples[, median_depth_bg]}}, "samples_3d", "samples_grad"}."""
+        hp = self.hyper_params
+        raycast = intersect_bounding_primitive(self.bounding_primitive, rays_o, rays_d)
+        pack, _ = get_rays_samples_packed_nerf(
+            rays_o, rays_d, raycast["t_near"], raycast["t_far"], self.models["density"], self.occupancy_grid, iter_nr,
+            hp.min_dist_between_samples, hp.min_nr_samples_per_ray, hp.max_nr_samples_per_ray,
+            hp.max_nr_imp_samples_per_ray, jitter_samples=self.is_training, importance_sampling=hp.do_importance_sampling)
+        median_bg = None
+        if self.models["bg"] is None:
+            rgb_bg = self.bg_color.expand(raycast["nr_rays"], 3)
+        else:
+            bg = render_contracted_bg(self.models["bg"], raycast, nr_samples_bg=hp.nr_samples_bg,
+                                      jitter_samples=self.is_training, iter_nr=iter_nr)
+            rgb_bg, median_bg = bg["pred_rgb"], bg["median_depth"]
+        renders, samples_3d, samples_grad = self.render_fg_volumetric(
+            pack, iter_nr=iter_nr, override=override,
+            rgb_bg=self.bg_color.view(3) if self.models["bg"] is None else rgb_bg)
+        renders["rgb_bg"] = rgb_bg
+        if median_bg is not None:
+            renders["median_depth_bg"] = median_bg
+        return {"renders": {"volumetric": renders}, "samples_3d": samples_3d, "samples_grad": samples_grad}
+
+    # ---- training (nerf.py:423-507)
+    def forward(self, rays_o, rays_d, gt_rgb, gt_mask=None, iter_nr=0, is_first_iter=False, is_training_masked=None,
+                **kwargs):
+        hp = self.hyper_params
+        masked = hp.is_training_masked if is_training_masked is None else is_training_masked
+        self.update_method_state(iter_nr)
+        self._warmup_scheduler(is_first_iter)
+        res = self.render_rays(rays_o, rays_d, iter_nr=iter_nr)
+        vol = res["renders"]["volumetric"]
+        pred_rgb, pred_mask = vol["rgb"], vol["weights_sum"]
+        R = hp.nr_training_rays_per_pixel
+        if R > 1:
+            pred_rgb = pred_rgb.view(-1, R, 3).mean(dim=1)
+            pred_mask = pred_mask.view(-1, R, 1).mean(dim=1)
+        loss_rgb = loss_l1(gt_rgb, pred_rgb, mask=gt_mask) if masked else loss_l1(gt_rgb, pred_rgb)
+        loss = loss_rgb
+        loss_sparsity = loss_mask = 0.0
+        points = self.bounding_primitive.get_random_points_inside(self.SPARSITY_NR_POINTS)
+        if iter_nr > self.SPARSITY_FROM_ITER and hp.sparsity_weight > 0.0:
+            dens, _ = self.models["density"](points, iter_nr)
+            loss_sparsity = torch.clamp((1 - torch.exp(-dens)).mean(), min=0.0) * hp.sparsity_weight  # losses.py:22-25
+            loss = loss + loss_sparsity
+        if masked and hp.mask_weight > 0.0:
+            pm = torch.clamp(pred_mask, min=0.0, max=1.0)
+            loss_mask = loss_l1(pm, gt_mask, mask=1 - gt_mask) * hp.mask_weight
+            loss = loss + loss_mask
+        losses = {"loss": loss, "rgb": loss_rgb, "sparsity": loss_sparsity, "mask": loss_mask}
+        return losses, {}, res["samples_3d"]
+
+    # ---- checkpoints (base_method.py:118-264): <root>/<iter:07d>/models/{density,rgb,bg}.pt + the grid
+    def save(self, iter_nr):
+        if self.save_checkpoints_path is None:
+            return None
+        path = os.path.join(self.save_checkpoints_path, format(iter_nr, "07d"), "models")
+        os.makedirs(path, exist_ok=True)
+        for key, model in self.models.items():
+            if model is not None:
+                torch.save(model.state_dict(), os.path.join(path, f"{key}.pt"))
+        if self.occupancy_grid is not None:
+            torch.save(self.occupancy_grid.get_grid_values(), os.path.join(path, "grid_values.pt"))
+            torch.save(self.occupancy_grid.get_grid_occupancy(), os.path.join(path, "grid_occupancy.pt"))
+        if self.optimizer is not None:
+            torch.save(self.optimizer.state_dict(), os.path.join(path, "fusedadam.pt"))
+        return path
+
+    def load(self, iter_nr):
+        if self.load_checkpoints_path is None:
+            return None
+        path = os.path.join(self.load_checkpoints_path, format(iter_nr, "07d"), "models")
+        for key, model in self.models.items():
+            f = os.path.join(path, f"{key}.pt")
+            if model is not None and os.path.exists(f):
+                model.load_state_dict(torch.load(f, map_location="cuda"))
+        g = self.occupancy_grid
+        if g is not None:
+            fv, fo = os.path.join(path, "grid_values.pt"), os.path.join(path, "grid_occupancy.pt")
+            if os.path.exists(fv) and os.path.exists(fo):
+                g.set_grid_values(torch.load(fv, map_location="cuda"))
+                g.set_grid_occupancy(torch.load(fo, map_location="cuda"))
+            else:
+                self.update_occupancy_grid(iter_nr=iter_nr, decay=0.0, random_voxels=False, jitter_samples=False)
+        f = os.path.join(path, "fusedadam.pt")
+        if self.optimizer is not None and os.path.exists(f):
+            self.optimizer.load_state_dict(torch.load(f, map_location="cuda"))
+        return path
+
+    # ---- full frames (base_method.py:366-541)
+    @torch.no_grad()
+    def render(self, rays_o, rays_d, nr_rays_per_pixel=1, chunk=None):
+        chunk = int(chunk or self.hyper_params.test_rays_batch_size)
+        keys = ("rgb", "rgb_fg", "depth", "weights_sum", "bg_transmittance")
+        outs = {k: [] for k in keys}
+        for a in range(0, rays_o.shape[0], chunk):
+            v = self.render_rays(rays_o[a:a + chunk], rays_d[a:a + chunk])["renders"]["volumetric"]
+            for k in keys:
+                outs[k].append(v[k])
+        full = {k: torch.cat(v, 0) for k, v in outs.items()}
+        if nr_rays_per_pixel > 1:
+            full = {k: v.reshape(-1, nr_rays_per_pixel, v.shape[-1]).mean(1) for k, v in full.items()}
+        return full
+
+    @torch.no_grad()
+    def render_camera(self, camera, nr_rays_per_pixel=1, jitter_pixels=False, chunk=None):
+        """{key: [H, W, C]} of one camera (what evaluation.render_and_eval scores: "rgb")."""
+        from .camera import get_camera_rays
+        was = self.is_training
+        self.is_training = False
+        try:
+            rays_o, rays_d, _ = get_camera_rays(camera, nr_rays_per_pixel, jitter_pixels)
+            full = self.render(rays_o, rays_d, nr_rays_per_pixel, chunk)
+        finally:
+            self.is_training = was
+        return {k: v.reshape(camera.height, camera.width, v.shape[-1]) for k, v in full.items()}
