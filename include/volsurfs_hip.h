@@ -829,6 +829,37 @@ int vsa_nerf_composite_bwd(const int32_t* start_end, const float* density, const
  * w / max(sum_over_rays(w), 1e-6), compute_cdf.  Bit-identical to that chain of single ops. */
 int vsa_nerf_coarse_cdf(const int32_t* start_end, const float* density, const float* dt, float* cdf,
                         int nr_rays, void* stream);
+/* The Surf method's foreground render (volsurfs_py/methods/surf.py render_fg_volumetric with
+ * VolumeRenderingNeuS, and the bg blend of render_rays) as one launch each way (csrc/surf_render.hip
+ * states the summation orders).  Forward: the NeuS alpha of compute_alphas_from_logistic_beta from
+ * sdf [S], sdf_grad [S,3], dirs [S,3] and dt [S] with the scalars cos_anneal_ratio and logistic_beta,
+ * T = cumprod((1 - alpha) + 1e-6), w = alpha T; rgb_fg [N,3] = integrate_with_weights_3d(rgb, w),
+ * weights_sum [N] = sum_over_rays(w), depth [N] = integrate_with_weights_1d(samples_z, w),
+ * normals_out [N,3] = integrate_with_weights_3d(normals, w); with rgb_bg (NULL: none) rgb_out [N,3]
+ * = rgb_fg + (1 - weights_sum) rgb_bg, rgb_bg [N,3] (bg_per_ray = 1) or one colour [3] (0); weights
+ * [S] and alpha [S] are optional.  Backward: g_rgb [N,3] (of rgb_out, or of rgb_fg without a
+ * background), g_weights_sum [N] or NULL -> g_sdf [S], g_sdf_grad [S,3], g_rgb_samples [S,3],
+ * g_rgb_bg [N,3] (optional; needs rgb_bg and the forward's weights_sum); depth and normals pass no
+ * gradient; bug_compat as in vsa_packed_integrate_bwd; scratch: 2 S floats.  The per-sample arrays
+ * may be NULL when the pack has no samples. */
+int vsa_neus_composite_fwd(const int32_t* start_end, const float* sdf, const float* sdf_grad,
+                           const float* dirs, const float* dt, const float* samples_z,
+                           const float* normals, const float* rgb, const float* rgb_bg, int bg_per_ray,
+                           double cos_anneal_ratio, double logistic_beta, float* rgb_fg, float* rgb_out,
+                           float* weights_sum, float* depth, float* normals_out, float* weights,
+                           float* alpha, int nr_rays, void* stream);
+int vsa_neus_composite_bwd(const int32_t* start_end, const float* sdf, const float* sdf_grad,
+                           const float* dirs, const float* dt, const float* rgb, const float* rgb_bg,
+                           int bg_per_ray, double cos_anneal_ratio, double logistic_beta,
+                           const float* weights_sum, const float* g_rgb, const float* g_weights_sum,
+                           float* g_sdf, float* g_sdf_grad, float* g_rgb_samples, float* g_rgb_bg,
+                           float* scratch, int nr_rays, int bug_compat, void* stream);
+/* One round of importance_sampling_sdf (volsurfs_py/utils/sdf_utils.py:87-109, :153-175) from the
+ * pack's sdf [S] and dt [S] to cdf [S]: sdf2alpha with the scalar logistic_beta (the caller passes
+ * beta / 2 or beta), the cumprod with +1e-6, w = alpha T, w / max(sum_over_rays(w), 1e-6),
+ * compute_cdf.  Bit-identical to that chain of single ops. */
+int vsa_sdf_coarse_cdf(const int32_t* start_end, const float* sdf, const float* dt, float logistic_beta,
+                       float* cdf, int nr_rays, void* stream);
 /* median_depth_over_rays (:372-416); fallback_compat=1 reproduces VolumeRenderingGPU.cuh:407. */
 int vsa_packed_median_depth(const int32_t* start_end, const float* samples_z,
                             const float* weights, float threshold, float* out, int nr_rays,

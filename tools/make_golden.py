@@ -3,7 +3,7 @@
 
 Runs only in the build container (needs /root/reference).  The arrays it
 writes are the committed fixtures; the reference source itself is never copied.
-Usage:  python tools/make_golden.py [composite] [sh] [nt] [glue] [misc]
+Usage:  python tools/make_golden.py [composite] [sh] [nt] [glue] [misc] [surf]
 """
 import os
 import sys
@@ -400,8 +400,53 @@ def gen_misc():
     _save("train_misc.npz", **arrs)
 
 
+def _surf_test_sdf(p):
+    """The analytic field of the surf fixture: a wavy sphere (not a distance function, so the eikonal term and the
+    curvature are non-trivial) -> (sdf [N,1], None) like the SDF model."""
+    r = p.norm(dim=-1, keepdim=True)
+    return r - 0.3 + 0.05 * torch.sin(5.0 * p[:, 0:1]) * torch.cos(3.0 * p[:, 1:2]), None
+
+
+def gen_surf():
+    """The NeuS per-sample maths and the field derivatives of the surf method, executed by the reference's own
+    VolumeRenderingNeuS.compute_alphas_from_logistic_beta, eikonal_loss, get_field_gradients and get_sdf_curvature
+    on CPU (float32), for tests/test_surf_method.py."""
+    import warnings
+    warnings.filterwarnings("ignore")
+    ref_import.install_placeholders({})
+    from volsurfs_py.volume_rendering.volume_rendering_modules import VolumeRenderingNeuS
+    from volsurfs_py.utils.fields_utils import get_field_gradients, get_sdf_curvature
+    from volsurfs_py.utils.losses import eikonal_loss
+    g = torch.Generator().manual_seed(11)
+    S = 400
+    sdf = (torch.rand(S, 1, generator=g) - 0.5) * 0.2
+    grads = torch.randn(S, 3, generator=g)
+    dirs = torch.nn.functional.normalize(torch.randn(S, 3, generator=g), dim=1)
+    dt = torch.rand(S, 1, generator=g) * 0.02 + 1e-3
+    pack = SimpleNamespace(samples_dt=dt, samples_dirs=dirs)
+    arrs = dict(neus_sdf=sdf.numpy(), neus_grad=grads.numpy(), neus_dirs=dirs.numpy(), neus_dt=dt.numpy())
+    vr = VolumeRenderingNeuS()
+    for i, (car, beta) in enumerate([(0.0, float(np.exp(3.0))), (0.5, float(np.exp(5.0))), (1.0, float(np.exp(7.0))),
+                                     (0.3, float(np.exp(10 * 0.37)))]):
+        arrs[f"neus_cfg_{i}"] = np.array([car, beta], np.float64)
+        arrs[f"neus_alpha_{i}"] = vr.compute_alphas_from_logistic_beta(pack, sdf, grads, car, beta).numpy()
+    P = 300
+    pts = (torch.rand(P, 3, generator=g) - 0.5) * 0.8
+    fg = get_field_gradients(_surf_test_sdf, pts)
+    arrs.update(field_points=pts.numpy(), field_grad=fg.numpy(), eikonal=eikonal_loss(fg).numpy())
+    torch.manual_seed(12)
+    rand_dirs = torch.randn_like(pts)       # what get_sdf_curvature draws first after the same seed
+    torch.manual_seed(12)
+    curv = get_sdf_curvature(_surf_test_sdf, pts, fg)
+    # (at the default step of 1e-4 the angle is below the clamp for a smooth field; a step of 1e-2 measures it)
+    torch.manual_seed(12)
+    curv_wide = get_sdf_curvature(_surf_test_sdf, pts, fg, eps=1e-2)
+    arrs.update(curv_rand_dirs=rand_dirs.numpy(), curvature=curv.numpy(), curvature_eps1e2=curv_wide.numpy())
+    _save("surf_neus.npz", **arrs)
+
+
 GENS = {"composite": gen_composite, "nt": gen_nt, "glue": gen_glue, "legacy": gen_legacy,
-        "misc": gen_misc}
+        "misc": gen_misc, "surf": gen_surf}
 
 if __name__ == "__main__":
     # One generator per process: each one imports the reference with its own set of stand-ins

@@ -3,59 +3,20 @@
 // into one launch each.
 //
 // Layout as in packed.hip: a ray is owned by a 32-lane half-wave, lanes = consecutive samples
-// (coalesced rows), segmented scans / reductions by shuffles, chunks of 32 samples with a carried
-// running value for longer rays.  No atomics: every output element has exactly one writer, so the
-// output bits depend only on the inputs.  Every fp32 operation is the one the single-op chain
+// (coalesced rows), segmented scans / reductions by shuffles (ray_scan.h), chunks of 32 samples
+// with a carried running value for longer rays.  No atomics: every output element has exactly one
+// writer, so the output bits depend only on the inputs.  Every fp32 operation is the one the single-op chain
 // performs, in its order (the build has -ffp-contract=off): the scans and reductions below are the
 // ones of packed.hip's cumprod / cumsum / integrate / sum_over_rays / compute_cdf kernels, so the
 // results are bit-identical to that chain (tests/test_nerf_render.py).
-#include "common.h"
+#include "ray_scan.h"
 
 namespace {
 
 constexpr int NR_BLOCK = 256;
-constexpr int SUB = 32;  // lanes per ray
+using namespace vsa_ray;
 
-// the same shuffle scans / reduction as packed.hip (same partner order -> same bits)
-__device__ __forceinline__ float sub_scan_mul(float v, int l) {
-#pragma unroll
-  for (int off = 1; off < SUB; off <<= 1) {
-    const float u = __shfl_up(v, off, SUB);
-    if (l >= off) v *= u;
-  }
-  return v;
-}
-__device__ __forceinline__ float sub_scan_add(float v, int l) {
-#pragma unroll
-  for (int off = 1; off < SUB; off <<= 1) {
-    const float u = __shfl_up(v, off, SUB);
-    if (l >= off) v += u;
-  }
-  return v;
-}
-__device__ __forceinline__ float sub_reduce_add(float v) {
-#pragma unroll
-  for (int off = SUB / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, SUB);
-  return v;
-}
-
-#define NR_RAY_PROLOGUE()                                                        \
-  const int l = threadIdx.x & (SUB - 1);                                         \
-  const long long ray = ((long long)blockIdx.x * NR_BLOCK + threadIdx.x) / SUB;  \
-  if (ray >= N) return;                                                          \
-  const int i0 = start_end[2 * ray], i1 = start_end[2 * ray + 1];                \
-  const int n = i1 - i0;
-
-// One chunk step of T = cumprod((1 - alpha) + 1e-6) (exclusive, carried across chunks) for the
-// sample of lane l; returns T and advances `carry`.
-__device__ __forceinline__ float transmittance_step(float a1, bool in, int l, float& carry) {
-  const float incl = sub_scan_mul(in ? a1 : 1.0f, l);
-  float excl = __shfl_up(incl, 1, SUB);
-  if (l == 0) excl = 1.0f;
-  const float T = carry * excl;
-  carry *= __shfl(incl, SUB - 1, SUB);
-  return T;
-}
+#define NR_RAY_PROLOGUE() VSA_RAY_PROLOGUE(NR_BLOCK)
 
 // Forward.  Per ray, with w_i = alpha_i T_i:
 //   rgb_fg_d = sum_i w_i rgb_id   lane-strided partial sums over i = l, l + 32, .. then the
@@ -162,14 +123,9 @@ __global__ void nerf_composite_bwd_kernel(const int* __restrict__ start_end,
     const float T = transmittance_step(a1, in, l, carry);
     if (in) {
       const float w = alpha * T;
-      float gw = 0.f;
 #pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        g_rgb_samples[s * 3 + d] = g[d] * w;
-        const int col = (bug_compat && d == 2) ? 1 : d;
-        gw += g[d] * rgb[s * 3 + col];
-      }
-      gw = gw + g_ws;
+      for (int d = 0; d < 3; ++d) g_rgb_samples[s * 3 + d] = g[d] * w;
+      const float gw = integrate3_grad_w(g, rgb + s * 3, bug_compat) + g_ws;
       const float gT = gw * alpha;
       scratch[2 * s] = gT * T;
       scratch[2 * s + 1] = gw * T;
@@ -180,11 +136,7 @@ __global__ void nerf_composite_bwd_kernel(const int* __restrict__ start_end,
     const int i = c + l;
     const bool in = i < n;
     const long long s = in ? (long long)i1 - 1 - i : (long long)i0;
-    const float incl = sub_scan_add(in ? scratch[2 * s] : 0.0f, l);
-    const float cs = csum + incl;
-    float cs_next = __shfl_up(cs, 1, SUB);
-    if (l == 0) cs_next = csum;
-    csum += __shfl(incl, SUB - 1, SUB);
+    const float cs_next = cumprod_bwd_suffix_step(in ? scratch[2 * s] : 0.0f, in, l, csum);
     if (in) {
       const float dts = dt[s];
       const float e = expf((-density[s]) * dts);

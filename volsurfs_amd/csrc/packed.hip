@@ -12,33 +12,15 @@
 // exactly 32 samples per ray: background.py:51-58, hyper_params.py:65).
 #include "common.h"
 #include "pcg32.h"
+#include "ray_scan.h"
 
 namespace {
 
 constexpr int PK_BLOCK = 256;
-constexpr int SUB = 32;  // lanes per ray
-
-__device__ __forceinline__ float sub_scan_mul(float v, int l) {
-#pragma unroll
-  for (int off = 1; off < SUB; off <<= 1) {
-    const float u = __shfl_up(v, off, SUB);
-    if (l >= off) v *= u;
-  }
-  return v;
-}
-__device__ __forceinline__ float sub_scan_add(float v, int l) {
-#pragma unroll
-  for (int off = 1; off < SUB; off <<= 1) {
-    const float u = __shfl_up(v, off, SUB);
-    if (l >= off) v += u;
-  }
-  return v;
-}
-__device__ __forceinline__ float sub_reduce_add(float v) {
-#pragma unroll
-  for (int off = SUB / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, SUB);
-  return v;
-}
+using vsa_ray::SUB;
+using vsa_ray::sub_reduce_add;
+using vsa_ray::sub_scan_add;
+using vsa_ray::sub_scan_mul;
 
 #define PK_RAY_PROLOGUE()                                                        \
   const int l = threadIdx.x & (SUB - 1);                                         \
@@ -485,29 +467,13 @@ __global__ void sum_over_rays_bwd_kernel(const int* __restrict__ start_end,
   }
 }
 
-// VolumeRenderingGPU.cuh:185-244 (NeuS alpha from consecutive SDF samples).  The reference
-// mixes float variables with double literals, so several intermediate results are formed in
-// double and rounded to float on assignment; reproduced operation by operation.
-__device__ __forceinline__ float sigmoid_ref(float x) {   // :179-183: float res = 1.0 / (1.0 + exp(-x))
-  return (float)(1.0 / (1.0 + (double)expf(-x)));
-}
-
+// VolumeRenderingGPU.cuh:185-244 (NeuS alpha from consecutive SDF samples; ray_scan.h).
 __global__ void sdf2alpha_kernel(const int* __restrict__ start_end, const float* __restrict__ dt,
                                  const float* __restrict__ sdf, const float* __restrict__ beta,
                                  float* __restrict__ alpha, int N) {
   PK_RAY_PROLOGUE();
-  for (int i = l; i < n - 1; i += SUB) {
-    const float d = dt[i0 + i];
-    const float prev = sdf[i0 + i], next = sdf[i0 + i + 1];
-    const float mid = (float)((double)(prev + next) * 0.5);
-    float cosv = (float)((double)(next - prev) / ((double)d + 1e-6));
-    cosv = fminf(fmaxf(cosv, -1e3f), 0.0f);
-    const float prev_esti = (float)((double)mid - (double)(cosv * d) * 0.5);
-    const float next_esti = (float)((double)mid + (double)(cosv * d) * 0.5);
-    const float b = beta[i0 + i];
-    const float prev_cdf = sigmoid_ref(prev_esti * b), next_cdf = sigmoid_ref(next_esti * b);
-    alpha[i0 + i] = (float)(((double)(prev_cdf - next_cdf) + 1e-6) / ((double)prev_cdf + 1e-6));
-  }
+  for (int i = l; i < n - 1; i += SUB)
+    alpha[i0 + i] = vsa_ray::sdf2alpha_sample(sdf[i0 + i], sdf[i0 + i + 1], dt[i0 + i], beta[i0 + i]);
 }
 
 // VolumeRenderingGPU.cuh:412-460: exclusive running sum of the weights per ray; if the

@@ -318,6 +318,18 @@ def extract_nerf_level_sets(method, nr_points_per_dim, nr_meshes=1, delta_surfs=
     return _finish(grid, levels, n, bp, inside="above"), levels
 
 
+def extract_surf_level_sets(method, nr_points_per_dim, nr_meshes=1, delta_surfs=0.0025, extract_level_set=0.0,
+                            iter_nr=None):
+    """The baker's `--extract_meshes` for the surf method (baker.py:325-369): column 0 of
+    `method.models["sdf"].main_sdf` on the lattice of the method's bounding primitive, cut at the baker's levels
+    (level_set_values) with the inside BELOW the level, faces not wholly inside the bounding primitive dropped.
+    One grid evaluation and one marching-cubes call for all levels.  Returns (meshes, levels) in ascending level,
+    inner to outer."""
+    return extract_level_sets(method.models["sdf"].main_sdf, nr_points_per_dim, nr_meshes, delta_surfs,
+                              extract_level_set, bounding_primitive=method.bounding_primitive, out_idx=0,
+                              iter_nr=iter_nr)
+
+
 def save_level_sets(meshes, levels, out_dir):
     """The baker's `meshes/<round(level, 4)>.ply` files (baker.py:375-390), without texcoords; an empty level
     raises (load_ply refuses a file without geometry).  Returns the paths."""

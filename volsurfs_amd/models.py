@@ -702,3 +702,38 @@ class Density(torch.nn.Module):
         else:
             density, geom_feat = density_and_feat, None
         return self.softplus(density), geom_feat
+
+
+class SDF(torch.nn.Module):
+    """models/sdf.py:11-101: the Surf method's signed distance field.  Encoder from get_encoder(encoding_type,
+    nr_levels=24, ...), MLP(dims + [1 + geom_feat_size]) with a linear last layer and no output nonlinearity;
+    returns (sdf [P,1], geom_feat [P,F] or None).  Same attribute names as the reference, so its state_dict keys
+    (pos_encoder.encoder.*, mlp_sdf.layers.*) are the reference's and a reference `sdf.pt` loads."""
+
+    def __init__(self, in_channels, mlp_layers_dims, encoding_type, geom_feat_size=32, nr_iters_for_c2f=0,
+                 bb_sides=2.0, device="cuda"):
+        super().__init__()
+        self.in_channels = in_channels
+        self.mlp_layers_dims = copy.deepcopy(mlp_layers_dims)
+        self.geom_feat_size = geom_feat_size
+        self.encoding_type = encoding_type
+        self.out_channels = 1
+        self.is_training_main_surf = True
+        self.bb_sides = _bb_sides(bb_sides, in_channels, device)
+        self.pos_encoder = get_encoder(encoding_type, input_dim=in_channels, nr_levels=24,
+                                       nr_iters_for_c2f=nr_iters_for_c2f, multires=6, bb_sides=self.bb_sides)
+        self.pos_encoder.compute_out_of_bounds = False       # (sdf.py:73-74 never reads it)
+        self.encoding_output_dims = self.pos_encoder.output_dim
+        self.mlp_sdf = MLP(self.encoding_output_dims, self.mlp_layers_dims + [1 + self.geom_feat_size],
+                           last_layer_linear=True).to(device)
+
+    def forward(self, points, iter_nr=None):
+        assert points.shape[1] == self.in_channels, "points should be N x in_channels"
+        feats = self.pos_encoder(points, iter_nr=iter_nr)
+        pred = self.mlp_sdf(feats[0] if isinstance(feats, tuple) else feats)
+        if self.geom_feat_size > 0:
+            return pred[:, 0:1], pred[:, 1:]
+        return pred, None
+
+    def main_sdf(self, points, iter_nr=None):
+        return self.forward(points, iter_nr)

@@ -4,15 +4,14 @@ chains run as fused HIP kernels (csrc/nerf_render.hip): the foreground composite
 (`nerf_composite`) and the coarse pass of importance sampling (`nerf_coarse_cdf`); everything else is the
 project's existing HIP operators (permutohedral encoder, fused MLP, occupancy grid, packed samplers).
 `isosurface.extract_nerf_level_sets` meshes the trained density."""
-import os
-
 import torch
 
 from . import _lib
-from .background import BoundingSphere, intersect_bounding_primitive, render_contracted_bg
+from .background import intersect_bounding_primitive, render_contracted_bg
+from .field_method import FieldMethod, init_occupancy_grid
 from .models import RGB, ColorSH, Density, NerfHash
 from .trainer import loss_l1
-from .volsurfs import OccupancyGrid, RaySampler, VolumeRendering
+from .volsurfs import RaySampler, VolumeRendering
 
 
 class NeRFHyperParams:
@@ -74,15 +73,6 @@ class NeRFHyperParams:
         # hyper_params.py:173-178: the CDF of importance sampling needs 3 samples per ray
         if self.do_importance_sampling and self.min_nr_samples_per_ray < 3:
             self.min_nr_samples_per_ray = 3
-
-
-def init_occupancy_grid(bounding_primitive, res=256):
-    """utils/occupancy_grid.py:6-13."""
-    r = bounding_primitive.get_radius()
-    grid = OccupancyGrid(res, [r * 2, r * 2, r * 2])
-    if isinstance(bounding_primitive, BoundingSphere):
-        grid.init_sphere_roi(r, 0.0)
-    return grid
 
 
 # ---- fused per-ray chains (csrc/nerf_render.hip)
@@ -209,7 +199,7 @@ def get_rays_samples_packed_nerf(rays_o, rays_d, t_near, t_far, density_fn, occu
     return pack, imp
 
 
-class NeRF:
+class NeRF(FieldMethod):
     """methods/nerf.py:29-507.  models = {"density": Density, "rgb": RGB or ColorSH, "bg": NerfHash or None (with a
     constant bg_color [3])}; the occupancy grid of init_occupancy_grid (256^3, a sphere ROI for a BoundingSphere).
     Trains through trainer.train_step / train (the autograd path): `method(rays_o, rays_d, gt_rgb, gt_mask, iter_nr)`
@@ -263,12 +253,6 @@ class NeRF:
         self.update_method_state(iter_nr=start_iter_nr)
         self.update_occupancy_grid(iter_nr=start_iter_nr, decay=0.0, random_voxels=False, jitter_samples=False)
 
-    def __call__(self, *args, **kwargs):
-        return self.forward(*args, **kwargs)
-
-    def parameters(self):
-        return [p for m in self.models.values() if m is not None for p in m.parameters()]
-
     # ---- optimisation (base_method.py:60-94, nerf.py:143-192)
     def collect_opt_params(self):
         groups = [{"params": list(self.models["density"].parameters()), "lr": self.hyper_params.lr,
@@ -278,17 +262,6 @@ class NeRF:
             groups.append({"params": list(self.models["bg"].parameters()), "lr": self.hyper_params.lr,
                            "name": "model_bg"})
         return groups
-
-    def init_optim(self, opt_params=None):
-        from .optim import FusedAdam
-        from .schedulers import MultiStepLR
-        self.optimizer = FusedAdam(opt_params or self.collect_opt_params(), lr=self.hyper_params.lr,
-                                   betas=(0.9, 0.99), eps=1e-15, weight_decay=0.0)
-        self.scheduler_lr_decay = MultiStepLR(self.optimizer, milestones=self.hyper_params.lr_milestones, gamma=0.3)
-        return self.optimizer
-
-    def optim_step(self, overlap=False):
-        self.optimizer.step()
 
     def _warmup_scheduler(self, is_first_iter):
         if is_first_iter and self.scheduler_lr_decay is not None:           # nerf.py:437-443
@@ -396,67 +369,5 @@ class NeRF:
         losses = {"loss": loss, "rgb": loss_rgb, "sparsity": loss_sparsity, "mask": loss_mask}
         return losses, {}, res["samples_3d"]
 
-    # ---- checkpoints (base_method.py:118-264): <root>/<iter:07d>/models/{density,rgb,bg}.pt + the grid
-    def save(self, iter_nr):
-        if self.save_checkpoints_path is None:
-            return None
-        path = os.path.join(self.save_checkpoints_path, format(iter_nr, "07d"), "models")
-        os.makedirs(path, exist_ok=True)
-        for key, model in self.models.items():
-            if model is not None:
-                torch.save(model.state_dict(), os.path.join(path, f"{key}.pt"))
-        if self.occupancy_grid is not None:
-            torch.save(self.occupancy_grid.get_grid_values(), os.path.join(path, "grid_values.pt"))
-            torch.save(self.occupancy_grid.get_grid_occupancy(), os.path.join(path, "grid_occupancy.pt"))
-        if self.optimizer is not None:
-            torch.save(self.optimizer.state_dict(), os.path.join(path, "fusedadam.pt"))
-        return path
-
-    def load(self, iter_nr):
-        if self.load_checkpoints_path is None:
-            return None
-        path = os.path.join(self.load_checkpoints_path, format(iter_nr, "07d"), "models")
-        for key, model in self.models.items():
-            f = os.path.join(path, f"{key}.pt")
-            if model is not None and os.path.exists(f):
-                model.load_state_dict(torch.load(f, map_location="cuda"))
-        g = self.occupancy_grid
-        if g is not None:
-            fv, fo = os.path.join(path, "grid_values.pt"), os.path.join(path, "grid_occupancy.pt")
-            if os.path.exists(fv) and os.path.exists(fo):
-                g.set_grid_values(torch.load(fv, map_location="cuda"))
-                g.set_grid_occupancy(torch.load(fo, map_location="cuda"))
-            else:
-                self.update_occupancy_grid(iter_nr=iter_nr, decay=0.0, random_voxels=False, jitter_samples=False)
-        f = os.path.join(path, "fusedadam.pt")
-        if self.optimizer is not None and os.path.exists(f):
-            self.optimizer.load_state_dict(torch.load(f, map_location="cuda"))
-        return path
-
-    # ---- full frames (base_method.py:366-541)
-    @torch.no_grad()
-    def render(self, rays_o, rays_d, nr_rays_per_pixel=1, chunk=None):
-        chunk = int(chunk or self.hyper_params.test_rays_batch_size)
-        keys = ("rgb", "rgb_fg", "depth", "weights_sum", "bg_transmittance")
-        outs = {k: [] for k in keys}
-        for a in range(0, rays_o.shape[0], chunk):
-            v = self.render_rays(rays_o[a:a + chunk], rays_d[a:a + chunk])["renders"]["volumetric"]
-            for k in keys:
-                outs[k].append(v[k])
-        full = {k: torch.cat(v, 0) for k, v in outs.items()}
-        if nr_rays_per_pixel > 1:
-            full = {k: v.reshape(-1, nr_rays_per_pixel, v.shape[-1]).mean(1) for k, v in full.items()}
-        return full
-
-    @torch.no_grad()
-    def render_camera(self, camera, nr_rays_per_pixel=1, jitter_pixels=False, chunk=None):
-        """{key: [H, W, C]} of one camera (what evaluation.render_and_eval scores: "rgb")."""
-        from .camera import get_camera_rays
-        was = self.is_training
-        self.is_training = False
-        try:
-            rays_o, rays_d, _ = get_camera_rays(camera, nr_rays_per_pixel, jitter_pixels)
-            full = self.render(rays_o, rays_d, nr_rays_per_pixel, chunk)
-        finally:
-            self.is_training = was
-        return {k: v.reshape(camera.height, camera.width, v.shape[-1]) for k, v in full.items()}
+    def _rebuild_occupancy(self, iter_nr):
+        self.update_occupancy_grid(iter_nr=iter_nr, decay=0.0, random_voxels=False, jitter_samples=False)
