@@ -860,6 +860,43 @@ int vsa_neus_composite_bwd(const int32_t* start_end, const float* sdf, const flo
  * compute_cdf.  Bit-identical to that chain of single ops. */
 int vsa_sdf_coarse_cdf(const int32_t* start_end, const float* sdf, const float* dt, float logistic_beta,
                        float* cdf, int nr_rays, void* stream);
+/* The OffsetsSurfs method's foreground render (volsurfs_py/methods/offsets_surfs.py render_fg_volumetric,
+ * and the bg blend of render_rays) as one launch each way (csrc/offsets_render.hip states the summation
+ * orders).  K = nr_surfs in 1..16 (VSA_ERR_UNSUPPORTED otherwise); per-sample arrays are [S, K] sample-major,
+ * column k the k-th surface inner to outer.  Forward, per surface: the NeuS alpha of vsa_neus_composite_fwd
+ * from sdfs [S,K], sdfs_grad [S,K,3], dirs [S,3], dt [S]; T = cumprod((1 - alpha) + 1e-6), w = alpha T;
+ * surfs_rgb [N,K,3] = integral of rgb [S,K,3], surfs_alpha [N,K] = integral of transparency [S,K] (times
+ * sigmoid(f clamp(-d.n, 0, 1)) 2 - 1 with f = alpha_decay_factor when with_alpha_decay, n = normals [S,K,3]),
+ * surfs_depths [N,K], surfs_normals [N,K,3], surfs_weight_sum [N,K].  Then the blend outer to inner:
+ * surfs_transmittance [N,K], surfs_blending_weights [N,K], rgb_fg [N,3], bg_transmittance [N] and rgb_out
+ * [N,3] = rgb_fg + rgb_bg bg_transmittance (rgb_bg NULL: rgb_fg; [N,3] with bg_per_ray = 1 or one colour);
+ * alpha [S,K], the per-sample NeuS alpha, is optional.
+ * Backward: g_rgb [N,3] of rgb_out -> g_sdfs [S,K], g_sdfs_grad [S,K,3], g_rgb_samples [S,K,3],
+ * g_transparency [S,K], g_rgb_bg [N,3] (optional); depths, normals and weight sums pass no gradient, nor does
+ * the decay; bug_compat as in vsa_packed_integrate_bwd; scratch: 2 S K floats.  The per-sample arrays may be
+ * NULL when the pack has no samples. */
+int vsa_offsets_composite_fwd(const int32_t* start_end, int nr_surfs, const float* sdfs, const float* sdfs_grad,
+                              const float* normals, const float* rgb, const float* transparency, const float* dirs,
+                              const float* dt, const float* samples_z, const float* rgb_bg, int bg_per_ray,
+                              double cos_anneal_ratio, double logistic_beta, int with_alpha_decay,
+                              double alpha_decay_factor, float* surfs_rgb, float* surfs_normals, float* surfs_depths,
+                              float* surfs_weight_sum, float* surfs_alpha, float* surfs_transmittance,
+                              float* surfs_blending_weights, float* rgb_fg, float* bg_transmittance, float* rgb_out,
+                              float* alpha, int nr_rays, void* stream);
+int vsa_offsets_composite_bwd(const int32_t* start_end, int nr_surfs, const float* sdfs, const float* sdfs_grad,
+                              const float* normals, const float* rgb, const float* transparency, const float* dirs,
+                              const float* dt, const float* rgb_bg, int bg_per_ray, double cos_anneal_ratio,
+                              double logistic_beta, int with_alpha_decay, double alpha_decay_factor,
+                              const float* surfs_rgb, const float* surfs_alpha, const float* surfs_transmittance,
+                              const float* bg_transmittance, const float* g_rgb, float* g_sdfs, float* g_sdfs_grad,
+                              float* g_rgb_samples, float* g_transparency, float* g_rgb_bg, float* scratch,
+                              int nr_rays, int bug_compat, void* stream);
+/* One round of importance_sampling_sdfs_iter (volsurfs_py/utils/sdfs_utils.py:12-64) from the pack's sdfs
+ * [S,K] and dt [S] to cdf [S]: per surface the round of vsa_sdf_coarse_cdf with the transmittance clipped to
+ * [0, 1], the K CDFs summed in order and divided by K.  Bit-identical to that chain of single ops.  K in
+ * 1..16 (VSA_ERR_UNSUPPORTED otherwise). */
+int vsa_sdfs_coarse_cdf(const int32_t* start_end, int nr_surfs, const float* sdfs, const float* dt,
+                        float logistic_beta, float* cdf, int nr_rays, void* stream);
 /* median_depth_over_rays (:372-416); fallback_compat=1 reproduces VolumeRenderingGPU.cuh:407. */
 int vsa_packed_median_depth(const int32_t* start_end, const float* samples_z,
                             const float* weights, float threshold, float* out, int nr_rays,

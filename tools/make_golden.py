@@ -3,7 +3,7 @@
 
 Runs only in the build container (needs /root/reference).  The arrays it
 writes are the committed fixtures; the reference source itself is never copied.
-Usage:  python tools/make_golden.py [composite] [sh] [nt] [glue] [misc] [surf]
+Usage:  python tools/make_golden.py [composite] [sh] [nt] [glue] [misc] [surf] [offsets]
 """
 import os
 import sys
@@ -445,8 +445,77 @@ def gen_surf():
     _save("surf_neus.npz", **arrs)
 
 
+OFFSETS_KS = (1, 3, 5, 9)
+OFFSETS_SHIFTS = (0.02, 0.0, -0.015, 0.03, -0.04, 0.01, 0.05, -0.025, 0.0)
+
+
+def _offsets_test_sdfs(p):
+    """The analytic K-column field of the offsets fixture: the wavy sphere of the surf fixture plus a different
+    smooth term per column -> (sdfs [N,K,1], None, None) like OffsetsSDF.forward (K from the global below)."""
+    base = _surf_test_sdf(p)[0]
+    cols = [base + OFFSETS_SHIFTS[i] * torch.cos(4.0 * p[:, 2:3] + i) for i in range(_OFFSETS_K[0])]
+    return torch.cat(cols, 1).unsqueeze(-1), None, None
+
+
+_OFFSETS_K = [1]
+
+
+def gen_offsets():
+    """The offsets_surfs method's per-surface maths, executed by the reference's own get_offsets_gt,
+    logistic_distribution_stdev, OffsetsSDF.get_offsets (unbound, on an object carrying CPU heads with seeded
+    weights: the constructor moves to CUDA) and the K-column get_field_gradients / get_sdf_curvature, on CPU
+    (float32), for tests/test_offsets_surfs_method.py.  The heads' weights are stored under the reference's
+    state-dict names (layers.<i>.weight / bias) with a per-K, per-head prefix."""
+    import warnings
+    warnings.filterwarnings("ignore")
+    ref_import.install_placeholders({})
+    from volsurfs_py.models.mlp import MLP
+    from volsurfs_py.models.offsets_sdf import OffsetsSDF
+    from volsurfs_py.utils.fields_utils import get_field_gradients, get_sdf_curvature
+    from volsurfs_py.utils.logistic_distribution import (get_logistic_beta_from_variance,
+                                                         logistic_distribution_stdev)
+    from volsurfs_py.utils.offsets_utils import get_offsets_gt
+    arrs = {}
+    g = torch.Generator().manual_seed(21)
+    M = 256
+    feats = torch.randn(M, 32, generator=g)
+    pts = (torch.rand(200, 3, generator=g) - 0.5) * 0.8
+    arrs.update(geom_feats=feats.numpy(), field_points=pts.numpy())
+    for K in OFFSETS_KS:
+        # base_K.cfg: nr_inner_surfs = K - 1, nr_outer_surfs = 0, first_phase_variance_start_value 0.7, and a
+        # multiplier other than 1 as well
+        for mult in (1.0, 0.25):
+            stdev = logistic_distribution_stdev(get_logistic_beta_from_variance(0.7))
+            delta = stdev * mult
+            gt = get_offsets_gt(0, K - 1, delta)
+            arrs[f"delta_{K}_{mult}"] = np.array(delta, np.float64)
+            arrs[f"offsets_gt_{K}_{mult}"] = gt.numpy()
+        _OFFSETS_K[0] = K
+        fg = get_field_gradients(_offsets_test_sdfs, pts)
+        torch.manual_seed(12)
+        rand_dirs = torch.randn_like(pts)
+        torch.manual_seed(12)
+        curv = get_sdf_curvature(_offsets_test_sdfs, pts, fg, eps=1e-2)
+        arrs.update({f"field_grad_{K}": fg.numpy(), f"curv_rand_dirs_{K}": rand_dirs.numpy(),
+                     f"curvature_eps1e2_{K}": curv.numpy()})
+        if K == 1:
+            continue
+        torch.manual_seed(100 + K)
+        heads = [MLP(32, [32, 1], last_layer_linear=True) for _ in range(K - 1)]
+        for i, h in enumerate(heads):
+            for k, v in h.state_dict().items():
+                arrs[f"eps_{K}_{i}.{k}"] = v.numpy()
+        host = SimpleNamespace(mlps_eps=heads, use_per_offset_mlp=True, nr_surfs=K, nr_outer_surfs=0,
+                               min_offset=1e-4)
+        with torch.no_grad():
+            cum_inner, cum_outer, inner, outer = OffsetsSDF.get_offsets(host, feats)
+        arrs.update({f"cum_inner_{K}": cum_inner.numpy(), f"cum_outer_{K}": cum_outer.numpy(),
+                     f"inner_{K}": inner.numpy(), f"outer_{K}": outer.numpy()})
+    _save("offsets_surfs.npz", **arrs)
+
+
 GENS = {"composite": gen_composite, "nt": gen_nt, "glue": gen_glue, "legacy": gen_legacy,
-        "misc": gen_misc, "surf": gen_surf}
+        "misc": gen_misc, "surf": gen_surf, "offsets": gen_offsets}
 
 if __name__ == "__main__":
     # One generator per process: each one imports the reference with its own set of stand-ins

@@ -199,14 +199,17 @@ def marching_cubes(grid, levels, origin, spacing, inside="below"):
 
 
 @torch.no_grad()
-def sample_grid(fn, nr_points_per_dim, scene_radius=1.0, out_idx=None, iter_nr=None, chunk=64, device="cuda"):
+def sample_grid(fn, nr_points_per_dim, scene_radius=1.0, out_idx=None, iter_nr=None, chunk=64, device="cuda",
+                nr_columns=None):
     """mesh_extraction.py:248-305 without the host copy: fn evaluated on the lattice
     X, Y, Z = torch.linspace(-r, r, n) (fp32) with indexing "ij", in chunk^3 blocks, into a device grid
     [n, n, n] f32 (grid[i, j, k] = fn(X[i], Y[j], Z[k])).  fn takes points [P, 3] (and iter_nr= when given); a
-    tuple output gives its first element, `out_idx` selects a column."""
+    tuple output gives its first element, `out_idx` selects a column.  With `nr_columns` = K, all K output columns
+    of fn ([P, K] or [P, K, 1]) from one pass into a grid [K, n, n, n]."""
     n, r = int(nr_points_per_dim), float(scene_radius)
     axis = torch.linspace(-r, r, n, dtype=torch.float32).to(device)
-    grid = torch.empty(n, n, n, device=device)
+    K = None if nr_columns is None else int(nr_columns)
+    grid = torch.empty(n, n, n, device=device) if K is None else torch.empty(K, n, n, n, device=device)
     for x0 in range(0, n, chunk):
         for y0 in range(0, n, chunk):
             for z0 in range(0, n, chunk):
@@ -218,8 +221,12 @@ def sample_grid(fn, nr_points_per_dim, scene_radius=1.0, out_idx=None, iter_nr=N
                     pred = pred[0]
                 if out_idx is not None:
                     pred = pred[:, out_idx]
-                grid[x0:x0 + len(xs), y0:y0 + len(ys), z0:z0 + len(zs)] = \
-                    pred.reshape(len(xs), len(ys), len(zs)).to(torch.float32)
+                if K is None:
+                    grid[x0:x0 + len(xs), y0:y0 + len(ys), z0:z0 + len(zs)] = \
+                        pred.reshape(len(xs), len(ys), len(zs)).to(torch.float32)
+                else:
+                    grid[:, x0:x0 + len(xs), y0:y0 + len(ys), z0:z0 + len(zs)] = \
+                        pred.reshape(pts.shape[0], K).t().reshape(K, len(xs), len(ys), len(zs)).to(torch.float32)
     return grid
 
 
@@ -328,6 +335,39 @@ def extract_surf_level_sets(method, nr_points_per_dim, nr_meshes=1, delta_surfs=
     return extract_level_sets(method.models["sdf"].main_sdf, nr_points_per_dim, nr_meshes, delta_surfs,
                               extract_level_set, bounding_primitive=method.bounding_primitive, out_idx=0,
                               iter_nr=iter_nr)
+
+
+def extract_offsets_surfs_meshes(method, nr_points_per_dim, nr_meshes_to_extract=1, delta_surfs=0.0025,
+                                 extract_level_set=0.0, iter_nr=None):
+    """The baker's `--extract_meshes` for the offsets_surfs method (baker.py:325-369).  nr_meshes_to_extract == 1:
+    the zero level of each of the K sdfs of `method.models["sdfs"]` (all K columns from one pass over the lattice),
+    inner to outer, levels [0.0] * K.  nr_meshes_to_extract > 1: the baker's level sets of the main surface, as
+    extract_surf_level_sets.  Inside is below the level; faces not wholly inside the bounding primitive are dropped.
+    Returns (meshes, levels)."""
+    model = method.models["sdfs"]
+    bp = method.bounding_primitive
+    n = int(nr_points_per_dim)
+    if int(nr_meshes_to_extract) > 1:
+        return extract_level_sets(model.main_sdf, n, nr_meshes_to_extract, delta_surfs, extract_level_set,
+                                  bounding_primitive=bp, out_idx=0, iter_nr=iter_nr)
+    K = model.nr_surfs
+    grid = sample_grid(model, n, _radius(bp), iter_nr=iter_nr, nr_columns=K)
+    meshes = [_finish(grid[k].contiguous(), [0.0], n, bp)[0] for k in range(K)]
+    return meshes, [0.0] * K
+
+
+def save_offsets_surfs_meshes(meshes, out_dir):
+    """The K-SDF mode's `meshes/<i>.ply` files (i = 0 the innermost); an empty surface raises.  Returns the paths."""
+    for i, m in enumerate(meshes):
+        if m.faces.shape[0] == 0:
+            raise ValueError(f"surface {i} has no faces: nothing to save")
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for i, m in enumerate(meshes):
+        path = os.path.join(out_dir, f"{i}.ply")
+        save_ply(path, TensorMesh(m.vertices, m.faces, None, device=m.vertices.device))
+        paths.append(path)
+    return paths
 
 
 def save_level_sets(meshes, levels, out_dir):

@@ -737,3 +737,133 @@ class SDF(torch.nn.Module):
 
     def main_sdf(self, points, iter_nr=None):
         return self.forward(points, iter_nr)
+
+
+class OffsetsSDF(torch.nn.Module):
+    """models/offsets_sdf.py:12-281 (per-offset heads): the main SDF of `SDF` (pos_encoder + mlp_sdf
+    [in, dims.., 1 + geom_feat]) and nr_surfs - 1 heads MLP(geom_feat, [32, 1]) on its features, whose softplus
+    offsets, summed cumulatively (+ / - min_offset), shift the main SDF to the inner and outer surfaces.
+    forward -> (sdfs [M, K, 1] inner to outer, offsets [M, K, 1] or None for K = 1, geom_feat).  As in the
+    reference the heads sit in a plain Python list (`mlps_eps`), so state_dict() holds only the pos_encoder.* and
+    mlp_sdf.* keys and each head is its own checkpoint (`heads_state_dicts` / `load_heads_state_dicts`).  On the
+    GPU the K - 1 heads run as ONE grouped fused-MLP launch over the replicated features."""
+
+    def __init__(self, in_channels=3, mlp_layers_dims=(32, 32, 32), encoding_type="permutohash", nr_inner_surfs=1,
+                 nr_outer_surfs=1, geom_feat_size=32, min_offset=1e-4, nr_iters_for_c2f=0, bb_sides=2.0,
+                 device="cuda"):
+        super().__init__()
+        self.in_channels = in_channels
+        self.mlp_layers_dims = list(copy.deepcopy(mlp_layers_dims))
+        self.nr_inner_surfs, self.nr_outer_surfs = nr_inner_surfs, nr_outer_surfs
+        self.nr_surfs = nr_inner_surfs + nr_outer_surfs + 1
+        self.geom_feat_size = geom_feat_size
+        self.out_channels = self.nr_surfs
+        self.encoding_type = encoding_type
+        self.is_training_main_surf = True
+        self.is_training_offsets = True
+        self.use_per_offset_mlp = True
+        self.min_offset = min_offset
+        self.main_surf_idx = nr_inner_surfs
+        self.bb_sides = _bb_sides(bb_sides, in_channels, device)
+        self.pos_encoder = get_encoder(encoding_type, input_dim=in_channels, nr_levels=24,
+                                       nr_iters_for_c2f=nr_iters_for_c2f, multires=6, bb_sides=self.bb_sides)
+        self.pos_encoder.compute_out_of_bounds = False
+        self.encoding_output_dims = self.pos_encoder.output_dim
+        self.mlp_sdf = MLP(self.encoding_output_dims, self.mlp_layers_dims + [1 + self.geom_feat_size],
+                           last_layer_linear=True).to(device)
+        # (a plain list, not a ModuleList: the reference's state-dict layout)
+        self.mlps_eps = [MLP(self.geom_feat_size, [32, 1], last_layer_linear=True).to(device)
+                         for _ in range(self.nr_surfs - 1)]
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        for m in self.mlps_eps:
+            m._apply(fn, *args, **kwargs)
+        return self
+
+    def heads_parameters(self):
+        return [p_ for m in self.mlps_eps for p_ in m.parameters()]
+
+    def main_sdf(self, points, iter_nr=None):
+        assert points.shape[1] == self.in_channels, "points should be N x in_channels"
+        feats = self.pos_encoder(points, iter_nr=iter_nr)
+        pred = self.mlp_sdf(feats[0] if isinstance(feats, tuple) else feats)
+        if self.geom_feat_size > 0:
+            return pred[:, 0:1], pred[:, 1:]
+        return pred, None
+
+    def _heads(self, geom_feats):
+        """[M, K - 1]: column i = mlps_eps[i](geom_feats) (torch.stack(.., dim=1).squeeze(-1))."""
+        M, H = geom_feats.shape[0], len(self.mlps_eps)
+        if geom_feats.is_cuda and mlps_groupable(self.mlps_eps, geom_feats):
+            x = geom_feats.repeat(H, 1)
+            y = fused_mlp_grouped(self.mlps_eps, x, [M] * H)
+            return y.reshape(H, M).t()
+        return torch.stack([m(geom_feats) for m in self.mlps_eps], dim=1).squeeze(dim=-1)
+
+    def get_offsets(self, geom_feats):
+        """offsets_sdf.py:140-171 -> (cum_inner_eps flipped, cum_outer_eps, inner_eps, outer_eps)."""
+        eps = self._heads(geom_feats)
+        inner_eps = torch.nn.functional.softplus(eps[:, self.nr_outer_surfs:])
+        outer_eps = -1 * torch.nn.functional.softplus(eps[:, :self.nr_outer_surfs])
+        cum_outer_eps = torch.cumsum(outer_eps, dim=1) - self.min_offset
+        cum_inner_eps = torch.cumsum(inner_eps, dim=1) + self.min_offset
+        cum_inner_eps = torch.flip(cum_inner_eps, dims=[1])
+        return cum_inner_eps, cum_outer_eps, inner_eps, outer_eps
+
+    def forward(self, points, iter_nr=None):
+        sdf, geom_feats = self.main_sdf(points, iter_nr=iter_nr)
+        if not self.is_training_main_surf:
+            sdf, geom_feats = sdf.detach(), geom_feats.detach()
+        if self.nr_surfs == 1:
+            return sdf.unsqueeze(-1), None, geom_feats
+        cum_inner, cum_outer, inner_eps, outer_eps = self.get_offsets(geom_feats)
+        sdfs = torch.cat([sdf + cum_inner, sdf, sdf + cum_outer], dim=1).unsqueeze(-1)
+        offsets = torch.cat([inner_eps, torch.zeros_like(sdf), outer_eps], dim=1).unsqueeze(-1)
+        return sdfs, offsets, geom_feats
+
+    def __getitem__(self, i):
+        def surface_sdf(points, iter_nr=None):
+            return self.forward(points, iter_nr)[0][:, i]
+        return surface_sdf
+
+    def _set_trainable(self, params, flag):
+        for p_ in params:
+            p_.requires_grad = flag
+
+    def freeze_main_surf(self):
+        if self.is_training_main_surf:
+            self._set_trainable(list(self.mlp_sdf.parameters()) + list(self.pos_encoder.parameters()), False)
+            self.is_training_main_surf = False
+
+    def unfreeze_main_surf(self):
+        if not self.is_training_main_surf:
+            self._set_trainable(list(self.mlp_sdf.parameters()) + list(self.pos_encoder.parameters()), True)
+            self.is_training_main_surf = True
+
+    def freeze_offsets(self):
+        if self.is_training_offsets:
+            self._set_trainable(self.heads_parameters(), False)
+            self.is_training_offsets = False
+
+    def unfreeze_offsets(self):
+        if not self.is_training_offsets:
+            self._set_trainable(self.heads_parameters(), True)
+            self.is_training_offsets = True
+
+    def load_main_sdf_ckpt(self, ckpt_path):
+        """offsets_sdf.py:213-235: the pos_encoder.* and mlp_sdf.* entries of a `sdf.pt` (Surf.save or the
+        reference's) into the main surface."""
+        ckpt = torch.load(ckpt_path, map_location=self.bb_sides.device)
+        self.pos_encoder.load_state_dict({k.replace("pos_encoder.", ""): v for k, v in ckpt.items()
+                                          if "pos_encoder" in k})
+        self.mlp_sdf.load_state_dict({k.replace("mlp_sdf.", ""): v for k, v in ckpt.items() if "mlp_sdf" in k})
+
+    def heads_state_dicts(self):
+        return [m.state_dict() for m in self.mlps_eps]
+
+    def load_heads_state_dicts(self, sds, strict=True):
+        if len(sds) != len(self.mlps_eps):
+            raise ValueError(f"{len(sds)} head checkpoints for {len(self.mlps_eps)} heads")
+        for m, sd in zip(self.mlps_eps, sds):
+            m.load_state_dict(sd, strict=strict)

@@ -1,0 +1,640 @@
+"""The OffsetsSurfs method (volsurfs_py/methods/offsets_surfs.py, config/offsets_surfs/base_5.cfg,
+models/offsets_sdf.py, utils/offsets_utils.py, utils/sdfs_utils.py): K nested surfaces, the zero levels of a main
+SDF shifted by learned, spatially varying offsets, each with its own colour and transparency, trained from posed
+images starting from a `surf` run's `sdf.pt`.  Its meshes (`isosurface.extract_offsets_surfs_meshes`) are the shells
+the VolSurfs stages take.
+
+The per-ray chains run as fused HIP kernels (csrc/offsets_render.hip): the K NeuS composites with the dense blend
+of the shells and the background (`offsets_composite`) and one importance round over K CDFs (`sdfs_coarse_cdf`).
+The rest is the project's existing HIP operators and the Surf method's helpers."""
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from .background import intersect_bounding_primitive, render_contracted_bg
+from .field_method import FieldMethod, init_occupancy_grid
+from .models import RGB, ColorSH, NerfHash, OffsetsSDF
+from .surf import (SurfHyperParams, _bg_arg, eikonal_loss, field_stencil, get_logistic_beta_from_variance,
+                   logistic_distribution_stdev, map_range_val, stencil_gradients, FD_EPS)
+from .trainer import loss_l1
+from .volsurfs import RaySampler, VolumeRendering
+
+MAX_SURFS = 16          # csrc/offsets_render.hip OR_MAX_SURFS
+
+
+class OffsetsSurfsHyperParams(SurfHyperParams):
+    """params/hyper_params.py (HyperParamsOffsetsSuRFs) with config/offsets_surfs/base_5.cfg applied.  Keyword
+    arguments override single values; what Surf does not implement raises here too."""
+
+    def __init__(self, **overrides):
+        super().__init__()
+        # base_5.cfg
+        self.init_phase_end_iter = 2000
+        self.color_init_phase_end_iter = 3000
+        self.nr_warmup_iters = 1000
+        self.lr_milestones = [40000, 45000, 47500]
+        self.nr_inner_surfs = 4
+        self.nr_outer_surfs = 0
+        self.delta_surfs_multiplier = 1.0
+        self.training_end_iter = 50000
+        self.first_phase_end_iter = 45000
+        self.first_phase_stop_main_surf = False
+        self.first_phase_variance_start_value = 0.7
+        self.first_phase_variance_end_value = 1.0
+        self.sdf_nr_iters_for_c2f = 0
+        self.rgb_nr_iters_for_c2f = 0
+        self.appearance_predict_sh_coeffs = False
+        self.min_nr_samples_per_ray = 1
+        # HyperParamsOffsetsSuRFs
+        self.are_surfs_colors_indep = False
+        self.are_surfs_transparency_indep = False
+        self.is_inner_surf_solid = False
+        self.transp_view_dep = True
+        self.transp_normal_dep = True
+        self.transp_geom_feat_dep = True
+        self.offsets_weight = 0.0
+        self.support_surfs_eikonal_weight = 0.04
+        self.with_alpha_decay = True
+        for k, v in overrides.items():
+            if not hasattr(self, k):
+                raise KeyError(f"unknown hyper-parameter {k!r}")
+            setattr(self, k, v)
+        if self.rgb_use_lipshitz_mlp or self.lipshitz_weight > 0.0:
+            raise NotImplementedError("the Lipschitz MLP and its loss are not implemented")
+        if self.use_color_calibration or self.use_grad_scaler:
+            raise NotImplementedError("colour calibration and the grad scaler are not implemented")
+        if self.nr_inner_surfs + self.nr_outer_surfs + 1 > MAX_SURFS:
+            raise _lib.VolsurfsHipError(f"at most {MAX_SURFS} surfaces")
+        if self.do_importance_sampling and self.min_nr_samples_per_ray < 3:
+            self.min_nr_samples_per_ray = 3
+
+
+def get_offsets_gt(nr_outer_surfs, nr_inner_surfs, delta_surfs, main_surf_shift=0.0):
+    """utils/offsets_utils.py:4-21: [inner offsets, largest first, then outer ones] (float64, as the reference's
+    tensor of numpy float64 values; an empty float32 tensor for K = 1)."""
+    outer, cur = [], main_surf_shift
+    for _ in range(nr_outer_surfs):
+        cur -= delta_surfs
+        outer.append(cur)
+    inner, cur = [], main_surf_shift
+    for _ in range(nr_inner_surfs):
+        cur += delta_surfs
+        inner.append(cur)
+    vals = inner[::-1] + outer
+    return (torch.tensor(vals, dtype=torch.float64) if vals else torch.tensor([])) - main_surf_shift
+
+
+def get_sdfs_curvature(sdfs_fn, points, sdfs_gradients, rand_directions, iter_nr=None, eps=FD_EPS):
+    """fields_utils.py:69-166 for K surfaces with the random directions given: the K shifted point sets
+    (points + tangent_k eps) evaluated as ONE stencil call of 4 K M rows, column k of block k -> [M, K, 1]
+    ([M] for one surface).  Same rows and values as the reference's K calls."""
+    normals = F.normalize(sdfs_gradients, dim=-1)
+    K = sdfs_gradients.shape[1] if sdfs_gradients.dim() > 2 else 1
+    rand_directions = F.normalize(rand_directions, dim=-1)
+    if normals.dim() > 2:
+        rand_directions = rand_directions.unsqueeze(1)
+    tangent = torch.cross(normals, rand_directions, dim=-1)
+    M = points.shape[0]
+    if tangent.dim() > 2:
+        shifted = torch.cat([points + tangent[:, i] * eps for i in range(K)], 0)
+    else:
+        shifted = points + tangent * eps
+    res = field_stencil(sdfs_fn, shifted, iter_nr)
+    grads = stencil_gradients(res[0] if isinstance(res, tuple) else res)       # [K M, K, 3] or [M, 3]
+    if normals.dim() > 2:
+        shifted_n = torch.stack([F.normalize(grads[i * M:(i + 1) * M, i], dim=-1) if grads.dim() > 2
+                                 else F.normalize(grads[i * M:(i + 1) * M], dim=-1) for i in range(K)], 1)
+    else:
+        shifted_n = F.normalize(grads[:, 0] if grads.dim() > 2 else grads, dim=-1)
+    dot = torch.sum(torch.mul(normals, shifted_n), dim=-1, keepdim=True)
+    angle = torch.acos(torch.clamp(dot, -1.0 + 1e-6, 1.0 - 1e-6))
+    curv = angle / np.pi
+    return curv.squeeze(1) if K == 1 else curv
+
+
+# ---- fused per-ray chains (csrc/offsets_render.hip)
+class _OffsetsComposite(torch.autograd.Function):
+    """render_fg_volumetric's K NeuS chains and the blend, and render_rays' background, as one launch each way
+    (vsa_offsets_composite_fwd / _bwd).  Differentiable inputs: sdfs, sdfs_grad, rgb, transparency, rgb_bg;
+    differentiable output: rgb.  The other outputs carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, pack, sdfs, sdfs_grad, normals, rgb, transparency, rgb_bg, car, beta, decay, want_alpha):
+        sdfs = _lib.check_f32(sdfs.contiguous())
+        S, K = sdfs.shape
+        N = pack.get_nr_rays()
+        if K < 1 or K > MAX_SURFS:
+            raise _lib.VolsurfsHipError(f"offsets composite: 1 <= K <= {MAX_SURFS} surfaces, got {K}")
+        sdfs_grad = _lib.check_f32(sdfs_grad.contiguous())
+        normals = _lib.check_f32(normals.contiguous())
+        rgb = _lib.check_f32(rgb.contiguous())
+        ctx.tr_shape = transparency.shape
+        transparency = _lib.check_f32(transparency.reshape(S, K).contiguous())
+        if sdfs_grad.shape != (S, K, 3) or normals.shape != (S, K, 3) or rgb.shape != (S, K, 3) or \
+                pack.samples_dt.numel() != S:
+            raise _lib.VolsurfsHipError("offsets composite: sdfs [S,K], sdfs_grad / normals / rgb [S,K,3], "
+                                        "transparency [S,K], a pack with dt")
+        bg, per_ray, bg_shape = _bg_arg(rgb_bg, N)
+        dev = sdfs.device
+        e = lambda *s: torch.empty(*s, device=dev)
+        s_rgb, s_nrm, s_depth, s_ws = e(N, K, 3), e(N, K, 3), e(N, K, 1), e(N, K, 1)
+        s_alpha, s_T, s_bw = e(N, K, 1), e(N, K, 1), e(N, K, 1)
+        rgb_fg, bgT, rgb_out = e(N, 3), e(N, 1), e(N, 3)
+        alpha = e(S, K) if want_alpha else None
+        dirs = pack.samples_dirs.contiguous()
+        with_decay = decay is not None
+        _lib.call("vsa_offsets_composite_fwd", pack.ray_start_end_idx, K, sdfs, sdfs_grad, normals, rgb,
+                  transparency, dirs, pack.samples_dt, pack.samples_z, bg, per_ray, float(car), float(beta),
+                  int(with_decay), float(decay) if with_decay else 0.0, s_rgb, s_nrm, s_depth, s_ws, s_alpha, s_T,
+                  s_bw, rgb_fg, bgT, rgb_out, alpha, N, _lib.stream_ptr())
+        ctx.save_for_backward(sdfs, sdfs_grad, normals, rgb, transparency, dirs, bg, s_rgb, s_alpha, s_T, bgT)
+        ctx.pack, ctx.per_ray, ctx.bg_shape = pack, per_ray, bg_shape
+        ctx.car, ctx.beta, ctx.decay = float(car), float(beta), decay
+        ctx.set_materialize_grads(False)
+        nd = [rgb_fg, bgT, s_rgb, s_nrm, s_depth, s_ws, s_alpha, s_T, s_bw] + ([alpha] if want_alpha else [])
+        ctx.mark_non_differentiable(*nd)
+        return (rgb_out, *nd, *([] if want_alpha else [None]))
+
+    @staticmethod
+    def backward(ctx, g_rgb, *_):
+        sdfs, sdfs_grad, normals, rgb, transparency, dirs, bg, s_rgb, s_alpha, s_T, bgT = ctx.saved_tensors
+        pack, ctx.pack = ctx.pack, None
+        N = pack.get_nr_rays()
+        S, K = sdfs.shape
+        if g_rgb is None:
+            g_rgb = torch.zeros(N, 3, device=sdfs.device)
+        g_sdfs, g_grad, g_rgb_s = torch.empty_like(sdfs), torch.empty_like(sdfs_grad), torch.empty_like(rgb)
+        g_t = torch.empty_like(transparency)
+        need_bg = bg is not None and ctx.needs_input_grad[6]
+        g_bg = torch.empty(N, 3, device=sdfs.device) if need_bg else None
+        scratch = torch.empty(2 * S * K, device=sdfs.device)
+        d = ctx.decay
+        _lib.call("vsa_offsets_composite_bwd", pack.ray_start_end_idx, K, sdfs, sdfs_grad, normals, rgb,
+                  transparency, dirs, pack.samples_dt, bg, ctx.per_ray, ctx.car, ctx.beta, int(d is not None),
+                  float(d) if d is not None else 0.0, s_rgb, s_alpha, s_T, bgT, g_rgb.contiguous(), g_sdfs, g_grad,
+                  g_rgb_s, g_t, g_bg, scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
+        if need_bg and not ctx.per_ray:
+            g_bg = g_bg.sum(0).view(ctx.bg_shape)
+        return None, g_sdfs, g_grad, None, g_rgb_s, g_t.view(ctx.tr_shape), g_bg, None, None, None, None
+
+
+def offsets_composite(pack, sdfs, sdfs_grad, normals, rgb, transparency, rgb_bg=None, cos_anneal_ratio=1.0,
+                      logistic_beta=2048.0, alpha_decay_factor=None, return_alpha=False):
+    """render_fg_volumetric (offsets_surfs.py:420-713) and render_rays' blend (:983-1005) from the samples' sdfs
+    [S,K(,1)], sdfs_grad [S,K,3], normals [S,K,3] (no gradient), rgb [S,K,3] and transparency [S,K(,1)] on a
+    compacted pack with dt; rgb_bg [N,3], one colour or None; alpha_decay_factor None = no decay.  Returns the
+    reference's buffers inner to outer: surfs_rgb / surfs_normals [N,K,3], surfs_depths / surfs_weight_sum /
+    surfs_alpha / surfs_transmittance / surfs_blending_weights [N,K,1], and rgb_fg [N,3], bg_transmittance [N,1],
+    rgb [N,3]; with return_alpha the per-sample NeuS alpha [S,K] too.  Per surface bit-identical downstream of
+    alpha to the packed ops (tests/test_offsets_surfs_render.py)."""
+    S = sdfs.shape[0]
+    out = _OffsetsComposite.apply(pack, sdfs.reshape(S, sdfs.shape[1]), sdfs_grad, normals, rgb, transparency, rgb_bg,
+                                  cos_anneal_ratio, logistic_beta, alpha_decay_factor, bool(return_alpha))
+    rgb_out, rgb_fg, bgT, s_rgb, s_nrm, s_depth, s_ws, s_alpha, s_T, s_bw, alpha = out
+    return {"alpha": alpha, "rgb": rgb_out, "rgb_fg": rgb_fg, "bg_transmittance": bgT, "surfs_rgb": s_rgb, "surfs_normals": s_nrm,
+            "surfs_depths": s_depth, "surfs_weight_sum": s_ws, "surfs_alpha": s_alpha, "surfs_transmittance": s_T,
+            "surfs_blending_weights": s_bw}
+
+
+@torch.no_grad()
+def sdfs_coarse_cdf(pack, sdfs, logistic_beta):
+    """One round of importance_sampling_sdfs_iter (sdfs_utils.py:12-64) from the pack's sdfs [S,K(,1)] to the CDF
+    [S,1] in one launch (vsa_sdfs_coarse_cdf); `logistic_beta` is the fp32 value the chain multiplies by.
+    Bit-identical to the chain of single ops."""
+    S = sdfs.shape[0]
+    sdfs = _lib.check_f32(sdfs.reshape(S, sdfs.shape[1]).contiguous())
+    K = sdfs.shape[1]
+    if K < 1 or K > MAX_SURFS:
+        raise _lib.VolsurfsHipError(f"sdfs_coarse_cdf: 1 <= K <= {MAX_SURFS} surfaces, got {K}")
+    if S != pack.samples_dt.numel():
+        raise _lib.VolsurfsHipError("sdfs_coarse_cdf: one row of sdfs per sample")
+    cdf = torch.empty(S, 1, device=sdfs.device)
+    _lib.call("vsa_sdfs_coarse_cdf", pack.ray_start_end_idx, K, sdfs, pack.samples_dt, float(logistic_beta), cdf,
+              pack.get_nr_rays(), _lib.stream_ptr())
+    return cdf
+
+
+def _sdfs_columns(res):
+    sdfs = res[0] if isinstance(res, tuple) else res
+    return sdfs[..., 0:1] if sdfs.shape[2] > 1 else sdfs
+
+
+@torch.no_grad()
+def importance_sampling_sdfs(sdfs_fn, nr_surfs, pack_uniform, iter_nr, nr_imp_samples, logistic_beta_value,
+                             min_dist_between_samples, jitter_samples=False):
+    """sdfs_utils.py:67-180 -> (imp_1, imp_2): round one on the uniform samples with beta / 2, round two on the
+    combined pack (K-column samples_values) with beta, nr_imp_samples // 2 each; each round's CDF is the fused
+    kernel."""
+    if pack_uniform.is_empty():
+        raise _lib.VolsurfsHipError("ray_samples_packed_uniform should not be empty")
+    call = (lambda p: sdfs_fn(p)) if iter_nr is None else (lambda p: sdfs_fn(p, iter_nr))
+    sdfs = _sdfs_columns(call(pack_uniform.samples_3d))
+    pack_uniform.update_dt(False)
+    beta = np.float32(logistic_beta_value)
+    cdf = sdfs_coarse_cdf(pack_uniform, sdfs, beta / np.float32(2.0))
+    imp_1 = VolumeRendering.importance_sample(pack_uniform, cdf, nr_imp_samples // 2, jitter_samples)
+    sdfs_1 = _sdfs_columns(call(imp_1.samples_3d))
+    pack_uniform.set_samples_values(sdfs.reshape(-1, nr_surfs))
+    imp_1.set_samples_values(sdfs_1.reshape(-1, nr_surfs))
+    combined = VolumeRendering.combine_ray_samples_packets(pack_uniform, imp_1, min_dist_between_samples)
+    sdfs_c = combined.samples_values
+    pack_uniform.remove_samples_values()
+    imp_1.remove_samples_values()
+    combined.remove_samples_values()         # (so that imp_2 is created without values, like imp_1)
+    combined.update_dt(False)
+    cdf = sdfs_coarse_cdf(combined, sdfs_c, beta)
+    imp_2 = VolumeRendering.importance_sample(combined, cdf, nr_imp_samples // 2, jitter_samples)
+    return imp_1, imp_2
+
+
+def get_rays_samples_packed_sdfs(rays_o, rays_d, t_near, t_far, sdfs_fn, nr_surfs, logistic_beta_value,
+                                 occupancy_grid=None, iter_nr=None, min_dist_between_samples=1e-4,
+                                 min_nr_samples_per_ray=1, max_nr_samples_per_ray=64, max_nr_imp_samples_per_ray=32,
+                                 jitter_samples=False, importance_sampling=True, values_dim=1):
+    """sdfs_utils.py:435-510 -> (pack with dt, importance pack or None)."""
+    with torch.no_grad():
+        if occupancy_grid is not None:
+            pack = RaySampler.compute_samples_fg_in_grid_occupied_regions(
+                rays_o, rays_d, t_near, t_far, min_dist_between_samples, min_nr_samples_per_ray,
+                max_nr_samples_per_ray, jitter_samples, occupancy_grid.get_nr_voxels_per_dim(),
+                occupancy_grid.get_grid_extent(), occupancy_grid.get_grid_occupancy(), occupancy_grid.get_grid_roi(),
+                values_dim)
+        else:
+            pack = RaySampler.compute_samples_fg(rays_o, rays_d, t_near, t_far, min_dist_between_samples,
+                                                 min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples,
+                                                 values_dim)
+        imp = None
+        if not pack.is_empty():
+            if importance_sampling:
+                imp_1, imp_2 = importance_sampling_sdfs(sdfs_fn, nr_surfs, pack, iter_nr, max_nr_imp_samples_per_ray,
+                                                        logistic_beta_value, min_dist_between_samples, jitter_samples)
+                imp = VolumeRendering.combine_ray_samples_packets(imp_1, imp_2, min_dist_between_samples)
+                pack = VolumeRendering.combine_ray_samples_packets(pack, imp, min_dist_between_samples)
+            pack.update_dt(False)
+    return pack, imp
+
+
+def appearance_rows(model, points, dirs, normals, geom_feat, iter_nr=None):
+    """One appearance model evaluated ONCE over K S rows (surface-major: the points, directions and features
+    repeated, the K surfaces' normals [S,K,3] stacked) -> [S, K, C]: row for row what the reference's K calls
+    model(points, dirs, normals[:, k], geom_feat) give."""
+    S, K = normals.shape[0], normals.shape[1]
+    rep = lambda t: None if t is None else t.repeat(K, 1)
+    out = model(points=rep(points), samples_dirs=rep(dirs), normals=normals.transpose(0, 1).reshape(K * S, 3),
+                iter_nr=iter_nr, geom_feat=rep(geom_feat))
+    return out.reshape(K, S, -1).transpose(0, 1)
+
+
+class OffsetsSurfs(FieldMethod):
+    """methods/offsets_surfs.py:32-1449 (volumetric rendering; the sphere-traced render, the debug-ray plot and colour
+    calibration are not implemented).  models = {"sdfs": OffsetsSDF, "rgb" or "rgb_<i>": RGB / ColorSH (3 channels),
+    "alpha" or "alpha_<i>": RGB / ColorSH (1 channel) or None for a solid inner shell, "bg": NerfHash or None}.
+    Trains through trainer.train_step / train: `method(rays_o, rays_d, gt_rgb, gt_mask, iter_nr)` returns (losses,
+    info, foreground samples or None during the offsets init)."""
+
+    method_name = "offsets_surfs"
+    RENDER_KEYS = ("rgb", "rgb_fg", "bg_transmittance")
+    OCCUPANCY_EVERY = 50                   # update_occupancy_grid_every_nr_iters
+    OCCUPANCY_MAX_VARIANCE = 0.8
+    OCCUPANCY_THRESH = 1e-4
+    OFFSETS_INIT_NR_POINTS = 30000         # offsets_surfs.py:1175
+    NR_RANDOM_POINTS = 1024                # :1264
+    OFFSURFACE_SCALE = 1e2
+    DECAY_START, DECAY_END = 1000.0, 10.0  # alpha_decay_factor over the first phase
+
+    def __init__(self, train, hyper_params, load_checkpoints_path, save_checkpoints_path, bounding_primitive,
+                 models_path, bg_color=None, start_iter_nr=0):
+        hp = hyper_params
+        self.hyper_params = hp
+        self.load_checkpoints_path, self.save_checkpoints_path = load_checkpoints_path, save_checkpoints_path
+        self.bounding_primitive = bounding_primitive
+        self.bg_color = None if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32).cuda().view(1, 3)
+        self.optimizer = self.lr_scheduler = self.scheduler_lr_decay = None
+        self.is_training = bool(train)
+        if models_path is None and start_iter_nr == 0:
+            raise ValueError("models_path must be a folder holding the surf method's sdf.pt")
+        stdev = logistic_distribution_stdev(get_logistic_beta_from_variance(hp.first_phase_variance_start_value))
+        self.delta_surfs = stdev * hp.delta_surfs_multiplier
+        self.offsets_gt = get_offsets_gt(hp.nr_outer_surfs, hp.nr_inner_surfs, self.delta_surfs)
+        bb = bounding_primitive.get_radius() * 2.0
+        self.models = {}
+        sdfs = OffsetsSDF(in_channels=3, mlp_layers_dims=hp.sdf_mlp_layers_dims, encoding_type=hp.sdf_encoding_type,
+                          nr_inner_surfs=hp.nr_inner_surfs, nr_outer_surfs=hp.nr_outer_surfs,
+                          geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=0, bb_sides=bb)
+        self.models["sdfs"] = sdfs
+        self.nr_surfs, self.main_surf_idx = sdfs.nr_surfs, sdfs.main_surf_idx
+        self.nr_inner_surfs, self.nr_outer_surfs = sdfs.nr_inner_surfs, sdfs.nr_outer_surfs
+        self.in_offsets_init = self.in_color_init = self.in_first_phase = self.in_second_phase = False
+        self.just_started_offsets_init = self.just_started_color_init = True
+        self.just_started_first_phase = self.just_started_second_phase = True
+        self.variance = 1.0
+        self.cos_anneal_ratio = 1.0
+        self.with_alpha_decay = hp.with_alpha_decay
+        self.alpha_decay_factor = self.DECAY_START
+        self.occupancy_grid = init_occupancy_grid(bounding_primitive) if hp.use_occupancy_grid else None
+        for i in range(self.nr_surfs):
+            m = self._appearance_model(3, hp.rgb_view_dep, hp.rgb_normal_dep, hp.rgb_geom_feat_dep, bb)
+            if hp.are_surfs_colors_indep:
+                self.models[f"rgb_{i}"] = m
+            else:
+                self.models["rgb"] = m
+                break
+        for i in range(self.nr_surfs):
+            m = None if (hp.is_inner_surf_solid and i == 0) else \
+                self._appearance_model(1, hp.transp_view_dep, hp.transp_normal_dep, hp.transp_geom_feat_dep, bb)
+            if hp.are_surfs_transparency_indep:
+                self.models[f"alpha_{i}"] = m
+            else:
+                self.models["alpha"] = m
+                break
+        self.models["bg"] = NerfHash(in_channels=3, pos_encoder_type=hp.bg_pos_encoder_type,
+                                     dir_encoder_type=hp.bg_dir_encoder_type,
+                                     nr_iters_for_c2f=hp.bg_nr_iters_for_c2f) if self.bg_color is None else None
+        if start_iter_nr > 0:
+            self.load(start_iter_nr)
+        if train:
+            self.init_optim()
+        if models_path is not None and start_iter_nr == 0:
+            ckpt = os.path.join(models_path, "sdf.pt")
+            if not os.path.exists(ckpt):
+                raise FileNotFoundError(f"checkpoint {ckpt} does not exist")
+            sdfs.load_main_sdf_ckpt(ckpt)
+            if self.models["bg"] is not None:
+                ckpt = os.path.join(models_path, "bg.pt")
+                if not os.path.exists(ckpt):
+                    raise FileNotFoundError(f"checkpoint {ckpt} does not exist")
+                self.models["bg"].load_state_dict(torch.load(ckpt, map_location="cuda"))
+        self.update_method_state(start_iter_nr)
+        self.update_occupancy_grid(iter_nr=start_iter_nr)
+
+    def _appearance_model(self, out_channels, view_dep, normal_dep, geom_feat_dep, bb):
+        hp = self.hyper_params
+        if hp.appearance_predict_sh_coeffs:
+            return ColorSH(in_channels=3, out_channels=out_channels, mlp_layers_dims=hp.rgb_mlp_layers_dims,
+                           pos_encoder_type=hp.rgb_pos_encoder_type, sh_deg=hp.sh_degree, normal_dep=normal_dep,
+                           geom_feat_dep=geom_feat_dep, in_geom_feat_size=hp.geom_feat_size,
+                           nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
+        return RGB(in_channels=3, out_channels=out_channels, mlp_layers_dims=hp.rgb_mlp_layers_dims,
+                   pos_encoder_type=hp.rgb_pos_encoder_type, dir_encoder_type=hp.rgb_dir_encoder_type,
+                   sh_deg=hp.sh_degree, view_dep=view_dep, normal_dep=normal_dep, geom_feat_dep=geom_feat_dep,
+                   in_geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
+
+    def parameters(self):
+        return super().parameters() + self.models["sdfs"].heads_parameters()
+
+    # ---- optimisation (offsets_surfs.py:325-385)
+    def collect_opt_params(self):
+        lr, m = self.hyper_params.lr, self.models
+        s = m["sdfs"]
+        groups = [{"params": list(s.pos_encoder.parameters()), "weight_decay": 0.0, "lr": lr, "name": "sdfs_pos_encoder"},
+                  {"params": list(s.mlp_sdf.parameters()), "weight_decay": 0.0, "lr": lr, "name": "sdfs_mlp_sdf"}]
+        for i, h in enumerate(s.mlps_eps):
+            groups.append({"params": list(h.parameters()), "weight_decay": 0.0, "lr": lr, "name": f"sdfs_mlp_eps_{i}"})
+        for key, model in m.items():
+            if ("rgb" in key or "alpha" in key or "bg" in key) and model is not None:
+                groups.append({"params": list(model.parameters()), "weight_decay": 0.0, "lr": lr, "name": key})
+        return [g for g in groups if g["params"]]
+
+    # ---- checkpoints: the reference's sdfs.pt (main surface only) plus sdfs_eps_<i>.pt per head
+    def save(self, iter_nr):
+        path = super().save(iter_nr)
+        if path is not None:
+            for i, sd in enumerate(self.models["sdfs"].heads_state_dicts()):
+                torch.save(sd, os.path.join(path, f"sdfs_eps_{i}.pt"))
+        return path
+
+    def load(self, iter_nr):
+        path = super().load(iter_nr)
+        if path is not None:
+            s = self.models["sdfs"]
+            files = [os.path.join(path, f"sdfs_eps_{i}.pt") for i in range(len(s.mlps_eps))]
+            missing = [f for f in files if not os.path.exists(f)]
+            if missing:
+                raise FileNotFoundError(f"offset head checkpoint(s) {missing} do not exist")
+            s.load_heads_state_dicts([torch.load(f, map_location="cuda") for f in files])
+        return path
+
+    # ---- occupancy grid (offsets_surfs.py:387-418): the full grid, min_k |sdf_k|, decay 0
+    @torch.no_grad()
+    def update_occupancy_grid(self, iter_nr=None, decay=0.0):
+        g = self.occupancy_grid
+        if g is None:
+            return
+        pts, idx = g.get_grid_samples(False)
+        sdfs = [self.models["sdfs"](b, iter_nr=iter_nr)[0] for b in torch.split(pts, 256 * 256 * 100, dim=0)]
+        sdfs = torch.cat(sdfs, 0) if len(sdfs) > 1 else sdfs[0]
+        sdf = torch.min(torch.abs(sdfs.squeeze(-1)), dim=-1, keepdim=True)[0]
+        beta = torch.ones_like(sdf) * get_logistic_beta_from_variance(min(self.OCCUPANCY_MAX_VARIANCE, self.variance))
+        g.update_grid_values(idx, sdf, decay)
+        g.update_grid_occupancy_with_sdf_values(idx, beta, self.OCCUPANCY_THRESH, False)
+
+    def _rebuild_occupancy(self, iter_nr):
+        self.update_occupancy_grid(iter_nr=iter_nr)
+
+    # ---- phases (offsets_surfs.py:1011-1128)
+    def update_method_state(self, iter_nr):
+        hp = self.hyper_params
+        s = self.models["sdfs"]
+        off_end, col_end, first_end = hp.init_phase_end_iter, hp.color_init_phase_end_iter, hp.first_phase_end_iter
+        self.in_offsets_init = iter_nr < off_end
+        self.in_color_init = off_end <= iter_nr < col_end
+        self.in_first_phase = col_end <= iter_nr < first_end
+        self.in_second_phase = iter_nr >= first_end
+        if self.is_training and not self.in_color_init and hp.use_occupancy_grid and \
+                iter_nr % self.OCCUPANCY_EVERY == 0:
+            self.update_occupancy_grid(iter_nr=iter_nr)
+        if self.in_offsets_init and self.is_training and self.just_started_offsets_init:
+            s.freeze_main_surf()
+            self.cos_anneal_ratio, self.alpha_decay_factor = 1.0, self.DECAY_START
+            self.variance = hp.first_phase_variance_start_value
+            self.update_occupancy_grid(iter_nr)
+            self.just_started_offsets_init = False
+        if self.in_color_init and self.is_training and self.just_started_color_init:
+            s.freeze_main_surf()
+            s.freeze_offsets()
+            self.cos_anneal_ratio, self.alpha_decay_factor = 1.0, self.DECAY_START
+            self.variance = hp.first_phase_variance_start_value
+            self.update_occupancy_grid(iter_nr)
+            self.just_started_color_init = False
+        if self.in_first_phase:
+            if self.is_training and self.just_started_first_phase:
+                s.unfreeze_main_surf()
+                s.unfreeze_offsets()
+                self.update_occupancy_grid(iter_nr)
+                if self.lr_scheduler is None and self.scheduler_lr_decay is not None:
+                    from .schedulers import GradualWarmupScheduler
+                    self.lr_scheduler = GradualWarmupScheduler(self.optimizer, multiplier=1,
+                                                               total_epoch=hp.nr_warmup_iters,
+                                                               after_scheduler=self.scheduler_lr_decay)
+                self.just_started_first_phase = False
+            self.cos_anneal_ratio = 1.0
+            self.variance = map_range_val(iter_nr, col_end, first_end, hp.first_phase_variance_start_value,
+                                          hp.first_phase_variance_end_value)
+            self.alpha_decay_factor = map_range_val(iter_nr, col_end, first_end, self.DECAY_START, self.DECAY_END)
+        if self.in_second_phase and self.is_training and self.just_started_second_phase:
+            s.unfreeze_main_surf()
+            s.unfreeze_offsets()
+            self.update_occupancy_grid(iter_nr)
+            self.just_started_second_phase = False
+            self.cos_anneal_ratio = 1.0
+            self.variance = hp.first_phase_variance_end_value
+            self.alpha_decay_factor = self.DECAY_END
+
+    # ---- rendering (offsets_surfs.py:420-1009)
+    def render_appearance(self, samples_3d, dirs, normals, geom_feat, iter_nr=None):
+        """-> (rgb [S,K,3], transparency [S,K,1]): a shared model evaluated once over K S rows, independent models
+        once per surface; a solid inner shell's transparency is 1."""
+        hp = self.hyper_params
+        S, K = samples_3d.shape[0], self.nr_surfs
+        out = []
+        for kind, C, indep in (("rgb", 3, hp.are_surfs_colors_indep), ("alpha", 1, hp.are_surfs_transparency_indep)):
+            ones = lambda: torch.ones(S, C, device=samples_3d.device)
+            if not indep:
+                m = self.models[kind]
+                out.append(appearance_rows(m, samples_3d, dirs, normals, geom_feat, iter_nr) if m is not None
+                           else ones().unsqueeze(1).expand(S, K, C))
+                continue
+            cols = []
+            for i in range(K):
+                m = self.models[f"{kind}_{i}"]
+                cols.append(ones() if m is None else m(points=samples_3d, samples_dirs=dirs, normals=normals[:, i],
+                                                       iter_nr=iter_nr, geom_feat=geom_feat))
+            out.append(torch.stack(cols, 1))
+        return out[0], out[1]
+
+    def _empty_renders(self, N, dev, rgb_bg):
+        K = self.nr_surfs
+        z = lambda *s: torch.zeros(*s, device=dev)
+        r = {"surfs_rgb": z(N, K, 3), "surfs_normals": z(N, K, 3), "surfs_depths": z(N, K, 1),
+             "surfs_weight_sum": z(N, K, 1), "surfs_alpha": z(N, K, 1),
+             "surfs_transmittance": torch.ones(N, K, 1, device=dev), "surfs_blending_weights": z(N, K, 1),
+             "rgb_fg": z(N, 3), "bg_transmittance": torch.ones(N, 1, device=dev),
+             "nr_samples": torch.zeros(N, 1, dtype=torch.int32, device=dev)}
+        r["rgb"] = r["rgb_fg"] if rgb_bg is None else r["rgb_fg"] + rgb_bg * r["bg_transmittance"]
+        return r
+
+    def render_fg_volumetric(self, pack, logistic_beta_value=2048.0, cos_anneal_ratio=1.0, iter_nr=None,
+                             rgb_bg=None):
+        """-> (renders dict, samples_3d, samples_sdfs_grad [S,K,3]).  The sdfs, their features and their
+        finite-difference gradients come from ONE evaluation of the 4-point stencil; `rgb_bg` folds render_rays'
+        blend into the composite launch."""
+        N = pack.get_nr_rays()
+        dev = pack.ray_o.device
+        if pack.is_empty():
+            return self._empty_renders(N, dev, rgb_bg), None, None
+        samples_3d = pack.samples_3d
+        S = samples_3d.shape[0]
+        sdfs_full, _, feat_full = field_stencil(self.models["sdfs"].forward, samples_3d, iter_nr)
+        sdfs, geom_feat = sdfs_full[:S], None if feat_full is None else feat_full[:S]
+        sdfs_grad = stencil_gradients(sdfs_full)                         # [S, K, 3]
+        normals = F.normalize(sdfs_grad, dim=-1)
+        dirs = pack.samples_dirs
+        rgb, transp = self.render_appearance(samples_3d, dirs, normals, geom_feat, iter_nr)
+        decay = float(self.alpha_decay_factor) if self.with_alpha_decay else None
+        r = offsets_composite(pack, sdfs, sdfs_grad, normals.detach(), rgb, transp, rgb_bg, cos_anneal_ratio,
+                              logistic_beta_value, decay)
+        r.pop("alpha")
+        r["nr_samples"] = pack.get_nr_samples_per_ray().view(-1, 1).int()
+        return r, samples_3d, sdfs_grad
+
+    def render_rays(self, rays_o, rays_d, iter_nr=None, override=None, **kwargs):
+        """The reference's dict: {"renders": {"volumetric": {surfs_rgb, surfs_normals, surfs_depths,
+        surfs_weight_sum, surfs_alpha, surfs_transmittance, surfs_blending_weights, nr_samples, rgb_fg,
+        bg_transmittance, rgb_bg, rgb}}, "samples_3d", "samples_grad"}.  `override` takes "variance" and
+        "cos_anneal_ratio"."""
+        hp = self.hyper_params
+        override = override or {}
+        raycast = intersect_bounding_primitive(self.bounding_primitive, rays_o, rays_d)
+        variance = override.get("variance")
+        beta = get_logistic_beta_from_variance(self.variance if variance is None else variance)
+        car = override.get("cos_anneal_ratio")
+        car = self.cos_anneal_ratio if car is None else car
+        pack, _ = get_rays_samples_packed_sdfs(
+            rays_o, rays_d, raycast["t_near"], raycast["t_far"], self.models["sdfs"], self.nr_surfs, beta,
+            self.occupancy_grid, iter_nr, hp.min_dist_between_samples, hp.min_nr_samples_per_ray,
+            hp.max_nr_samples_per_ray, hp.max_nr_imp_samples_per_ray, jitter_samples=self.is_training,
+            importance_sampling=hp.do_importance_sampling)
+        if self.models["bg"] is None:
+            rgb_bg = self.bg_color.expand(raycast["nr_rays"], 3)
+            blend_bg = self.bg_color.view(3)
+        else:
+            bg = render_contracted_bg(self.models["bg"], raycast, nr_samples_bg=hp.nr_samples_bg,
+                                      jitter_samples=self.is_training, iter_nr=iter_nr)
+            rgb_bg = blend_bg = bg["pred_rgb"]
+        renders, samples_3d, samples_grad = self.render_fg_volumetric(pack, beta, car, iter_nr, blend_bg)
+        renders["rgb_bg"] = rgb_bg
+        return {"renders": {"volumetric": renders}, "samples_3d": samples_3d, "samples_grad": samples_grad}
+
+    # ---- training (offsets_surfs.py:1130-1449)
+    def _support(self, grads):
+        return torch.cat((grads[:, :self.main_surf_idx], grads[:, self.main_surf_idx + 1:]), dim=1)
+
+    def _offsets_init_losses(self, iter_nr):
+        s = self.models["sdfs"]
+        with torch.no_grad():
+            pts = self.bounding_primitive.get_random_points_inside(self.OFFSETS_INIT_NR_POINTS)
+        # main_sdf(points) and get_field_gradients(forward, points) share one stencil call (same rows)
+        full_sdfs, _, full_feat = field_stencil(s.forward, pts, iter_nr)
+        grads = stencil_gradients(full_sdfs)
+        feats = full_feat[:pts.shape[0]]
+        off_pos, off_neg, _, _ = s.get_offsets(feats)
+        offsets = torch.cat((off_pos, off_neg), dim=1)
+        gt = self.offsets_gt.to(offsets.device).unsqueeze(0).expand(pts.shape[0], self.nr_surfs - 1)
+        loss_offsets = torch.abs(offsets - gt).mean()
+        loss_supp = eikonal_loss(self._support(grads)) * self.hyper_params.support_surfs_eikonal_weight
+        return loss_offsets + loss_supp, loss_supp
+
+    def forward(self, rays_o, rays_d, gt_rgb, gt_mask=None, iter_nr=0, is_first_iter=False, is_training_masked=None,
+                **kwargs):
+        hp = self.hyper_params
+        masked = hp.is_training_masked if is_training_masked is None else is_training_masked
+        s = self.models["sdfs"]
+        loss = torch.zeros((), device="cuda", requires_grad=True)
+        loss_curv = loss_eik_main = loss_eik_supp = loss_offsurface = loss_rgb = loss_mask = 0.0
+        self.update_method_state(iter_nr)
+        samples_3d = None
+        if self.in_offsets_init:
+            if self.nr_surfs > 1 and s.is_training_offsets:
+                loss, loss_eik_supp = self._offsets_init_losses(iter_nr)
+        else:
+            res = self.render_rays(rays_o, rays_d, iter_nr=iter_nr)
+            vol = res["renders"]["volumetric"]
+            samples_3d, s_grad = res["samples_3d"], res["samples_grad"]
+            pred_rgb = vol["rgb"]
+            R = hp.nr_training_rays_per_pixel
+            if R > 1:
+                pred_rgb = pred_rgb.view(-1, R, 3).mean(dim=1)
+            loss_rgb = loss_l1(gt_rgb, pred_rgb, mask=gt_mask) if masked else loss_l1(gt_rgb, pred_rgb)
+            loss = loss_rgb
+            with torch.no_grad():
+                r_pts = self.bounding_primitive.get_random_points_inside(self.NR_RANDOM_POINTS)
+            r_full = field_stencil(s.forward, r_pts, iter_nr)[0]
+            r_sdfs, r_grad = r_full[:r_pts.shape[0]], stencil_gradients(r_full)
+            has_samples = samples_3d is not None and samples_3d.shape[0] > 0
+            main = self.main_surf_idx
+            if hp.eikonal_weight > 0.0 and s.is_training_main_surf:
+                loss_eik_main = eikonal_loss(r_grad[:, main]) * hp.eikonal_weight
+                if has_samples:
+                    loss_eik_main = loss_eik_main + eikonal_loss(s_grad[:, main]) * hp.eikonal_weight
+                loss = loss + loss_eik_main
+            if hp.eikonal_weight > 0.0 and hp.support_surfs_eikonal_weight > 0.0 and s.is_training_offsets and \
+                    self.nr_surfs > 1:
+                loss_eik_supp = eikonal_loss(self._support(r_grad)) * hp.support_surfs_eikonal_weight
+                if has_samples:
+                    loss_eik_supp = loss_eik_supp + eikonal_loss(self._support(s_grad)) * hp.support_surfs_eikonal_weight
+                loss = loss + loss_eik_supp
+            if hp.offsurface_weight > 0.0:
+                loss_offsurface = torch.exp(-self.OFFSURFACE_SCALE * torch.abs(r_sdfs[:, main])).mean() * \
+                    hp.offsurface_weight
+                loss = loss + loss_offsurface
+            if hp.curvature_weight > 0.0 and has_samples:
+                curv = get_sdfs_curvature(s, samples_3d, s_grad, torch.randn_like(samples_3d), iter_nr=iter_nr)
+                loss_curv = curv.mean() * hp.curvature_weight
+                loss = loss + loss_curv
+        losses = {"loss": loss, "curvature": loss_curv, "eikonal_main": loss_eik_main, "eikonal_supp": loss_eik_supp,
+                  "loss_offsurface_high_sdf": loss_offsurface, "rgb": loss_rgb, "mask": loss_mask}
+        info = {"stdev": logistic_distribution_stdev(get_logistic_beta_from_variance(self.variance))}
+        return losses, info, samples_3d
