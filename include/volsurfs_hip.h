@@ -1358,6 +1358,46 @@ long long vsa_atlas_rasterize_workspace_bytes(long long nr_faces);
 int vsa_atlas_rasterize(const float* faces_uvs, long long nr_faces, int resolution, void* workspace,
                         long long workspace_bytes, int32_t* out_face_id, int32_t* out_count, void* stream);
 
+/* ---- sphere tracing (volsurfs_py/utils/sphere_tracing.py:112-152; csrc/sphere_trace.hip) ----
+ * The round bookkeeping around an SDF that the host evaluates between the calls.  An item is one (ray, slot) pair,
+ * item = slot * nr_rays + ray, M = nr_rays * nr_slots items (M + 256 < 2^31); slot s reads column slot_cols[s] of the
+ * [rows, nr_columns] SDF block.  Buffers: pts [M,3] f32 (every item's current point), flags [M] u8 (bit 0 hit, bit 1
+ * done), two live lists [M] i32 and two dense point blocks [M,3] f32 (ping-pong), keep [M] u8, block_counts
+ * [ceil(M / 256)] i32, one i32 live count per round.
+ *   vsa_st_begin   every item starts at its ray's points_near [N,3] row, flags 0, live = 0..M-1 ascending, dense = the
+ *                  points, *count = M.
+ *   vsa_st_step    one round.  `bound` (host) >= the device's *count_in: rows [0, *count_in) of `sdf` belong to the
+ *                  live items live_in[j], in ascending item order; rows up to `bound` are padding and are not read.
+ *                  Per live item, fp32 without contraction: p += d * (sdf * sdf_multiplier); newly = |sdf| < thresh;
+ *                  hit |= newly; done |= newly; done |= !inside(p), inside = the closed test of the origin-centred cube
+ *                  of HALF side `size` (kind 0) or sphere of radius `size` (kind 1).  Then the items that are not done,
+ *                  in ascending item order, to live_out, their points to rows [0, *count_out) of dense_out; rows
+ *                  [*count_out, bound) of dense_out take the same rows of dense_in.  Two launches (step, ordered
+ *                  compaction); no atomics: the same inputs give the same bytes.
+ *   vsa_st_finish  z [M] = ||p - rays_o[ray]||, hit [M] u8 = the hit flag (or not done, when unconverged_are_hits),
+ *                  hit_list = the hit items in ascending order, *hit_count their number.
+ *   vsa_st_scatter dst[(item % N) * S + item / N, :] = src[h, :] for item = ids[h], h < nr_ids (host), rows of
+ *                  nr_channels f32.
+ *   vsa_st_blend   methods/offsets_surfs.py:810-858 for surfs_rgb [N,K,3] and surfs_alpha [N,K,1], surfaces inner to
+ *                  outer: surfs_transmittance, surfs_blending_weights [N,K,1], rgb_fg [N,3], bg_transmittance [N,1];
+ *                  one thread per ray, the K products taken one after the other from the outer shell inwards and the
+ *                  sum over the surfaces as four interleaved partial sums (torch's device orders: bit-identical). */
+int vsa_st_begin(const float* points_near, int nr_rays, int nr_slots, float* pts, uint8_t* flags, int32_t* live,
+                 float* dense, int32_t* count, void* stream);
+int vsa_st_step(const int32_t* live_in, const int32_t* count_in, const float* sdf, int nr_columns,
+                const int32_t* slot_cols, int nr_rays, const float* rays_d, float sdf_multiplier, float thresh,
+                int kind, float size, float* pts, uint8_t* flags, uint8_t* keep, int32_t* block_counts,
+                const float* dense_in, int32_t* live_out, float* dense_out, int32_t* count_out, int bound,
+                void* stream);
+int vsa_st_finish(const float* pts, const float* rays_o, int nr_rays, int nr_slots, const uint8_t* flags,
+                  int unconverged_are_hits, float* z, uint8_t* hit, uint8_t* keep, int32_t* block_counts,
+                  int32_t* hit_list, int32_t* hit_count, void* stream);
+int vsa_st_scatter(const int32_t* ids, long long nr_ids, const float* src, int nr_channels, int nr_rays,
+                   int nr_slots, float* dst, void* stream);
+int vsa_st_blend(const float* surfs_rgb, const float* surfs_alpha, int nr_rays, int nr_surfs,
+                 float* surfs_transmittance, float* surfs_blending_weights, float* rgb_fg, float* bg_transmittance,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

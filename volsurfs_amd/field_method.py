@@ -78,29 +78,44 @@ class FieldMethod:
         return path
 
     # ---- full frames (base_method.py:366-541)
+    RENDER_MODES = ("volumetric",)     # a method with a sphere-traced render adds "sphere_traced"
+
     @torch.no_grad()
-    def render(self, rays_o, rays_d, nr_rays_per_pixel=1, chunk=None):
+    def render(self, rays_o, rays_d, nr_rays_per_pixel=1, chunk=None, render_mode="volumetric"):
+        """`render_mode` picks the entry of render_rays' "renders" (utils/evaluation.py:95's render-mode folders);
+        "sphere_traced" sets `render_sphere_traced` for the call."""
+        if render_mode not in self.RENDER_MODES:
+            raise ValueError(f"{type(self).__name__}: render_mode {render_mode!r} is not one of {self.RENDER_MODES}")
+        if render_mode == "sphere_traced" and self.is_training:
+            raise ValueError("the sphere-traced render runs outside training only (render_camera sets that)")
         chunk = int(chunk or self.hyper_params.test_rays_batch_size)
         keys = self.RENDER_KEYS
         outs = {k: [] for k in keys}
-        for a in range(0, rays_o.shape[0], chunk):
-            v = self.render_rays(rays_o[a:a + chunk], rays_d[a:a + chunk])["renders"]["volumetric"]
-            for k in keys:
-                outs[k].append(v[k])
+        was =getattr(self, "render_sphere_traced", False)
+        if render_mode == "sphere_traced":
+            self.render_sphere_traced = True
+        try:
+            for a in range(0, rays_o.shape[0], chunk):
+                v = self.render_rays(rays_o[a:a + chunk], rays_d[a:a + chunk])["renders"][render_mode]
+                for k in keys:
+                    outs[k].append(v[k])
+        finally:
+            if render_mode == "sphere_traced":
+                self.render_sphere_traced = was
         full = {k: torch.cat(v, 0) for k, v in outs.items()}
         if nr_rays_per_pixel > 1:
             full = {k: v.reshape(-1, nr_rays_per_pixel, v.shape[-1]).mean(1) for k, v in full.items()}
         return full
 
     @torch.no_grad()
-    def render_camera(self, camera, nr_rays_per_pixel=1, jitter_pixels=False, chunk=None):
+    def render_camera(self, camera, nr_rays_per_pixel=1, jitter_pixels=False, chunk=None, render_mode="volumetric"):
         """{key: [H, W, C]} of one camera (what evaluation.render_and_eval scores: "rgb")."""
         from .camera import get_camera_rays
         was = self.is_training
         self.is_training = False
         try:
             rays_o, rays_d, _ = get_camera_rays(camera, nr_rays_per_pixel, jitter_pixels)
-            full = self.render(rays_o, rays_d, nr_rays_per_pixel, chunk)
+            full = self.render(rays_o, rays_d, nr_rays_per_pixel, chunk, render_mode)
         finally:
             self.is_training = was
         return {k: v.reshape(camera.height, camera.width, v.shape[-1]) for k, v in full.items()}

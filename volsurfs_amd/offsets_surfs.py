@@ -289,14 +289,17 @@ def appearance_rows(model, points, dirs, normals, geom_feat, iter_nr=None):
 
 
 class OffsetsSurfs(FieldMethod):
-    """methods/offsets_surfs.py:32-1449 (volumetric rendering; the sphere-traced render, the debug-ray plot and colour
-    calibration are not implemented).  models = {"sdfs": OffsetsSDF, "rgb" or "rgb_<i>": RGB / ColorSH (3 channels),
+    """methods/offsets_surfs.py:32-1449 (volumetric rendering, and the sphere-traced render of the K surfaces when
+    `render_sphere_traced` is set; the debug-ray plot and colour calibration are not implemented).  models = {"sdfs": OffsetsSDF, "rgb" or "rgb_<i>": RGB / ColorSH (3 channels),
     "alpha" or "alpha_<i>": RGB / ColorSH (1 channel) or None for a solid inner shell, "bg": NerfHash or None}.
     Trains through trainer.train_step / train: `method(rays_o, rays_d, gt_rgb, gt_mask, iter_nr)` returns (losses,
     info, foreground samples or None during the offsets init)."""
 
     method_name = "offsets_surfs"
     RENDER_KEYS = ("rgb", "rgb_fg", "bg_transmittance")
+    RENDER_MODES = ("volumetric", "sphere_traced")
+    render_sphere_traced = False           # render_rays adds renders["sphere_traced"] outside training
+    SPHERE_TRACED_MAX_STEPS, SPHERE_TRACED_THRESH = 100, 1e-3    # render_rays' call (offsets_surfs.py:955-961)
     OCCUPANCY_EVERY = 50                   # update_occupancy_grid_every_nr_iters
     OCCUPANCY_MAX_VARIANCE = 0.8
     OCCUPANCY_THRESH = 1e-4
@@ -540,11 +543,66 @@ class OffsetsSurfs(FieldMethod):
         r["nr_samples"] = pack.get_nr_samples_per_ray().view(-1, 1).int()
         return r, samples_3d, sdfs_grad
 
+    def _surface_model(self, kind, indep, i):
+        return self.models[f"{kind}_{i}"] if indep else self.models[kind]
+
+    @torch.no_grad()
+    def render_fg_sphere_traced(self, raycast, max_st_steps, converged_dist_tresh, iter_nr=None):
+        """offsets_surfs.py:687-890 -> (renders, samples_3d, samples_sdf, samples_sdf_grad); renders = surfs_rgb
+        [N,K,3], surfs_alpha, surfs_depths [N,K,1], surfs_normals [N,K,3], surfs_transmittance,
+        surfs_blending_weights [N,K,1] (surfaces inner to outer), rgb_fg [N,3], bg_transmittance [N,1].  The K
+        surfaces are traced as one batch of N K items (sphere_trace_columns' loop: an int surf_idx of the reference
+        read as that column); the hits of all surfaces share one stencil evaluation, a shared appearance model one
+        call; the blend is one launch.  The samples are the hits surface after surface, inner first."""
+        from .sphere_trace import _trace, blend_surfaces, scatter_rows
+        hp = self.hyper_params
+        N, K, rays_d = raycast["nr_rays"], self.nr_surfs, raycast["rays_d"]
+        dev = rays_d.device
+        res = _trace(self.models["sdfs"], raycast["rays_o"], rays_d, raycast["points_near"],
+                     self.bounding_primitive, list(range(K)), max_st_steps, converged_dist_tresh, 1.0, iter_nr, False)
+        per_slot = res.hits_per_slot()
+        H = sum(per_slot)
+        z = lambda c: torch.zeros(N, K, c, device=dev)
+        surfs_rgb, surfs_alpha, surfs_depths, surfs_normals = z(3), z(1), z(1), z(3)
+        samples_3d = samples_sdf = samples_grad = None
+        if H > 0:
+            items = res.hit_items[:H].long()
+            slot, ray = items // N, items % N
+            samples_3d = res.points.reshape(N * K, 3).index_select(0, items)
+            dirs = rays_d.index_select(0, ray)
+            sdfs_full, _, feat_full = field_stencil(self.models["sdfs"].forward, samples_3d, iter_nr)
+            samples_sdf = sdfs_full[:H]
+            feat = None if feat_full is None else feat_full[:H]
+            grads_all = stencil_gradients(sdfs_full).reshape(H, K, 3)
+            samples_grad = grads_all[torch.arange(H, device=dev), slot]
+            normals = F.normalize(samples_grad, dim=1)
+            ends = np.cumsum([0] + per_slot)
+            rows = {}
+            for kind, C, indep in (("rgb", 3, hp.are_surfs_colors_indep), ("alpha", 1, hp.are_surfs_transparency_indep)):
+                spans = [(ends[i], ends[i + 1], i) for i in range(K)] if indep else [(0, H, 0)]
+                out = torch.ones(H, C, device=dev)
+                for a, b, i in spans:
+                    m = self._surface_model(kind, indep, i)
+                    if m is not None and b > a:
+                        out[a:b] = m(points=samples_3d[a:b], samples_dirs=dirs[a:b], normals=normals[a:b],
+                                     iter_nr=iter_nr, geom_feat=None if feat is None else feat[a:b])
+                rows[kind] = out
+            sc = lambda r: scatter_rows(res.hit_items, H, r, N, K).reshape(N, K, -1)
+            surfs_rgb, surfs_alpha, surfs_normals = sc(rows["rgb"]), sc(rows["alpha"]), sc(normals)
+            surfs_depths = sc(res.z.reshape(N * K).index_select(0, items).unsqueeze(1))
+        T, w, rgb_fg, bg_T = blend_surfaces(surfs_rgb, surfs_alpha)
+        renders = {"surfs_rgb": surfs_rgb, "surfs_alpha": surfs_alpha, "surfs_depths": surfs_depths,
+                   "surfs_normals": surfs_normals, "surfs_transmittance": T, "surfs_blending_weights": w,
+                   "rgb_fg": rgb_fg, "bg_transmittance": bg_T}
+        return renders, samples_3d, samples_sdf, samples_grad
+
     def render_rays(self, rays_o, rays_d, iter_nr=None, override=None, **kwargs):
         """The reference's dict: {"renders": {"volumetric": {surfs_rgb, surfs_normals, surfs_depths,
         surfs_weight_sum, surfs_alpha, surfs_transmittance, surfs_blending_weights, nr_samples, rgb_fg,
         bg_transmittance, rgb_bg, rgb}}, "samples_3d", "samples_grad"}.  `override` takes "variance" and
-        "cos_anneal_ratio"."""
+        "cos_anneal_ratio".  With `render_sphere_traced` set and outside training, "renders" also holds
+        "sphere_traced": render_fg_sphere_traced's entries (100 rounds, 1e-3) with rgb_bg and rgb = rgb_fg +
+        bg_transmittance rgb_bg (the reference has this blend commented out, which leaves the entry without `rgb`)."""
         hp = self.hyper_params
         override = override or {}
         raycast = intersect_bounding_primitive(self.bounding_primitive, rays_o, rays_d)
@@ -566,7 +624,14 @@ class OffsetsSurfs(FieldMethod):
             rgb_bg = blend_bg = bg["pred_rgb"]
         renders, samples_3d, samples_grad = self.render_fg_volumetric(pack, beta, car, iter_nr, blend_bg)
         renders["rgb_bg"] = rgb_bg
-        return {"renders": {"volumetric": renders}, "samples_3d": samples_3d, "samples_grad": samples_grad}
+        all_renders = {"volumetric": renders}
+        if self.render_sphere_traced and not self.is_training:
+            st = self.render_fg_sphere_traced(raycast, self.SPHERE_TRACED_MAX_STEPS, self.SPHERE_TRACED_THRESH,
+                                              iter_nr)[0]
+            st["rgb_bg"] = rgb_bg
+            st["rgb"] = st["rgb_fg"] + st["bg_transmittance"] * rgb_bg
+            all_renders["sphere_traced"] = st
+        return {"renders": all_renders, "samples_3d": samples_3d, "samples_grad": samples_grad}
 
     # ---- training (offsets_surfs.py:1130-1449)
     def _support(self, grads):

@@ -339,14 +339,18 @@ def get_rays_samples_packed_sdf(rays_o, rays_d, t_near, t_far, sdf_fn, logistic_
 
 
 class Surf(FieldMethod):
-    """methods/surf.py:34-1128 (volumetric rendering; the sphere-traced render, the Lipschitz MLP, colour
-    calibration and train_appearance_only are not implemented).  models = {"sdf": SDF, "rgb": ColorSH or RGB,
+    """methods/surf.py:34-1128 (volumetric rendering, and the sphere-traced render of the zero level set when
+    `render_sphere_traced` is set; the Lipschitz MLP, colour calibration and train_appearance_only are not
+    implemented).  models = {"sdf": SDF, "rgb": ColorSH or RGB,
     "bg": NerfHash or None (with a constant bg_color [3])}; the occupancy grid of init_occupancy_grid.  Trains
     through trainer.train_step / train: `method(rays_o, rays_d, gt_rgb, gt_mask, iter_nr)` returns (losses, info,
     foreground samples or None during the sphere init)."""
 
     method_name = "surf"
     RENDER_KEYS = FieldMethod.RENDER_KEYS + ("normals",)
+    RENDER_MODES = ("volumetric", "sphere_traced")
+    render_sphere_traced = False           # render_rays adds renders["sphere_traced"] outside training
+    SPHERE_TRACED_MAX_STEPS, SPHERE_TRACED_THRESH = 100, 1e-3    # render_rays' call (surf.py:735-741)
     OCCUPANCY_EVERY = 50                   # update_method_state (surf.py:804-808)
     OCCUPANCY_MAX_VARIANCE = 0.8           # update_occupancy_grid (surf.py:286-299)
     OCCUPANCY_THRESH = 1e-4
@@ -488,10 +492,45 @@ class Surf(FieldMethod):
              "nr_samples": pack.get_nr_samples_per_ray().view(-1, 1).int()}
         return r, samples_3d, sdf_grad
 
+    @torch.no_grad()
+    def render_fg_sphere_traced(self, raycast, max_st_steps, converged_dist_tresh, iter_nr=None):
+        """surf.py:551-645 -> (renders, points of the hits [H,3] or None, samples_sdf_grad [N,3]); renders = rgb_fg,
+        depth_fg, weights_sum (1 on a hit), bg_transmittance, normals.  The zero level set is found by
+        sphere_trace's rounds; the hits' features and finite-difference gradient come from ONE evaluation of the
+        4-point stencil, their colour from models["rgb"] with the ray direction, the normal and the feature."""
+        from .sphere_trace import _trace, scatter_rows
+        N, rays_d = raycast["nr_rays"], raycast["rays_d"]
+        res = _trace(self.models["sdf"].main_sdf, raycast["rays_o"], rays_d, raycast["points_near"],
+                     self.bounding_primitive, [None], max_st_steps, converged_dist_tresh, 1.0, iter_nr, False)
+        H = res.hits_per_slot()[0]
+        hit = res.hit[0]
+        weights_sum = hit.float().unsqueeze(1)
+        dev = rays_d.device
+        zeros = lambda c: torch.zeros(N, c, device=dev)
+        points, normals, grads, depth, rgb_fg = None, zeros(3), zeros(3), zeros(1), zeros(3)
+        if H > 0:
+            items = res.hit_items[:H].long()
+            points = res.points[0].index_select(0, items)
+            sdf_full, feat_full = field_stencil(self.models["sdf"].main_sdf, points, iter_nr)
+            grad_hit = stencil_gradients(sdf_full)
+            normals_hit = F.normalize(grad_hit, dim=1)
+            rgb_hit = self.models["rgb"](points=points, samples_dirs=rays_d.index_select(0, items),
+                                         normals=normals_hit, iter_nr=iter_nr,
+                                         geom_feat=None if feat_full is None else feat_full[:H])
+            sc = lambda rows: scatter_rows(res.hit_items, H, rows, N)
+            normals, grads, rgb_fg = sc(normals_hit), sc(grad_hit), sc(rgb_hit)
+            depth = sc(res.z[0].index_select(0, items).unsqueeze(1))
+        renders = {"rgb_fg": rgb_fg, "depth_fg": depth, "weights_sum": weights_sum,
+                   "bg_transmittance": 1 - weights_sum, "normals": normals}
+        return renders, points, grads
+
     def render_rays(self, rays_o, rays_d, iter_nr=None, override=None, **kwargs):
         """The reference's dict: {"renders": {"volumetric": {rgb, rgb_fg, rgb_bg, depth_fg, depth_bg, depth,
         weights_sum, bg_transmittance, normals, nr_samples}}, "samples_3d", "samples_grad"}.  `override` takes
-        "variance", "cos_anneal_ratio" and "view_dir"."""
+        "variance", "cos_anneal_ratio" and "view_dir".  With `render_sphere_traced` set and outside training,
+        "renders" also holds "sphere_traced": render_fg_sphere_traced's entries (100 rounds, 1e-3) with rgb_bg,
+        depth_bg and rgb = rgb_fg + bg_transmittance rgb_bg, depth composed as the volumetric entry's (the
+        reference computes this render and has the blend commented out, which leaves it without an `rgb`)."""
         hp = self.hyper_params
         override = override or {}
         raycast = intersect_bounding_primitive(self.bounding_primitive, rays_o, rays_d)
@@ -515,7 +554,15 @@ class Surf(FieldMethod):
         renders["rgb_bg"] = rgb_bg
         renders["depth_bg"] = depth_bg
         renders["depth"] = renders["depth_fg"] * renders["weights_sum"] + depth_bg * renders["bg_transmittance"]
-        return {"renders": {"volumetric": renders}, "samples_3d": samples_3d, "samples_grad": samples_grad}
+        all_renders = {"volumetric": renders}
+        if self.render_sphere_traced and not self.is_training:
+            st, _, _ = self.render_fg_sphere_traced(raycast, self.SPHERE_TRACED_MAX_STEPS, self.SPHERE_TRACED_THRESH,
+                                                    iter_nr)
+            st["rgb_bg"], st["depth_bg"] = rgb_bg, depth_bg
+            st["rgb"] = st["rgb_fg"] + st["bg_transmittance"] * rgb_bg
+            st["depth"] = st["depth_fg"] * st["weights_sum"] + depth_bg * st["bg_transmittance"]
+            all_renders["sphere_traced"] = st
+        return {"renders": all_renders, "samples_3d": samples_3d, "samples_grad": samples_grad}
 
     # ---- training (surf.py:866-1128)
     def _sphere_init_losses(self):
