@@ -1398,6 +1398,78 @@ int vsa_st_blend(const float* surfs_rgb, const float* surfs_alpha, int nr_rays, 
                  float* surfs_transmittance, float* surfs_blending_weights, float* rgb_fg, float* bg_transmittance,
                  void* stream);
 
+/* ---- texture bake (volsurfs_py/utils/texture_extraction.py: extract_texture_from_color_model, dilate_texture;
+ *      csrc/texture_bake.hip) ----
+ * Turns an appearance model that is a 3-D field into a texture [R, R, C] over a mesh's UV atlas.  The model stays the
+ * host's (a Python callable evaluated between vsa_tb_emit and vsa_tb_resolve); the sampling, the ownership of texels,
+ * the ordered list of rows the model is evaluated on and the mean per texel are here.
+ *   faces_uvs [F, 3, 2] f32 per-corner UVs in [0, 1]; verts [V, 3] f32; faces [F, 3] i32 (indices in [0, V): the caller
+ *   checks; volsurfs_amd/texture_bake.py does).  R in [1, 8192] texels a side, S in [1, 64] samples per texel, R^2 S < 2^31, F < 2^31 - 256.
+ * Texel (ix, iy), ix along u and iy along v, has index t = ix R + iy: the texture is [ix, iy, c], the reference's layout.
+ * Rules (fp32, in the order written, no contraction; tests/texture_bake_restated.py restates them in torch and the
+ * kernels are held to it bit for bit):
+ *   box       face f visits ix in [floor(min_u R), ceil(max_u R)), iy likewise with v, both clamped to [0, R] (min / max
+ *             over its three corners, the product in fp32).
+ *   samples   sample 0 of a texel is its centre ((float)ix / (float)R + h, (float)iy / (float)R + h), h = (float)(1.0 /
+ *             (2.0 R)) (the reference's `ix / R + 1 / (2 R)`).  Sample s in 1 .. S-1 is centre + ((r - 0.5f) - 1e-6f) /
+ *             (float)R per axis.  r = r(seed, f, t, s, axis) is counter based (the reference draws from torch's global
+ *             generator): with M = 0x5851f42d4c957f2d, I = 1442695040888963407 and 64-bit unsigned wrap-around,
+ *               h = (seed + f + 1) M;  h ^= h >> 32;  h = (h + ((t S + s) 2 + axis) + 1) M;  h ^= h >> 32;  h = h M + I;
+ *               x = (uint32)(((h >> 18) ^ h) >> 27);  k = h >> 59;  o = (x >> k) | (x << ((32 - k) & 31))  (PCG32's
+ *               output of state h, csrc/pcg32.h);  r = bits_as_float((o >> 9) | 0x3f800000) - 1.0f in [0, 1).
+ *             So a sample depends on nothing but its key, and S = 1 draws no number.
+ *   inside    with (p1, p2, p3) the face's corner UVs: v0 = p3 - p1, v1 = p2 - p1, v2 = p - p1; dotab = va.x vb.x +
+ *             va.y vb.y; inv = 1.0f / (dot00 dot11 - dot01 dot01); b2 = (dot11 dot02 - dot01 dot12) inv; b1 = (dot00
+ *             dot12 - dot01 dot02) inv; b0 = (1.0f - b1) - b2.  Inside: b0, b1, b2 >= 0 and |((b0 + b1) + b2) - 1.0f| <
+ *             1e-6f.  A face whose denominator is 0 or not finite has no inside sample (the reference's NaN / inf
+ *             barycentrics fail the test the same way, except a few inf cases that are not reproduced).
+ *   owner     a texel is covered by f when one of its S samples for f is inside; its owner is the HIGHEST such f (the
+ *             reference writes faces in ascending order, each over the last), -1 when none.  (vsa_atlas_rasterize
+ *             reports the lowest face under another fill rule: it is not this map.)
+ *   rows      the owner's inside samples of every covered texel, ordered by t and then by s: point = (b0 A + b1 B) +
+ *             b2 C per component for the face's vertices A, B, C; normal = n / max(sqrt((nx nx + ny ny) + nz nz), 1e-12)
+ *             with n = (B - A) x (C - A) = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), the same for all
+ *             the face's rows.  row_start [R^2 + 1] i32: rows of texel t are [row_start[t], row_start[t + 1]).
+ *   mean      texture[t, c] = (vals[r0, c] + vals[r0 + 1, c] + ...) / (float)count, summed from the first row on;
+ *             texels without rows are not written (the caller zeroes the texture).
+ * vsa_tb_samples: boxes -> a one-block scan of the box sizes -> one thread per (face, texel of its box) pair, by binary
+ *   search in the scanned sizes, over a fixed grid that strides to the device's pair total (work is proportional to the
+ *   summed box areas, whatever the spread of the faces' sizes; atomicMax on owner, the only atomic besides the error
+ *   flag) -> per texel the 64-bit inside mask of its owner and the rows per 256 texels -> a one-block scan of those ->
+ *   the plan.  Six launches and two memsets whatever F; nothing is read back.  ctl [ctl_len >= 4 + 2 (max_chunks + 1)]
+ *   i32 receives [0] the number of rows M, [1] the number of chunks n (-1: the table overflowed), [2] bit 0 set when a UV
+ *   is NaN, inf or outside [0, 1] (then nothing is baked: owner is -1 everywhere and M = 0), [4 + 2 c] the first texel
+ *   of chunk c and [5 + 2 c] its first row, entry n being (R^2, M): chunk c is the longest run of texels from its first
+ *   whose rows number <= chunk_rows (chunk_rows >= S), so chunks never split a texel's rows.  owner [R, R] i32.
+ *   vsa_tb_max_chunks bounds n: R^2 S / (chunk_rows - S + 1) + 2, VSA_ERR_ARG when that exceeds 2^20 (the plan walks the
+ *   chunks on one thread).
+ *   workspace: vsa_tb_workspace_bytes(F, R) = 12 bytes per face and 8 per texel plus 12 per 256 texels, kept for
+ *   vsa_tb_emit.
+ * vsa_tb_emit: row_start, points [M, 3] and normals [M, 3] by an ordered compaction (block offsets from the scan, a
+ *   shuffle scan inside the block); same arguments and workspace as the vsa_tb_samples call before it.
+ * vsa_tb_resolve: the mean of the texels [texel_begin, texel_end) from vals [rows, C], whose first row is row
+ *   row_start[texel_begin].
+ * vsa_tb_dilate: dilate_texture on img [H, W, C] in place.  A pixel is full when all its channels are != 0, empty when
+ *   all are == 0, and never a source or a destination otherwise.  Iteration 1's sources are the full pixels, iteration
+ *   i's the pixels filled in iteration i - 1; an empty pixel with a source among its 8 neighbours copies the first one
+ *   in the order (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1) of (row, column) offsets (the source the
+ *   reference's np.unique keeps).  stamp [H W] i32 (the iteration that filled a pixel: a gather, race-free in place)
+ *   and filled [nr_iterations + 1] i32 are scratch; once an iteration fills nothing the remaining launches return at
+ *   once (the reference's early stop), nr_iterations + 1 launches, at most 4097.
+ * VSA_ERR_ARG: a NULL pointer, a size outside the ranges above, chunk_rows < S, a workspace or ctl smaller than asked. */
+long long vsa_tb_workspace_bytes(long long nr_faces, int resolution);
+long long vsa_tb_max_chunks(int resolution, int nr_samples, long long chunk_rows);
+int vsa_tb_samples(const float* faces_uvs, long long nr_faces, int resolution, int nr_samples,
+                   unsigned long long seed, long long chunk_rows, void* workspace, long long workspace_bytes,
+                   int32_t* owner, int32_t* ctl, int ctl_len, void* stream);
+int vsa_tb_emit(const float* verts, const int32_t* faces, const float* faces_uvs, long long nr_faces, int resolution,
+                int nr_samples, unsigned long long seed, const void* workspace, long long workspace_bytes,
+                const int32_t* owner, int32_t* row_start, float* points, float* normals, void* stream);
+int vsa_tb_resolve(const float* vals, int nr_channels, const int32_t* row_start, int texel_begin, int texel_end,
+                   int resolution, float* texture, void* stream);
+int vsa_tb_dilate(float* img, int height, int width, int nr_channels, int nr_iterations, int32_t* stamp,
+                  int32_t* filled, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
