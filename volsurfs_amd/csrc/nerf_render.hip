@@ -1,22 +1,24 @@
 // The two per-ray chains of the NeRF method (volsurfs_py/methods/nerf.py, utils/nerf_utils.py)
 // that the reference runs as long sequences of single ops on every ray of every iteration, fused
-// into one launch each.
-//
-// Layout as in packed.hip: a ray is owned by a 32-lane half-wave, lanes = consecutive samples
-// (coalesced rows), segmented scans / reductions by shuffles (ray_scan.h), chunks of 32 samples
-// with a carried running value for longer rays.  No atomics: every output element has exactly one
-// writer, so the output bits depend only on the inputs.  Every fp32 operation is the one the single-op chain
-// performs, in its order (the build has -ffp-contract=off): the scans and reductions below are the
-// ones of packed.hip's cumprod / cumsum / integrate / sum_over_rays / compute_cdf kernels, so the
-// results are bit-identical to that chain (tests/test_nerf_render.py).
-#include "ray_scan.h"
+// into one launch each.  The half-wave layout, the sweeps and the order of their fp32 operations
+// are ray_sweep.h's; this file holds what is the NeRF method's: its alpha and what it accumulates.
+#include "ray_sweep.h"
 
 namespace {
 
-constexpr int NR_BLOCK = 256;
 using namespace vsa_ray;
 
-#define NR_RAY_PROLOGUE() VSA_RAY_PROLOGUE(NR_BLOCK)
+// alpha = 1 - exp(-density dt) of one sample, with the e its backward multiplies by
+struct NerfAlpha {
+  float e, alpha;
+};
+__device__ __forceinline__ float alpha_value(const NerfAlpha& a) { return a.alpha; }
+__device__ __forceinline__ NerfAlpha nerf_alpha(float density, float dt) {
+  NerfAlpha a;
+  a.e = expf((-density) * dt);
+  a.alpha = 1.0f - a.e;
+  return a;
+}
 
 // Forward.  Per ray, with w_i = alpha_i T_i:
 //   rgb_fg_d = sum_i w_i rgb_id   lane-strided partial sums over i = l, l + 32, .. then the
@@ -34,27 +36,20 @@ __global__ void nerf_composite_fwd_kernel(const int* __restrict__ start_end,
                                           float* __restrict__ wsum_out,
                                           float* __restrict__ depth_out,
                                           float* __restrict__ weights, int N) {
-  NR_RAY_PROLOGUE();
+  RAY_PROLOGUE();
   float acc[3] = {0.f, 0.f, 0.f};
   float accz = 0.f, ws = 0.f;
-  float carry = 1.0f;
-  for (int c = 0; c < n; c += SUB) {
-    const int i = c + l;
-    const bool in = i < n;
-    const long long s = i0 + (in ? i : 0);
-    const float e = expf((-density[s]) * dt[s]);
-    const float alpha = 1.0f - e;
-    const float a1 = (1.0f - alpha) + 1e-6f;
-    const float T = transmittance_step(a1, in, l, carry);
-    const float w = alpha * T;
-    if (in) {
-      if (weights) weights[s] = w;
+  for_each_weight(
+      n, l, i0, [&](long long s, int) { return nerf_alpha(density[s], dt[s]); },
+      [&](long long s, bool in, const NerfAlpha&, float, float w) {
+        if (in) {
+          if (weights) weights[s] = w;
 #pragma unroll
-      for (int d = 0; d < 3; ++d) acc[d] += w * rgb[s * 3 + d];
-      accz += w * z[s];
-    }
-    ws += sub_reduce_add(in ? w : 0.f);
-  }
+          for (int d = 0; d < 3; ++d) acc[d] += w * rgb[s * 3 + d];
+          accz += w * z[s];
+        }
+        ws += sub_reduce_add(in ? w : 0.f);
+      });
   float fg[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) fg[d] = sub_reduce_add(acc[d]);
@@ -71,16 +66,9 @@ __global__ void nerf_composite_fwd_kernel(const int* __restrict__ start_end,
   }
 }
 
-// Backward.  Per ray: g_d = g_rgb_d;  with a background
-//   g_bgT = (g_0 bg_0 + g_1 bg_1) + g_2 bg_2,  g_bg_d = g_d (1 - wsum),
-//   g_wsum = g_wsum_in + (-g_bgT)             (g_wsum_in = 0 without the mask term).
-// Per sample, forward sweep (T recomputed as in the forward kernel):
-//   g_w   = (g_0 rgb_0 + g_1 rgb_1) + g_2 rgb_c   (c = 1 under bug_compat, else 2: integrate_bwd_kernel<3>)
-//           + g_wsum                               (sum_over_rays_bwd_kernel: the per-ray gradient)
-//   g_rgb_sample_d = g_d w;  lv = (g_w alpha) T;  g_w T kept for the reversed sweep.
-// Reversed sweep: the suffix sums of lv in cumsum_kernel(inverse)'s order, the cumprod backward
-// (next suffix sum / max(a1, 1e-6), 0 for the ray's last sample), then
-//   g_alpha = g_w T + (-g_a1),  g_density = -(((-g_alpha) e) dt).
+// Backward (bg_grad, wsum_grad and the two sweeps of ray_sweep.h).  The weight's use besides the
+// colour integral is the weight sum, so g_w's other term is g_wsum; the alpha backward is
+//   g_density = -(((-g_alpha) e) dt).
 // scratch: 2 floats per sample.
 __global__ void nerf_composite_bwd_kernel(const int* __restrict__ start_end,
                                           const float* __restrict__ density,
@@ -94,120 +82,40 @@ __global__ void nerf_composite_bwd_kernel(const int* __restrict__ start_end,
                                           float* __restrict__ g_rgb_samples,
                                           float* __restrict__ g_rgb_bg,
                                           float* __restrict__ scratch, int N, int bug_compat) {
-  NR_RAY_PROLOGUE();
+  RAY_PROLOGUE();
   float g[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) g[d] = g_rgb[ray * 3 + d];
-  float g_ws = g_wsum_in ? g_wsum_in[ray] : 0.0f;
-  if (rgb_bg) {
-    const float* b = rgb_bg + ray * bg_stride;
-    float g_bgT = g[0] * b[0];
-    g_bgT += g[1] * b[1];
-    g_bgT += g[2] * b[2];
-    g_ws = g_wsum_in ? g_ws + (-g_bgT) : -g_bgT;
-    if (g_rgb_bg && l == 0) {
-      const float bgT = 1.0f - wsum[ray];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) g_rgb_bg[ray * 3 + d] = g[d] * bgT;
-    }
-  }
+  const float g_bgT =
+      bg_grad(g, rgb_bg, bg_stride, ray, l, g_rgb_bg, [&] { return 1.0f - wsum[ray]; });
+  const float g_ws = wsum_grad(g_wsum_in, ray, rgb_bg != nullptr, g_bgT);
   if (n <= 0) return;
-  float carry = 1.0f;
-  for (int c = 0; c < n; c += SUB) {
-    const int i = c + l;
-    const bool in = i < n;
-    const long long s = i0 + (in ? i : 0);
-    const float e = expf((-density[s]) * dt[s]);
-    const float alpha = 1.0f - e;
-    const float a1 = (1.0f - alpha) + 1e-6f;
-    const float T = transmittance_step(a1, in, l, carry);
-    if (in) {
-      const float w = alpha * T;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) g_rgb_samples[s * 3 + d] = g[d] * w;
-      const float gw = integrate3_grad_w(g, rgb + s * 3, bug_compat) + g_ws;
-      const float gT = gw * alpha;
-      scratch[2 * s] = gT * T;
-      scratch[2 * s + 1] = gw * T;
-    }
-  }
-  float csum = 0.0f;
-  for (int c = 0; c < n; c += SUB) {
-    const int i = c + l;
-    const bool in = i < n;
-    const long long s = in ? (long long)i1 - 1 - i : (long long)i0;
-    const float cs_next = cumprod_bwd_suffix_step(in ? scratch[2 * s] : 0.0f, in, l, csum);
-    if (in) {
-      const float dts = dt[s];
-      const float e = expf((-density[s]) * dts);
-      const float alpha = 1.0f - e;
-      const float a1 = (1.0f - alpha) + 1e-6f;
-      float ga1 = 0.f;
-      if (i > 0) ga1 = cs_next / fmaxf(a1, 1e-6f);
-      const float g_alpha = scratch[2 * s + 1] + (-ga1);
-      const float gu = (-g_alpha) * e;
-      g_density[s] = -(gu * dts);
-    }
-  }
+  const auto alpha_of = [&](long long s, int) { return nerf_alpha(density[s], dt[s]); };
+  composite_bwd_weights(
+      n, l, i0, 1, 0, alpha_of, g, rgb, bug_compat,
+      [&](long long, const NerfAlpha&, float) { return g_ws; }, g_rgb_samples, scratch);
+  composite_bwd_alphas(n, l, i0, i1, 1, 0, alpha_of, scratch,
+                       [&](long long s, const NerfAlpha& a, float g_alpha) {
+                         const float gu = (-g_alpha) * a.e;
+                         g_density[s] = -(gu * dt[s]);
+                       });
 }
 
 // The coarse pass of importance_sampling_nerf (utils/nerf_utils.py:61-82) from the uniform
-// samples' densities to the CDF:
-//   alpha = min(max(1 - exp(-density dt), 0), 1);  T = cumprod((1 - alpha) + 1e-6);  w = alpha T;
-//   wsum  = sum over chunks of the butterfly sum of the chunk (sum_over_rays_kernel<1>);
-//   w    /= max(wsum, 1e-6);
-//   cdf_i = carry + (incl_i - w_i) with incl the chunk's inclusive shuffle scan, and the last entry
-//           snapped to 1 when |wsum' - 1| < 1e-3 and |cdf_last - 1| > 1e-3 (compute_cdf_kernel).
-// Rays with fewer than 2 samples get a zero CDF (compute_cdf leaves them at zero).  The first
-// sweep parks w in `cdf` (each lane re-reads only what it wrote).
+// samples' densities to the CDF: coarse_cdf with
+//   alpha = min(max(1 - exp(-density dt), 0), 1).
 __global__ void nerf_coarse_cdf_kernel(const int* __restrict__ start_end,
                                        const float* __restrict__ density,
                                        const float* __restrict__ dt, float* __restrict__ cdf,
                                        int N) {
-  NR_RAY_PROLOGUE();
-  if (n < 2) {
-    if (n == 1 && l == 0) cdf[i0] = 0.0f;
-    return;
-  }
-  float carry = 1.0f, ws = 0.f;
-  for (int c = 0; c < n; c += SUB) {
-    const int i = c + l;
-    const bool in = i < n;
-    const long long s = i0 + (in ? i : 0);
+  RAY_PROLOGUE();
+  coarse_cdf(n, l, i0, i1, [&](long long s, int) {
     const float e = expf((-density[s]) * dt[s]);
-    const float alpha = fminf(fmaxf(1.0f - e, 0.0f), 1.0f);
-    const float a1 = (1.0f - alpha) + 1e-6f;
-    const float T = transmittance_step(a1, in, l, carry);
-    const float w = alpha * T;
-    if (in) cdf[s] = w;
-    ws += sub_reduce_add(in ? w : 0.f);
-  }
-  const float wn = fmaxf(ws, 1e-6f);
-  float run = 0.0f, last_cdf = 0.0f;
-  for (int c = 0; c < n; c += SUB) {
-    const int i = c + l;
-    const float x = i < n ? cdf[i0 + i] / wn : 0.0f;
-    const float incl = sub_scan_add(x, l);
-    const float excl = run + (incl - x);
-    if (i < n) cdf[i0 + i] = excl;
-    if (i == n - 1) last_cdf = excl;
-    run += __shfl(incl, SUB - 1, SUB);
-  }
-  const int owner = (n - 1) & (SUB - 1);
-  if (l == owner && fabs((double)run - 1.0) < 1e-3 && fabs((double)last_cdf - 1.0) > 1e-3)
-    cdf[i1 - 1] = 1.0f;
+    return fminf(fmaxf(1.0f - e, 0.0f), 1.0f);
+  }, cdf);
 }
 
-inline dim3 nr_grid(int N) { return dim3(vsa_div_up((long long)N * SUB, NR_BLOCK)); }
-
 }  // namespace
-
-#define NR_CHECK(cond) \
-  if (!(cond)) return VSA_ERR_ARG
-#define NR_LAUNCH(kernel, N, ...)                                                          \
-  if ((N) == 0) return VSA_OK;                                                             \
-  hipLaunchKernelGGL(kernel, nr_grid(N), dim3(NR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); \
-  VSA_RETURN_LAUNCH_STATUS()
 
 extern "C" int vsa_nerf_composite_fwd(const int32_t* start_end, const float* density,
                                       const float* dt, const float* samples_z, const float* rgb,
@@ -215,11 +123,11 @@ extern "C" int vsa_nerf_composite_fwd(const int32_t* start_end, const float* den
                                       float* rgb_out, float* weights_sum, float* depth,
                                       float* weights, int nr_rays, void* stream) {
   // the per-sample arrays are only read for rays with samples: NULL is fine for a pack without any
-  NR_CHECK(nr_rays >= 0);
+  RAY_CHECK(nr_rays >= 0);
   if (nr_rays == 0) return VSA_OK;
-  NR_CHECK(start_end && rgb_fg && weights_sum && depth && (bg_per_ray == 0 || bg_per_ray == 1) &&
+  RAY_CHECK(start_end && rgb_fg && weights_sum && depth && (bg_per_ray == 0 || bg_per_ray == 1) &&
            (!rgb_bg || rgb_out));
-  NR_LAUNCH(nerf_composite_fwd_kernel, nr_rays, start_end, density, dt, samples_z, rgb, rgb_bg,
+  RAY_LAUNCH(nerf_composite_fwd_kernel, nr_rays, start_end, density, dt, samples_z, rgb, rgb_bg,
             bg_per_ray ? 3 : 0, rgb_fg, rgb_out, weights_sum, depth, weights, nr_rays);
 }
 
@@ -229,19 +137,19 @@ extern "C" int vsa_nerf_composite_bwd(const int32_t* start_end, const float* den
                                       const float* g_weights_sum, float* g_density,
                                       float* g_rgb_samples, float* g_rgb_bg, float* scratch,
                                       int nr_rays, int bug_compat, void* stream) {
-  NR_CHECK(nr_rays >= 0);
+  RAY_CHECK(nr_rays >= 0);
   if (nr_rays == 0) return VSA_OK;
-  NR_CHECK(start_end && g_rgb && (bg_per_ray == 0 || bg_per_ray == 1) &&
+  RAY_CHECK(start_end && g_rgb && (bg_per_ray == 0 || bg_per_ray == 1) &&
            (!g_rgb_bg || (rgb_bg && weights_sum)));
-  NR_LAUNCH(nerf_composite_bwd_kernel, nr_rays, start_end, density, dt, rgb, rgb_bg,
+  RAY_LAUNCH(nerf_composite_bwd_kernel, nr_rays, start_end, density, dt, rgb, rgb_bg,
             bg_per_ray ? 3 : 0, weights_sum, g_rgb, g_weights_sum, g_density, g_rgb_samples,
             g_rgb_bg, scratch, nr_rays, bug_compat);
 }
 
 extern "C" int vsa_nerf_coarse_cdf(const int32_t* start_end, const float* density, const float* dt,
                                    float* cdf, int nr_rays, void* stream) {
-  NR_CHECK(nr_rays >= 0);
+  RAY_CHECK(nr_rays >= 0);
   if (nr_rays == 0) return VSA_OK;
-  NR_CHECK(start_end);
-  NR_LAUNCH(nerf_coarse_cdf_kernel, nr_rays, start_end, density, dt, cdf, nr_rays);
+  RAY_CHECK(start_end);
+  RAY_LAUNCH(nerf_coarse_cdf_kernel, nr_rays, start_end, density, dt, cdf, nr_rays);
 }

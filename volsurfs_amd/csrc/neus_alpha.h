@@ -19,6 +19,8 @@ struct NeusAlpha {
   float tc, r1, r2, h, pc, nc, num, den, q, alpha;
 };
 
+__device__ __forceinline__ float alpha_value(const NeusAlpha& a) { return a.alpha; }  // ray_sweep.h
+
 __device__ __forceinline__ float relu(float x) { return x > 0.0f ? x : 0.0f; }
 __device__ __forceinline__ float sigmoid_torch(float x) { return 1.0f / (1.0f + expf(-x)); }
 

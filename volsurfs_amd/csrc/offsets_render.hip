@@ -4,22 +4,19 @@
 // importance round that averages K CDFs.  The reference runs these as K chains of single ops per ray;
 // here each is one launch.
 //
-// Layout as in surf_render.hip: a ray is owned by a 32-lane half-wave, lanes = consecutive samples,
-// the scans / reductions of ray_scan.h, chunks of 32 samples with a carried running value for
-// longer rays, the surfaces one after the other inside the half-wave.  Per-sample arrays are
-// [S, K] (sample-major, as the model returns them).  No atomics: every output element has exactly
-// one writer.  The per-ray K-vectors of the blend live in fixed arrays of OR_MAX_SURFS registers
-// indexed only by unrolled constants (k < K guards), so they never go to scratch.  The build has
-// -ffp-contract=off, so every fp32 operation below is a single rounding, in the order written.
+// The half-wave layout, the sweeps and the order of their fp32 operations are ray_sweep.h's, the
+// surfaces one after the other inside the half-wave.  Per-sample arrays are [S, K] (sample-major,
+// as the model returns them).  This file holds what is the OffsetsSurfs method's: the second
+// integral (the transparency), the blend of the K shells and the average of K CDFs.  The per-ray
+// K-vectors of the blend live in fixed arrays of OR_MAX_SURFS registers indexed only by unrolled
+// constants (k < K guards), so they never go to scratch.
 #include "neus_alpha.h"
+#include "ray_sweep.h"
 
 namespace {
 
-constexpr int OR_BLOCK = 256;
 constexpr int OR_MAX_SURFS = 16;
 using namespace vsa_ray;
-
-#define OR_RAY_PROLOGUE() VSA_RAY_PROLOGUE(OR_BLOCK)
 
 // arr[k] = v / arr[k] for a runtime k, as a chain of selects over constant indices (registers only)
 __device__ __forceinline__ void put_k(float (&arr)[OR_MAX_SURFS], int k, float v) {
@@ -65,37 +62,34 @@ __global__ void offsets_composite_fwd_kernel(
     float* __restrict__ surfs_depths, float* __restrict__ surfs_wsum, float* __restrict__ surfs_alpha,
     float* __restrict__ surfs_T, float* __restrict__ surfs_bw, float* __restrict__ rgb_fg_out,
     float* __restrict__ bgT_out, float* __restrict__ rgb_out, float* __restrict__ alpha_out, int N) {
-  OR_RAY_PROLOGUE();
+  RAY_PROLOGUE();
   float ra[OR_MAX_SURFS], rr[OR_MAX_SURFS], rg[OR_MAX_SURFS], rb[OR_MAX_SURFS];
   for (int k = 0; k < K; ++k) {
     float acc[3] = {0.f, 0.f, 0.f}, accn[3] = {0.f, 0.f, 0.f};
     float acct = 0.f, accz = 0.f, ws = 0.f;
-    float carry = 1.0f;
-    for (int c = 0; c < n; c += SUB) {
-      const int i = c + l;
-      const bool in = i < n;
-      const long long s = i0 + (in ? i : 0);
-      const long long sk = s * K + k;
-      const float* dir = dirs + s * 3;
-      const NeusAlpha a = neus_alpha(sdfs[sk], sdfs_grad + sk * 3, dir, dt[s], car, omc, beta);
-      const float a1 = (1.0f - a.alpha) + 1e-6f;
-      const float T = transmittance_step(a1, in, l, carry);
-      const float w = a.alpha * T;
-      if (in) {
-        if (alpha_out) alpha_out[sk] = a.alpha;
-        const float* nrm = normals + sk * 3;
-        float t = transp[sk];
-        if (with_decay) t = t * transparency_decay(dir, nrm, decay_f);
+    for_each_weight(
+        n, l, i0,
+        [&](long long s, int) {
+          const long long sk = s * K + k;
+          return neus_alpha(sdfs[sk], sdfs_grad + sk * 3, dirs + s * 3, dt[s], car, omc, beta);
+        },
+        [&](long long s, bool in, const NeusAlpha& a, float, float w) {
+          if (in) {
+            const long long sk = s * K + k;
+            if (alpha_out) alpha_out[sk] = a.alpha;
+            const float* nrm = normals + sk * 3;
+            float t = transp[sk];
+            if (with_decay) t = t * transparency_decay(dirs + s * 3, nrm, decay_f);
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-          acc[d] += w * rgb[sk * 3 + d];
-          accn[d] += w * nrm[d];
-        }
-        acct += w * t;
-        accz += w * z[s];
-      }
-      ws += sub_reduce_add(in ? w : 0.f);
-    }
+            for (int d = 0; d < 3; ++d) {
+              acc[d] += w * rgb[sk * 3 + d];
+              accn[d] += w * nrm[d];
+            }
+            acct += w * t;
+            accz += w * z[s];
+          }
+          ws += sub_reduce_add(in ? w : 0.f);
+        });
     float fg[3], nf[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -151,10 +145,10 @@ __global__ void offsets_composite_fwd_kernel(
 //   g_rgb_j,d = g_d bw_j;  g_bw_j = (g_0 rgb_j0 + g_1 rgb_j1) + g_2 rgb_j2;
 //   from j = K - 1 down to 0 with gt = g_bgT:  g_a_j = g_bw_j Tsurf_j - gt Tsurf_j,
 //                                               gt = gt (1 - a_j) + g_bw_j a_j.
-// Then per surface k, as neus_composite_bwd_kernel: forward sweep
-//   g_w = integrate3_grad_w(g_rgb_k, rgb) + g_a_k t   (the two integrals' weight gradients),
-//   g_rgb_samples = g_rgb_k w,  g_transparency = (g_a_k w) decay,  lv = (g_w alpha) T;
-// reversed sweep: the cumprod backward and neus_alpha_bwd.  scratch: 2 S K floats.
+// Then per surface k the two sweeps of ray_sweep.h on column k with g_rgb_k = g bw_k: the weight's
+// use besides the colour integral is the transparency integral, so g_w's other term is g_a_k t,
+// with g_transparency = (g_a_k w) decay written on the way; the alpha backward is neus_alpha_bwd.
+// scratch: 2 S K floats.
 __global__ void offsets_composite_bwd_kernel(
     const int* __restrict__ start_end, int K, const float* __restrict__ sdfs,
     const float* __restrict__ sdfs_grad, const float* __restrict__ normals,
@@ -166,22 +160,11 @@ __global__ void offsets_composite_bwd_kernel(
     const float* __restrict__ g_rgb, float* __restrict__ g_sdfs, float* __restrict__ g_sdfs_grad,
     float* __restrict__ g_rgb_samples, float* __restrict__ g_transp, float* __restrict__ g_rgb_bg,
     float* __restrict__ scratch, int N, int bug_compat) {
-  OR_RAY_PROLOGUE();
+  RAY_PROLOGUE();
   float g[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) g[d] = g_rgb[ray * 3 + d];
-  const float bgT = bgT_in[ray];
-  float g_bgT = 0.0f;
-  if (rgb_bg) {
-    const float* b = rgb_bg + ray * bg_stride;
-    g_bgT = g[0] * b[0];
-    g_bgT += g[1] * b[1];
-    g_bgT += g[2] * b[2];
-    if (g_rgb_bg && l == 0) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) g_rgb_bg[ray * 3 + d] = g[d] * bgT;
-    }
-  }
+  const float g_bgT = bg_grad(g, rgb_bg, bg_stride, ray, l, g_rgb_bg, [&] { return bgT_in[ray]; });
   // the blend's reverse sweep: per-surface g of surfs_rgb (times g_d below) and of surfs_alpha
   float gbw[OR_MAX_SURFS], ga[OR_MAX_SURFS];
   float gt = g_bgT;
@@ -207,51 +190,30 @@ __global__ void offsets_composite_bwd_kernel(
     float gk[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) gk[d] = g[d] * bwk;
-    float carry = 1.0f;
-    for (int c = 0; c < n; c += SUB) {
-      const int i = c + l;
-      const bool in = i < n;
-      const long long s = i0 + (in ? i : 0);
+    const auto alpha_of = [&](long long s, int) {
       const long long sk = s * K + k;
-      const float* dir = dirs + s * 3;
-      const NeusAlpha a = neus_alpha(sdfs[sk], sdfs_grad + sk * 3, dir, dt[s], car, omc, beta);
-      const float a1 = (1.0f - a.alpha) + 1e-6f;
-      const float T = transmittance_step(a1, in, l, carry);
-      if (in) {
-        const float w = a.alpha * T;
-        const float dec = with_decay ? transparency_decay(dir, normals + sk * 3, decay_f) : 1.0f;
-        const float t = with_decay ? transp[sk] * dec : transp[sk];
+      return neus_alpha(sdfs[sk], sdfs_grad + sk * 3, dirs + s * 3, dt[s], car, omc, beta);
+    };
+    composite_bwd_weights(
+        n, l, i0, K, k, alpha_of, gk, rgb, bug_compat,
+        [&](long long s, const NeusAlpha&, float w) {
+          const long long sk = s * K + k;
+          const float dec =
+              with_decay ? transparency_decay(dirs + s * 3, normals + sk * 3, decay_f) : 1.0f;
+          const float t = with_decay ? transp[sk] * dec : transp[sk];
+          g_transp[sk] = (gak * w) * dec;
+          return gak * t;
+        },
+        g_rgb_samples, scratch);
+    composite_bwd_alphas(n, l, i0, i1, K, k, alpha_of, scratch,
+                         [&](long long s, const NeusAlpha& a, float g_alpha) {
+                           const long long sk = s * K + k;
+                           float gs, gg[3];
+                           neus_alpha_bwd(a, g_alpha, dirs + s * 3, dt[s], car, omc, beta, gs, gg);
+                           g_sdfs[sk] = gs;
 #pragma unroll
-        for (int d = 0; d < 3; ++d) g_rgb_samples[sk * 3 + d] = gk[d] * w;
-        g_transp[sk] = (gak * w) * dec;
-        const float gw = integrate3_grad_w(gk, rgb + sk * 3, bug_compat) + gak * t;
-        const float gT = gw * a.alpha;
-        scratch[2 * sk] = gT * T;
-        scratch[2 * sk + 1] = gw * T;
-      }
-    }
-    float csum = 0.0f;
-    for (int c = 0; c < n; c += SUB) {
-      const int i = c + l;
-      const bool in = i < n;
-      const long long s = in ? (long long)i1 - 1 - i : (long long)i0;
-      const long long sk = s * K + k;
-      const float cs_next = cumprod_bwd_suffix_step(in ? scratch[2 * sk] : 0.0f, in, l, csum);
-      if (in) {
-        const float dts = dt[s];
-        const float* dir = dirs + s * 3;
-        const NeusAlpha a = neus_alpha(sdfs[sk], sdfs_grad + sk * 3, dir, dts, car, omc, beta);
-        const float a1 = (1.0f - a.alpha) + 1e-6f;
-        float ga1 = 0.f;
-        if (i > 0) ga1 = cs_next / fmaxf(a1, 1e-6f);
-        const float g_alpha = scratch[2 * sk + 1] + (-ga1);
-        float gs, gg[3];
-        neus_alpha_bwd(a, g_alpha, dir, dts, car, omc, beta, gs, gg);
-        g_sdfs[sk] = gs;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) g_sdfs_grad[sk * 3 + d] = gg[d];
-      }
-    }
+                           for (int d = 0; d < 3; ++d) g_sdfs_grad[sk * 3 + d] = gg[d];
+                         });
   }
 }
 
@@ -266,41 +228,28 @@ __global__ void offsets_composite_bwd_kernel(
 __global__ void sdfs_coarse_cdf_kernel(const int* __restrict__ start_end, int K,
                                        const float* __restrict__ sdfs, const float* __restrict__ dt,
                                        float beta, float inv_k, float* __restrict__ cdf, int N) {
-  OR_RAY_PROLOGUE();
-  if (n < 2) {
-    if (n == 1 && l == 0) cdf[i0] = 0.0f;
-    return;
-  }
+  RAY_PROLOGUE();
+  if (cdf_of_short_ray(n, l, i0, cdf)) return;
   const int owner = (n - 1) & (SUB - 1);
   for (int k = 0; k < K; ++k) {
-    float carry = 1.0f, ws = 0.f;
-    for (int c = 0; c < n; c += SUB) {
-      const int i = c + l;
-      const bool in = i < n;
-      const long long s = i0 + (in ? i : 0);
-      const float alpha =
-          (i < n - 1) ? sdf2alpha_sample(sdfs[s * K + k], sdfs[(s + 1) * K + k], dt[s], beta) : 0.0f;
-      const float a1 = (1.0f - alpha) + 1e-6f;
-      const float T = fminf(fmaxf(transmittance_step(a1, in, l, carry), 0.0f), 1.0f);
-      ws += sub_reduce_add(in ? alpha * T : 0.f);
-    }
+    const auto alpha_of = [&](long long s, int i) {
+      return (i < n - 1) ? sdf2alpha_sample(sdfs[s * K + k], sdfs[(s + 1) * K + k], dt[s], beta)
+                         : 0.0f;
+    };
+    // the reference clips T before it forms the weight, so the sweep's own w (alpha times the
+    // unclipped T) is not used in either body
+    const auto clip01 = [](float T) { return fminf(fmaxf(T, 0.0f), 1.0f); };
+    float ws = 0.f;
+    for_each_weight(n, l, i0, alpha_of, [&](long long, bool in, float alpha, float T, float) {
+      ws += sub_reduce_add(in ? alpha * clip01(T) : 0.f);
+    });
     const float wn = fmaxf(ws, 1e-6f);
     float run = 0.0f, last_cdf = 0.0f, agg_last = 0.0f;
-    carry = 1.0f;
-    for (int c = 0; c < n; c += SUB) {
-      const int i = c + l;
-      const bool in = i < n;
-      const long long s = i0 + (in ? i : 0);
-      const float alpha =
-          (i < n - 1) ? sdf2alpha_sample(sdfs[s * K + k], sdfs[(s + 1) * K + k], dt[s], beta) : 0.0f;
-      const float a1 = (1.0f - alpha) + 1e-6f;
-      const float T = fminf(fmaxf(transmittance_step(a1, in, l, carry), 0.0f), 1.0f);
-      const float x = in ? (alpha * T) / wn : 0.0f;
-      const float incl = sub_scan_add(x, l);
-      const float excl = run + (incl - x);
+    for_each_weight(n, l, i0, alpha_of, [&](long long s, bool in, float alpha, float T, float) {
+      const float excl = cdf_scan_step(in ? (alpha * clip01(T)) / wn : 0.0f, l, run);
       if (in) {
         const float prev = k == 0 ? 0.0f : cdf[s];
-        if (i == n - 1) {
+        if (s == i1 - 1) {
           last_cdf = excl;
           agg_last = prev;
         } else {
@@ -308,27 +257,17 @@ __global__ void sdfs_coarse_cdf_kernel(const int* __restrict__ start_end, int K,
           cdf[s] = k == K - 1 ? agg * inv_k : agg;
         }
       }
-      run += __shfl(incl, SUB - 1, SUB);
-    }
+    });
     // the ray's last sample: compute_cdf's snap to 1, then the aggregate
     if (l == owner) {
-      float v = last_cdf;
-      if (fabs((double)run - 1.0) < 1e-3 && fabs((double)last_cdf - 1.0) > 1e-3) v = 1.0f;
+      const float v = cdf_snaps_last(run, last_cdf) ? 1.0f : last_cdf;
       const float agg = agg_last + v;
       cdf[i1 - 1] = k == K - 1 ? agg * inv_k : agg;
     }
   }
 }
 
-inline dim3 or_grid(int N) { return dim3(vsa_div_up((long long)N * SUB, OR_BLOCK)); }
-
 }  // namespace
-
-#define OR_CHECK(cond) \
-  if (!(cond)) return VSA_ERR_ARG
-#define OR_LAUNCH(kernel, N, ...)                                                          \
-  hipLaunchKernelGGL(kernel, or_grid(N), dim3(OR_BLOCK), 0, (hipStream_t)stream, __VA_ARGS__); \
-  VSA_RETURN_LAUNCH_STATUS()
 
 extern "C" int vsa_offsets_composite_fwd(
     const int32_t* start_end, int nr_surfs, const float* sdfs, const float* sdfs_grad,
@@ -338,13 +277,13 @@ extern "C" int vsa_offsets_composite_fwd(
     float* surfs_rgb, float* surfs_normals, float* surfs_depths, float* surfs_weight_sum,
     float* surfs_alpha, float* surfs_transmittance, float* surfs_blending_weights, float* rgb_fg,
     float* bg_transmittance, float* rgb_out, float* alpha, int nr_rays, void* stream) {
-  OR_CHECK(nr_rays >= 0);
+  RAY_CHECK(nr_rays >= 0);
   if (nr_surfs < 1 || nr_surfs > OR_MAX_SURFS) return VSA_ERR_UNSUPPORTED;
   if (nr_rays == 0) return VSA_OK;
-  OR_CHECK(start_end && surfs_rgb && surfs_normals && surfs_depths && surfs_weight_sum &&
+  RAY_CHECK(start_end && surfs_rgb && surfs_normals && surfs_depths && surfs_weight_sum &&
            surfs_alpha && surfs_transmittance && surfs_blending_weights && rgb_fg &&
            bg_transmittance && rgb_out && (bg_per_ray == 0 || bg_per_ray == 1));
-  OR_LAUNCH(offsets_composite_fwd_kernel, nr_rays, start_end, nr_surfs, sdfs, sdfs_grad, normals,
+  RAY_LAUNCH(offsets_composite_fwd_kernel, nr_rays, start_end, nr_surfs, sdfs, sdfs_grad, normals,
             rgb, transparency, dirs, dt, samples_z, rgb_bg, bg_per_ray ? 3 : 0,
             (float)cos_anneal_ratio, (float)(1.0 - cos_anneal_ratio), (float)logistic_beta,
             with_alpha_decay ? 1 : 0, (float)alpha_decay_factor, surfs_rgb, surfs_normals,
@@ -361,12 +300,12 @@ extern "C" int vsa_offsets_composite_bwd(
     const float* g_rgb, float* g_sdfs, float* g_sdfs_grad, float* g_rgb_samples,
     float* g_transparency, float* g_rgb_bg, float* scratch, int nr_rays, int bug_compat,
     void* stream) {
-  OR_CHECK(nr_rays >= 0);
+  RAY_CHECK(nr_rays >= 0);
   if (nr_surfs < 1 || nr_surfs > OR_MAX_SURFS) return VSA_ERR_UNSUPPORTED;
   if (nr_rays == 0) return VSA_OK;
-  OR_CHECK(start_end && surfs_rgb && surfs_alpha && surfs_transmittance && bg_transmittance &&
+  RAY_CHECK(start_end && surfs_rgb && surfs_alpha && surfs_transmittance && bg_transmittance &&
            g_rgb && (bg_per_ray == 0 || bg_per_ray == 1) && (!g_rgb_bg || rgb_bg));
-  OR_LAUNCH(offsets_composite_bwd_kernel, nr_rays, start_end, nr_surfs, sdfs, sdfs_grad, normals,
+  RAY_LAUNCH(offsets_composite_bwd_kernel, nr_rays, start_end, nr_surfs, sdfs, sdfs_grad, normals,
             rgb, transparency, dirs, dt, rgb_bg, bg_per_ray ? 3 : 0, (float)cos_anneal_ratio,
             (float)(1.0 - cos_anneal_ratio), (float)logistic_beta, with_alpha_decay ? 1 : 0,
             (float)alpha_decay_factor, surfs_rgb, surfs_alpha, surfs_transmittance,
@@ -377,10 +316,10 @@ extern "C" int vsa_offsets_composite_bwd(
 extern "C" int vsa_sdfs_coarse_cdf(const int32_t* start_end, int nr_surfs, const float* sdfs,
                                    const float* dt, float logistic_beta, float* cdf, int nr_rays,
                                    void* stream) {
-  OR_CHECK(nr_rays >= 0);
+  RAY_CHECK(nr_rays >= 0);
   if (nr_surfs < 1 || nr_surfs > OR_MAX_SURFS) return VSA_ERR_UNSUPPORTED;
   if (nr_rays == 0) return VSA_OK;
-  OR_CHECK(start_end && cdf);
-  OR_LAUNCH(sdfs_coarse_cdf_kernel, nr_rays, start_end, nr_surfs, sdfs, dt, logistic_beta,
+  RAY_CHECK(start_end && cdf);
+  RAY_LAUNCH(sdfs_coarse_cdf_kernel, nr_rays, start_end, nr_surfs, sdfs, dt, logistic_beta,
             1.0f / (float)nr_surfs, cdf, nr_rays);
 }

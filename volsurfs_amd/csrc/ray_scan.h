@@ -1,5 +1,5 @@
-// Per-ray building blocks of the packed (ragged) sample kernels: packed.hip, nerf_render.hip and
-// surf_render.hip include this one copy, so that a fused kernel performs exactly the fp32
+// Per-ray building blocks of the packed (ragged) sample kernels: packed.hip and the fused sweeps
+// of ray_sweep.h include this one copy, so that a fused kernel performs exactly the fp32
 // operations, in exactly the order, of the single-op kernel it replaces.
 //
 // Layout: a ray is owned by a 32-lane half-wave, lanes = consecutive samples (coalesced rows),

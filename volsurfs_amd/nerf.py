@@ -7,72 +7,31 @@ project's existing HIP operators (permutohedral encoder, fused MLP, occupancy gr
 import torch
 
 from . import _lib
-from .background import intersect_bounding_primitive, render_contracted_bg
-from .field_method import FieldMethod, init_occupancy_grid
-from .models import RGB, ColorSH, Density, NerfHash
-from .trainer import loss_l1
-from .volsurfs import RaySampler, VolumeRendering
+from .background import intersect_bounding_primitive
+from .field_method import (FieldHyperParams, FieldMethod, bg_arg, composite_bg_grad, composite_grad_buffers,
+                           get_rays_samples_packed)
+from .models import Density
+from .volsurfs import VolumeRendering
 
 
-class NeRFHyperParams:
+class NeRFHyperParams(FieldHyperParams):
     """params/hyper_params.py (HyperParams, HyperParamsNeRF) with config/nerf/base.cfg applied: the keys and values
     a `nerf` run of the reference trains with.  Keyword arguments override single values."""
 
-    def __init__(self, **overrides):
+    def set_defaults(self):
+        super().set_defaults()
         # lr schedule
-        self.lr = 1e-3
-        self.nr_warmup_iters = 3000
         self.lr_milestones = [100000, 150000, 180000, 190000]
         self.training_end_iter = 200000
-        # rays
-        self.training_rays_batch_size = 512
-        self.is_nr_training_rays_dynamic = True
-        self.target_nr_of_training_samples = 512 * (64 + 16 + 16)
-        self.test_rays_batch_size = 16384
-        self.nr_training_rays_per_pixel = 1
-        self.nr_test_rays_per_pixel = 1
-        self.jitter_training_rays = True
-        self.jitter_test_rays = False
-        # masks
-        self.is_training_masked = False
-        self.is_testing_masked = False
-        self.mask_weight = 0.0
         # density
-        self.geom_feat_size = 32
         self.density_encoding_type = "permutohash"
         self.density_mlp_layers_dims = [32, 32, 32]
         self.density_nr_iters_for_c2f = 1000
         # appearance
-        self.rgb_pos_encoder_type = "permutohash"
-        self.rgb_dir_encoder_type = "spherical_harmonics"
-        self.rgb_mlp_layers_dims = [128, 128, 64]
-        self.sh_degree = 3
         self.appearance_predict_sh_coeffs = False
-        self.rgb_view_dep = True
         self.rgb_normal_dep = False
-        self.rgb_geom_feat_dep = True
-        self.rgb_nr_iters_for_c2f = 0
-        # background
-        self.bg_pos_encoder_type = "permutohash"
-        self.bg_dir_encoder_type = "spherical_harmonics"
-        self.bg_nr_iters_for_c2f = 0
-        self.nr_samples_bg = 64
-        # sampling
-        self.use_occupancy_grid = True
-        self.do_importance_sampling = True
-        self.min_dist_between_samples = 1e-4
-        self.min_nr_samples_per_ray = 1
-        self.max_nr_samples_per_ray = 64
-        self.max_nr_imp_samples_per_ray = 32
         # losses
         self.sparsity_weight = 1e-4
-        for k, v in overrides.items():
-            if not hasattr(self, k):
-                raise KeyError(f"unknown hyper-parameter {k!r}")
-            setattr(self, k, v)
-        # hyper_params.py:173-178: the CDF of importance sampling needs 3 samples per ray
-        if self.do_importance_sampling and self.min_nr_samples_per_ray < 3:
-            self.min_nr_samples_per_ray = 3
 
 
 # ---- fused per-ray chains (csrc/nerf_render.hip)
@@ -89,16 +48,7 @@ class _NerfComposite(torch.autograd.Function):
         S, N = rgb.shape[0], pack.get_nr_rays()
         if density.numel() != S or pack.samples_dt.numel() != S or rgb.shape[1] != 3:
             raise _lib.VolsurfsHipError("nerf composite: rgb [S,3], density [S,1], a pack with S samples and dt")
-        per_ray, bg_shape = 0, None
-        if rgb_bg is not None:
-            bg_shape = rgb_bg.shape
-            if rgb_bg.dim() == 2 and rgb_bg.shape == (N, 3) and N != 1:
-                per_ray = 1
-            elif rgb_bg.numel() == 3:
-                pass
-            else:
-                raise _lib.VolsurfsHipError(f"nerf composite: rgb_bg must be [N,3] or one colour, got {tuple(rgb_bg.shape)}")
-            rgb_bg = _lib.check_f32(rgb_bg.contiguous().view(-1, 3) if per_ray else rgb_bg.reshape(3).contiguous())
+        rgb_bg, per_ray, bg_shape = bg_arg(rgb_bg, N, "nerf")
         dev = rgb.device
         rgb_fg = torch.empty(N, 3, device=dev)
         rgb_out = torch.empty(N, 3, device=dev)
@@ -120,18 +70,13 @@ class _NerfComposite(torch.autograd.Function):
         density, rgb, rgb_bg, wsum = ctx.saved_tensors
         pack, ctx.pack = ctx.pack, None
         N = pack.get_nr_rays()
-        if g_rgb is None:
-            g_rgb = torch.zeros(N, 3, device=rgb.device)
         g_density, g_rgb_s = torch.empty_like(density), torch.empty_like(rgb)
-        need_bg = rgb_bg is not None and ctx.needs_input_grad[3]
-        g_bg = torch.empty(N, 3, device=rgb.device) if need_bg else None
         scratch = torch.empty(2 * rgb.shape[0], device=rgb.device)
+        g_rgb, g_bg = composite_grad_buffers(pack, g_rgb, rgb_bg, ctx.needs_input_grad[3])
         _lib.call("vsa_nerf_composite_bwd", pack.ray_start_end_idx, density, pack.samples_dt, rgb, rgb_bg,
-                  ctx.per_ray, wsum, g_rgb.contiguous(), None if g_wsum is None else g_wsum.contiguous(),
-                  g_density, g_rgb_s, g_bg, scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
-        if need_bg and not ctx.per_ray:
-            g_bg = g_bg.sum(0).view(ctx.bg_shape)
-        return None, g_density, g_rgb_s, g_bg, None
+                  ctx.per_ray, wsum, g_rgb, None if g_wsum is None else g_wsum.contiguous(), g_density, g_rgb_s, g_bg,
+                  scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
+        return None, g_density, g_rgb_s, composite_bg_grad(ctx, g_bg), None
 
 
 def nerf_composite(pack, density, rgb, rgb_bg=None, return_weights=False):
@@ -179,24 +124,10 @@ def get_rays_samples_packed_nerf(rays_o, rays_d, t_near, t_far, density_fn, occu
                                  max_nr_imp_samples_per_ray=32, jitter_samples=False, importance_sampling=True,
                                  values_dim=1):
     """utils/nerf_utils.py:100-190 -> (pack with dt, importance pack or None)."""
-    with torch.no_grad():
-        if occupancy_grid is not None:
-            pack = RaySampler.compute_samples_fg_in_grid_occupied_regions(
-                rays_o, rays_d, t_near, t_far, min_dist_between_samples, min_nr_samples_per_ray,
-                max_nr_samples_per_ray, jitter_samples, occupancy_grid.get_nr_voxels_per_dim(),
-                occupancy_grid.get_grid_extent(), occupancy_grid.get_grid_occupancy(), occupancy_grid.get_grid_roi(),
-                values_dim)
-        else:
-            pack = RaySampler.compute_samples_fg(rays_o, rays_d, t_near, t_far, min_dist_between_samples,
-                                                 min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples,
-                                                 values_dim)
-    imp = None
-    if not pack.is_empty():
-        if importance_sampling:
-            imp = importance_sampling_nerf(density_fn, pack, iter_nr, max_nr_imp_samples_per_ray, jitter_samples)
-            pack = VolumeRendering.combine_ray_samples_packets(pack, imp, min_dist_between_samples)
-        pack.update_dt(False)
-    return pack, imp
+    imp_fn = (lambda pack: importance_sampling_nerf(density_fn, pack, iter_nr, max_nr_imp_samples_per_ray,
+                                                    jitter_samples)) if importance_sampling else None
+    return get_rays_samples_packed(rays_o, rays_d, t_near, t_far, imp_fn, occupancy_grid, min_dist_between_samples,
+                                   min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples, values_dim)
 
 
 class NeRF(FieldMethod):
@@ -206,50 +137,22 @@ class NeRF(FieldMethod):
     returns (losses, info, foreground samples) — the sample count drives the dynamic ray count."""
 
     method_name = "nerf"
-    OCCUPANCY_EVERY = 50                   # update_method_state (nerf.py:414-421)
-    OCCUPANCY_RANDOM_VOXELS = 256 * 256 * 4
+    OCCUPANCY_RANDOM_VOXELS = 256 * 256 * 4   # update_occupancy_grid (nerf.py:194-255); every 50 iterations
     OCCUPANCY_DECAY = 0.8
-    OCCUPANCY_THRESH = 1e-4
     SPARSITY_FROM_ITER = 5000              # the sparsity term is on for iter_nr > 5000 (nerf.py:467)
     SPARSITY_NR_POINTS = 1024
 
     def __init__(self, train, hyper_params, load_checkpoints_path, save_checkpoints_path, bounding_primitive,
                  bg_color=None, start_iter_nr=0):
         hp = hyper_params
-        self.hyper_params = hp
-        self.load_checkpoints_path, self.save_checkpoints_path = load_checkpoints_path, save_checkpoints_path
-        self.bounding_primitive = bounding_primitive
-        self.bg_color = None if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32).cuda().view(1, 3)
-        self.optimizer = self.lr_scheduler = self.scheduler_lr_decay = None
-        self.is_training = bool(train)
-        self.occupancy_grid = init_occupancy_grid(bounding_primitive) if hp.use_occupancy_grid else None
-        bb = bounding_primitive.get_radius() * 2.0
-        self.models = {}
+        bb = self._init_common(train, hp, load_checkpoints_path, save_checkpoints_path, bounding_primitive, bg_color)
         self.models["density"] = Density(in_channels=3, out_channels=1, geom_feat_size=hp.geom_feat_size,
                                          mlp_layers_dims=hp.density_mlp_layers_dims,
                                          encoding_type=hp.density_encoding_type,
                                          nr_iters_for_c2f=hp.density_nr_iters_for_c2f, bb_sides=bb)
-        if hp.appearance_predict_sh_coeffs:
-            assert hp.rgb_view_dep, "SH coeffs only implemented for view dependent color"
-            self.models["rgb"] = ColorSH(in_channels=3, out_channels=3, mlp_layers_dims=hp.rgb_mlp_layers_dims,
-                                         pos_encoder_type=hp.rgb_pos_encoder_type, sh_deg=hp.sh_degree,
-                                         normal_dep=hp.rgb_normal_dep, geom_feat_dep=hp.rgb_geom_feat_dep,
-                                         in_geom_feat_size=hp.geom_feat_size,
-                                         nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
-        else:
-            self.models["rgb"] = RGB(in_channels=3, out_channels=3, mlp_layers_dims=hp.rgb_mlp_layers_dims,
-                                     pos_encoder_type=hp.rgb_pos_encoder_type, dir_encoder_type=hp.rgb_dir_encoder_type,
-                                     sh_deg=hp.sh_degree, pos_dep=True, view_dep=hp.rgb_view_dep,
-                                     normal_dep=hp.rgb_normal_dep, geom_feat_dep=hp.rgb_geom_feat_dep,
-                                     in_geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f,
-                                     use_lipshitz_mlp=False, bb_sides=bb)
-        self.models["bg"] = NerfHash(in_channels=3, pos_encoder_type=hp.bg_pos_encoder_type,
-                                     dir_encoder_type=hp.bg_dir_encoder_type,
-                                     nr_iters_for_c2f=hp.bg_nr_iters_for_c2f) if self.bg_color is None else None
-        if start_iter_nr > 0:
-            self.load(start_iter_nr)
-        if train:
-            self.init_optim()
+        self.models["rgb"] = self._rgb_model(bb)
+        self.models["bg"] = self._background_model()
+        self._load_and_init_optim(train, start_iter_nr)
         self.update_method_state(iter_nr=start_iter_nr)
         self.update_occupancy_grid(iter_nr=start_iter_nr, decay=0.0, random_voxels=False, jitter_samples=False)
 
@@ -262,16 +165,6 @@ class NeRF(FieldMethod):
             groups.append({"params": list(self.models["bg"].parameters()), "lr": self.hyper_params.lr,
                            "name": "model_bg"})
         return groups
-
-    def _warmup_scheduler(self, is_first_iter):
-        if is_first_iter and self.scheduler_lr_decay is not None:           # nerf.py:437-443
-            from .schedulers import GradualWarmupScheduler
-            if self.hyper_params.nr_warmup_iters > 0:
-                self.lr_scheduler = GradualWarmupScheduler(self.optimizer, multiplier=1,
-                                                           total_epoch=self.hyper_params.nr_warmup_iters,
-                                                           after_scheduler=self.scheduler_lr_decay)
-            else:
-                self.lr_scheduler = self.scheduler_lr_decay
 
     # ---- occupancy grid (nerf.py:194-255, 414-421)
     @torch.no_grad()
@@ -298,11 +191,7 @@ class NeRF(FieldMethod):
         N = pack.get_nr_rays()
         dev = pack.ray_o.device
         if pack.is_empty():
-            zeros = lambda c: torch.zeros(N, c, device=dev)
-            r = {"rgb_fg": zeros(3), "depth": zeros(1), "weights_sum": zeros(1),
-                 "bg_transmittance": torch.ones(N, 1, device=dev), "nr_samples": torch.zeros(N, 1, dtype=torch.int32, device=dev)}
-            r["rgb"] = r["rgb_fg"] if rgb_bg is None else r["rgb_fg"] + r["bg_transmittance"] * rgb_bg
-            return r, None, None
+            return self._zero_renders(N, dev, rgb_bg, {"rgb_fg": (3,), "depth": (1,), "weights_sum": (1,)}), None, None
         samples_3d = pack.samples_3d
         density, geom_feat = self.models["density"](points=samples_3d, iter_nr=iter_nr)
         dirs = pack.samples_dirs
@@ -325,16 +214,9 @@ class NeRF(FieldMethod):
             rays_o, rays_d, raycast["t_near"], raycast["t_far"], self.models["density"], self.occupancy_grid, iter_nr,
             hp.min_dist_between_samples, hp.min_nr_samples_per_ray, hp.max_nr_samples_per_ray,
             hp.max_nr_imp_samples_per_ray, jitter_samples=self.is_training, importance_sampling=hp.do_importance_sampling)
-        median_bg = None
-        if self.models["bg"] is None:
-            rgb_bg = self.bg_color.expand(raycast["nr_rays"], 3)
-        else:
-            bg = render_contracted_bg(self.models["bg"], raycast, nr_samples_bg=hp.nr_samples_bg,
-                                      jitter_samples=self.is_training, iter_nr=iter_nr)
-            rgb_bg, median_bg = bg["pred_rgb"], bg["median_depth"]
-        renders, samples_3d, samples_grad = self.render_fg_volumetric(
-            pack, iter_nr=iter_nr, override=override,
-            rgb_bg=self.bg_color.view(3) if self.models["bg"] is None else rgb_bg)
+        rgb_bg, blend_bg, median_bg = self._render_bg(raycast, iter_nr)
+        renders, samples_3d, samples_grad = self.render_fg_volumetric(pack, iter_nr=iter_nr, override=override,
+                                                                      rgb_bg=blend_bg)
         renders["rgb_bg"] = rgb_bg
         if median_bg is not None:
             renders["median_depth_bg"] = median_bg
@@ -346,15 +228,10 @@ class NeRF(FieldMethod):
         hp = self.hyper_params
         masked = hp.is_training_masked if is_training_masked is None else is_training_masked
         self.update_method_state(iter_nr)
-        self._warmup_scheduler(is_first_iter)
+        if is_first_iter and self.scheduler_lr_decay is not None:           # nerf.py:437-443
+            self._install_warmup()
         res = self.render_rays(rays_o, rays_d, iter_nr=iter_nr)
-        vol = res["renders"]["volumetric"]
-        pred_rgb, pred_mask = vol["rgb"], vol["weights_sum"]
-        R = hp.nr_training_rays_per_pixel
-        if R > 1:
-            pred_rgb = pred_rgb.view(-1, R, 3).mean(dim=1)
-            pred_mask = pred_mask.view(-1, R, 1).mean(dim=1)
-        loss_rgb = loss_l1(gt_rgb, pred_rgb, mask=gt_mask) if masked else loss_l1(gt_rgb, pred_rgb)
+        loss_rgb, pred_mask = self._loss_rgb(res["renders"]["volumetric"], gt_rgb, gt_mask, masked)
         loss = loss_rgb
         loss_sparsity = loss_mask = 0.0
         points = self.bounding_primitive.get_random_points_inside(self.SPARSITY_NR_POINTS)
@@ -363,8 +240,7 @@ class NeRF(FieldMethod):
             loss_sparsity = torch.clamp((1 - torch.exp(-dens)).mean(), min=0.0) * hp.sparsity_weight  # losses.py:22-25
             loss = loss + loss_sparsity
         if masked and hp.mask_weight > 0.0:
-            pm = torch.clamp(pred_mask, min=0.0, max=1.0)
-            loss_mask = loss_l1(pm, gt_mask, mask=1 - gt_mask) * hp.mask_weight
+            loss_mask = self._loss_mask(pred_mask, gt_mask)
             loss = loss + loss_mask
         losses = {"loss": loss, "rgb": loss_rgb, "sparsity": loss_sparsity, "mask": loss_mask}
         return losses, {}, res["samples_3d"]

@@ -14,13 +14,13 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .background import intersect_bounding_primitive, render_contracted_bg
-from .field_method import FieldMethod, init_occupancy_grid
-from .models import RGB, ColorSH, NerfHash, OffsetsSDF
-from .surf import (SurfHyperParams, _bg_arg, eikonal_loss, field_stencil, get_logistic_beta_from_variance,
-                   logistic_distribution_stdev, map_range_val, stencil_gradients, FD_EPS)
-from .trainer import loss_l1
-from .volsurfs import RaySampler, VolumeRendering
+from .background import intersect_bounding_primitive
+from .field_method import (FieldMethod, bg_arg, composite_bg_grad, composite_grad_buffers, eikonal_loss,
+                           field_stencil, get_logistic_beta_from_variance, get_rays_samples_packed,
+                           importance_sampling_sdf_rounds, stencil_gradients)
+from .models import OffsetsSDF
+from .surf import SurfHyperParams, get_sdfs_curvature, logistic_distribution_stdev, map_range_val
+from .volsurfs import VolumeRendering
 
 MAX_SURFS = 16          # csrc/offsets_render.hip OR_MAX_SURFS
 
@@ -29,8 +29,8 @@ class OffsetsSurfsHyperParams(SurfHyperParams):
     """params/hyper_params.py (HyperParamsOffsetsSuRFs) with config/offsets_surfs/base_5.cfg applied.  Keyword
     arguments override single values; what Surf does not implement raises here too."""
 
-    def __init__(self, **overrides):
-        super().__init__()
+    def set_defaults(self):
+        super().set_defaults()
         # base_5.cfg
         self.init_phase_end_iter = 2000
         self.color_init_phase_end_iter = 3000
@@ -58,18 +58,11 @@ class OffsetsSurfsHyperParams(SurfHyperParams):
         self.offsets_weight = 0.0
         self.support_surfs_eikonal_weight = 0.04
         self.with_alpha_decay = True
-        for k, v in overrides.items():
-            if not hasattr(self, k):
-                raise KeyError(f"unknown hyper-parameter {k!r}")
-            setattr(self, k, v)
-        if self.rgb_use_lipshitz_mlp or self.lipshitz_weight > 0.0:
-            raise NotImplementedError("the Lipschitz MLP and its loss are not implemented")
-        if self.use_color_calibration or self.use_grad_scaler:
-            raise NotImplementedError("colour calibration and the grad scaler are not implemented")
+
+    def validate(self):
+        super().validate()
         if self.nr_inner_surfs + self.nr_outer_surfs + 1 > MAX_SURFS:
             raise _lib.VolsurfsHipError(f"at most {MAX_SURFS} surfaces")
-        if self.do_importance_sampling and self.min_nr_samples_per_ray < 3:
-            self.min_nr_samples_per_ray = 3
 
 
 def get_offsets_gt(nr_outer_surfs, nr_inner_surfs, delta_surfs, main_surf_shift=0.0):
@@ -85,34 +78,6 @@ def get_offsets_gt(nr_outer_surfs, nr_inner_surfs, delta_surfs, main_surf_shift=
         inner.append(cur)
     vals = inner[::-1] + outer
     return (torch.tensor(vals, dtype=torch.float64) if vals else torch.tensor([])) - main_surf_shift
-
-
-def get_sdfs_curvature(sdfs_fn, points, sdfs_gradients, rand_directions, iter_nr=None, eps=FD_EPS):
-    """fields_utils.py:69-166 for K surfaces with the random directions given: the K shifted point sets
-    (points + tangent_k eps) evaluated as ONE stencil call of 4 K M rows, column k of block k -> [M, K, 1]
-    ([M] for one surface).  Same rows and values as the reference's K calls."""
-    normals = F.normalize(sdfs_gradients, dim=-1)
-    K = sdfs_gradients.shape[1] if sdfs_gradients.dim() > 2 else 1
-    rand_directions = F.normalize(rand_directions, dim=-1)
-    if normals.dim() > 2:
-        rand_directions = rand_directions.unsqueeze(1)
-    tangent = torch.cross(normals, rand_directions, dim=-1)
-    M = points.shape[0]
-    if tangent.dim() > 2:
-        shifted = torch.cat([points + tangent[:, i] * eps for i in range(K)], 0)
-    else:
-        shifted = points + tangent * eps
-    res = field_stencil(sdfs_fn, shifted, iter_nr)
-    grads = stencil_gradients(res[0] if isinstance(res, tuple) else res)       # [K M, K, 3] or [M, 3]
-    if normals.dim() > 2:
-        shifted_n = torch.stack([F.normalize(grads[i * M:(i + 1) * M, i], dim=-1) if grads.dim() > 2
-                                 else F.normalize(grads[i * M:(i + 1) * M], dim=-1) for i in range(K)], 1)
-    else:
-        shifted_n = F.normalize(grads[:, 0] if grads.dim() > 2 else grads, dim=-1)
-    dot = torch.sum(torch.mul(normals, shifted_n), dim=-1, keepdim=True)
-    angle = torch.acos(torch.clamp(dot, -1.0 + 1e-6, 1.0 - 1e-6))
-    curv = angle / np.pi
-    return curv.squeeze(1) if K == 1 else curv
 
 
 # ---- fused per-ray chains (csrc/offsets_render.hip)
@@ -137,7 +102,7 @@ class _OffsetsComposite(torch.autograd.Function):
                 pack.samples_dt.numel() != S:
             raise _lib.VolsurfsHipError("offsets composite: sdfs [S,K], sdfs_grad / normals / rgb [S,K,3], "
                                         "transparency [S,K], a pack with dt")
-        bg, per_ray, bg_shape = _bg_arg(rgb_bg, N)
+        bg, per_ray, bg_shape = bg_arg(rgb_bg, N, "neus")
         dev = sdfs.device
         e = lambda *s: torch.empty(*s, device=dev)
         s_rgb, s_nrm, s_depth, s_ws = e(N, K, 3), e(N, K, 3), e(N, K, 1), e(N, K, 1)
@@ -164,21 +129,17 @@ class _OffsetsComposite(torch.autograd.Function):
         pack, ctx.pack = ctx.pack, None
         N = pack.get_nr_rays()
         S, K = sdfs.shape
-        if g_rgb is None:
-            g_rgb = torch.zeros(N, 3, device=sdfs.device)
         g_sdfs, g_grad, g_rgb_s = torch.empty_like(sdfs), torch.empty_like(sdfs_grad), torch.empty_like(rgb)
         g_t = torch.empty_like(transparency)
-        need_bg = bg is not None and ctx.needs_input_grad[6]
-        g_bg = torch.empty(N, 3, device=sdfs.device) if need_bg else None
         scratch = torch.empty(2 * S * K, device=sdfs.device)
         d = ctx.decay
+        g_rgb, g_bg = composite_grad_buffers(pack, g_rgb, bg, ctx.needs_input_grad[6])
         _lib.call("vsa_offsets_composite_bwd", pack.ray_start_end_idx, K, sdfs, sdfs_grad, normals, rgb,
                   transparency, dirs, pack.samples_dt, bg, ctx.per_ray, ctx.car, ctx.beta, int(d is not None),
-                  float(d) if d is not None else 0.0, s_rgb, s_alpha, s_T, bgT, g_rgb.contiguous(), g_sdfs, g_grad,
-                  g_rgb_s, g_t, g_bg, scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
-        if need_bg and not ctx.per_ray:
-            g_bg = g_bg.sum(0).view(ctx.bg_shape)
-        return None, g_sdfs, g_grad, None, g_rgb_s, g_t.view(ctx.tr_shape), g_bg, None, None, None, None
+                  float(d) if d is not None else 0.0, s_rgb, s_alpha, s_T, bgT, g_rgb, g_sdfs, g_grad, g_rgb_s, g_t, g_bg,
+                  scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
+        return (None, g_sdfs, g_grad, None, g_rgb_s, g_t.view(ctx.tr_shape), composite_bg_grad(ctx, g_bg), None, None,
+                None, None)
 
 
 def offsets_composite(pack, sdfs, sdfs_grad, normals, rgb, transparency, rgb_bg=None, cos_anneal_ratio=1.0,
@@ -222,32 +183,13 @@ def _sdfs_columns(res):
     return sdfs[..., 0:1] if sdfs.shape[2] > 1 else sdfs
 
 
-@torch.no_grad()
 def importance_sampling_sdfs(sdfs_fn, nr_surfs, pack_uniform, iter_nr, nr_imp_samples, logistic_beta_value,
                              min_dist_between_samples, jitter_samples=False):
-    """sdfs_utils.py:67-180 -> (imp_1, imp_2): round one on the uniform samples with beta / 2, round two on the
-    combined pack (K-column samples_values) with beta, nr_imp_samples // 2 each; each round's CDF is the fused
-    kernel."""
-    if pack_uniform.is_empty():
-        raise _lib.VolsurfsHipError("ray_samples_packed_uniform should not be empty")
-    call = (lambda p: sdfs_fn(p)) if iter_nr is None else (lambda p: sdfs_fn(p, iter_nr))
-    sdfs = _sdfs_columns(call(pack_uniform.samples_3d))
-    pack_uniform.update_dt(False)
-    beta = np.float32(logistic_beta_value)
-    cdf = sdfs_coarse_cdf(pack_uniform, sdfs, beta / np.float32(2.0))
-    imp_1 = VolumeRendering.importance_sample(pack_uniform, cdf, nr_imp_samples // 2, jitter_samples)
-    sdfs_1 = _sdfs_columns(call(imp_1.samples_3d))
-    pack_uniform.set_samples_values(sdfs.reshape(-1, nr_surfs))
-    imp_1.set_samples_values(sdfs_1.reshape(-1, nr_surfs))
-    combined = VolumeRendering.combine_ray_samples_packets(pack_uniform, imp_1, min_dist_between_samples)
-    sdfs_c = combined.samples_values
-    pack_uniform.remove_samples_values()
-    imp_1.remove_samples_values()
-    combined.remove_samples_values()         # (so that imp_2 is created without values, like imp_1)
-    combined.update_dt(False)
-    cdf = sdfs_coarse_cdf(combined, sdfs_c, beta)
-    imp_2 = VolumeRendering.importance_sample(combined, cdf, nr_imp_samples // 2, jitter_samples)
-    return imp_1, imp_2
+    """sdfs_utils.py:67-180 -> (imp_1, imp_2): importance_sampling_sdf_rounds on the K SDF columns, each round's CDF
+    the fused kernel."""
+    values_fn = lambda p: _sdfs_columns(sdfs_fn(p) if iter_nr is None else sdfs_fn(p, iter_nr))
+    return importance_sampling_sdf_rounds(values_fn, sdfs_coarse_cdf, nr_surfs, pack_uniform, nr_imp_samples,
+                                          logistic_beta_value, min_dist_between_samples, jitter_samples)
 
 
 def get_rays_samples_packed_sdfs(rays_o, rays_d, t_near, t_far, sdfs_fn, nr_surfs, logistic_beta_value,
@@ -255,26 +197,12 @@ def get_rays_samples_packed_sdfs(rays_o, rays_d, t_near, t_far, sdfs_fn, nr_surf
                                  min_nr_samples_per_ray=1, max_nr_samples_per_ray=64, max_nr_imp_samples_per_ray=32,
                                  jitter_samples=False, importance_sampling=True, values_dim=1):
     """sdfs_utils.py:435-510 -> (pack with dt, importance pack or None)."""
-    with torch.no_grad():
-        if occupancy_grid is not None:
-            pack = RaySampler.compute_samples_fg_in_grid_occupied_regions(
-                rays_o, rays_d, t_near, t_far, min_dist_between_samples, min_nr_samples_per_ray,
-                max_nr_samples_per_ray, jitter_samples, occupancy_grid.get_nr_voxels_per_dim(),
-                occupancy_grid.get_grid_extent(), occupancy_grid.get_grid_occupancy(), occupancy_grid.get_grid_roi(),
-                values_dim)
-        else:
-            pack = RaySampler.compute_samples_fg(rays_o, rays_d, t_near, t_far, min_dist_between_samples,
-                                                 min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples,
-                                                 values_dim)
-        imp = None
-        if not pack.is_empty():
-            if importance_sampling:
-                imp_1, imp_2 = importance_sampling_sdfs(sdfs_fn, nr_surfs, pack, iter_nr, max_nr_imp_samples_per_ray,
-                                                        logistic_beta_value, min_dist_between_samples, jitter_samples)
-                imp = VolumeRendering.combine_ray_samples_packets(imp_1, imp_2, min_dist_between_samples)
-                pack = VolumeRendering.combine_ray_samples_packets(pack, imp, min_dist_between_samples)
-            pack.update_dt(False)
-    return pack, imp
+    imp_fn = (lambda pack: VolumeRendering.combine_ray_samples_packets(
+        *importance_sampling_sdfs(sdfs_fn, nr_surfs, pack, iter_nr, max_nr_imp_samples_per_ray, logistic_beta_value,
+                                  min_dist_between_samples, jitter_samples),
+        min_dist_between_samples)) if importance_sampling else None
+    return get_rays_samples_packed(rays_o, rays_d, t_near, t_far, imp_fn, occupancy_grid, min_dist_between_samples,
+                                   min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples, values_dim)
 
 
 def appearance_rows(model, points, dirs, normals, geom_feat, iter_nr=None):
@@ -300,30 +228,18 @@ class OffsetsSurfs(FieldMethod):
     RENDER_MODES = ("volumetric", "sphere_traced")
     render_sphere_traced = False           # render_rays adds renders["sphere_traced"] outside training
     SPHERE_TRACED_MAX_STEPS, SPHERE_TRACED_THRESH = 100, 1e-3    # render_rays' call (offsets_surfs.py:955-961)
-    OCCUPANCY_EVERY = 50                   # update_occupancy_grid_every_nr_iters
-    OCCUPANCY_MAX_VARIANCE = 0.8
-    OCCUPANCY_THRESH = 1e-4
     OFFSETS_INIT_NR_POINTS = 30000         # offsets_surfs.py:1175
-    NR_RANDOM_POINTS = 1024                # :1264
-    OFFSURFACE_SCALE = 1e2
     DECAY_START, DECAY_END = 1000.0, 10.0  # alpha_decay_factor over the first phase
 
     def __init__(self, train, hyper_params, load_checkpoints_path, save_checkpoints_path, bounding_primitive,
                  models_path, bg_color=None, start_iter_nr=0):
         hp = hyper_params
-        self.hyper_params = hp
-        self.load_checkpoints_path, self.save_checkpoints_path = load_checkpoints_path, save_checkpoints_path
-        self.bounding_primitive = bounding_primitive
-        self.bg_color = None if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32).cuda().view(1, 3)
-        self.optimizer = self.lr_scheduler = self.scheduler_lr_decay = None
-        self.is_training = bool(train)
         if models_path is None and start_iter_nr == 0:
             raise ValueError("models_path must be a folder holding the surf method's sdf.pt")
+        bb = self._init_common(train, hp, load_checkpoints_path, save_checkpoints_path, bounding_primitive, bg_color)
         stdev = logistic_distribution_stdev(get_logistic_beta_from_variance(hp.first_phase_variance_start_value))
         self.delta_surfs = stdev * hp.delta_surfs_multiplier
         self.offsets_gt = get_offsets_gt(hp.nr_outer_surfs, hp.nr_inner_surfs, self.delta_surfs)
-        bb = bounding_primitive.get_radius() * 2.0
-        self.models = {}
         sdfs = OffsetsSDF(in_channels=3, mlp_layers_dims=hp.sdf_mlp_layers_dims, encoding_type=hp.sdf_encoding_type,
                           nr_inner_surfs=hp.nr_inner_surfs, nr_outer_surfs=hp.nr_outer_surfs,
                           geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=0, bb_sides=bb)
@@ -337,7 +253,6 @@ class OffsetsSurfs(FieldMethod):
         self.cos_anneal_ratio = 1.0
         self.with_alpha_decay = hp.with_alpha_decay
         self.alpha_decay_factor = self.DECAY_START
-        self.occupancy_grid = init_occupancy_grid(bounding_primitive) if hp.use_occupancy_grid else None
         for i in range(self.nr_surfs):
             m = self._appearance_model(3, hp.rgb_view_dep, hp.rgb_normal_dep, hp.rgb_geom_feat_dep, bb)
             if hp.are_surfs_colors_indep:
@@ -353,13 +268,8 @@ class OffsetsSurfs(FieldMethod):
             else:
                 self.models["alpha"] = m
                 break
-        self.models["bg"] = NerfHash(in_channels=3, pos_encoder_type=hp.bg_pos_encoder_type,
-                                     dir_encoder_type=hp.bg_dir_encoder_type,
-                                     nr_iters_for_c2f=hp.bg_nr_iters_for_c2f) if self.bg_color is None else None
-        if start_iter_nr > 0:
-            self.load(start_iter_nr)
-        if train:
-            self.init_optim()
+        self.models["bg"] = self._background_model()
+        self._load_and_init_optim(train, start_iter_nr)
         if models_path is not None and start_iter_nr == 0:
             ckpt = os.path.join(models_path, "sdf.pt")
             if not os.path.exists(ckpt):
@@ -372,18 +282,6 @@ class OffsetsSurfs(FieldMethod):
                 self.models["bg"].load_state_dict(torch.load(ckpt, map_location="cuda"))
         self.update_method_state(start_iter_nr)
         self.update_occupancy_grid(iter_nr=start_iter_nr)
-
-    def _appearance_model(self, out_channels, view_dep, normal_dep, geom_feat_dep, bb):
-        hp = self.hyper_params
-        if hp.appearance_predict_sh_coeffs:
-            return ColorSH(in_channels=3, out_channels=out_channels, mlp_layers_dims=hp.rgb_mlp_layers_dims,
-                           pos_encoder_type=hp.rgb_pos_encoder_type, sh_deg=hp.sh_degree, normal_dep=normal_dep,
-                           geom_feat_dep=geom_feat_dep, in_geom_feat_size=hp.geom_feat_size,
-                           nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
-        return RGB(in_channels=3, out_channels=out_channels, mlp_layers_dims=hp.rgb_mlp_layers_dims,
-                   pos_encoder_type=hp.rgb_pos_encoder_type, dir_encoder_type=hp.rgb_dir_encoder_type,
-                   sh_deg=hp.sh_degree, view_dep=view_dep, normal_dep=normal_dep, geom_feat_dep=geom_feat_dep,
-                   in_geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
 
     def parameters(self):
         return super().parameters() + self.models["sdfs"].heads_parameters()
@@ -420,22 +318,11 @@ class OffsetsSurfs(FieldMethod):
             s.load_heads_state_dicts([torch.load(f, map_location="cuda") for f in files])
         return path
 
-    # ---- occupancy grid (offsets_surfs.py:387-418): the full grid, min_k |sdf_k|, decay 0
-    @torch.no_grad()
+    # ---- occupancy grid (offsets_surfs.py:387-418): min_k |sdf_k|, decay 0
     def update_occupancy_grid(self, iter_nr=None, decay=0.0):
-        g = self.occupancy_grid
-        if g is None:
-            return
-        pts, idx = g.get_grid_samples(False)
-        sdfs = [self.models["sdfs"](b, iter_nr=iter_nr)[0] for b in torch.split(pts, 256 * 256 * 100, dim=0)]
-        sdfs = torch.cat(sdfs, 0) if len(sdfs) > 1 else sdfs[0]
-        sdf = torch.min(torch.abs(sdfs.squeeze(-1)), dim=-1, keepdim=True)[0]
-        beta = torch.ones_like(sdf) * get_logistic_beta_from_variance(min(self.OCCUPANCY_MAX_VARIANCE, self.variance))
-        g.update_grid_values(idx, sdf, decay)
-        g.update_grid_occupancy_with_sdf_values(idx, beta, self.OCCUPANCY_THRESH, False)
-
-    def _rebuild_occupancy(self, iter_nr):
-        self.update_occupancy_grid(iter_nr=iter_nr)
+        self._update_sdf_occupancy(self.models["sdfs"],
+                                   lambda sdfs: torch.min(torch.abs(sdfs.squeeze(-1)), dim=-1, keepdim=True)[0],
+                                   iter_nr, decay)
 
     # ---- phases (offsets_surfs.py:1011-1128)
     def update_method_state(self, iter_nr):
@@ -468,10 +355,7 @@ class OffsetsSurfs(FieldMethod):
                 s.unfreeze_offsets()
                 self.update_occupancy_grid(iter_nr)
                 if self.lr_scheduler is None and self.scheduler_lr_decay is not None:
-                    from .schedulers import GradualWarmupScheduler
-                    self.lr_scheduler = GradualWarmupScheduler(self.optimizer, multiplier=1,
-                                                               total_epoch=hp.nr_warmup_iters,
-                                                               after_scheduler=self.scheduler_lr_decay)
+                    self._install_warmup()
                 self.just_started_first_phase = False
             self.cos_anneal_ratio = 1.0
             self.variance = map_range_val(iter_nr, col_end, first_end, hp.first_phase_variance_start_value,
@@ -510,13 +394,10 @@ class OffsetsSurfs(FieldMethod):
 
     def _empty_renders(self, N, dev, rgb_bg):
         K = self.nr_surfs
-        z = lambda *s: torch.zeros(*s, device=dev)
-        r = {"surfs_rgb": z(N, K, 3), "surfs_normals": z(N, K, 3), "surfs_depths": z(N, K, 1),
-             "surfs_weight_sum": z(N, K, 1), "surfs_alpha": z(N, K, 1),
-             "surfs_transmittance": torch.ones(N, K, 1, device=dev), "surfs_blending_weights": z(N, K, 1),
-             "rgb_fg": z(N, 3), "bg_transmittance": torch.ones(N, 1, device=dev),
-             "nr_samples": torch.zeros(N, 1, dtype=torch.int32, device=dev)}
-        r["rgb"] = r["rgb_fg"] if rgb_bg is None else r["rgb_fg"] + rgb_bg * r["bg_transmittance"]
+        r = self._zero_renders(N, dev, rgb_bg, {
+            "surfs_rgb": (K, 3), "surfs_normals": (K, 3), "surfs_depths": (K, 1), "surfs_weight_sum": (K, 1),
+            "surfs_alpha": (K, 1), "surfs_blending_weights": (K, 1), "rgb_fg": (3,)})
+        r["surfs_transmittance"] = torch.ones(N, K, 1, device=dev)
         return r
 
     def render_fg_volumetric(self, pack, logistic_beta_value=2048.0, cos_anneal_ratio=1.0, iter_nr=None,
@@ -615,13 +496,7 @@ class OffsetsSurfs(FieldMethod):
             self.occupancy_grid, iter_nr, hp.min_dist_between_samples, hp.min_nr_samples_per_ray,
             hp.max_nr_samples_per_ray, hp.max_nr_imp_samples_per_ray, jitter_samples=self.is_training,
             importance_sampling=hp.do_importance_sampling)
-        if self.models["bg"] is None:
-            rgb_bg = self.bg_color.expand(raycast["nr_rays"], 3)
-            blend_bg = self.bg_color.view(3)
-        else:
-            bg = render_contracted_bg(self.models["bg"], raycast, nr_samples_bg=hp.nr_samples_bg,
-                                      jitter_samples=self.is_training, iter_nr=iter_nr)
-            rgb_bg = blend_bg = bg["pred_rgb"]
+        rgb_bg, blend_bg, _ = self._render_bg(raycast, iter_nr)
         renders, samples_3d, samples_grad = self.render_fg_volumetric(pack, beta, car, iter_nr, blend_bg)
         renders["rgb_bg"] = rgb_bg
         all_renders = {"volumetric": renders}
@@ -666,34 +541,23 @@ class OffsetsSurfs(FieldMethod):
                 loss, loss_eik_supp = self._offsets_init_losses(iter_nr)
         else:
             res = self.render_rays(rays_o, rays_d, iter_nr=iter_nr)
-            vol = res["renders"]["volumetric"]
             samples_3d, s_grad = res["samples_3d"], res["samples_grad"]
-            pred_rgb = vol["rgb"]
-            R = hp.nr_training_rays_per_pixel
-            if R > 1:
-                pred_rgb = pred_rgb.view(-1, R, 3).mean(dim=1)
-            loss_rgb = loss_l1(gt_rgb, pred_rgb, mask=gt_mask) if masked else loss_l1(gt_rgb, pred_rgb)
+            loss_rgb, _ = self._loss_rgb(res["renders"]["volumetric"], gt_rgb, gt_mask, masked)
             loss = loss_rgb
-            with torch.no_grad():
-                r_pts = self.bounding_primitive.get_random_points_inside(self.NR_RANDOM_POINTS)
-            r_full = field_stencil(s.forward, r_pts, iter_nr)[0]
-            r_sdfs, r_grad = r_full[:r_pts.shape[0]], stencil_gradients(r_full)
+            r_sdfs, r_grad = self._random_points_stencil(s.forward, iter_nr)
             has_samples = samples_3d is not None and samples_3d.shape[0] > 0
             main = self.main_surf_idx
             if hp.eikonal_weight > 0.0 and s.is_training_main_surf:
-                loss_eik_main = eikonal_loss(r_grad[:, main]) * hp.eikonal_weight
-                if has_samples:
-                    loss_eik_main = loss_eik_main + eikonal_loss(s_grad[:, main]) * hp.eikonal_weight
+                loss_eik_main = self._loss_eikonal(r_grad[:, main], s_grad[:, main] if has_samples else None,
+                                                   hp.eikonal_weight)
                 loss = loss + loss_eik_main
             if hp.eikonal_weight > 0.0 and hp.support_surfs_eikonal_weight > 0.0 and s.is_training_offsets and \
                     self.nr_surfs > 1:
-                loss_eik_supp = eikonal_loss(self._support(r_grad)) * hp.support_surfs_eikonal_weight
-                if has_samples:
-                    loss_eik_supp = loss_eik_supp + eikonal_loss(self._support(s_grad)) * hp.support_surfs_eikonal_weight
+                loss_eik_supp = self._loss_eikonal(self._support(r_grad), self._support(s_grad) if has_samples else None,
+                                                   hp.support_surfs_eikonal_weight)
                 loss = loss + loss_eik_supp
             if hp.offsurface_weight > 0.0:
-                loss_offsurface = torch.exp(-self.OFFSURFACE_SCALE * torch.abs(r_sdfs[:, main])).mean() * \
-                    hp.offsurface_weight
+                loss_offsurface = self._loss_offsurface(r_sdfs[:, main])
                 loss = loss + loss_offsurface
             if hp.curvature_weight > 0.0 and has_samples:
                 curv = get_sdfs_curvature(s, samples_3d, s_grad, torch.randn_like(samples_3d), iter_nr=iter_nr)

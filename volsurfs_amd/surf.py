@@ -4,28 +4,27 @@ a NeuS signed distance field and a radiance field trained from posed images by v
 the NeuS foreground composite with the background blend (`neus_composite`) and one round of the coarse CDF of
 importance sampling (`sdf_coarse_cdf`); everything else is the project's existing HIP operators (permutohedral
 encoder, fused MLP, occupancy grid, packed samplers).  `isosurface.extract_surf_level_sets` meshes the SDF."""
-import math
-
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .background import intersect_bounding_primitive, render_contracted_bg
-from .field_method import FieldMethod, init_occupancy_grid
-from .models import RGB, SDF, ColorSH, NerfHash
-from .trainer import loss_l1
-from .volsurfs import RaySampler, VolumeRendering
+from .background import intersect_bounding_primitive
+from .field_method import (FD_EPS, FieldHyperParams, FieldMethod, bg_arg, composite_bg_grad, composite_grad_buffers,
+                           field_stencil, get_logistic_beta_from_variance, get_rays_samples_packed,
+                           importance_sampling_sdf_rounds, stencil_gradients)
+from .field_method import eikonal_loss  # noqa: F401  (its users import it from here)
+from .models import SDF
+from .volsurfs import VolumeRendering
 
 
-class SurfHyperParams:
+class SurfHyperParams(FieldHyperParams):
     """params/hyper_params.py (HyperParams, HyperParamsSuRF) with config/surf/base.cfg applied: the keys and values
     a `surf` run of the reference trains with.  Keyword arguments override single values."""
 
-    def __init__(self, **overrides):
+    def set_defaults(self):
+        super().set_defaults()
         # lr schedule
-        self.lr = 1e-3
-        self.nr_warmup_iters = 3000
         self.lr_milestones = [80000, 90000]
         self.training_end_iter = 100000
         # phases
@@ -35,67 +34,30 @@ class SurfHyperParams:
         self.first_phase_variance_end_value = 0.7
         self.reduce_curv_start_iter = None
         self.reduce_curv_end_iter = None
-        # rays
-        self.training_rays_batch_size = 512
-        self.is_nr_training_rays_dynamic = True
-        self.target_nr_of_training_samples = 512 * (64 + 16 + 16)
-        self.test_rays_batch_size = 16384
-        self.nr_training_rays_per_pixel = 1
-        self.nr_test_rays_per_pixel = 1
-        self.jitter_training_rays = True
-        self.jitter_test_rays = False
-        # masks
-        self.is_training_masked = False
-        self.is_testing_masked = False
-        self.mask_weight = 0.0
         # sdf
-        self.geom_feat_size = 32
         self.sdf_encoding_type = "permutohash"
         self.sdf_mlp_layers_dims = [32, 32, 32]
         self.sdf_mlp_output_dims = 1
         self.sdf_nr_iters_for_c2f = 5000
         # appearance
-        self.rgb_pos_encoder_type = "permutohash"
-        self.rgb_dir_encoder_type = "spherical_harmonics"
-        self.rgb_mlp_layers_dims = [128, 128, 64]
         self.rgb_mlp_output_dims = 3
-        self.sh_degree = 3
         self.appearance_predict_sh_coeffs = True
-        self.rgb_view_dep = True
         self.rgb_normal_dep = True
-        self.rgb_geom_feat_dep = True
         self.rgb_use_lipshitz_mlp = False
-        self.rgb_nr_iters_for_c2f = 0
         self.use_color_calibration = False
         self.use_grad_scaler = False
-        # background
-        self.bg_pos_encoder_type = "permutohash"
-        self.bg_dir_encoder_type = "spherical_harmonics"
-        self.bg_nr_iters_for_c2f = 0
-        self.nr_samples_bg = 64
-        # sampling
-        self.use_occupancy_grid = True
-        self.do_importance_sampling = True
-        self.min_dist_between_samples = 1e-4
-        self.min_nr_samples_per_ray = 1
-        self.max_nr_samples_per_ray = 64
-        self.max_nr_imp_samples_per_ray = 32
         # losses
         self.eikonal_weight = 0.04
         self.curvature_weight = 0.65
         self.lipshitz_weight = 0.0
         self.offsurface_weight = 1e-4
-        for k, v in overrides.items():
-            if not hasattr(self, k):
-                raise KeyError(f"unknown hyper-parameter {k!r}")
-            setattr(self, k, v)
+
+    def validate(self):
         if self.rgb_use_lipshitz_mlp or self.lipshitz_weight > 0.0:
             raise NotImplementedError("the Lipschitz MLP and its loss are not implemented")
         if self.use_color_calibration or self.use_grad_scaler:
             raise NotImplementedError("colour calibration and the grad scaler are not implemented")
-        # hyper_params.py:173-178: the CDF of importance sampling needs 3 samples per ray
-        if self.do_importance_sampling and self.min_nr_samples_per_ray < 3:
-            self.min_nr_samples_per_ray = 3
+        super().validate()
 
 
 # ---- schedule helpers (utils/common.py, utils/logistic_distribution.py)
@@ -105,11 +67,6 @@ def map_range_val(input_val, input_start, input_end, output_start, output_end):
     if input_start >= input_end:
         return output_end
     return output_start + ((output_end - output_start) / (input_end - input_start)) * (clamped - input_start)
-
-
-def get_logistic_beta_from_variance(variance):
-    """logistic_distribution.py:5-8: clip(exp(10 variance), 1e-6, 1e6) (float64)."""
-    return float(np.clip(np.exp(variance * 10.0), 1e-6, 1e6))
 
 
 def logistic_distribution_stdev(beta=1.0):
@@ -125,53 +82,46 @@ def curvature_weight_schedule(iter_nr, reduce_curv_start_iter, reduce_curv_end_i
     return 0.0
 
 
-# ---- field derivatives and losses (utils/fields_utils.py, utils/losses.py)
-FD_EPS = 1e-4
-
-
-def field_stencil(field_fn, points, iter_nr=None, eps=FD_EPS):
-    """The field on [p, p + eps x, p + eps y, p + eps z] as ONE call of 4M rows (fields_utils.py:9-31)."""
-    with torch.no_grad():
-        px, py, pz = points.clone(), points.clone(), points.clone()
-        px[:, 0] += eps
-        py[:, 1] += eps
-        pz[:, 2] += eps
-        full = torch.cat([points, px, py, pz], 0)
-    return field_fn(full) if iter_nr is None else field_fn(full, iter_nr)
-
-
-def stencil_gradients(sdfs_full, eps=FD_EPS):
-    """fields_utils.py:33-56: the forward differences of the stencil's first column -> [M, 3]."""
-    if sdfs_full.dim() < 2:
-        sdfs_full = sdfs_full.unsqueeze(1)
-    if sdfs_full.shape[-1] > 1:
-        sdfs_full = sdfs_full[:, 0].unsqueeze(1)
-    sdf, sx, sy, sz = sdfs_full.chunk(4, dim=0)
-    return torch.cat([(sx - sdf) / eps, (sy - sdf) / eps, (sz - sdf) / eps], dim=-1)
-
-
+# ---- field derivatives (utils/fields_utils.py; the stencil itself is field_method.py's)
 def get_field_gradients(field_fn, points, iter_nr=None, eps=FD_EPS):
     """fields_utils.py:6-66 (grad_method "finite-diff")."""
     res = field_stencil(field_fn, points, iter_nr, eps)
     return stencil_gradients(res[0] if isinstance(res, tuple) else res, eps)
 
 
+def get_sdfs_curvature(sdfs_fn, points, sdfs_gradients, rand_directions, iter_nr=None, eps=FD_EPS):
+    """fields_utils.py:69-166 for K surfaces with the random directions given: the K shifted point sets
+    (points + tangent_k eps) evaluated as ONE stencil call of 4 K M rows, column k of block k -> [M, K, 1]
+    ([M] for one surface).  Same rows and values as the reference's K calls."""
+    normals = F.normalize(sdfs_gradients, dim=-1)
+    K = sdfs_gradients.shape[1] if sdfs_gradients.dim() > 2 else 1
+    rand_directions = F.normalize(rand_directions, dim=-1)
+    if normals.dim() > 2:
+        rand_directions = rand_directions.unsqueeze(1)
+    tangent = torch.cross(normals, rand_directions, dim=-1)
+    M = points.shape[0]
+    if tangent.dim() > 2:
+        shifted = torch.cat([points + tangent[:, i] * eps for i in range(K)], 0)
+    else:
+        shifted = points + tangent * eps
+    res = field_stencil(sdfs_fn, shifted, iter_nr)
+    grads = stencil_gradients(res[0] if isinstance(res, tuple) else res)       # [K M, K, 3] or [M, 3]
+    if normals.dim() > 2:
+        shifted_n = torch.stack([F.normalize(grads[i * M:(i + 1) * M, i], dim=-1) if grads.dim() > 2
+                                 else F.normalize(grads[i * M:(i + 1) * M], dim=-1) for i in range(K)], 1)
+    else:
+        shifted_n = F.normalize(grads[:, 0] if grads.dim() > 2 else grads, dim=-1)
+    dot = torch.sum(torch.mul(normals, shifted_n), dim=-1, keepdim=True)
+    angle = torch.acos(torch.clamp(dot, -1.0 + 1e-6, 1.0 - 1e-6))
+    curv = angle / np.pi
+    return curv.squeeze(1) if K == 1 else curv
+
+
 def get_sdf_curvature(sdf_fn, points, sdf_gradients, rand_directions, iter_nr=None, eps=FD_EPS):
     """fields_utils.py:69-166 for one surface, with the random directions given (the method passes
     torch.randn_like(points)): the angle between the normal and the normal a step eps along a random tangent,
-    over pi -> [M]."""
-    normals = F.normalize(sdf_gradients, dim=-1)
-    rand_directions = F.normalize(rand_directions, dim=-1)
-    tangent = torch.cross(normals, rand_directions, dim=-1)
-    shifted_normals = F.normalize(get_field_gradients(sdf_fn, points + tangent * eps, iter_nr=iter_nr), dim=-1)
-    dot = torch.sum(torch.mul(normals, shifted_normals), dim=-1, keepdim=True)
-    angle = torch.acos(torch.clamp(dot, -1.0 + 1e-6, 1.0 - 1e-6))
-    return (angle / math.pi).squeeze(1)
-
-
-def eikonal_loss(sdf_gradients, distance_scale=1.0):
-    """utils/losses.py:28-33."""
-    return ((torch.linalg.norm(sdf_gradients, ord=2, dim=-1) - distance_scale) ** 2).mean()
+    over pi -> [M].  get_sdfs_curvature on gradients [M, 3]."""
+    return get_sdfs_curvature(sdf_fn, points, sdf_gradients, rand_directions, iter_nr, eps)
 
 
 def neus_alphas_torch(samples_dirs, samples_dt, sdf, gradients, cos_anneal_ratio, logistic_beta):
@@ -187,16 +137,6 @@ def neus_alphas_torch(samples_dirs, samples_dt, sdf, gradients, cos_anneal_ratio
 
 
 # ---- fused per-ray chains (csrc/surf_render.hip)
-def _bg_arg(rgb_bg, N):
-    if rgb_bg is None:
-        return None, 0, None
-    if rgb_bg.dim() == 2 and rgb_bg.shape == (N, 3) and N != 1:
-        return _lib.check_f32(rgb_bg.contiguous()), 1, rgb_bg.shape
-    if rgb_bg.numel() == 3:
-        return _lib.check_f32(rgb_bg.reshape(3).contiguous()), 0, rgb_bg.shape
-    raise _lib.VolsurfsHipError(f"neus composite: rgb_bg must be [N,3] or one colour, got {tuple(rgb_bg.shape)}")
-
-
 class _NeusComposite(torch.autograd.Function):
     """render_fg_volumetric's NeuS alpha / transmittance / weights / integrals and render_rays' background blend as
     one launch each way (vsa_neus_composite_fwd / _bwd).  Differentiable inputs: sdf, sdf_grad, rgb, rgb_bg;
@@ -213,7 +153,7 @@ class _NeusComposite(torch.autograd.Function):
         if sdf.numel() != S or sdf_grad.shape != (S, 3) or normals.shape != (S, 3) or rgb.shape[1] != 3 or \
                 pack.samples_dt.numel() != S:
             raise _lib.VolsurfsHipError("neus composite: sdf [S,1], sdf_grad / normals / rgb [S,3], a pack with dt")
-        bg, per_ray, bg_shape = _bg_arg(rgb_bg, N)
+        bg, per_ray, bg_shape = bg_arg(rgb_bg, N, "neus")
         dev = rgb.device
         rgb_fg, rgb_out, nrm = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev)
         wsum, depth = torch.empty(N, 1, device=dev), torch.empty(N, 1, device=dev)
@@ -236,19 +176,13 @@ class _NeusComposite(torch.autograd.Function):
         sdf, sdf_grad, dirs, rgb, bg, wsum = ctx.saved_tensors
         pack, ctx.pack = ctx.pack, None
         N = pack.get_nr_rays()
-        if g_rgb is None:
-            g_rgb = torch.zeros(N, 3, device=rgb.device)
         g_sdf, g_grad, g_rgb_s = torch.empty_like(sdf), torch.empty_like(sdf_grad), torch.empty_like(rgb)
-        need_bg = bg is not None and ctx.needs_input_grad[5]
-        g_bg = torch.empty(N, 3, device=rgb.device) if need_bg else None
         scratch = torch.empty(2 * rgb.shape[0], device=rgb.device)
+        g_rgb, g_bg = composite_grad_buffers(pack, g_rgb, bg, ctx.needs_input_grad[5])
         _lib.call("vsa_neus_composite_bwd", pack.ray_start_end_idx, sdf, sdf_grad, dirs, pack.samples_dt, rgb, bg,
-                  ctx.per_ray, ctx.car, ctx.beta, wsum, g_rgb.contiguous(),
-                  None if g_wsum is None else g_wsum.contiguous(), g_sdf, g_grad, g_rgb_s, g_bg, scratch, N,
-                  bool(VolumeRendering.bug_compat), _lib.stream_ptr())
-        if need_bg and not ctx.per_ray:
-            g_bg = g_bg.sum(0).view(ctx.bg_shape)
-        return None, g_sdf, g_grad, None, g_rgb_s, g_bg, None, None, None
+                  ctx.per_ray, ctx.car, ctx.beta, wsum, g_rgb, None if g_wsum is None else g_wsum.contiguous(), g_sdf,
+                  g_grad, g_rgb_s, g_bg, scratch, N, bool(VolumeRendering.bug_compat), _lib.stream_ptr())
+        return None, g_sdf, g_grad, None, g_rgb_s, composite_bg_grad(ctx, g_bg), None, None, None
 
 
 def neus_composite(pack, sdf, sdf_grad, normals, rgb, rgb_bg=None, cos_anneal_ratio=1.0, logistic_beta=2048.0,
@@ -285,30 +219,13 @@ def _sdf_column(res):
     return sdf[:, 0:1] if sdf.shape[1] > 1 else sdf
 
 
-@torch.no_grad()
 def importance_sampling_sdf(sdf_fn, pack_uniform, iter_nr, nr_samples, logistic_beta_value, min_dist_between_samples,
                             jitter_samples=False):
-    """sdf_utils.py:40-175 -> (imp_1, imp_2): round one on the uniform samples with beta / 2, round two on the
-    combined pack with beta, nr_samples // 2 each; the coarse CDF of each round is the fused kernel."""
-    if pack_uniform.is_empty():
-        raise _lib.VolsurfsHipError("ray_samples_packed_uniform should not be empty")
-    sdf = _sdf_column(sdf_fn(pack_uniform.samples_3d) if iter_nr is None else sdf_fn(pack_uniform.samples_3d, iter_nr))
-    pack_uniform.update_dt(False)
-    beta = np.float32(logistic_beta_value)          # torch.ones_like(dt) * logistic_beta_value
-    cdf = sdf_coarse_cdf(pack_uniform, sdf, beta / np.float32(2.0))
-    imp_1 = VolumeRendering.importance_sample(pack_uniform, cdf, nr_samples // 2, jitter_samples)
-    sdf_1 = _sdf_column(sdf_fn(imp_1.samples_3d) if iter_nr is None else sdf_fn(imp_1.samples_3d, iter_nr))
-    pack_uniform.set_samples_values(sdf)
-    imp_1.set_samples_values(sdf_1)
-    combined = VolumeRendering.combine_ray_samples_packets(pack_uniform, imp_1, min_dist_between_samples)
-    sdf_c = combined.samples_values
-    pack_uniform.remove_samples_values()
-    imp_1.remove_samples_values()
-    combined.remove_samples_values()         # (so that imp_2 is created without values, like imp_1)
-    combined.update_dt(False)
-    cdf = sdf_coarse_cdf(combined, sdf_c, beta)
-    imp_2 = VolumeRendering.importance_sample(combined, cdf, nr_samples // 2, jitter_samples)
-    return imp_1, imp_2
+    """sdf_utils.py:40-175 -> (imp_1, imp_2): importance_sampling_sdf_rounds on the one SDF column, the coarse CDF
+    of each round the fused kernel."""
+    values_fn = lambda p: _sdf_column(sdf_fn(p) if iter_nr is None else sdf_fn(p, iter_nr))
+    return importance_sampling_sdf_rounds(values_fn, sdf_coarse_cdf, 1, pack_uniform, nr_samples, logistic_beta_value,
+                                          min_dist_between_samples, jitter_samples)
 
 
 def get_rays_samples_packed_sdf(rays_o, rays_d, t_near, t_far, sdf_fn, logistic_beta_value, occupancy_grid=None,
@@ -316,26 +233,12 @@ def get_rays_samples_packed_sdf(rays_o, rays_d, t_near, t_far, sdf_fn, logistic_
                                 max_nr_samples_per_ray=64, max_nr_imp_samples_per_ray=32, jitter_samples=False,
                                 importance_sampling=True, values_dim=1):
     """sdf_utils.py:178-281 -> (pack with dt, importance pack or None)."""
-    with torch.no_grad():
-        if occupancy_grid is not None:
-            pack = RaySampler.compute_samples_fg_in_grid_occupied_regions(
-                rays_o, rays_d, t_near, t_far, min_dist_between_samples, min_nr_samples_per_ray,
-                max_nr_samples_per_ray, jitter_samples, occupancy_grid.get_nr_voxels_per_dim(),
-                occupancy_grid.get_grid_extent(), occupancy_grid.get_grid_occupancy(), occupancy_grid.get_grid_roi(),
-                values_dim)
-        else:
-            pack = RaySampler.compute_samples_fg(rays_o, rays_d, t_near, t_far, min_dist_between_samples,
-                                                 min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples,
-                                                 values_dim)
-        imp = None
-        if not pack.is_empty():
-            if importance_sampling:
-                imp_1, imp_2 = importance_sampling_sdf(sdf_fn, pack, iter_nr, max_nr_imp_samples_per_ray,
-                                                       logistic_beta_value, min_dist_between_samples, jitter_samples)
-                imp = VolumeRendering.combine_ray_samples_packets(imp_1, imp_2, min_dist_between_samples)
-                pack = VolumeRendering.combine_ray_samples_packets(pack, imp, min_dist_between_samples)
-            pack.update_dt(False)
-    return pack, imp
+    imp_fn = (lambda pack: VolumeRendering.combine_ray_samples_packets(
+        *importance_sampling_sdf(sdf_fn, pack, iter_nr, max_nr_imp_samples_per_ray, logistic_beta_value,
+                                 min_dist_between_samples, jitter_samples),
+        min_dist_between_samples)) if importance_sampling else None
+    return get_rays_samples_packed(rays_o, rays_d, t_near, t_far, imp_fn, occupancy_grid, min_dist_between_samples,
+                                   min_nr_samples_per_ray, max_nr_samples_per_ray, jitter_samples, values_dim)
 
 
 class Surf(FieldMethod):
@@ -351,13 +254,8 @@ class Surf(FieldMethod):
     RENDER_MODES = ("volumetric", "sphere_traced")
     render_sphere_traced = False           # render_rays adds renders["sphere_traced"] outside training
     SPHERE_TRACED_MAX_STEPS, SPHERE_TRACED_THRESH = 100, 1e-3    # render_rays' call (surf.py:735-741)
-    OCCUPANCY_EVERY = 50                   # update_method_state (surf.py:804-808)
-    OCCUPANCY_MAX_VARIANCE = 0.8           # update_occupancy_grid (surf.py:286-299)
-    OCCUPANCY_THRESH = 1e-4
     SPHERE_INIT_NR_POINTS = 30000          # surf.py:905
     SPHERE_INIT_EIKONAL_WEIGHT = 1e-3      # surf.py:927
-    NR_RANDOM_POINTS = 1024                # surf.py:985
-    OFFSURFACE_SCALE = 1e2                 # surf.py:1031
 
     def __init__(self, train, hyper_params, load_checkpoints_path, save_checkpoints_path, bounding_primitive,
                  bg_color=None, start_iter_nr=0, init_sphere_radius=None):
@@ -365,44 +263,18 @@ class Surf(FieldMethod):
         if (start_iter_nr == 0 or start_iter_nr < hp.init_phase_end_iter) and init_sphere_radius is None:
             raise ValueError("init_sphere_radius must be given when training starts in the sphere-init phase "
                              f"(start_iter_nr {start_iter_nr} < init_phase_end_iter {hp.init_phase_end_iter})")
-        self.hyper_params = hp
-        self.load_checkpoints_path, self.save_checkpoints_path = load_checkpoints_path, save_checkpoints_path
-        self.bounding_primitive = bounding_primitive
-        self.bg_color = None if bg_color is None else torch.as_tensor(bg_color, dtype=torch.float32).cuda().view(1, 3)
-        self.optimizer = self.lr_scheduler = self.scheduler_lr_decay = None
-        self.is_training = bool(train)
-        self.occupancy_grid = init_occupancy_grid(bounding_primitive) if hp.use_occupancy_grid else None
+        bb = self._init_common(train, hp, load_checkpoints_path, save_checkpoints_path, bounding_primitive, bg_color)
         self.variance = hp.first_phase_variance_end_value
         self.cos_anneal_ratio = 1.0
         self.in_process_of_sphere_init = False
         self.just_started_first_phase = False
         self.init_sphere_radius = init_sphere_radius
-        bb = bounding_primitive.get_radius() * 2.0
-        self.models = {}
         self.models["sdf"] = SDF(in_channels=3, geom_feat_size=hp.geom_feat_size, mlp_layers_dims=hp.sdf_mlp_layers_dims,
                                  encoding_type=hp.sdf_encoding_type, nr_iters_for_c2f=hp.sdf_nr_iters_for_c2f,
                                  bb_sides=bb)
-        if hp.appearance_predict_sh_coeffs:
-            assert hp.rgb_view_dep, "SH coeffs only implemented for view dependent color"
-            self.models["rgb"] = ColorSH(in_channels=3, out_channels=3, mlp_layers_dims=hp.rgb_mlp_layers_dims,
-                                         pos_encoder_type=hp.rgb_pos_encoder_type, sh_deg=hp.sh_degree,
-                                         normal_dep=hp.rgb_normal_dep, geom_feat_dep=hp.rgb_geom_feat_dep,
-                                         in_geom_feat_size=hp.geom_feat_size,
-                                         nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f, bb_sides=bb)
-        else:
-            self.models["rgb"] = RGB(in_channels=3, out_channels=3, mlp_layers_dims=hp.rgb_mlp_layers_dims,
-                                     pos_encoder_type=hp.rgb_pos_encoder_type, dir_encoder_type=hp.rgb_dir_encoder_type,
-                                     sh_deg=hp.sh_degree, pos_dep=True, view_dep=hp.rgb_view_dep,
-                                     normal_dep=hp.rgb_normal_dep, geom_feat_dep=hp.rgb_geom_feat_dep,
-                                     in_geom_feat_size=hp.geom_feat_size, nr_iters_for_c2f=hp.rgb_nr_iters_for_c2f,
-                                     use_lipshitz_mlp=hp.rgb_use_lipshitz_mlp, bb_sides=bb)
-        self.models["bg"] = NerfHash(in_channels=3, pos_encoder_type=hp.bg_pos_encoder_type,
-                                     dir_encoder_type=hp.bg_dir_encoder_type,
-                                     nr_iters_for_c2f=hp.bg_nr_iters_for_c2f) if self.bg_color is None else None
-        if start_iter_nr > 0:
-            self.load(start_iter_nr)
-        if train:
-            self.init_optim()
+        self.models["rgb"] = self._rgb_model(bb)
+        self.models["bg"] = self._background_model()
+        self._load_and_init_optim(train, start_iter_nr)
         self.update_method_state(iter_nr=start_iter_nr)
         self.update_occupancy_grid(iter_nr=start_iter_nr)
 
@@ -419,21 +291,9 @@ class Surf(FieldMethod):
             groups.append({"params": list(m["bg"].parameters()), "weight_decay": 0.0, "lr": lr, "name": "bg"})
         return [g for g in groups if g["params"]]
 
-    # ---- occupancy grid (surf.py:246-302): the full grid, |sdf|, decay 0, beta of min(0.8, variance)
-    @torch.no_grad()
+    # ---- occupancy grid (surf.py:246-302): |sdf|, decay 0
     def update_occupancy_grid(self, iter_nr=None, decay=0.0):
-        g = self.occupancy_grid
-        if g is None:
-            return
-        pts, idx = g.get_grid_samples(False)
-        sdf = [self.models["sdf"].main_sdf(b, iter_nr=iter_nr)[0] for b in torch.split(pts, 256 * 256 * 100, dim=0)]
-        sdf = torch.abs(torch.cat(sdf, 0) if len(sdf) > 1 else sdf[0])
-        beta = torch.ones_like(sdf) * get_logistic_beta_from_variance(min(self.OCCUPANCY_MAX_VARIANCE, self.variance))
-        g.update_grid_values(idx, sdf, decay)
-        g.update_grid_occupancy_with_sdf_values(idx, beta, self.OCCUPANCY_THRESH, False)
-
-    def _rebuild_occupancy(self, iter_nr):
-        self.update_occupancy_grid(iter_nr=iter_nr)
+        self._update_sdf_occupancy(self.models["sdf"].main_sdf, torch.abs, iter_nr, decay)
 
     # ---- phases (surf.py:789-864)
     def update_method_state(self, iter_nr):
@@ -451,13 +311,7 @@ class Surf(FieldMethod):
         if self.just_started_first_phase:
             self.update_occupancy_grid(iter_nr)
             if self.is_training and self.lr_scheduler is None and self.scheduler_lr_decay is not None:
-                from .schedulers import GradualWarmupScheduler
-                if hp.nr_warmup_iters > 0:
-                    self.lr_scheduler = GradualWarmupScheduler(self.optimizer, multiplier=1,
-                                                               total_epoch=hp.nr_warmup_iters,
-                                                               after_scheduler=self.scheduler_lr_decay)
-                else:
-                    self.lr_scheduler = self.scheduler_lr_decay
+                self._install_warmup()
 
     # ---- rendering (surf.py:305-787)
     def render_fg_volumetric(self, pack, logistic_beta_value=2048.0, cos_anneal_ratio=1.0, iter_nr=None,
@@ -468,12 +322,9 @@ class Surf(FieldMethod):
         N = pack.get_nr_rays()
         dev = pack.ray_o.device
         if pack.is_empty():
-            zeros = lambda c: torch.zeros(N, c, device=dev)
-            r = {"rgb_fg": zeros(3), "depth_fg": zeros(1), "weights_sum": zeros(1), "normals": zeros(3),
-                 "bg_transmittance": torch.ones(N, 1, device=dev),
-                 "nr_samples": torch.zeros(N, 1, dtype=torch.int32, device=dev)}
-            r["rgb"] = r["rgb_fg"] if rgb_bg is None else r["rgb_fg"] + r["bg_transmittance"] * rgb_bg
-            return r, None, zeros(3)
+            r = self._zero_renders(N, dev, rgb_bg, {"rgb_fg": (3,), "depth_fg": (1,), "weights_sum": (1,),
+                                                     "normals": (3,)})
+            return r, None, torch.zeros(N, 3, device=dev)
         samples_3d = pack.samples_3d
         S = samples_3d.shape[0]
         sdf_full, feat_full = field_stencil(self.models["sdf"].forward, samples_3d, iter_nr)
@@ -542,14 +393,9 @@ class Surf(FieldMethod):
             hp.max_nr_imp_samples_per_ray, jitter_samples=self.is_training, importance_sampling=hp.do_importance_sampling)
         car = override.get("cos_anneal_ratio")
         car = self.cos_anneal_ratio if car is None else car
-        if self.models["bg"] is None:
-            rgb_bg, depth_bg = self.bg_color.expand(raycast["nr_rays"], 3), raycast["t_far"]
-            blend_bg = self.bg_color.view(3)
-        else:
-            bg = render_contracted_bg(self.models["bg"], raycast, nr_samples_bg=hp.nr_samples_bg,
-                                      jitter_samples=self.is_training, iter_nr=iter_nr)
-            rgb_bg, depth_bg = bg["pred_rgb"], bg["median_depth"]
-            blend_bg = rgb_bg
+        rgb_bg, blend_bg, depth_bg = self._render_bg(raycast, iter_nr)
+        if depth_bg is None:
+            depth_bg = raycast["t_far"]
         renders, samples_3d, samples_grad = self.render_fg_volumetric(pack, beta, car, iter_nr, override, blend_bg)
         renders["rgb_bg"] = rgb_bg
         renders["depth_bg"] = depth_bg
@@ -588,27 +434,16 @@ class Surf(FieldMethod):
             loss, loss_sdf, loss_eikonal = self._sphere_init_losses()
         else:
             res = self.render_rays(rays_o, rays_d, iter_nr=iter_nr)
-            vol = res["renders"]["volumetric"]
             samples_3d, samples_grad = res["samples_3d"], res["samples_grad"]
-            pred_rgb, pred_mask = vol["rgb"], vol["weights_sum"]
-            R = hp.nr_training_rays_per_pixel
-            if R > 1:
-                pred_rgb = pred_rgb.view(-1, R, 3).mean(dim=1)
-                pred_mask = pred_mask.view(-1, R, 1).mean(dim=1)
-            loss_rgb = loss_l1(gt_rgb, pred_rgb, mask=gt_mask) if masked else loss_l1(gt_rgb, pred_rgb)
+            loss_rgb, pred_mask = self._loss_rgb(res["renders"]["volumetric"], gt_rgb, gt_mask, masked)
             loss = loss_rgb
-            with torch.no_grad():
-                r_points = self.bounding_primitive.get_random_points_inside(self.NR_RANDOM_POINTS)
-            r_sdf_full = field_stencil(self.models["sdf"].main_sdf, r_points, iter_nr)[0]
-            r_sdf, r_grad = r_sdf_full[:r_points.shape[0]], stencil_gradients(r_sdf_full)
+            r_sdf, r_grad = self._random_points_stencil(self.models["sdf"].main_sdf, iter_nr)
             has_samples = samples_3d is not None and samples_3d.shape[0] > 0
             if hp.eikonal_weight > 0.0:
-                loss_eikonal = eikonal_loss(r_grad) * hp.eikonal_weight
-                if has_samples:
-                    loss_eikonal = loss_eikonal + eikonal_loss(samples_grad) * hp.eikonal_weight
+                loss_eikonal = self._loss_eikonal(r_grad, samples_grad if has_samples else None, hp.eikonal_weight)
                 loss = loss + loss_eikonal
             if hp.offsurface_weight > 0.0:
-                loss_offsurface = torch.exp(-self.OFFSURFACE_SCALE * torch.abs(r_sdf)).mean() * hp.offsurface_weight
+                loss_offsurface = self._loss_offsurface(r_sdf)
                 loss = loss + loss_offsurface
             w_curv = curvature_weight_schedule(iter_nr, hp.reduce_curv_start_iter, hp.reduce_curv_end_iter)
             if hp.curvature_weight > 0.0 and w_curv > 0.0 and has_samples:
@@ -617,8 +452,7 @@ class Surf(FieldMethod):
                 loss_curvature = curv.mean() * hp.curvature_weight * w_curv
                 loss = loss + loss_curvature
             if masked and hp.mask_weight > 0.0:
-                pm = torch.clamp(pred_mask, min=0.0, max=1.0)
-                loss_mask = loss_l1(pm, gt_mask, mask=1 - gt_mask) * hp.mask_weight
+                loss_mask = self._loss_mask(pred_mask, gt_mask)
                 loss = loss + loss_mask
         losses = {"loss": loss, "sdf": loss_sdf, "eikonal": loss_eikonal, "rgb": loss_rgb,
                   "curvature": loss_curvature, "lipshitz": 0.0, "offsurface_high_sdf": loss_offsurface,
