@@ -1470,6 +1470,49 @@ int vsa_tb_resolve(const float* vals, int nr_channels, const int32_t* row_start,
 int vsa_tb_dilate(float* img, int height, int width, int nr_channels, int nr_iterations, int32_t* stamp,
                   int32_t* filled, void* stream);
 
+/* ---- TSDF fusion (volsurfs_py/utils/mesh_from_depth.py:220-300: compute_sdf_perframe, compute_unbounded_tsdf;
+ *      csrc/tsdf_fuse.hip) ----
+ * The background mesh of the baker: V depth maps fused into a truncated signed distance at query points.  The
+ * reference makes V passes of torch ops over all points; here a point walks the views i = 0 .. V-1 IN ORDER with its
+ * state in registers and is written once.
+ *   proj [V, 4, 4] f32 row-major: the `full_proj_transform` of to_cam_open3d (mesh_from_depth.py:122-147),
+ *   getProjectionMatrix(0.1, 100, fovx, fovy) @ w2c, the fovs from intrinsic_to_fov with the image size taken as
+ *   (2 cx, 2 cy); volsurfs_amd/bg_mesh.py builds it.  depth [V, H, W] f32 (camera z, 0 where nothing was hit),
+ *   rgb_maps [V, 3, H, W] f32.  H, W in [1, 2^15], V in [1, 2^20].
+ * Rule per point p and view i (fp32, in the order written, no contraction; tests/bg_mesh_restated.py restates it in
+ * torch as the reference formulates it).  State: tsdf = 1, rgb = 0, w = 1 (the initial 1 counts as a sample).
+ *   h_r   = ((p.x P[r][0] + p.y P[r][1]) + p.z P[r][2]) + P[r][3] for r = 0, 1, 3;  z = h_3;  u = h_0 / z;  v = h_1 / z
+ *   mask  = u > -1 and u < 1 and v > -1 and v < 1 and z > 0
+ *   d     = grid_sample(depth_i, (u, v), bilinear, align_corners=True): ix = ((u + 1) / 2) (W - 1), iy likewise with
+ *           H, clamped to the image; x0 = floor(ix), y0 = floor(iy); weights nw = ((x0 + 1) - ix) ((y0 + 1) - iy),
+ *           ne = (ix - x0) ((y0 + 1) - iy), sw = ((x0 + 1) - ix) (iy - y0), se = (ix - x0) (iy - y0); d = the sum of
+ *           tap * weight in the order nw, ne, sw, se from 0, a tap outside the image left out
+ *   sdf   = d - z;  mask = mask and sdf > -sdf_trunc;  s = min(max(sdf / sdf_trunc, -1), 1)
+ *   under the mask: tsdf = (tsdf w + s) / (w + 1);  rgb_c = (rgb_c w + colour_c) / (w + 1) with colour_c the same
+ *           four taps of channel c;  w = w + 1
+ * `uncontract`: the query position is the inverse contraction of the given point (RaySamplerGPU.cuh:595-650 without
+ *   the ray part, as vsa_uncontract_samples: q = 2 p, norm = sqrt((q.x q.x + q.y q.y) + q.z q.z); when norm > 1,
+ *   factor = 1 / (2 - norm) and p = (factor p) / norm).  A point with norm >= 2 lies outside the contraction's image:
+ *   it is not fused and keeps tsdf = 1, rgb = 0.  (The reference has this line commented out, mesh_from_depth.py:264.)
+ * vsa_tsdf_fuse_lattice: the points are the lattice (axis[i], axis[j], axis[k]), axis [n] f32 on the device (the values
+ *   of torch.linspace in fp32, as isosurface.sample_grid builds them), n in [2, 4096]; out_tsdf [n, n, n] f32,
+ *   C-contiguous (what vsa_isosurface_count takes).  A wave is a 4 x 4 x 4 brick of the lattice.
+ * vsa_tsdf_fuse_points: points [P, 3] f32 -> out_tsdf [P] and, when rgb_maps and out_rgb are given (both or neither),
+ *   out_rgb [P, 3]: the vertex-colour pass.  P = 0 is fine.  The same device function: the lattice entry and this one
+ *   give the same bits on the same positions.
+ * vsa_tsdf_uncontract_points: the vertex step of the extraction: out [P, 3] = the inverse contraction of points
+ *   [P, 3], clipped per component to +-max_range; a point with norm >= 2 goes to infinity along its own direction
+ *   before the clip (+-max_range in its non-zero components, 0 in the others).  In place is fine.
+ * No atomics: the same inputs give the same bytes.
+ * VSA_ERR_ARG: a NULL pointer, nr_views < 1, n < 2, sdf_trunc <= 0 or not finite, a size outside the ranges above,
+ *   one of rgb_maps / out_rgb without the other, max_range <= 0 or not finite. */
+int vsa_tsdf_fuse_lattice(const float* proj, const float* depth, int nr_views, int height, int width,
+                          const float* axis, int n, float sdf_trunc, int uncontract, float* out_tsdf, void* stream);
+int vsa_tsdf_fuse_points(const float* proj, const float* depth, const float* rgb_maps, int nr_views, int height,
+                         int width, const float* points, long long nr_points, float sdf_trunc, int uncontract,
+                         float* out_tsdf, float* out_rgb, void* stream);
+int vsa_tsdf_uncontract_points(const float* points, long long nr_points, float max_range, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

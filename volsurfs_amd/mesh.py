@@ -218,13 +218,14 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 
 
-def load_ply(path, device="cuda"):
+def load_ply(path, device="cuda", return_colors=False):
     """Stanford PLY -> TensorMesh (the reference accepts `.ply` next to `.obj`,
     utils/mesh_loaders.py:22-31; marching-cubes shells before the xatlas pass are PLY).
     ascii, binary_little_endian and binary_big_endian; vertex x/y/z (+ optional per-vertex
     s/t or u/v or texture_u/texture_v); face `vertex_indices` lists (polygons are
     fan-triangulated) + optional per-face `texcoord` list of 2*n floats (MeshLab wedge uvs).
-    Other elements / properties are skipped."""
+    Other elements / properties are skipped.  return_colors: -> (mesh, colours [V, 3] f32 on `device` from the
+    vertices' uchar red / green / blue as u8 / 255 (DESIGN §13's 8-bit rule), or None for a file without them)."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -331,33 +332,55 @@ def load_ply(path, device="cuda"):
     fuv = np.asarray(fuvs, np.float32).reshape(-1, 3, 2) if has_uvs else np.zeros((len(faces), 3, 2), np.float32)
     mesh = TensorMesh(verts, np.asarray(faces, np.int32), fuv, device=device)
     mesh.has_uvs = has_uvs
-    return mesh
+    if not return_colors:
+        return mesh
+    colors = None
+    if all(k in vd for k in ("red", "green", "blue")):
+        rgb = np.stack([np.asarray(vd[k], np.float64) for k in ("red", "green", "blue")], 1).astype(np.float32)
+        colors = (torch.from_numpy(rgb) / 255.0).to(device)
+    return mesh, colors
 
 
-def save_ply(path, mesh, binary=True):
+def save_ply(path, mesh, binary=True, vertex_colors=None):
     """TensorMesh -> PLY with MeshLab-style per-face `texcoord` wedge uvs (round-trips
-    through load_ply)."""
+    through load_ply).  vertex_colors [V, 3] floats: written as uchar red / green / blue vertex properties,
+    u8 = trunc(clamp(x, 0, 1) * 255) in fp32 (DESIGN §13's 8-bit rule); None writes the file without them."""
     v = mesh.vertices.detach().cpu().numpy().astype("<f4")
+    rgb = None
+    if vertex_colors is not None:
+        c = torch.as_tensor(vertex_colors).detach().to(torch.float32).cpu()
+        if tuple(c.shape) != (len(v), 3):
+            raise ValueError(f"vertex_colors must be [{len(v)}, 3], got {tuple(c.shape)}")
+        rgb = (c.clamp(0.0, 1.0) * 255.0).to(torch.uint8).numpy()
     f = mesh.faces.detach().cpu().numpy().astype("<i4")
     fuv = mesh.get_faces_uvs()
     fuv = None if fuv is None else fuv.detach().cpu().numpy().astype("<f4").reshape(-1, 6)
     hdr = ["ply", "format %s 1.0" % ("binary_little_endian" if binary else "ascii"),
            "comment volsurfs_amd", f"element vertex {len(v)}", "property float x", "property float y",
-           "property float z", f"element face {len(f)}", "property list uchar int vertex_indices"]
+           "property float z"]
+    if rgb is not None:
+        hdr += ["property uchar red", "property uchar green", "property uchar blue"]
+    hdr += [f"element face {len(f)}", "property list uchar int vertex_indices"]
     if fuv is not None:
         hdr.append("property list uchar float texcoord")
     hdr.append("end_header")
     with open(path, "wb") as out:
         out.write(("\n".join(hdr) + "\n").encode("ascii"))
         if binary:
-            out.write(v.tobytes())
+            if rgb is None:
+                out.write(v.tobytes())
+            else:
+                rec = np.empty(len(v), np.dtype([("p", "<f4", (3,)), ("c", "u1", (3,))]))
+                rec["p"], rec["c"] = v, rgb
+                out.write(rec.tobytes())
             for i in range(len(f)):
                 out.write(b"\x03" + f[i].tobytes())
                 if fuv is not None:
                     out.write(b"\x06" + fuv[i].tobytes())
         else:
-            for p_ in v.tolist():
-                out.write(("%.9g %.9g %.9g\n" % tuple(p_)).encode())
+            for i, p_ in enumerate(v.tolist()):
+                tail = "" if rgb is None else " %d %d %d" % tuple(rgb[i].tolist())
+                out.write((("%.9g %.9g %.9g" % tuple(p_)) + tail + "\n").encode())
             for i in range(len(f)):
                 line = "3 %d %d %d" % tuple(f[i].tolist())
                 if fuv is not None:
