@@ -1513,6 +1513,70 @@ int vsa_tsdf_fuse_points(const float* proj, const float* depth, const float* rgb
                          float* out_tsdf, float* out_rgb, void* stream);
 int vsa_tsdf_uncontract_points(const float* points, long long nr_points, float max_range, float* out, void* stream);
 
+/* ---- Mesh cleaning (volsurfs_py/utils/mesh_extraction.py:18-46 `post_process_mesh`; csrc/mesh_clean.hip) ----
+ * Connected triangle clusters of a plain mesh and the removal of the small ones ("floaters").  The reference calls
+ * Open3D (cluster_connected_triangles, remove_triangles_by_mask, remove_unreferenced_vertices,
+ * remove_degenerate_triangles), which is absent: the rule is restated here and in tests/mesh_clean_restated.py, and is
+ * UNPINNED against Open3D itself.
+ *   verts [V, 3] f32 and faces [F, 3] i32 on the device: finite, indices in [0, V) (the caller checks).  V, F >= 1.  A
+ *   face may name a vertex twice.
+ * Rules (the outputs are a function of the mesh and the arguments only):
+ *   adjacency     two faces are adjacent when they share an undirected edge: the same unordered pair of vertex
+ *                 INDICES (key = min << s | max, s = the bits of V - 1) among their three corner pairs (0, 1), (1, 2),
+ *                 (2, 0).  Every face of an edge with three or more faces is joined; faces that share only a vertex are
+ *                 not.  A face (a, a, b) has the pairs (a, a), (a, b), (a, b) and takes part through them.
+ *   clusters      the connected components of the adjacency, numbered 0 .. C-1 in ascending order of their smallest
+ *                 face index (union-find hooks the larger root under the smaller, so a root is its component's minimum
+ *                 face whatever the order of the hooks).  triangle_clusters [F] i32; cluster_n_triangles [C] i32
+ *                 (integer atomics).
+ *   areas         cluster_area [C] f64: the sum over the cluster's faces of 0.5 sqrt((nx nx + ny ny) + nz nz), n = (p1 -
+ *                 p0) x (p2 - p0) as e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x, every operation in fp64 on
+ *                 the fp32 coordinates, no contraction.  The faces are taken in ascending index (a stable sort by
+ *                 cluster); sorted positions are cut into chunks of 2048, a chunk is summed by 256 lanes (8 consecutive
+ *                 faces each, in order, then a Hillis-Steele segmented scan of the lanes), and a cluster that spans
+ *                 several chunks adds its pieces by one wave (lane l the pieces l, l + 64, ... in order, then a shuffle
+ *                 tree).  The shape is fixed: same mesh, same bits.
+ *   threshold     (mode 2) n = max(the k-th largest cluster_n_triangles, min_cluster_faces), k = min(cluster_to_keep,
+ *                 C) -- the reference indexes the sorted counts with cluster_to_keep itself and raises when C is
+ *                 smaller; this is the one departure.  A face passes when its cluster has >= n faces (the reference
+ *                 removes on a strict <), so clusters tied at n all stay.
+ *   filter        mode 0: every face passes; 1: face f passes when keep_mask[f] != 0 (u8 [F]); 2: the threshold.  Then,
+ *                 in the reference's order: drop_unreferenced keeps the vertices named by a passing face (else all),
+ *                 in input order with their bits, and the faces are renumbered; drop_degenerate then drops the passing
+ *                 faces that name a vertex twice -- the vertices such a face named stay.  Faces keep input order.
+ *   output        out_verts [V, 3] f32 and out_faces [F, 3] i32 sized for the input, the first V_out / F_out rows
+ *                 written; out_vertex_map [V] and out_face_map [F] i32: old -> new index, -1 for a dropped one.
+ *                 stats [host] 6 long long: V_out, F_out, C, n, the clusters with >= n faces (the three 0 unless mode
+ *                 2), the faces that passed (degenerate ones included).
+ *   stage_ms      [host] 9 floats or NULL: device ms of edges, sort, hook, roots, number, areas (vsa_mesh_clusters
+ *                 only), threshold, mask, compact (vsa_mesh_filter only) (events, one stream synchronisation per
+ *                 stage; NULL: none).
+ * Blocking reads: C once (vsa_mesh_clusters, and vsa_mesh_filter in mode 2), then the totals once; their number does
+ * not depend on F or C.  Both calls synchronise `stream` before they return.
+ *   workspace     vsa_mesh_clusters_workspace_bytes(V, F), for both calls: 96 bytes per face and 8 per max(V, F) plus 4
+ *                 per vertex of this library's arrays, and rocPRIM's temporary storage, which for its sort of the 3F
+ *                 (u64, u32) pairs is itself about 36 bytes per face -- about 140 bytes per face in all, O(V + F).
+ * vsa_mesh_clusters: out_triangle_clusters [F] i32; out_cluster_n_triangles [F] i32 and out_cluster_area [F] f64, the
+ *   first C entries meaningful; out_nr_clusters [host] one long long.
+ * vsa_mesh_compact_rows: out[map[i]] = rows[i] for map[i] >= 0, rows of row_words 32-bit words: the per-vertex and
+ *   per-corner attributes through a map of vsa_mesh_filter.  nr_rows = 0 is fine.
+ * VSA_ERR_ARG: a NULL pointer (keep_mask only in mode 1; stage_ms may be NULL), V or F < 1, mode outside 0..2,
+ *   cluster_to_keep < 1 or min_cluster_faces < 0 in mode 2, a workspace smaller than asked for, row_words < 1,
+ *   nr_rows < 0.  VSA_ERR_UNSUPPORTED: V >= 2^31 or 3 F + 3 >= 2^31 (and from the query, a failed rocPRIM size query: no
+ *   device).  The outputs are untouched on either.  The workspace query returns the byte count or one of those codes. */
+long long vsa_mesh_clusters_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_mesh_clusters(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                      void* workspace, long long workspace_bytes, int32_t* out_triangle_clusters,
+                      int32_t* out_cluster_n_triangles, double* out_cluster_area, long long* out_nr_clusters,
+                      float* stage_ms, void* stream);
+int vsa_mesh_filter(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, int mode,
+                    const uint8_t* keep_mask, long long cluster_to_keep, long long min_cluster_faces,
+                    int drop_unreferenced, int drop_degenerate, void* workspace, long long workspace_bytes,
+                    float* out_verts, int32_t* out_faces, int32_t* out_vertex_map, int32_t* out_face_map,
+                    long long* stats, float* stage_ms, void* stream);
+int vsa_mesh_compact_rows(const void* rows, long long nr_rows, int row_words, const int32_t* map, void* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

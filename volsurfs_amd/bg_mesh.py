@@ -125,12 +125,14 @@ class MeshExtractor:
 
     @torch.no_grad()
     def extract_mesh_unbounded(self, resolution=512, uncontract_samples=False, inv_contraction="default",
-                               max_range=32.0):
+                               max_range=32.0, cluster_to_keep=None):
         """mesh_from_depth.py:213-342: the level-0 surface of the fused lattice (`isosurface.marching_cubes`, inside
         where tsdf < 0), its vertices through the inverse contraction and clipped to +-max_range, and, with
         `with_vertex_colors`, the colours fused at the final vertex positions as the reference does (world positions,
         no contraction).  `inv_contraction`: "default" (uncontract_points), None (vertices stay contracted, no clip,
         as marching_cubes_with_contraction does without one) or a callable [V, 3] -> [V, 3], clipped afterwards.
+        `cluster_to_keep`: None leaves the mesh as fused; an integer runs `mesh_clean.post_process_mesh` on it, the
+        colours included (the reference's commented-out post-processing, mesh_from_depth.py:449-464).
         Returns a TensorMesh (no UVs), or (mesh, colours [V, 3] f32) with `with_vertex_colors`."""
         n = int(resolution)
         grid = self.fuse_lattice(n, uncontract_samples)
@@ -144,9 +146,14 @@ class MeshExtractor:
         elif inv_contraction is not None:
             verts = inv_contraction(verts).to(torch.float32).clamp(-float(max_range), float(max_range)).contiguous()
         mesh = _uvless(verts, mesh.faces)
-        if not self.with_vertex_colors:
-            return mesh
-        return mesh, self.fuse_points(verts, return_rgb=True, resolution=n)[1]
+        colors = self.fuse_points(verts, return_rgb=True, resolution=n)[1] if self.with_vertex_colors else None
+        if cluster_to_keep is not None:
+            from .mesh_clean import post_process_mesh
+            if colors is None:
+                mesh = post_process_mesh(mesh, cluster_to_keep)
+            else:
+                mesh, colors = post_process_mesh(mesh, cluster_to_keep, vertex_colors=colors)
+        return mesh if colors is None else (mesh, colors)
 
 
 # ---- the baker stage (baker.py:454-579)
@@ -186,7 +193,7 @@ def ray_length_to_camera_z(depth, camera):
 
 @torch.no_grad()
 def extract_bg_mesh(method, cameras, out_dir=None, resolution=512, depth="fg", depth_is_ray_length=True,
-                    with_vertex_colors=True, reuse_renders=True, **extractor_kwargs):
+                    with_vertex_colors=True, reuse_renders=True, cluster_to_keep=None, **extractor_kwargs):
     """The baker's `--extract_bg_mesh` (baker.py:454-579) for a method with a background model (it raises for one
     without; the reference prints and exits).  Every camera is rendered in "volumetric" mode; rgb, depth_fg, depth_bg
     and weights_sum go to `<out_dir>/tmp_renders/{rgbs,depths_fg,depths_bg,fg_mask}.npz` keyed by the camera index, as
@@ -199,7 +206,9 @@ def extract_bg_mesh(method, cameras, out_dir=None, resolution=512, depth="fg", d
     `depth_is_ray_length` (default True): the methods' depth is the parameter along unit-length rays
     (`camera.get_camera_rays` normalises its directions), the fusion compares with camera z, so the depth is
     converted on the device, z = t (ray direction . camera forward axis).  False hands the renders over unconverted,
-    the reference's unfinished state.  `extractor_kwargs` go to `extract_mesh_unbounded`.
+    the reference's unfinished state.  `cluster_to_keep`: None writes the fused mesh as it is; an integer removes its
+    floaters first (`mesh_clean.post_process_mesh` on the unbounded mesh, colours included).  `extractor_kwargs` go to
+    `extract_mesh_unbounded`.
     Returns (mesh, colours or None)."""
     if depth not in ("fg", "composed"):
         raise ValueError(f"depth must be 'fg' or 'composed', got {depth!r}")
@@ -245,6 +254,8 @@ def extract_bg_mesh(method, cameras, out_dir=None, resolution=512, depth="fg", d
         c2ws.append(c2w.numpy())
         ixts.append(cam.intrinsics.double().numpy())
     extractor = MeshExtractor(depths, rgbs, c2ws, ixts, with_vertex_colors=with_vertex_colors, device=dev)
+    if cluster_to_keep is not None:
+        extractor_kwargs = dict(extractor_kwargs, cluster_to_keep=cluster_to_keep)
     res = extractor.extract_mesh_unbounded(resolution=resolution, **extractor_kwargs)
     mesh, colors = res if with_vertex_colors else (res, None)
     if out_dir is not None:

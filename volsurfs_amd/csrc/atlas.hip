@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "face_union.h"
 
 #define ATL_BLOCK 256
 #define ATL_TILE 8
@@ -145,18 +146,13 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_labels(const int32_t* __restric
   label[f] = (dn >= 0.0 && 4.0 * (dn * dn) >= nn) ? cand : atl_argmax6(nx, ny, nz);
 }
 
-__device__ __forceinline__ u64 atl_pack(int x, int y, int s) {
-  const int lo = x < y ? x : y, hi = x < y ? y : x;
-  return (u64)(unsigned)lo << s | (u64)(unsigned)hi;
-}
-
 __global__ __launch_bounds__(ATL_BLOCK) void atl_edge_keys(const int32_t* __restrict__ faces, long long n3, int s,
                                                           u64* __restrict__ keys, uint32_t* __restrict__ vals) {
   const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (i >= n3) return;
   const long long f = i / 3;
   const int c = (int)(i - 3 * f);
-  keys[i] = atl_pack(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
+  keys[i] = fu_edge_key(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
   vals[i] = (uint32_t)i;
 }
 
@@ -191,22 +187,12 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_join_compact(const uint32_t* __
 
 // ------------------------------------------------------------------------------------------------ charts
 
-__device__ __forceinline__ int atl_find(int* par, int x) {
-  while (true) {
-    const int p = __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    const int g = __hip_atomic_load(par + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (g != p) __hip_atomic_store(par + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // halving: an ancestor
-    x = p;
-  }
-}
-
 __global__ __launch_bounds__(ATL_BLOCK) void atl_iota(int32_t* __restrict__ par, long long F) {
   const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (f < F) par[f] = (int32_t)f;
 }
 
-// Every parent is <= its child, so the root of a component is its minimum face index.
+// Every parent is <= its child, so the root of a component is its minimum face index (face_union.h).
 __global__ __launch_bounds__(ATL_BLOCK) void atl_hook(const int2* __restrict__ pairs, const long long* __restrict__ ctr,
                                                      const uint32_t* __restrict__ code, int32_t* par) {
   const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
@@ -214,29 +200,7 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_hook(const int2* __restrict__ p
   const int2 pr = pairs[i];
   const uint32_t k = code[pr.x];
   if (k == 0u || k != code[pr.y]) return;
-  int a = pr.x, b = pr.y;
-  while (true) {
-    a = atl_find(par, a);
-    b = atl_find(par, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    if (atomicCAS(par + b, b, a) == b) return;
-  }
-}
-
-// Root of x by a walk that only reads: `par` is left as the hooks built it while other lanes walk it, so every lane
-// sees the same final forest and finds the same root.
-__device__ __forceinline__ int atl_root(const int32_t* __restrict__ par, int x) {
-  int p = par[x];
-  while (p != x) {
-    x = p;
-    p = par[x];
-  }
-  return x;
+  fu_union(par, pr.x, pr.y);
 }
 
 // root[f] = the root of f (a separate array: no lane writes to a node another lane walks).
@@ -244,7 +208,7 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_compress(const int32_t* __restr
                                                          int32_t* __restrict__ root, int32_t* __restrict__ flags) {
   const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (f >= F) return;
-  const int r = atl_root(par, (int)f);
+  const int r = fu_root(par, (int)f);
   root[f] = r;
   flags[f] = r == f;
 }
