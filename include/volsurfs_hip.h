@@ -1577,6 +1577,42 @@ int vsa_mesh_filter(const float* verts, long long nr_verts, const int32_t* faces
 int vsa_mesh_compact_rows(const void* rows, long long nr_rows, int row_words, const int32_t* map, void* out,
                           void* stream);
 
+/* ---- Face visibility (volsurfs_py/baker.py:140-144 `--remove_invisible_faces`, a stub in the reference;
+ *      csrc/face_visibility.hip) ----
+ * Which faces of K shells are some view's closest hit.  The reference never implemented the stage: the rule below is
+ * this library's own, restated and UNPINNED.
+ * vsa_face_view_counts: qnodes / tris / mesh_roots / mesh_frames / max_depth as vsa_trace_q takes them (q16 nodes);
+ *   c2w_all [V, 3, 4] and intrinsics_inv_all [V, 3, 3] f32 on the device, all views height x width.
+ *   samples       pixel (col, row) has supersample^2 samples: (i, j) goes through the point x = col + (i + 0.5f) / s,
+ *                 y = row + (j + 0.5f) / s (fp32, in that order); its ray is vsa_camera_rays' pinhole ray of (x, y).
+ *                 s = 1 is col + 0.5f: the unjittered ray of vsa_camera_rays bit for bit.
+ *   hit           per shell on its own (other shells do not occlude), the closest hit of vsa_trace_q: smallest t, ties
+ *                 to the smallest original face id, a hit iff t > t_min.
+ *   counts        [device] u32, zeroed by the caller: counts[face_base[k] + f] += 1 for every sample of every view whose
+ *                 closest hit on shell k is face f (the original id, word 3 of the triangle record).  face_base [host]
+ *                 nr_meshes long long >= 0.  Integer atomics only: exact, the same for every schedule.  Nothing else is
+ *                 written to memory.
+ *   One launch of one wave per (view, tile of 64 samples, shell); the tile is 8 x 8 samples, or 64 samples of a row after
+ *   vsa_face_view_counts_tile(1) (process-wide; 0 = 8 x 8, the default; the counts do not depend on it).
+ *   VSA_ERR_ARG (before any HIP call): a NULL pointer, nr_meshes outside 1..16, nr_views / height / width < 1,
+ *   supersample outside 1..8, max_depth >= 48, nr_views * height * width * supersample^2 >= 2^32 (a u32 count could
+ *   wrap), a negative face_base.  VSA_ERR_UNSUPPORTED: more than 2^31 - 1 tiles over all views (within the sample bound
+ *   only images a few samples wide or high, whose tiles are mostly empty, get there).
+ * vsa_face_ring_dilate: keep [F] u8 in / out grown by `rings` (0..16) vertex rings of faces [F, 3] i32 (indices in
+ *   [0, V): the caller checks).  Per ring: vert_scratch [V] u8 cleared; every face with keep != 0 sets vert_scratch = 1
+ *   at its three vertices; then every face with a set vertex sets keep = 1.  Two passes, so a ring reads the previous
+ *   ring's mask only: the result is a function of the mesh and the mask.  rings = 0 touches nothing.
+ *   VSA_ERR_ARG (before any HIP call): a NULL pointer, nr_faces or nr_verts < 1, rings outside 0..16. */
+int vsa_face_view_counts(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots,
+                         const float* mesh_frames, int nr_meshes, int max_depth,
+                         const float* c2w_all, const float* intrinsics_inv_all,
+                         int nr_views, int height, int width, int supersample, float t_min,
+                         const long long* face_base, uint32_t* counts,
+                         void* stream);
+int vsa_face_view_counts_tile(int tile);
+int vsa_face_ring_dilate(const int32_t* faces, long long nr_faces, long long nr_verts, uint8_t* keep,
+                         int rings, uint8_t* vert_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

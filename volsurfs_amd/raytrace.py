@@ -306,6 +306,13 @@ class RayTracer:
         v = st.cpu().tolist()
         return dict(zip(("lane_visits", "tri_tests", "wave_trips", "waves", "max_wave_trips"), v))
 
+    def face_view_counts(self, cameras, supersample=1, t_min=0.0):
+        """Per shell, how many samples of how many views had each face as the shell's closest hit: a list of K int64
+        [F_k] tensors (vsa_face_view_counts: rays made in registers, the walk of `trace_all`, hits counted per face in
+        one launch; q16 nodes).  `visibility.face_view_counts` is the same call from a list of meshes."""
+        from .visibility import tracer_face_view_counts
+        return tracer_face_view_counts(self, cameras, supersample, t_min)
+
     def sah_cost(self):
         """Per-mesh SAH cost of the trees, from the fp32 nodes (measurement; copies them to the host):
         1 (the root's visit) + sum over every child box of area / root area x (1 for an inner node, its triangle
