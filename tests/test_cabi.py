@@ -117,6 +117,23 @@ def test_argument_errors_are_reported_not_ignored():
         _lib.call("vsa_sh_encode", None, 10, 7, None, None)
 
 
+def test_workspace_queries_report_a_failed_size_query():
+    """Without a device rocPRIM's size queries fail with a positive HIP status; every mesh stage's workspace query turns
+    it into a negative VSA_ERR_* status, never into a byte count, and the Python layer raises."""
+    import pytest
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a device is visible: the size queries succeed")
+    from volsurfs_amd import simplify
+    L = _lib.lib()
+    assert L.vsa_simplify_workspace_bytes(1000, 2000) < 0
+    assert L.vsa_atlas_workspace_bytes(1000, 2000, 256) < 0
+    assert L.vsa_atlas_rasterize_workspace_bytes(2000) < 0
+    assert L.vsa_mesh_clusters_workspace_bytes(1000, 2000) < 0
+    with pytest.raises(_lib.VolsurfsHipError):
+        simplify.workspace_bytes(1000, 2000)
+
+
 def test_import_volsurfs_resolves_to_the_mirror():
     """src/PyBridge.cxx:19 names the extension `volsurfs`; utils/background.py:3,5 and
     params/cmd_params.py:2,8-9 import it under that name and locate the repo root from it."""

@@ -180,6 +180,26 @@ def call(name, *args):
     return rc
 
 
+def workspace_bytes(name, *args):
+    """The byte count a `*_workspace_bytes` query returns; raises on a negative status."""
+    n = getattr(lib(), name)(*args)
+    if n < 0:
+        raise VolsurfsHipError(f"{name} failed with status {n}")
+    return int(n)
+
+
+def stage_array(stages, stage_ms):
+    """The `stage_ms` argument of an entry point with these stages: a float array when the caller asked for timings
+    (`stage_ms` is a dict), else None."""
+    return (ctypes.c_float * len(stages))() if stage_ms is not None else None
+
+
+def stage_update(stages, stage_ms, ms):
+    """The device ms per stage of `stage_array`'s array into the caller's dict."""
+    if ms is not None:
+        stage_ms.update({k: float(ms[i]) for i, k in enumerate(stages)})
+
+
 def check_f32(t, *shape):
     import torch
     if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:

@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import _lib
-from .mesh import TensorMesh, load_ply, save_obj
+from .mesh import TensorMesh, check_mesh, level_files, load_ply, save_obj
 
 STAGES = ("label", "charts", "pack", "emit", "raster")
 ERR_ATLAS_FULL = -3
@@ -23,10 +23,7 @@ ERR_ATLAS_FULL = -3
 
 def workspace_bytes(nr_verts, nr_faces, resolution):
     """Device workspace of one atlas of a mesh with `nr_verts` vertices and `nr_faces` faces at `resolution`^2."""
-    n = _lib.lib().vsa_atlas_workspace_bytes(int(nr_verts), int(nr_faces), int(resolution))
-    if n < 0:
-        raise _lib.VolsurfsHipError(f"vsa_atlas_workspace_bytes failed with status {n}")
-    return int(n)
+    return _lib.workspace_bytes("vsa_atlas_workspace_bytes", int(nr_verts), int(nr_faces), int(resolution))
 
 
 def min_resolution(charts, padding):
@@ -52,24 +49,7 @@ def _check(mesh, resolution, padding):
         raise ValueError(f"compute_atlas: resolution must lie in [8, 16384], got {resolution}")
     if padding < 0 or 2 * padding >= resolution:
         raise ValueError(f"compute_atlas: padding must satisfy 0 <= 2 * padding < resolution, got {padding}")
-    V, F = mesh.vertices, mesh.faces
-    if not (V.is_cuda and F.is_cuda):
-        raise ValueError(f"compute_atlas: the mesh must be on cuda, got {V.device} / {F.device}")
-    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError(f"compute_atlas: expected vertices [V, 3] and faces [F, 3], got {tuple(V.shape)} / "
-                         f"{tuple(F.shape)}")
-    V = V.to(torch.float32).contiguous()
-    F = F.to(torch.int32).contiguous()
-    if F.shape[0] == 0:
-        return V, F, resolution, padding
-    if not bool(torch.isfinite(V).all()):
-        raise _lib.VolsurfsHipError("compute_atlas: the vertices hold NaN or inf")
-    lo, hi = torch.aminmax(F)
-    if int(lo) < 0 or int(hi) >= V.shape[0]:
-        raise _lib.VolsurfsHipError(f"compute_atlas: face indices out of range [0, {V.shape[0]}): "
-                                    f"min {int(lo)}, max {int(hi)}")
-    if bool(((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 2] == F[:, 0])).any()):
-        raise _lib.VolsurfsHipError("compute_atlas: a face names one vertex twice")
+    V, F = check_mesh(mesh, "compute_atlas", refuse_degenerate=True)
     return V, F, resolution, padding
 
 
@@ -82,7 +62,7 @@ def _atlas(V, F, R, p, stage_ms=None):
     chart = torch.empty(nf, dtype=torch.int32, device=V.device)
     stats = (ctypes.c_longlong * 4)()
     scale = ctypes.c_float(0.0)
-    ms = (ctypes.c_float * len(STAGES))() if stage_ms is not None else None
+    ms = _lib.stage_array(STAGES, stage_ms)
     rc = _lib.lib().vsa_atlas(V.data_ptr(), nv, F.data_ptr(), nf, R, p, ws.data_ptr(), ws.numel(), uv.data_ptr(),
                               chart.data_ptr(), ctypes.addressof(stats), ctypes.addressof(scale),
                               ctypes.addressof(ms) if ms is not None else None, _lib.stream_ptr().value)
@@ -90,8 +70,7 @@ def _atlas(V, F, R, p, stage_ms=None):
         raise _lib.VolsurfsHipError(full_message(int(stats[0]), R, p, int(stats[3])))
     if rc != 0:
         raise _lib.VolsurfsHipError(f"vsa_atlas failed with status {rc}")
-    if ms is not None:
-        stage_ms.update({k: float(ms[i]) for i, k in enumerate(STAGES)})
+    _lib.stage_update(STAGES, stage_ms, ms)
     charts, splits, covered = int(stats[0]), int(stats[1]), int(stats[2])
     st = {"charts": charts, "split_rounds": splits, "scale": float(scale.value), "covered": covered,
           "utilization": covered / float(R * R), "resolution": R, "padding": p}
@@ -151,10 +130,8 @@ def rasterize_atlas(mesh, resolution):
         return face_id, count
     if not bool(torch.isfinite(uv).all()):
         raise _lib.VolsurfsHipError("rasterize_atlas: the UVs hold NaN or inf")
-    n = _lib.lib().vsa_atlas_rasterize_workspace_bytes(nf)
-    if n < 0:
-        raise _lib.VolsurfsHipError(f"vsa_atlas_rasterize_workspace_bytes failed with status {n}")
-    ws = torch.empty(int(n), dtype=torch.uint8, device=uv.device)
+    n = _lib.workspace_bytes("vsa_atlas_rasterize_workspace_bytes", nf)
+    ws = torch.empty(n, dtype=torch.uint8, device=uv.device)
     _lib.call("vsa_atlas_rasterize", uv, nf, R, ws, ws.numel(), face_id, count, _lib.stream_ptr())
     return face_id, count
 
@@ -170,14 +147,6 @@ def chart_image(charts, face_id):
     return torch.flip(rgb, [0])
 
 
-def _level_files(meshes_dir):
-    names = [n for n in os.listdir(meshes_dir) if n.endswith(".ply") or n.endswith(".obj")]
-    names.sort(key=lambda x: float(x[:-4]))
-    if not names:
-        raise FileNotFoundError(f"no <level>.ply / <level>.obj meshes in {meshes_dir}")
-    return names
-
-
 def compute_meshes_atlas(meshes_dir, out_dir, resolution=1024, padding=4, device="cuda"):
     """The baker's `--compute_meshes_xatlas` (baker.py:727-776): every `<level>.ply` of `meshes_dir` (the reference's
     `meshes_simplified/`) atlased on its own and written to `out_dir` (its `meshes_simplified_uvs/`) as `<level>.obj`
@@ -185,7 +154,7 @@ def compute_meshes_atlas(meshes_dir, out_dir, resolution=1024, padding=4, device
     `VolSurfs.from_meshes_path(out_dir, ..., using_neural_textures=True)` trains on them."""
     from .evaluation import _save_png
     from .mesh import load_mesh
-    names = _level_files(meshes_dir)
+    names = level_files(meshes_dir, obj=True)
     os.makedirs(out_dir, exist_ok=True)
     paths = []
     for n in names:

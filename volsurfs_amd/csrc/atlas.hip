@@ -22,15 +22,13 @@
 // No float is summed by atomics: the normal sums have a fixed order, and integer atomics form minima, maxima, unions,
 // flags and counts.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <cstdint>
+#include <cstring>
 
-#include "common.h"
-#include "face_union.h"
+#include "mesh_topology.h"
 
-#define ATL_BLOCK 256
+#define ATL_BLOCK MT_BLOCK
 #define ATL_TILE 8
 #define ATL_SNAP 256
 #define ATL_DEPTH_CAP 24
@@ -48,7 +46,8 @@
 #define ACT_PROG 6
 #define ACT_N 8
 
-typedef unsigned long long u64;
+using mt::at;
+using mt::u64;
 
 // Projection axes per label (+x, -x, +y, -y, +z, -z): +x -> (y, z), -x -> (z, y), +y -> (z, x), -y -> (x, z),
 // +z -> (x, y), -z -> (y, x).
@@ -76,22 +75,6 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_normals(const float* __restrict
   fn[3 * f] = e1y * e2z - e1z * e2y;
   fn[3 * f + 1] = e1z * e2x - e1x * e2z;
   fn[3 * f + 2] = e1x * e2y - e1y * e2x;
-}
-
-__global__ __launch_bounds__(ATL_BLOCK) void atl_vf_pairs(const int32_t* __restrict__ faces, long long n3,
-                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  keys[i] = (uint32_t)faces[i];
-  vals[i] = (uint32_t)(i / 3);
-}
-
-__global__ __launch_bounds__(ATL_BLOCK) void atl_vf_ranges(const uint32_t* __restrict__ k, long long n3,
-                                                          int32_t* __restrict__ vstart, int32_t* __restrict__ vend) {
-  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  if (i == 0 || k[i] != k[i - 1]) vstart[k[i]] = (int32_t)i;
-  if (i == n3 - 1 || k[i] != k[i + 1]) vend[k[i]] = (int32_t)(i + 1);
 }
 
 // N_v: the fp32 sum of n_f over the faces at v, in ascending face index, from 0.
@@ -146,16 +129,6 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_labels(const int32_t* __restric
   label[f] = (dn >= 0.0 && 4.0 * (dn * dn) >= nn) ? cand : atl_argmax6(nx, ny, nz);
 }
 
-__global__ __launch_bounds__(ATL_BLOCK) void atl_edge_keys(const int32_t* __restrict__ faces, long long n3, int s,
-                                                          u64* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  const long long f = i / 3;
-  const int c = (int)(i - 3 * f);
-  keys[i] = fu_edge_key(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
-  vals[i] = (uint32_t)i;
-}
-
 // Join flag at the first sorted slot of an edge with exactly two slots, opposite directions and one label.
 __global__ __launch_bounds__(ATL_BLOCK) void atl_join_flags(const u64* __restrict__ sorted,
                                                            const uint32_t* __restrict__ slot,
@@ -187,12 +160,7 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_join_compact(const uint32_t* __
 
 // ------------------------------------------------------------------------------------------------ charts
 
-__global__ __launch_bounds__(ATL_BLOCK) void atl_iota(int32_t* __restrict__ par, long long F) {
-  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
-  if (f < F) par[f] = (int32_t)f;
-}
-
-// Every parent is <= its child, so the root of a component is its minimum face index (face_union.h).
+// Every parent is <= its child, so the root of a component is its minimum face index (mesh_topology.h).
 __global__ __launch_bounds__(ATL_BLOCK) void atl_hook(const int2* __restrict__ pairs, const long long* __restrict__ ctr,
                                                      const uint32_t* __restrict__ code, int32_t* par) {
   const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
@@ -201,16 +169,6 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_hook(const int2* __restrict__ p
   const uint32_t k = code[pr.x];
   if (k == 0u || k != code[pr.y]) return;
   fu_union(par, pr.x, pr.y);
-}
-
-// root[f] = the root of f (a separate array: no lane writes to a node another lane walks).
-__global__ __launch_bounds__(ATL_BLOCK) void atl_compress(const int32_t* __restrict__ par, long long F,
-                                                         int32_t* __restrict__ root, int32_t* __restrict__ flags) {
-  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
-  if (f >= F) return;
-  const int r = fu_root(par, (int)f);
-  root[f] = r;
-  flags[f] = r == f;
 }
 
 // cidx[f] = the chart number of f's root, in place over root[f] (each lane reads and writes its own entry only).
@@ -529,153 +487,90 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_split(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------ host
 
-static size_t atl_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct AtlLayout {
   size_t fn, nv, vstart, vend, label, code, par, cidx, flags, rank, A, B, va, vb, pairs, box, off, flag, pre, wid,
       sh_start, sh_y, toff, ntile, count, ctr, tmp, tmp_bytes, total;
 };
 
 static int atl_check(long long V, long long F, int R) {
-  if (V < 1 || F < 1 || R < ATL_MIN_RES || R > ATL_MAX_RES) return VSA_ERR_ARG;
-  if (V > 0x7FFFFFFFll || F > 0x7FFFFFFFll / 3 - 1) return VSA_ERR_UNSUPPORTED;
-  return VSA_OK;
-}
-
-// rocPRIM temporary storage for every sort and scan of a mesh of V vertices and F faces (F only: rasterize).
-static int atl_tmp_bytes(long long V, long long F, size_t* out) {
-  const size_t n3 = 3 * (size_t)F, f = (size_t)F;
-  size_t t = 0, need = 16;
-  VSA_HIP_TRY(rocprim::inclusive_scan(nullptr, t, (const long long*)nullptr, (long long*)nullptr, f,
-                                      rocprim::plus<long long>(), (hipStream_t)0));
-  need = t > need ? t : need;
-  if (V > 0) {
-    VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (const uint32_t*)nullptr,
-                                          (uint32_t*)nullptr, n3, 0, 64, (hipStream_t)0));
-    need = t > need ? t : need;
-    VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                          (const uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0, 32, (hipStream_t)0));
-    need = t > need ? t : need;
-    VSA_HIP_TRY(rocprim::radix_sort_keys(nullptr, t, (const u64*)nullptr, (u64*)nullptr, f, 0, 64, (hipStream_t)0));
-    need = t > need ? t : need;
-    VSA_HIP_TRY(rocprim::exclusive_scan(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, 0, n3,
-                                        rocprim::plus<int32_t>(), (hipStream_t)0));
-    need = t > need ? t : need;
-  }
-  *out = need;
-  return VSA_OK;
+  if (R < ATL_MIN_RES || R > ATL_MAX_RES) return VSA_ERR_ARG;
+  return mt::check_vf(V, F);
 }
 
 // V = 0: the rasterize-only layout (toff, ntile, count unused, ctr, tmp).
 static int atl_layout(long long V, long long F, int R, AtlLayout* l) {
   const size_t v = (size_t)V, f = (size_t)F, n3 = 3 * f, rr = (size_t)R * (size_t)R;
-  size_t need = 0;
-  const int rc = atl_tmp_bytes(V, F, &need);
-  if (rc != VSA_OK) return rc;
-  size_t o = 0;
   const bool full = V > 0;
-#define ATL_AT(field, bytes) \
-  l->field = o;              \
-  o += atl_align(bytes)
-  ATL_AT(toff, 8 * (f + 1));
-  ATL_AT(ntile, 8 * f);
-  ATL_AT(ctr, 8 * ACT_N);
-  ATL_AT(fn, full ? 12 * f : 0);
-  ATL_AT(nv, 12 * v);
-  ATL_AT(vstart, 4 * v);
-  ATL_AT(vend, 4 * v);
-  ATL_AT(label, full ? 4 * f : 0);
-  ATL_AT(code, full ? 4 * f : 0);
-  ATL_AT(par, full ? 4 * f : 0);
-  ATL_AT(cidx, full ? 4 * f : 0);
-  ATL_AT(flags, full ? 4 * n3 : 0);
-  ATL_AT(rank, full ? 4 * n3 : 0);
-  ATL_AT(A, full ? 8 * n3 : 0);
-  ATL_AT(B, full ? 8 * n3 : 0);
-  ATL_AT(va, full ? 4 * n3 : 0);
-  ATL_AT(vb, full ? 4 * n3 : 0);
-  ATL_AT(pairs, full ? 8 * n3 : 0);
-  ATL_AT(box, full ? 16 * f : 0);
-  ATL_AT(off, full ? 8 * f : 0);
-  ATL_AT(flag, full ? 4 * f : 0);
-  ATL_AT(pre, full ? 8 * (f + 1) : 0);
-  ATL_AT(wid, full ? 8 * f : 0);
-  ATL_AT(sh_start, full ? 4 * f : 0);
-  ATL_AT(sh_y, full ? 4 * f : 0);
-  ATL_AT(count, full ? 4 * rr : 0);
-  ATL_AT(tmp, need);
-#undef ATL_AT
-  l->tmp_bytes = need;
-  l->total = o;
+  mt::TmpCounts cnt = {};
+  cnt.iscan64 = f;
+  if (full) {
+    cnt.pairs64 = n3;
+    cnt.pairs32 = n3;
+    cnt.keys64 = f;
+    cnt.xscan32 = n3;
+  }
+  MT_TRY(mt::tmp_bytes(cnt, &l->tmp_bytes));
+  mt::Bump b;
+  l->toff = b.take(8 * (f + 1));
+  l->ntile = b.take(8 * f);
+  l->ctr = b.take(8 * ACT_N);
+  l->fn = b.take(full ? 12 * f : 0);
+  l->nv = b.take(12 * v);
+  l->vstart = b.take(4 * v);
+  l->vend = b.take(4 * v);
+  l->label = b.take(full ? 4 * f : 0);
+  l->code = b.take(full ? 4 * f : 0);
+  l->par = b.take(full ? 4 * f : 0);
+  l->cidx = b.take(full ? 4 * f : 0);
+  l->flags = b.take(full ? 4 * n3 : 0);
+  l->rank = b.take(full ? 4 * n3 : 0);
+  l->A = b.take(full ? 8 * n3 : 0);
+  l->B = b.take(full ? 8 * n3 : 0);
+  l->va = b.take(full ? 4 * n3 : 0);
+  l->vb = b.take(full ? 4 * n3 : 0);
+  l->pairs = b.take(full ? 8 * n3 : 0);
+  l->box = b.take(full ? 16 * f : 0);
+  l->off = b.take(full ? 8 * f : 0);
+  l->flag = b.take(full ? 4 * f : 0);
+  l->pre = b.take(full ? 8 * (f + 1) : 0);
+  l->wid = b.take(full ? 8 * f : 0);
+  l->sh_start = b.take(full ? 4 * f : 0);
+  l->sh_y = b.take(full ? 4 * f : 0);
+  l->count = b.take(full ? 4 * rr : 0);
+  l->tmp = b.take(l->tmp_bytes);
+  l->total = b.o;
   return VSA_OK;
 }
 
 extern "C" long long vsa_atlas_workspace_bytes(long long nr_verts, long long nr_faces, int resolution) {
-  const int rc = atl_check(nr_verts, nr_faces, resolution);
-  if (rc != VSA_OK) return rc;
   AtlLayout l;
-  const int rl = atl_layout(nr_verts, nr_faces, resolution, &l);
-  if (rl != VSA_OK) return rl > 0 ? VSA_ERR_UNSUPPORTED : rl;   // a HIP status of rocPRIM's size query
-  return (long long)l.total;
+  int rc = atl_check(nr_verts, nr_faces, resolution);
+  if (rc == VSA_OK) rc = mt::abi_status(atl_layout(nr_verts, nr_faces, resolution, &l));
+  return rc != VSA_OK ? rc : (long long)l.total;
 }
 
 extern "C" long long vsa_atlas_rasterize_workspace_bytes(long long nr_faces) {
   if (nr_faces < 1) return VSA_ERR_ARG;
   if (nr_faces > 0x7FFFFFFFll) return VSA_ERR_UNSUPPORTED;
   AtlLayout l;
-  const int rl = atl_layout(0, nr_faces, ATL_MIN_RES, &l);
-  if (rl != VSA_OK) return rl > 0 ? VSA_ERR_UNSUPPORTED : rl;
-  return (long long)l.total;
+  const int rc = mt::abi_status(atl_layout(0, nr_faces, ATL_MIN_RES, &l));
+  return rc != VSA_OK ? rc : (long long)l.total;
 }
 
 namespace {
-
-#define ATL_TRY(expr)              \
-  do {                             \
-    const int r__ = (expr);        \
-    if (r__ != VSA_OK) return r__; \
-  } while (0)
-
-dim3 agrid(long long n) { return dim3((unsigned)vsa_div_up(n > 0 ? n : 1, ATL_BLOCK)); }
-
-template <typename T>
-T* at(char* ws, size_t o) {
-  return reinterpret_cast<T*>(ws + o);
-}
 
 struct Atl {
   hipStream_t st;
   char* ws;
   AtlLayout l;
+  mt::Tmp tmp;
   long long V, F, C;
   int R, p, s_bits;
   const float* P;
   const int32_t* faces;
   long long* ctr;
-  hipEvent_t ev[2];
-  float* stage_ms;
+  mt::StageTimer timer;
 };
-
-int stage_open(Atl& m) {
-  if (m.stage_ms) VSA_HIP_TRY(hipEventRecord(m.ev[0], m.st));
-  return VSA_OK;
-}
-
-int stage_close(Atl& m, int k) {
-  if (!m.stage_ms) return VSA_OK;
-  float ms = 0.f;
-  VSA_HIP_TRY(hipEventRecord(m.ev[1], m.st));
-  VSA_HIP_TRY(hipEventSynchronize(m.ev[1]));
-  VSA_HIP_TRY(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
-  m.stage_ms[k] += ms;
-  return VSA_OK;
-}
-
-int read_ctr(Atl& m, int k, long long* out) {
-  VSA_HIP_TRY(hipMemcpyAsync(out, m.ctr + k, sizeof(long long), hipMemcpyDeviceToHost, m.st));
-  VSA_HIP_TRY(hipStreamSynchronize(m.st));
-  return VSA_OK;
-}
 
 // Rasterization of F faces' UVs: tile counts, their scan and the item passes (mode 0 counts, then mode 1 flags when
 // `flag` is given).  count / face_id must be zeroed / 0xFF-filled by the caller.
@@ -683,23 +578,21 @@ int raster(hipStream_t st, char* ws, const AtlLayout& l, const float* uv, long l
            uint32_t* face_id, const int32_t* cidx, int32_t* flag) {
   long long* toff = at<long long>(ws, l.toff);
   long long* ntile = at<long long>(ws, l.ntile);
-  hipLaunchKernelGGL(atl_tile_counts, agrid(F), dim3(ATL_BLOCK), 0, st, uv, F, R, ntile);
-  VSA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(atl_tile_counts, mt::grid(F), dim3(ATL_BLOCK), 0, st, uv, F, R, ntile);
+  MT_LAUNCHED();
   VSA_HIP_TRY(hipMemsetAsync(toff, 0, 8, st));
-  size_t bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::inclusive_scan(ws + l.tmp, bytes, ntile, toff + 1, (size_t)F, rocprim::plus<long long>(), st));
+  MT_TRY(mt::inclusive_scan({ws + l.tmp, l.tmp_bytes}, ntile, toff + 1, (size_t)F, st));
   long long total = 0;
-  VSA_HIP_TRY(hipMemcpyAsync(&total, toff + F, sizeof(total), hipMemcpyDeviceToHost, st));
-  VSA_HIP_TRY(hipStreamSynchronize(st));
+  MT_TRY(mt::read_counters(st, toff + F, &total));
   if (total < 0) return VSA_ERR_UNSUPPORTED;
   if (total == 0) return VSA_OK;
   const long long blocks = (total + ATL_BLOCK - 1) / ATL_BLOCK;
   const dim3 g((unsigned)(blocks < 65536 ? blocks : 65536));
   hipLaunchKernelGGL(atl_raster, g, dim3(ATL_BLOCK), 0, st, uv, F, R, toff, total, 0, count, face_id, cidx, flag);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_LAUNCHED();
   if (flag) {
     hipLaunchKernelGGL(atl_raster, g, dim3(ATL_BLOCK), 0, st, uv, F, R, toff, total, 1, count, face_id, cidx, flag);
-    VSA_HIP_TRY(hipGetLastError());
+    MT_LAUNCHED();
   }
   return VSA_OK;
 }
@@ -709,46 +602,35 @@ int label_stage(Atl& m) {
   char* ws = m.ws;
   const AtlLayout& l = m.l;
   float* fn = at<float>(ws, l.fn);
-  size_t bytes = l.tmp_bytes;
-  hipLaunchKernelGGL(atl_normals, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, fn);
-  VSA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(atl_normals, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, fn);
+  MT_LAUNCHED();
   uint32_t* kin = at<uint32_t>(ws, l.A);
   uint32_t* kout = at<uint32_t>(ws, l.B);
   uint32_t* vin = at<uint32_t>(ws, l.va);
   uint32_t* vff = at<uint32_t>(ws, l.vb);
-  hipLaunchKernelGGL(atl_vf_pairs, agrid(n3), dim3(ATL_BLOCK), 0, m.st, m.faces, n3, kin, vin);
-  VSA_HIP_TRY(hipGetLastError());
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(ws + l.tmp, bytes, kin, kout, vin, vff, (size_t)n3, 0, m.s_bits, m.st));
   int32_t* vstart = at<int32_t>(ws, l.vstart);
   int32_t* vend = at<int32_t>(ws, l.vend);
-  VSA_HIP_TRY(hipMemsetAsync(vstart, 0, 4 * (size_t)V, m.st));
-  VSA_HIP_TRY(hipMemsetAsync(vend, 0, 4 * (size_t)V, m.st));
-  hipLaunchKernelGGL(atl_vf_ranges, agrid(n3), dim3(ATL_BLOCK), 0, m.st, kout, n3, vstart, vend);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_TRY(mt::vertex_rings(m.faces, F, V, m.s_bits, kin, kout, vin, vff, vstart, vend, m.tmp, m.st));
   float* nv = at<float>(ws, l.nv);
-  hipLaunchKernelGGL(atl_vertex_sums, agrid(V), dim3(ATL_BLOCK), 0, m.st, fn, vff, vstart, vend, V, nv);
-  VSA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(atl_vertex_sums, mt::grid(V), dim3(ATL_BLOCK), 0, m.st, fn, vff, vstart, vend, V, nv);
+  MT_LAUNCHED();
   int32_t* label = at<int32_t>(ws, l.label);
-  hipLaunchKernelGGL(atl_labels, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.faces, F, fn, nv, label,
+  hipLaunchKernelGGL(atl_labels, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.faces, F, fn, nv, label,
                      at<uint32_t>(ws, l.code));
-  VSA_HIP_TRY(hipGetLastError());
+  MT_LAUNCHED();
   // edges -> join pairs
   u64* ek = at<u64>(ws, l.A);
   u64* es = at<u64>(ws, l.B);
   uint32_t* slot = at<uint32_t>(ws, l.vb);
-  hipLaunchKernelGGL(atl_edge_keys, agrid(n3), dim3(ATL_BLOCK), 0, m.st, m.faces, n3, m.s_bits, ek, vin);
-  VSA_HIP_TRY(hipGetLastError());
-  bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(ws + l.tmp, bytes, ek, es, vin, slot, (size_t)n3, 0, 2 * m.s_bits, m.st));
+  MT_TRY(mt::sorted_edges(m.faces, F, m.s_bits, ek, es, vin, slot, m.tmp, m.st));
   int32_t* flags = at<int32_t>(ws, l.flags);
   int32_t* rank = at<int32_t>(ws, l.rank);
-  hipLaunchKernelGGL(atl_join_flags, agrid(n3), dim3(ATL_BLOCK), 0, m.st, es, slot, m.faces, label, n3, flags);
-  VSA_HIP_TRY(hipGetLastError());
-  bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, flags, rank, 0, (size_t)n3, rocprim::plus<int32_t>(), m.st));
-  hipLaunchKernelGGL(atl_join_compact, agrid(n3), dim3(ATL_BLOCK), 0, m.st, slot, flags, rank, n3,
+  hipLaunchKernelGGL(atl_join_flags, mt::grid(n3), dim3(ATL_BLOCK), 0, m.st, es, slot, m.faces, label, n3, flags);
+  MT_LAUNCHED();
+  MT_TRY(mt::exclusive_scan(m.tmp, flags, rank, (size_t)n3, m.st));
+  hipLaunchKernelGGL(atl_join_compact, mt::grid(n3), dim3(ATL_BLOCK), 0, m.st, slot, flags, rank, n3,
                      at<int2>(ws, l.pairs), m.ctr);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_LAUNCHED();
   return VSA_OK;
 }
 
@@ -759,27 +641,24 @@ int chart_stage(Atl& m) {
   int32_t* par = at<int32_t>(ws, l.par);
   int32_t* flags = at<int32_t>(ws, l.flags);
   int32_t* rank = at<int32_t>(ws, l.rank);
-  hipLaunchKernelGGL(atl_iota, agrid(F), dim3(ATL_BLOCK), 0, m.st, par, F);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_TRY(mt::iota(par, F, m.st));
   // J <= 3F / 2: the grid covers every pair, the kernel reads J on the device
-  hipLaunchKernelGGL(atl_hook, agrid(3 * F / 2 + 1), dim3(ATL_BLOCK), 0, m.st, at<int2>(ws, l.pairs), m.ctr,
+  hipLaunchKernelGGL(atl_hook, mt::grid(3 * F / 2 + 1), dim3(ATL_BLOCK), 0, m.st, at<int2>(ws, l.pairs), m.ctr,
                      at<uint32_t>(ws, l.code), par);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_LAUNCHED();
   int32_t* cidx = at<int32_t>(ws, l.cidx);
-  hipLaunchKernelGGL(atl_compress, agrid(F), dim3(ATL_BLOCK), 0, m.st, par, F, cidx, flags);
-  VSA_HIP_TRY(hipGetLastError());
-  size_t bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, flags, rank, 0, (size_t)F, rocprim::plus<int32_t>(), m.st));
-  hipLaunchKernelGGL(atl_chart_index, agrid(F), dim3(ATL_BLOCK), 0, m.st, flags, rank, F, cidx, m.ctr);
-  VSA_HIP_TRY(hipGetLastError());
-  ATL_TRY(read_ctr(m, ACT_C, &m.C));
+  MT_TRY(mt::roots(par, F, cidx, flags, m.st));
+  MT_TRY(mt::exclusive_scan(m.tmp, flags, rank, (size_t)F, m.st));
+  hipLaunchKernelGGL(atl_chart_index, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, flags, rank, F, cidx, m.ctr);
+  MT_LAUNCHED();
+  MT_TRY(mt::read_counters(m.st, m.ctr + ACT_C, &m.C));
   if (m.C < 1 || m.C > F) return VSA_ERR_UNSUPPORTED;
   unsigned* box = at<unsigned>(ws, l.box);
-  hipLaunchKernelGGL(atl_box_init, agrid(4 * m.C), dim3(ATL_BLOCK), 0, m.st, box, 4 * m.C);
-  VSA_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(atl_boxes, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
+  hipLaunchKernelGGL(atl_box_init, mt::grid(4 * m.C), dim3(ATL_BLOCK), 0, m.st, box, 4 * m.C);
+  MT_LAUNCHED();
+  hipLaunchKernelGGL(atl_boxes, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
                      box);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_LAUNCHED();
   return VSA_OK;
 }
 
@@ -794,19 +673,17 @@ int pack_step(Atl& m, uint32_t sb, int emit, long long* fit) {
   u64* sorted = at<u64>(ws, l.B);
   long long* wid = at<long long>(ws, l.wid);
   long long* pre = at<long long>(ws, l.pre);
-  hipLaunchKernelGGL(atl_rect_keys, agrid(C), dim3(ATL_BLOCK), 0, m.st, at<unsigned>(ws, l.box), C, s, m.R, m.p, keys);
-  VSA_HIP_TRY(hipGetLastError());
-  size_t bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::radix_sort_keys(ws + l.tmp, bytes, keys, sorted, (size_t)C, 0, 64, m.st));
-  hipLaunchKernelGGL(atl_rect_widths, agrid(C), dim3(ATL_BLOCK), 0, m.st, sorted, C, wid);
-  VSA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(atl_rect_keys, mt::grid(C), dim3(ATL_BLOCK), 0, m.st, at<unsigned>(ws, l.box), C, s, m.R, m.p, keys);
+  MT_LAUNCHED();
+  MT_TRY(mt::sort_keys(m.tmp, keys, sorted, (size_t)C, 0, 64, m.st));
+  hipLaunchKernelGGL(atl_rect_widths, mt::grid(C), dim3(ATL_BLOCK), 0, m.st, sorted, C, wid);
+  MT_LAUNCHED();
   VSA_HIP_TRY(hipMemsetAsync(pre, 0, 8, m.st));
-  bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::inclusive_scan(ws + l.tmp, bytes, wid, pre + 1, (size_t)C, rocprim::plus<long long>(), m.st));
+  MT_TRY(mt::inclusive_scan(m.tmp, wid, pre + 1, (size_t)C, m.st));
   hipLaunchKernelGGL(atl_shelf_walk, dim3(1), dim3(1), 0, m.st, sorted, pre, C, m.R, emit,
                      at<int32_t>(ws, l.sh_start), at<int32_t>(ws, l.sh_y), m.ctr);
-  VSA_HIP_TRY(hipGetLastError());
-  return read_ctr(m, ACT_FIT, fit);
+  MT_LAUNCHED();
+  return mt::read_counters(m.st, m.ctr + ACT_FIT, fit);
 }
 
 // Smallest resolution at which C charts of (2p)^2 texels fit by next-fit shelves.
@@ -831,18 +708,18 @@ int pack_stage(Atl& m, uint32_t* s_out, long long* minres) {
   while (hi - lo > 1u) {
     const uint32_t mid = lo + (hi - lo) / 2u;
     long long fit = 0;
-    ATL_TRY(pack_step(m, mid, 0, &fit));
+    MT_TRY(pack_step(m, mid, 0, &fit));
     if (fit) lo = mid;
     else hi = mid;
   }
   long long fit = 0;
-  ATL_TRY(pack_step(m, lo, 1, &fit));
+  MT_TRY(pack_step(m, lo, 1, &fit));
   if (!fit) return VSA_ERR_UNSUPPORTED;
   char* ws = m.ws;
   const AtlLayout& l = m.l;
-  hipLaunchKernelGGL(atl_offsets, agrid(C), dim3(ATL_BLOCK), 0, m.st, at<u64>(ws, l.B), at<long long>(ws, l.pre), C,
+  hipLaunchKernelGGL(atl_offsets, mt::grid(C), dim3(ATL_BLOCK), 0, m.st, at<u64>(ws, l.B), at<long long>(ws, l.pre), C,
                      at<int32_t>(ws, l.sh_start), at<int32_t>(ws, l.sh_y), m.ctr, at<int2>(ws, l.off));
-  VSA_HIP_TRY(hipGetLastError());
+  MT_LAUNCHED();
   *s_out = lo;
   return VSA_OK;
 }
@@ -852,19 +729,19 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
   const AtlLayout& l = m.l;
   const long long F = m.F;
   VSA_HIP_TRY(hipMemsetAsync(m.ctr, 0, 8 * ACT_N, m.st));
-  ATL_TRY(stage_open(m));
-  ATL_TRY(label_stage(m));
-  ATL_TRY(stage_close(m, 0));
+  MT_TRY(m.timer.open());
+  MT_TRY(label_stage(m));
+  MT_TRY(m.timer.close(0));
   int32_t* count = at<int32_t>(ws, l.count);
   int32_t* flag = at<int32_t>(ws, l.flag);
   int32_t* cidx = at<int32_t>(ws, l.cidx);
   long long splits = 0;
   uint32_t sb = 0;
   while (true) {
-    ATL_TRY(stage_open(m));
-    ATL_TRY(chart_stage(m));
-    ATL_TRY(stage_close(m, 1));
-    ATL_TRY(stage_open(m));
+    MT_TRY(m.timer.open());
+    MT_TRY(chart_stage(m));
+    MT_TRY(m.timer.close(1));
+    MT_TRY(m.timer.open());
     long long minres = 0;
     const int rc = pack_stage(m, &sb, &minres);
     if (rc == VSA_ERR_ATLAS_FULL) {
@@ -874,31 +751,31 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
       stats[3] = minres;
     }
     if (rc != VSA_OK) return rc;
-    ATL_TRY(stage_close(m, 2));
-    ATL_TRY(stage_open(m));
+    MT_TRY(m.timer.close(2));
+    MT_TRY(m.timer.open());
     float s;
     memcpy(&s, &sb, 4);
-    hipLaunchKernelGGL(atl_emit, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
+    hipLaunchKernelGGL(atl_emit, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
                        at<unsigned>(ws, l.box), at<int2>(ws, l.off), s, m.R, m.p, uv);
-    VSA_HIP_TRY(hipGetLastError());
-    ATL_TRY(stage_close(m, 3));
-    ATL_TRY(stage_open(m));
+    MT_LAUNCHED();
+    MT_TRY(m.timer.close(3));
+    MT_TRY(m.timer.open());
     VSA_HIP_TRY(hipMemsetAsync(count, 0, 4 * (size_t)m.R * (size_t)m.R, m.st));
     VSA_HIP_TRY(hipMemsetAsync(flag, 0, 4 * (size_t)m.C, m.st));
     VSA_HIP_TRY(hipMemsetAsync(m.ctr + ACT_OVL, 0, 16, m.st));
-    ATL_TRY(raster(m.st, ws, l, uv, F, m.R, count, nullptr, cidx, flag));
-    hipLaunchKernelGGL(atl_count_flags, agrid(m.C), dim3(ATL_BLOCK), 0, m.st, flag, m.C, m.ctr);
-    VSA_HIP_TRY(hipGetLastError());
+    MT_TRY(raster(m.st, ws, l, uv, F, m.R, count, nullptr, cidx, flag));
+    hipLaunchKernelGGL(atl_count_flags, mt::grid(m.C), dim3(ATL_BLOCK), 0, m.st, flag, m.C, m.ctr);
+    MT_LAUNCHED();
     long long ovl = 0;
-    ATL_TRY(read_ctr(m, ACT_OVL, &ovl));
+    MT_TRY(mt::read_counters(m.st, m.ctr + ACT_OVL, &ovl));
     if (ovl == 0) {
       const long long rr = (long long)m.R * m.R;
-      hipLaunchKernelGGL(atl_covered, agrid(rr), dim3(ATL_BLOCK), 0, m.st, count, rr, m.ctr);
-      VSA_HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(atl_covered, mt::grid(rr), dim3(ATL_BLOCK), 0, m.st, count, rr, m.ctr);
+      MT_LAUNCHED();
       VSA_HIP_TRY(hipMemcpyAsync(out_chart, cidx, 4 * (size_t)F, hipMemcpyDeviceToDevice, m.st));
       long long cov = 0;
-      ATL_TRY(read_ctr(m, ACT_COV, &cov));
-      ATL_TRY(stage_close(m, 4));
+      MT_TRY(mt::read_counters(m.st, m.ctr + ACT_COV, &cov));
+      MT_TRY(m.timer.close(4));
       stats[0] = m.C;
       stats[1] = splits;
       stats[2] = cov;
@@ -909,13 +786,13 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
     // a texel counted twice across two charts, or one-face charts flagged, would repeat the round unchanged
     if (splits + 1 >= ATL_MAX_ROUNDS) return VSA_ERR_UNSUPPORTED;
     VSA_HIP_TRY(hipMemsetAsync(m.ctr + ACT_PROG, 0, 8, m.st));
-    hipLaunchKernelGGL(atl_split, agrid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
+    hipLaunchKernelGGL(atl_split, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
                        at<unsigned>(ws, l.box), flag, at<uint32_t>(ws, l.code), m.ctr);
-    VSA_HIP_TRY(hipGetLastError());
+    MT_LAUNCHED();
     long long changed = 0;
-    ATL_TRY(read_ctr(m, ACT_PROG, &changed));
+    MT_TRY(mt::read_counters(m.st, m.ctr + ACT_PROG, &changed));
     if (changed == 0) return VSA_ERR_UNSUPPORTED;
-    ATL_TRY(stage_close(m, 4));
+    MT_TRY(m.timer.close(4));
     ++splits;
   }
 }
@@ -926,15 +803,14 @@ extern "C" int vsa_atlas(const float* verts, long long nr_verts, const int32_t* 
                          int resolution, int padding, void* workspace, long long workspace_bytes, float* out_faces_uvs,
                          int32_t* out_chart, long long* stats, float* scale, float* stage_ms, void* stream) {
   if (!verts || !faces || !workspace || !out_faces_uvs || !out_chart || !stats || !scale) return VSA_ERR_ARG;
-  int rc = atl_check(nr_verts, nr_faces, resolution);
-  if (rc != VSA_OK) return rc;
+  MT_TRY(atl_check(nr_verts, nr_faces, resolution));
   if (padding < 0 || 2 * padding >= resolution) return VSA_ERR_ARG;
   Atl m;
-  rc = atl_layout(nr_verts, nr_faces, resolution, &m.l);
-  if (rc != VSA_OK) return rc;
+  MT_TRY(mt::abi_status(atl_layout(nr_verts, nr_faces, resolution, &m.l)));
   if (workspace_bytes < (long long)m.l.total) return VSA_ERR_ARG;
   m.st = (hipStream_t)stream;
   m.ws = static_cast<char*>(workspace);
+  m.tmp = {m.ws + m.l.tmp, m.l.tmp_bytes};
   m.V = nr_verts;
   m.F = nr_faces;
   m.C = 0;
@@ -942,20 +818,11 @@ extern "C" int vsa_atlas(const float* verts, long long nr_verts, const int32_t* 
   m.p = padding;
   m.P = verts;
   m.faces = faces;
-  m.s_bits = 1;
-  while ((1ll << m.s_bits) < nr_verts) ++m.s_bits;
+  m.s_bits = mt::bits_of(nr_verts);
   m.ctr = at<long long>(m.ws, m.l.ctr);
-  m.stage_ms = stage_ms;
-  if (stage_ms) {
-    for (int k = 0; k < 5; ++k) stage_ms[k] = 0.f;
-    VSA_HIP_TRY(hipEventCreate(&m.ev[0]));
-    VSA_HIP_TRY(hipEventCreate(&m.ev[1]));
-  }
-  rc = run(m, out_faces_uvs, out_chart, stats, scale);
-  if (stage_ms) {
-    (void)hipEventDestroy(m.ev[0]);
-    (void)hipEventDestroy(m.ev[1]);
-  }
+  MT_TRY(m.timer.create(stage_ms, 5, m.st));
+  const int rc = run(m, out_faces_uvs, out_chart, stats, scale);
+  m.timer.destroy();
   return rc;
 }
 
@@ -965,16 +832,14 @@ extern "C" int vsa_atlas_rasterize(const float* faces_uvs, long long nr_faces, i
   if (nr_faces < 1 || resolution < ATL_MIN_RES || resolution > ATL_MAX_RES) return VSA_ERR_ARG;
   if (nr_faces > 0x7FFFFFFFll) return VSA_ERR_UNSUPPORTED;
   AtlLayout l;
-  int rc = atl_layout(0, nr_faces, resolution, &l);
-  if (rc != VSA_OK) return rc;
+  MT_TRY(mt::abi_status(atl_layout(0, nr_faces, resolution, &l)));
   if (workspace_bytes < (long long)l.total) return VSA_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const size_t rr = (size_t)resolution * (size_t)resolution;
   VSA_HIP_TRY(hipMemsetAsync(out_count, 0, 4 * rr, st));
   VSA_HIP_TRY(hipMemsetAsync(out_face_id, 0xFF, 4 * rr, st));
-  rc = raster(st, static_cast<char*>(workspace), l, faces_uvs, nr_faces, resolution, out_count,
-              reinterpret_cast<uint32_t*>(out_face_id), nullptr, nullptr);
-  if (rc != VSA_OK) return rc;
+  MT_TRY(raster(st, static_cast<char*>(workspace), l, faces_uvs, nr_faces, resolution, out_count,
+                reinterpret_cast<uint32_t*>(out_face_id), nullptr, nullptr));
   VSA_HIP_TRY(hipStreamSynchronize(st));
   return VSA_OK;
 }

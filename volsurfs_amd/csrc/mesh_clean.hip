@@ -6,7 +6,7 @@
 //   sort:     one radix sort of the pairs (rocPRIM).
 //   hook:     one lane per sorted slot joins its face with the previous slot's when their keys are equal: chaining
 //             neighbours joins every face of an edge, however many there are.  CAS hooks of the larger root under the
-//             smaller (face_union.h): a root is its cluster's minimum face, whatever the order.
+//             smaller (mesh_topology.h): a root is its cluster's minimum face, whatever the order.
 //   roots:    one lane per face walks to its root without writing.
 //   number:   roots flagged and scanned into cluster numbers (ascending minimum face); the face counts by integer
 //             atomics, one per wave and cluster.  The host reads C here.
@@ -21,15 +21,12 @@
 //   compact:  scans of the face and vertex flags; faces renumbered and written in order, vertices written in order,
 //             both old -> new maps written.  The host reads the totals once.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <cstdint>
 
-#include "common.h"
-#include "face_union.h"
+#include "mesh_topology.h"
 
-#define MC_BLOCK 256
+#define MC_BLOCK MT_BLOCK
 #define MC_ITEMS 8
 #define MC_CHUNK (MC_BLOCK * MC_ITEMS)
 
@@ -45,39 +42,16 @@
 #define MC_STAGES 9
 enum { ST_EDGES, ST_SORT, ST_HOOK, ST_ROOTS, ST_NUMBER, ST_AREAS, ST_THRESHOLD, ST_MASK, ST_COMPACT };
 
-typedef unsigned long long u64;
+using mt::at;
+using mt::u64;
 
 // ------------------------------------------------------------------------------------------------ clusters
-
-__global__ __launch_bounds__(MC_BLOCK) void mcl_edge_keys(const int32_t* __restrict__ faces, long long n3, int s,
-                                                         u64* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const long long i = (long long)blockIdx.x * MC_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  const long long f = i / 3;
-  const int c = (int)(i - 3 * f);
-  keys[i] = fu_edge_key(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
-  vals[i] = (uint32_t)i;
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mcl_iota(int32_t* __restrict__ par, long long F) {
-  const long long f = (long long)blockIdx.x * MC_BLOCK + threadIdx.x;
-  if (f < F) par[f] = (int32_t)f;
-}
 
 __global__ __launch_bounds__(MC_BLOCK) void mcl_hook(const u64* __restrict__ sorted, const uint32_t* __restrict__ slot,
                                                     long long n3, int32_t* par) {
   const long long i = (long long)blockIdx.x * MC_BLOCK + threadIdx.x;
   if (i < 1 || i >= n3 || sorted[i] != sorted[i - 1]) return;
   fu_union(par, (int)(slot[i - 1] / 3), (int)(slot[i] / 3));
-}
-
-__global__ __launch_bounds__(MC_BLOCK) void mcl_roots(const int32_t* __restrict__ par, long long F,
-                                                     int32_t* __restrict__ root, int32_t* __restrict__ flags) {
-  const long long f = (long long)blockIdx.x * MC_BLOCK + threadIdx.x;
-  if (f >= F) return;
-  const int r = fu_root(par, (int)f);
-  root[f] = r;
-  flags[f] = r == f;
 }
 
 // cluster[f] = rank[root[f]]; counts[c] += 1 with one atomic per wave and distinct cluster in it (integer sums do not
@@ -332,130 +306,63 @@ __global__ __launch_bounds__(MC_BLOCK) void mcl_compact_rows(const uint32_t* __r
 
 // ------------------------------------------------------------------------------------------------ host
 
-static size_t mcl_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct MclLayout {
   size_t A, B, va, vb, par, cluster, flags, rank, counts, sorted, start, head, tail, pflag, vflag, ctr, tmp, tmp_bytes,
       total;
 };
 
-static int mcl_check(long long V, long long F) {
-  if (V < 1 || F < 1) return VSA_ERR_ARG;
-  if (V > 0x7FFFFFFFll || F > 0x7FFFFFFFll / 3 - 1) return VSA_ERR_UNSUPPORTED;
-  return VSA_OK;
-}
-
-static int mcl_tmp_bytes(long long V, long long F, size_t* out) {
-  const size_t n3 = 3 * (size_t)F, f = (size_t)F, n = f > (size_t)V ? f : (size_t)V;
-  size_t t = 0, need = 16;
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (const uint32_t*)nullptr,
-                                        (uint32_t*)nullptr, n3, 0, 64, (hipStream_t)0));
-  need = t > need ? t : need;
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, f, 0, 32, (hipStream_t)0));
-  need = t > need ? t : need;
-  VSA_HIP_TRY(rocprim::radix_sort_keys_desc(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, f, 0, 32,
-                                            (hipStream_t)0));
-  need = t > need ? t : need;
-  VSA_HIP_TRY(rocprim::exclusive_scan(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, 0, n,
-                                      rocprim::plus<int32_t>(), (hipStream_t)0));
-  need = t > need ? t : need;
-  *out = need;
-  return VSA_OK;
-}
-
 static int mcl_layout(long long V, long long F, MclLayout* l) {
   const size_t v = (size_t)V, f = (size_t)F, n3 = 3 * f, n = f > v ? f : v;
   const size_t chunks = (f + MC_CHUNK - 1) / MC_CHUNK;
-  size_t need = 0;
-  const int rc = mcl_tmp_bytes(V, F, &need);
-  if (rc != VSA_OK) return rc;
-  size_t o = 0;
-#define MCL_AT(field, bytes) \
-  l->field = o;              \
-  o += mcl_align(bytes)
-  MCL_AT(ctr, 8 * MCT_N);
-  MCL_AT(A, 8 * n3);        // edge keys; then the cluster sort's keys and faces (4 x F u32)
-  MCL_AT(B, 8 * n3);        // sorted edge keys
-  MCL_AT(va, 4 * n3);
-  MCL_AT(vb, 4 * n3);
-  MCL_AT(par, 4 * f);
-  MCL_AT(cluster, 4 * f);
-  MCL_AT(flags, 4 * n);     // root flags; then the emitted-face flags
-  MCL_AT(rank, 4 * n);
-  MCL_AT(counts, 4 * f);
-  MCL_AT(sorted, 4 * f);
-  MCL_AT(start, 4 * f);
-  MCL_AT(head, 8 * chunks);
-  MCL_AT(tail, 8 * chunks);
-  MCL_AT(pflag, 4 * f);
-  MCL_AT(vflag, 4 * v);
-  MCL_AT(tmp, need);
-#undef MCL_AT
-  l->tmp_bytes = need;
-  l->total = o;
+  mt::TmpCounts cnt = {};
+  cnt.pairs64 = n3;
+  cnt.pairs32 = f;
+  cnt.keys_desc32 = f;
+  cnt.xscan32 = n;
+  MT_TRY(mt::tmp_bytes(cnt, &l->tmp_bytes));
+  mt::Bump b;
+  l->ctr = b.take(8 * MCT_N);
+  l->A = b.take(8 * n3);        // edge keys; then the cluster sort's keys and faces (4 x F u32)
+  l->B = b.take(8 * n3);        // sorted edge keys
+  l->va = b.take(4 * n3);
+  l->vb = b.take(4 * n3);
+  l->par = b.take(4 * f);
+  l->cluster = b.take(4 * f);
+  l->flags = b.take(4 * n);     // root flags; then the emitted-face flags
+  l->rank = b.take(4 * n);
+  l->counts = b.take(4 * f);
+  l->sorted = b.take(4 * f);
+  l->start = b.take(4 * f);
+  l->head = b.take(8 * chunks);
+  l->tail = b.take(8 * chunks);
+  l->pflag = b.take(4 * f);
+  l->vflag = b.take(4 * v);
+  l->tmp = b.take(l->tmp_bytes);
+  l->total = b.o;
   return VSA_OK;
 }
 
 extern "C" long long vsa_mesh_clusters_workspace_bytes(long long nr_verts, long long nr_faces) {
-  const int rc = mcl_check(nr_verts, nr_faces);
-  if (rc != VSA_OK) return rc;
   MclLayout l;
-  const int rl = mcl_layout(nr_verts, nr_faces, &l);
-  if (rl != VSA_OK) return rl > 0 ? VSA_ERR_UNSUPPORTED : rl;   // a HIP status of rocPRIM's size query
-  return (long long)l.total;
+  int rc = mt::check_vf(nr_verts, nr_faces);
+  if (rc == VSA_OK) rc = mt::abi_status(mcl_layout(nr_verts, nr_faces, &l));
+  return rc != VSA_OK ? rc : (long long)l.total;
 }
 
 namespace {
-
-#define MCL_TRY(expr)              \
-  do {                             \
-    const int r__ = (expr);        \
-    if (r__ != VSA_OK) return r__; \
-  } while (0)
-
-#define MCL_LAUNCHED() VSA_HIP_TRY(hipGetLastError())
-
-dim3 mgrid(long long n) { return dim3((unsigned)vsa_div_up(n > 0 ? n : 1, MC_BLOCK)); }
-
-template <typename T>
-T* at(char* ws, size_t o) {
-  return reinterpret_cast<T*>(ws + o);
-}
 
 struct Mcl {
   hipStream_t st;
   char* ws;
   MclLayout l;
+  mt::Tmp tmp;
   long long V, F, C;
   int s_bits;
   const float* P;
   const int32_t* faces;
   long long* ctr;
-  hipEvent_t ev[2];
-  float* stage_ms;
+  mt::StageTimer timer;
 };
-
-int stage_open(Mcl& m) {
-  if (m.stage_ms) VSA_HIP_TRY(hipEventRecord(m.ev[0], m.st));
-  return VSA_OK;
-}
-
-int stage_close(Mcl& m, int k) {
-  if (!m.stage_ms) return VSA_OK;
-  float ms = 0.f;
-  VSA_HIP_TRY(hipEventRecord(m.ev[1], m.st));
-  VSA_HIP_TRY(hipEventSynchronize(m.ev[1]));
-  VSA_HIP_TRY(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
-  m.stage_ms[k] += ms;
-  return VSA_OK;
-}
-
-int bits_of(long long n) {   // the bits of n - 1, at least 1
-  int s = 1;
-  while ((1ll << s) < n) ++s;
-  return s;
-}
 
 // triangle_clusters and counts (the first C written; counts is zeroed up to F); reads C to the host.
 int cluster_stages(Mcl& m, int32_t* cluster, int32_t* counts) {
@@ -470,34 +377,29 @@ int cluster_stages(Mcl& m, int32_t* cluster, int32_t* counts) {
   int32_t* flags = at<int32_t>(ws, l.flags);
   int32_t* rank = at<int32_t>(ws, l.rank);
   VSA_HIP_TRY(hipMemsetAsync(m.ctr, 0, 8 * MCT_N, m.st));
-  MCL_TRY(stage_open(m));
-  hipLaunchKernelGGL(mcl_edge_keys, mgrid(n3), dim3(MC_BLOCK), 0, m.st, m.faces, n3, m.s_bits, ek, vin);
-  MCL_LAUNCHED();
-  MCL_TRY(stage_close(m, ST_EDGES));
-  MCL_TRY(stage_open(m));
-  size_t bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(ws + l.tmp, bytes, ek, es, vin, slot, (size_t)n3, 0, 2 * m.s_bits, m.st));
-  MCL_TRY(stage_close(m, ST_SORT));
-  MCL_TRY(stage_open(m));
-  hipLaunchKernelGGL(mcl_iota, mgrid(F), dim3(MC_BLOCK), 0, m.st, par, F);
-  MCL_LAUNCHED();
-  hipLaunchKernelGGL(mcl_hook, mgrid(n3), dim3(MC_BLOCK), 0, m.st, es, slot, n3, par);
-  MCL_LAUNCHED();
-  MCL_TRY(stage_close(m, ST_HOOK));
-  MCL_TRY(stage_open(m));
+  // (the two halves of mt::sorted_edges, timed apart)
+  MT_TRY(m.timer.open());
+  MT_TRY(mt::edge_keys(m.faces, F, m.s_bits, ek, vin, m.st));
+  MT_TRY(m.timer.close(ST_EDGES));
+  MT_TRY(m.timer.open());
+  MT_TRY(mt::sort_pairs(m.tmp, ek, es, vin, slot, (size_t)n3, 0, 2 * m.s_bits, m.st));
+  MT_TRY(m.timer.close(ST_SORT));
+  MT_TRY(m.timer.open());
+  MT_TRY(mt::iota(par, F, m.st));
+  hipLaunchKernelGGL(mcl_hook, mt::grid(n3), dim3(MC_BLOCK), 0, m.st, es, slot, n3, par);
+  MT_LAUNCHED();
+  MT_TRY(m.timer.close(ST_HOOK));
+  MT_TRY(m.timer.open());
   // the roots go to `cluster` and are replaced by the numbers in place
-  hipLaunchKernelGGL(mcl_roots, mgrid(F), dim3(MC_BLOCK), 0, m.st, par, F, cluster, flags);
-  MCL_LAUNCHED();
-  MCL_TRY(stage_close(m, ST_ROOTS));
-  MCL_TRY(stage_open(m));
-  bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, flags, rank, 0, (size_t)F, rocprim::plus<int32_t>(), m.st));
+  MT_TRY(mt::roots(par, F, cluster, flags, m.st));
+  MT_TRY(m.timer.close(ST_ROOTS));
+  MT_TRY(m.timer.open());
+  MT_TRY(mt::exclusive_scan(m.tmp, flags, rank, (size_t)F, m.st));
   VSA_HIP_TRY(hipMemsetAsync(counts, 0, 4 * (size_t)F, m.st));
-  hipLaunchKernelGGL(mcl_number, mgrid(F), dim3(MC_BLOCK), 0, m.st, flags, rank, F, cluster, counts, m.ctr);
-  MCL_LAUNCHED();
-  VSA_HIP_TRY(hipMemcpyAsync(&m.C, m.ctr + MCT_C, sizeof(long long), hipMemcpyDeviceToHost, m.st));
-  VSA_HIP_TRY(hipStreamSynchronize(m.st));
-  MCL_TRY(stage_close(m, ST_NUMBER));
+  hipLaunchKernelGGL(mcl_number, mt::grid(F), dim3(MC_BLOCK), 0, m.st, flags, rank, F, cluster, counts, m.ctr);
+  MT_LAUNCHED();
+  MT_TRY(mt::read_counters(m.st, m.ctr + MCT_C, &m.C));
+  MT_TRY(m.timer.close(ST_NUMBER));
   if (m.C < 1 || m.C > F) return VSA_ERR_UNSUPPORTED;
   return VSA_OK;
 }
@@ -513,51 +415,37 @@ int area_stage(Mcl& m, const int32_t* cluster, const int32_t* counts, double* ar
   int32_t* start = at<int32_t>(ws, l.start);
   double* head = at<double>(ws, l.head);
   double* tail = at<double>(ws, l.tail);
-  MCL_TRY(stage_open(m));
-  hipLaunchKernelGGL(mcl_sort_pairs, mgrid(F), dim3(MC_BLOCK), 0, m.st, cluster, F, kin, fin);
-  MCL_LAUNCHED();
-  size_t bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(ws + l.tmp, bytes, kin, kout, fin, fout, (size_t)F, 0, bits_of(m.C), m.st));
-  hipLaunchKernelGGL(mcl_starts, mgrid(F), dim3(MC_BLOCK), 0, m.st, kout, F, start);
-  MCL_LAUNCHED();
+  MT_TRY(m.timer.open());
+  hipLaunchKernelGGL(mcl_sort_pairs, mt::grid(F), dim3(MC_BLOCK), 0, m.st, cluster, F, kin, fin);
+  MT_LAUNCHED();
+  MT_TRY(mt::sort_pairs(m.tmp, kin, kout, fin, fout, (size_t)F, 0, mt::bits_of(m.C), m.st));
+  hipLaunchKernelGGL(mcl_starts, mt::grid(F), dim3(MC_BLOCK), 0, m.st, kout, F, start);
+  MT_LAUNCHED();
   const long long chunks = (F + MC_CHUNK - 1) / MC_CHUNK;
   hipLaunchKernelGGL(mcl_area_chunks, dim3((unsigned)chunks), dim3(MC_BLOCK), 0, m.st, m.P, m.faces, kout, fout, F,
                      start, counts, areas, head, tail);
-  MCL_LAUNCHED();
+  MT_LAUNCHED();
   hipLaunchKernelGGL(mcl_area_spans, dim3((unsigned)m.C), dim3(VSA_WAVE), 0, m.st, start, counts, m.C, head, tail, areas);
-  MCL_LAUNCHED();
-  MCL_TRY(stage_close(m, ST_AREAS));
+  MT_LAUNCHED();
+  MT_TRY(m.timer.close(ST_AREAS));
   return VSA_OK;
 }
 
 int setup(Mcl& m, const float* verts, long long V, const int32_t* faces, long long F, void* workspace,
           long long workspace_bytes, float* stage_ms, void* stream) {
-  int rc = mcl_layout(V, F, &m.l);
-  if (rc != VSA_OK) return rc > 0 ? VSA_ERR_UNSUPPORTED : rc;
+  MT_TRY(mt::abi_status(mcl_layout(V, F, &m.l)));
   if (workspace_bytes < (long long)m.l.total) return VSA_ERR_ARG;
   m.st = (hipStream_t)stream;
   m.ws = static_cast<char*>(workspace);
+  m.tmp = {m.ws + m.l.tmp, m.l.tmp_bytes};
   m.V = V;
   m.F = F;
   m.C = 0;
   m.P = verts;
   m.faces = faces;
-  m.s_bits = bits_of(V);
+  m.s_bits = mt::bits_of(V);
   m.ctr = at<long long>(m.ws, m.l.ctr);
-  m.stage_ms = stage_ms;
-  if (stage_ms) {
-    for (int k = 0; k < MC_STAGES; ++k) stage_ms[k] = 0.f;
-    VSA_HIP_TRY(hipEventCreate(&m.ev[0]));
-    VSA_HIP_TRY(hipEventCreate(&m.ev[1]));
-  }
-  return VSA_OK;
-}
-
-void teardown(Mcl& m) {
-  if (m.stage_ms) {
-    (void)hipEventDestroy(m.ev[0]);
-    (void)hipEventDestroy(m.ev[1]);
-  }
+  return m.timer.create(stage_ms, MC_STAGES, m.st);
 }
 
 int run_filter(Mcl& m, int mode, const uint8_t* keep_mask, long long cluster_to_keep, long long min_cluster_faces,
@@ -569,14 +457,13 @@ int run_filter(Mcl& m, int mode, const uint8_t* keep_mask, long long cluster_to_
   int32_t* cluster = at<int32_t>(ws, l.cluster);
   int32_t* counts = at<int32_t>(ws, l.counts);
   if (mode == 2) {
-    MCL_TRY(cluster_stages(m, cluster, counts));
-    MCL_TRY(stage_open(m));
+    MT_TRY(cluster_stages(m, cluster, counts));
+    MT_TRY(m.timer.open());
     int32_t* sorted = at<int32_t>(ws, l.sorted);
-    size_t bytes = l.tmp_bytes;
-    VSA_HIP_TRY(rocprim::radix_sort_keys_desc(ws + l.tmp, bytes, counts, sorted, (size_t)m.C, 0, 32, m.st));
+    MT_TRY(mt::sort_keys_desc(m.tmp, counts, sorted, (size_t)m.C, 0, 32, m.st));
     hipLaunchKernelGGL(mcl_threshold, dim3(1), dim3(1), 0, m.st, sorted, cluster_to_keep, min_cluster_faces, m.ctr);
-    MCL_LAUNCHED();
-    MCL_TRY(stage_close(m, ST_THRESHOLD));
+    MT_LAUNCHED();
+    MT_TRY(m.timer.close(ST_THRESHOLD));
   } else {
     VSA_HIP_TRY(hipMemsetAsync(m.ctr, 0, 8 * MCT_N, m.st));
   }
@@ -584,34 +471,31 @@ int run_filter(Mcl& m, int mode, const uint8_t* keep_mask, long long cluster_to_
   int32_t* pflag = at<int32_t>(ws, l.pflag);
   int32_t* vflag = at<int32_t>(ws, l.vflag);
   int32_t* rank = at<int32_t>(ws, l.rank);
-  MCL_TRY(stage_open(m));
+  MT_TRY(m.timer.open());
   if (drop_unreferenced) {
     VSA_HIP_TRY(hipMemsetAsync(vflag, 0, 4 * (size_t)V, m.st));
   } else {
-    hipLaunchKernelGGL(mcl_fill, mgrid(V), dim3(MC_BLOCK), 0, m.st, vflag, V, 1);
-    MCL_LAUNCHED();
+    hipLaunchKernelGGL(mcl_fill, mt::grid(V), dim3(MC_BLOCK), 0, m.st, vflag, V, 1);
+    MT_LAUNCHED();
   }
-  hipLaunchKernelGGL(mcl_mask, mgrid(F), dim3(MC_BLOCK), 0, m.st, m.faces, F, mode, keep_mask, cluster, counts, m.ctr,
-                     drop_degenerate, fflag, pflag, drop_unreferenced ? vflag : (int32_t*)nullptr);
-  MCL_LAUNCHED();
-  MCL_TRY(stage_close(m, ST_MASK));
-  MCL_TRY(stage_open(m));
+  hipLaunchKernelGGL(mcl_mask, mt::grid(F), dim3(MC_BLOCK), 0, m.st, m.faces, F, mode, keep_mask, cluster, counts,
+                     m.ctr, drop_degenerate, fflag, pflag, drop_unreferenced ? vflag : (int32_t*)nullptr);
+  MT_LAUNCHED();
+  MT_TRY(m.timer.close(ST_MASK));
+  MT_TRY(m.timer.open());
   // vertices first: `rank` holds the vertex ranks while the faces are renumbered, so the face ranks go to `start`
-  size_t bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, vflag, rank, 0, (size_t)V, rocprim::plus<int32_t>(), m.st));
-  hipLaunchKernelGGL(mcl_emit_verts, mgrid(V), dim3(MC_BLOCK), 0, m.st, m.P, V, vflag, rank, out_verts, out_vmap,
+  MT_TRY(mt::exclusive_scan(m.tmp, vflag, rank, (size_t)V, m.st));
+  hipLaunchKernelGGL(mcl_emit_verts, mt::grid(V), dim3(MC_BLOCK), 0, m.st, m.P, V, vflag, rank, out_verts, out_vmap,
                      m.ctr);
-  MCL_LAUNCHED();
+  MT_LAUNCHED();
   int32_t* frank = at<int32_t>(ws, l.start);
-  bytes = l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::exclusive_scan(ws + l.tmp, bytes, fflag, frank, 0, (size_t)F, rocprim::plus<int32_t>(), m.st));
-  hipLaunchKernelGGL(mcl_emit_faces, mgrid(F), dim3(MC_BLOCK), 0, m.st, m.faces, F, fflag, frank, pflag, rank,
+  MT_TRY(mt::exclusive_scan(m.tmp, fflag, frank, (size_t)F, m.st));
+  hipLaunchKernelGGL(mcl_emit_faces, mt::grid(F), dim3(MC_BLOCK), 0, m.st, m.faces, F, fflag, frank, pflag, rank,
                      out_faces, out_fmap, m.ctr);
-  MCL_LAUNCHED();
+  MT_LAUNCHED();
   long long host[MCT_N];
-  VSA_HIP_TRY(hipMemcpyAsync(host, m.ctr, sizeof(host), hipMemcpyDeviceToHost, m.st));
-  VSA_HIP_TRY(hipStreamSynchronize(m.st));
-  MCL_TRY(stage_close(m, ST_COMPACT));
+  MT_TRY(mt::read_counters(m.st, m.ctr, host, MCT_N));
+  MT_TRY(m.timer.close(ST_COMPACT));
   stats[0] = host[MCT_VOUT];
   stats[1] = host[MCT_FOUT];
   stats[2] = mode == 2 ? host[MCT_C] : 0;
@@ -630,7 +514,7 @@ extern "C" int vsa_mesh_clusters(const float* verts, long long nr_verts, const i
   if (!verts || !faces || !workspace || !out_triangle_clusters || !out_cluster_n_triangles || !out_cluster_area ||
       !out_nr_clusters)
     return VSA_ERR_ARG;
-  int rc = mcl_check(nr_verts, nr_faces);
+  int rc = mt::check_vf(nr_verts, nr_faces);
   if (rc != VSA_OK) return rc;
   Mcl m;
   rc = setup(m, verts, nr_verts, faces, nr_faces, workspace, workspace_bytes, stage_ms, stream);
@@ -641,7 +525,7 @@ extern "C" int vsa_mesh_clusters(const float* verts, long long nr_verts, const i
     const hipError_t e = hipStreamSynchronize(m.st);
     rc = e == hipSuccess ? VSA_OK : (int)e;
   }
-  teardown(m);
+  m.timer.destroy();
   if (rc == VSA_OK) *out_nr_clusters = m.C;
   return rc;
 }
@@ -656,14 +540,14 @@ extern "C" int vsa_mesh_filter(const float* verts, long long nr_verts, const int
     return VSA_ERR_ARG;
   if (mode < 0 || mode > 2 || (mode == 1 && !keep_mask)) return VSA_ERR_ARG;
   if (mode == 2 && (cluster_to_keep < 1 || min_cluster_faces < 0)) return VSA_ERR_ARG;
-  int rc = mcl_check(nr_verts, nr_faces);
+  int rc = mt::check_vf(nr_verts, nr_faces);
   if (rc != VSA_OK) return rc;
   Mcl m;
   rc = setup(m, verts, nr_verts, faces, nr_faces, workspace, workspace_bytes, stage_ms, stream);
   if (rc != VSA_OK) return rc;
   rc = run_filter(m, mode, keep_mask, cluster_to_keep, min_cluster_faces, drop_unreferenced != 0, drop_degenerate != 0,
                   out_verts, out_faces, out_vertex_map, out_face_map, stats);
-  teardown(m);
+  m.timer.destroy();
   return rc;
 }
 

@@ -18,14 +18,12 @@
 // Winners share no vertex and no face (see the header), so the lanes of one round never touch the same data.  Every
 // float sum has a fixed order (no float atomics); integer atomics only form minima, ORs and counts.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <cstdint>
 
-#include "common.h"
+#include "mesh_topology.h"
 
-#define SMP_BLOCK 256
+#define SMP_BLOCK MT_BLOCK
 #define SMP_BOUNDARY 1u
 #define SMP_FROZEN 2u
 #define SMP_DET_REL 1e-10
@@ -41,7 +39,7 @@
 #define CTR_V 5
 #define CTR_N 8
 
-typedef unsigned long long u64;
+using mt::u64;
 
 // ------------------------------------------------------------------------------------------------ fp64 geometry
 
@@ -163,21 +161,6 @@ __device__ void smp_place(const double* __restrict__ Q, const float* __restrict_
 
 // ------------------------------------------------------------------------------------------------ edges and rings
 
-__device__ __forceinline__ u64 smp_pack(int x, int y, int s) {
-  const int lo = x < y ? x : y, hi = x < y ? y : x;
-  return (u64)(unsigned)lo << s | (u64)(unsigned)hi;
-}
-
-__global__ __launch_bounds__(SMP_BLOCK) void smp_edge_keys(const int32_t* __restrict__ faces, long long n3, int s,
-                                                          u64* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  const long long f = i / 3;
-  const int c = (int)(i - 3 * f);
-  keys[i] = smp_pack(faces[3 * f + c], faces[3 * f + (c == 2 ? 0 : c + 1)], s);
-  if (vals) vals[i] = (uint32_t)i;
-}
-
 __global__ __launch_bounds__(SMP_BLOCK) void smp_heads(const u64* __restrict__ sorted, long long n3,
                                                       int32_t* __restrict__ flags) {
   const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
@@ -223,22 +206,6 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_slot_counts(const int32_t* __re
   if (i >= n3) return;
   const int e = rank[i] + flags[i] - 1;
   slot_cnt[slot[i]] = ehead[e + 1] - ehead[e];
-}
-
-__global__ __launch_bounds__(SMP_BLOCK) void smp_vf_pairs(const int32_t* __restrict__ faces, long long n3,
-                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  keys[i] = (uint32_t)faces[i];
-  vals[i] = (uint32_t)(i / 3);
-}
-
-__global__ __launch_bounds__(SMP_BLOCK) void smp_vf_ranges(const uint32_t* __restrict__ k, long long n3,
-                                                          int32_t* __restrict__ vstart, int32_t* __restrict__ vend) {
-  const long long i = (long long)blockIdx.x * SMP_BLOCK + threadIdx.x;
-  if (i >= n3) return;
-  if (i == 0 || k[i] != k[i - 1]) vstart[k[i]] = (int32_t)i;
-  if (i == n3 - 1 || k[i] != k[i + 1]) vend[k[i]] = (int32_t)(i + 1);
 }
 
 // Init: Q_v = sum over the faces at v in ascending face order of (face quadric, then the penalties of the face's
@@ -550,78 +517,56 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_out_faces(const int32_t* __rest
 
 // ------------------------------------------------------------------------------------------------ host
 
-static size_t smp_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct SmpLayout {
   size_t pos, Q, vflag, vstart, vend, m1, m2, fa, fb, A, B, flags, rank, ehead, ekey, vfk, vff, ctr, tmp, tmp_bytes,
       total;
 };
 
-static int smp_check(long long V, long long F) {
-  if (V < 1 || F < 1) return VSA_ERR_ARG;
-  if (V > 0x7FFFFFFFll || F > 0x7FFFFFFFll / 3 - 1) return VSA_ERR_UNSUPPORTED;
-  return VSA_OK;
-}
-
 static int smp_layout(long long V, long long F, SmpLayout* l) {
-  const size_t v = (size_t)V, n3 = 3 * (size_t)F;
-  size_t t = 0, need = 0;
-  // rocPRIM temporary storage: the largest of every sort and scan below
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (const uint32_t*)nullptr,
-                                        (uint32_t*)nullptr, n3, 0, 64, (hipStream_t)0));
-  need = t > need ? t : need;
-  VSA_HIP_TRY(rocprim::radix_sort_keys(nullptr, t, (const u64*)nullptr, (u64*)nullptr, n3, 0, 64, (hipStream_t)0));
-  need = t > need ? t : need;
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(nullptr, t, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0, 32, (hipStream_t)0));
-  need = t > need ? t : need;
-  VSA_HIP_TRY(rocprim::exclusive_scan(nullptr, t, (const int32_t*)nullptr, (int32_t*)nullptr, 0, n3 > v ? n3 : v,
-                                      rocprim::plus<int32_t>(), (hipStream_t)0));
-  need = t > need ? t : need;
-  size_t o = 0;
-#define SMP_AT(field, bytes) \
-  l->field = o;              \
-  o += smp_align(bytes)
-  SMP_AT(pos, 12 * v);
-  SMP_AT(Q, 80 * v);
-  SMP_AT(vflag, 4 * v);
-  SMP_AT(vstart, 4 * v);
-  SMP_AT(vend, 4 * v);
-  SMP_AT(m1, 8 * v);
-  SMP_AT(m2, 8 * v);
-  SMP_AT(fa, 4 * n3);
-  SMP_AT(fb, 4 * n3);
-  SMP_AT(A, 8 * n3);
-  SMP_AT(B, 8 * n3);
-  SMP_AT(flags, 4 * (n3 > v ? n3 : v));
-  SMP_AT(rank, 4 * (n3 > v ? n3 : v));
-  SMP_AT(ehead, 4 * (n3 + 1));
-  SMP_AT(ekey, 8 * n3);
-  SMP_AT(vfk, 4 * n3);
-  SMP_AT(vff, 4 * n3);
-  SMP_AT(ctr, 8 * CTR_N);
-  SMP_AT(tmp, need ? need : 16);
-#undef SMP_AT
-  l->tmp_bytes = need ? need : 16;
-  l->total = o;
+  const size_t v = (size_t)V, n3 = 3 * (size_t)F, n = n3 > v ? n3 : v;
+  mt::TmpCounts cnt = {};
+  cnt.pairs64 = n3;
+  cnt.keys64 = n3;
+  cnt.pairs32 = n3;
+  cnt.xscan32 = n;
+  MT_TRY(mt::tmp_bytes(cnt, &l->tmp_bytes));
+  mt::Bump b;
+  l->pos = b.take(12 * v);
+  l->Q = b.take(80 * v);
+  l->vflag = b.take(4 * v);
+  l->vstart = b.take(4 * v);
+  l->vend = b.take(4 * v);
+  l->m1 = b.take(8 * v);
+  l->m2 = b.take(8 * v);
+  l->fa = b.take(4 * n3);
+  l->fb = b.take(4 * n3);
+  l->A = b.take(8 * n3);
+  l->B = b.take(8 * n3);
+  l->flags = b.take(4 * n);
+  l->rank = b.take(4 * n);
+  l->ehead = b.take(4 * (n3 + 1));
+  l->ekey = b.take(8 * n3);
+  l->vfk = b.take(4 * n3);
+  l->vff = b.take(4 * n3);
+  l->ctr = b.take(8 * CTR_N);
+  l->tmp = b.take(l->tmp_bytes);
+  l->total = b.o;
   return VSA_OK;
 }
 
 extern "C" long long vsa_simplify_workspace_bytes(long long nr_verts, long long nr_faces) {
-  const int rc = smp_check(nr_verts, nr_faces);
-  if (rc != VSA_OK) return rc;
   SmpLayout l;
-  const int rl = smp_layout(nr_verts, nr_faces, &l);
-  if (rl != VSA_OK) return rl;
-  return (long long)l.total;
+  int rc = mt::check_vf(nr_verts, nr_faces);
+  if (rc == VSA_OK) rc = mt::abi_status(smp_layout(nr_verts, nr_faces, &l));
+  return rc != VSA_OK ? rc : (long long)l.total;
 }
 
 namespace {
 
 struct Smp {
   hipStream_t st;
-  char* ws;
   SmpLayout l;
+  mt::Tmp tmp;
   long long V, F;
   int s;
   float* P;
@@ -631,168 +576,116 @@ struct Smp {
   u64 *m1, *m2, *A, *B, *ekey;
   uint32_t *vfk, *vff;
   long long* ctr;
-  hipEvent_t ev[2];
-  float* stage_ms;
+  mt::StageTimer timer;
 };
-
-dim3 grid_of(long long n) { return dim3((unsigned)vsa_div_up(n > 0 ? n : 1, SMP_BLOCK)); }
-
-int smp_scan(Smp& m, const int32_t* in, int32_t* out, long long n) {
-  size_t bytes = m.l.tmp_bytes;
-  VSA_HIP_TRY(rocprim::exclusive_scan(m.ws + m.l.tmp, bytes, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), m.st));
-  return VSA_OK;
-}
-
-// Stage timing (only when stage_ms is given): stage_open() opens a stage, stage_close(k) adds its device time to
-// stage_ms[k].
-int stage_open(Smp& m) {
-  if (m.stage_ms) VSA_HIP_TRY(hipEventRecord(m.ev[0], m.st));
-  return VSA_OK;
-}
-
-int stage_close(Smp& m, int k) {
-  if (!m.stage_ms) return VSA_OK;
-  float ms = 0.f;
-  VSA_HIP_TRY(hipEventRecord(m.ev[1], m.st));
-  VSA_HIP_TRY(hipEventSynchronize(m.ev[1]));
-  VSA_HIP_TRY(hipEventElapsedTime(&ms, m.ev[0], m.ev[1]));
-  m.stage_ms[k] += ms;
-  return VSA_OK;
-}
 
 // Unique edges of the F current faces (sorted keys in B, ids via flags / rank, ehead, E on the device); with
 // `slots`, the sorted slot of every key lands in vff and the edge's face count at every face slot in slot_cnt.
 int build_edges(Smp& m, bool slots, int32_t* slot_cnt) {
   const long long n3 = 3 * m.F;
-  size_t bytes = m.l.tmp_bytes;
-  uint32_t* vin = slots ? m.vfk : nullptr;
-  hipLaunchKernelGGL(smp_edge_keys, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.s, m.A, vin);
-  VSA_HIP_TRY(hipGetLastError());
-  if (slots)
-    VSA_HIP_TRY(rocprim::radix_sort_pairs(m.ws + m.l.tmp, bytes, m.A, m.B, vin, m.vff, (size_t)n3, 0, 2 * m.s, m.st));
-  else
-    VSA_HIP_TRY(rocprim::radix_sort_keys(m.ws + m.l.tmp, bytes, m.A, m.B, (size_t)n3, 0, 2 * m.s, m.st));
-  hipLaunchKernelGGL(smp_heads, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.B, n3, m.flags);
-  VSA_HIP_TRY(hipGetLastError());
-  int rc = smp_scan(m, m.flags, m.rank, n3);
-  if (rc != VSA_OK) return rc;
-  hipLaunchKernelGGL(smp_edge_index, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.flags, m.rank, n3, m.ehead, m.ctr);
-  VSA_HIP_TRY(hipGetLastError());
+  MT_TRY(mt::sorted_edges(m.fcur, m.F, m.s, m.A, m.B, slots ? m.vfk : nullptr, m.vff, m.tmp, m.st));
+  hipLaunchKernelGGL(smp_heads, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.B, n3, m.flags);
+  MT_LAUNCHED();
+  MT_TRY(mt::exclusive_scan(m.tmp, m.flags, m.rank, (size_t)n3, m.st));
+  hipLaunchKernelGGL(smp_edge_index, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.flags, m.rank, n3, m.ehead, m.ctr);
+  MT_LAUNCHED();
   if (slots) {
-    hipLaunchKernelGGL(smp_slot_counts, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.flags, m.rank, m.vff, m.ehead, n3,
+    hipLaunchKernelGGL(smp_slot_counts, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.flags, m.rank, m.vff, m.ehead, n3,
                        slot_cnt);
-    VSA_HIP_TRY(hipGetLastError());
+    MT_LAUNCHED();
   }
   return VSA_OK;
 }
 
 // The (vertex, face) list sorted by vertex (stable: ascending face within a vertex) -> vff, vstart / vend.
 int build_rings(Smp& m) {
-  const long long n3 = 3 * m.F;
   uint32_t* kin = reinterpret_cast<uint32_t*>(m.A);
-  uint32_t* vin = kin + n3;
-  size_t bytes = m.l.tmp_bytes;
-  hipLaunchKernelGGL(smp_vf_pairs, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, kin, vin);
-  VSA_HIP_TRY(hipGetLastError());
-  VSA_HIP_TRY(rocprim::radix_sort_pairs(m.ws + m.l.tmp, bytes, kin, m.vfk, vin, m.vff, (size_t)n3, 0, m.s, m.st));
-  VSA_HIP_TRY(hipMemsetAsync(m.vstart, 0, 4 * (size_t)m.V, m.st));
-  VSA_HIP_TRY(hipMemsetAsync(m.vend, 0, 4 * (size_t)m.V, m.st));
-  hipLaunchKernelGGL(smp_vf_ranges, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.vfk, n3, m.vstart, m.vend);
-  VSA_HIP_TRY(hipGetLastError());
-  return VSA_OK;
+  return mt::vertex_rings(m.fcur, m.F, m.V, m.s, kin, m.vfk, kin + 3 * m.F, m.vff, m.vstart, m.vend, m.tmp, m.st);
 }
-
-#define SMP_TRY(expr)              \
-  do {                             \
-    const int r__ = (expr);        \
-    if (r__ != VSA_OK) return r__; \
-  } while (0)
 
 int run(Smp& m, const float* verts, const int32_t* faces, long long target, float* out_verts, int32_t* out_faces,
         long long* stats) {
   const long long V = m.V;
   long long rounds = 0, collapses = 0, stalled = 0;
-  SMP_TRY(stage_open(m));
+  MT_TRY(m.timer.open());
   VSA_HIP_TRY(hipMemcpyAsync(m.P, verts, 12 * (size_t)V, hipMemcpyDeviceToDevice, m.st));
   VSA_HIP_TRY(hipMemcpyAsync(m.fcur, faces, 12 * (size_t)m.F, hipMemcpyDeviceToDevice, m.st));
   VSA_HIP_TRY(hipMemsetAsync(m.ctr, 0, 8 * CTR_N, m.st));
   int32_t* slot_cnt = reinterpret_cast<int32_t*>(m.ekey);
-  SMP_TRY(build_edges(m, true, slot_cnt));
-  SMP_TRY(build_rings(m));
-  hipLaunchKernelGGL(smp_quadrics, grid_of(V), dim3(SMP_BLOCK), 0, m.st, m.P, m.fcur, m.vff, m.vstart, m.vend,
+  MT_TRY(build_edges(m, true, slot_cnt));
+  MT_TRY(build_rings(m));
+  hipLaunchKernelGGL(smp_quadrics, mt::grid(V), dim3(SMP_BLOCK), 0, m.st, m.P, m.fcur, m.vff, m.vstart, m.vend,
                      slot_cnt, V, m.Q);
-  VSA_HIP_TRY(hipGetLastError());
-  SMP_TRY(stage_close(m, 0));
+  MT_LAUNCHED();
+  MT_TRY(m.timer.close(0));
   while (m.F > target) {
     const long long n3 = 3 * m.F;
     // edges
-    SMP_TRY(stage_open(m));
-    SMP_TRY(build_edges(m, false, nullptr));
+    MT_TRY(m.timer.open());
+    MT_TRY(build_edges(m, false, nullptr));
     VSA_HIP_TRY(hipMemsetAsync(m.vflag, 0, 4 * (size_t)V, m.st));
-    hipLaunchKernelGGL(smp_vertex_flags, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.B, m.ehead, n3, m.s, m.ctr, m.vflag);
-    VSA_HIP_TRY(hipGetLastError());
-    SMP_TRY(build_rings(m));
-    SMP_TRY(stage_close(m, 1));
+    hipLaunchKernelGGL(smp_vertex_flags, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.B, m.ehead, n3, m.s, m.ctr, m.vflag);
+    MT_LAUNCHED();
+    MT_TRY(build_rings(m));
+    MT_TRY(m.timer.close(1));
     // cost
-    SMP_TRY(stage_open(m));
-    hipLaunchKernelGGL(smp_cost, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.P, m.Q, m.vflag, m.fcur, m.B, m.ehead, m.vff,
+    MT_TRY(m.timer.open());
+    hipLaunchKernelGGL(smp_cost, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.P, m.Q, m.vflag, m.fcur, m.B, m.ehead, m.vff,
                        m.vstart, m.vend, n3, m.s, m.ctr, m.ekey);
-    VSA_HIP_TRY(hipGetLastError());
-    SMP_TRY(stage_close(m, 2));
+    MT_LAUNCHED();
+    MT_TRY(m.timer.close(2));
     // select
-    SMP_TRY(stage_open(m));
+    MT_TRY(m.timer.open());
     VSA_HIP_TRY(hipMemsetAsync(m.m1, 0xFF, 8 * (size_t)V, m.st));
     VSA_HIP_TRY(hipMemsetAsync(m.m2, 0xFF, 8 * (size_t)V, m.st));
     VSA_HIP_TRY(hipMemsetAsync(m.ctr + CTR_R, 0, 8, m.st));
-    hipLaunchKernelGGL(smp_m1, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.B, m.ehead, m.s, m.ctr, m.m1);
-    VSA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(smp_m2, grid_of(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.m1, m.m2);
-    VSA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(smp_win_flags, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.B, m.ehead, n3, m.s, m.m2,
+    hipLaunchKernelGGL(smp_m1, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.B, m.ehead, m.s, m.ctr, m.m1);
+    MT_LAUNCHED();
+    hipLaunchKernelGGL(smp_m2, mt::grid(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.m1, m.m2);
+    MT_LAUNCHED();
+    hipLaunchKernelGGL(smp_win_flags, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.B, m.ehead, n3, m.s, m.m2,
                        m.ctr, m.flags);
-    VSA_HIP_TRY(hipGetLastError());
-    SMP_TRY(smp_scan(m, m.flags, m.rank, n3));
+    MT_LAUNCHED();
+    MT_TRY(mt::exclusive_scan(m.tmp, m.flags, m.rank, (size_t)n3, m.st));
     u64* wkeys = m.A;
     u64* wsorted = m.A + m.F;   // winners share no face: W <= F
-    hipLaunchKernelGGL(smp_win_compact, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.flags, m.rank, n3, wkeys,
+    hipLaunchKernelGGL(smp_win_compact, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.ekey, m.flags, m.rank, n3, wkeys,
                        m.ctr);
-    VSA_HIP_TRY(hipGetLastError());
+    MT_LAUNCHED();
     long long wr[2];
-    VSA_HIP_TRY(hipMemcpyAsync(wr, m.ctr + CTR_W, sizeof(wr), hipMemcpyDeviceToHost, m.st));
-    VSA_HIP_TRY(hipStreamSynchronize(m.st));
+    MT_TRY(mt::read_counters(m.st, m.ctr + CTR_W, wr, 2));
     const long long W = wr[0], R = wr[1], need = m.F - target;
     if (W < 0 || W > m.F) return VSA_ERR_UNSUPPORTED;
     if (W == 0) {
-      SMP_TRY(stage_close(m, 3));
+      MT_TRY(m.timer.close(3));
       stalled = 1;
       break;
     }
     const u64* list = wkeys;
     const int32_t* pre = nullptr;
     if (R > need) {
-      size_t bytes = m.l.tmp_bytes;
-      VSA_HIP_TRY(rocprim::radix_sort_keys(m.ws + m.l.tmp, bytes, wkeys, wsorted, (size_t)W, 0, 64, m.st));
-      hipLaunchKernelGGL(smp_win_counts, grid_of(W), dim3(SMP_BLOCK), 0, m.st, wsorted, W, m.ehead, m.flags);
-      VSA_HIP_TRY(hipGetLastError());
-      SMP_TRY(smp_scan(m, m.flags, m.rank, W));
+      MT_TRY(mt::sort_keys(m.tmp, wkeys, wsorted, (size_t)W, 0, 64, m.st));
+      hipLaunchKernelGGL(smp_win_counts, mt::grid(W), dim3(SMP_BLOCK), 0, m.st, wsorted, W, m.ehead, m.flags);
+      MT_LAUNCHED();
+      MT_TRY(mt::exclusive_scan(m.tmp, m.flags, m.rank, (size_t)W, m.st));
       list = wsorted;
       pre = m.rank;
     }
-    SMP_TRY(stage_close(m, 3));
+    MT_TRY(m.timer.close(3));
     // collapse
-    SMP_TRY(stage_open(m));
-    hipLaunchKernelGGL(smp_collapse, grid_of(W), dim3(SMP_BLOCK), 0, m.st, list, W, pre, need, m.B, m.ehead, m.s,
+    MT_TRY(m.timer.open());
+    hipLaunchKernelGGL(smp_collapse, mt::grid(W), dim3(SMP_BLOCK), 0, m.st, list, W, pre, need, m.B, m.ehead, m.s,
                        m.vflag, m.vff, m.vstart, m.vend, m.P, m.Q, m.fcur, m.ctr);
-    VSA_HIP_TRY(hipGetLastError());
-    SMP_TRY(stage_close(m, 4));
+    MT_LAUNCHED();
+    MT_TRY(m.timer.close(4));
     // compact
-    SMP_TRY(stage_open(m));
-    hipLaunchKernelGGL(smp_face_alive, grid_of(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags);
-    VSA_HIP_TRY(hipGetLastError());
-    SMP_TRY(smp_scan(m, m.flags, m.rank, m.F));
-    hipLaunchKernelGGL(smp_face_scatter, grid_of(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags, m.rank, m.fnext,
+    MT_TRY(m.timer.open());
+    hipLaunchKernelGGL(smp_face_alive, mt::grid(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags);
+    MT_LAUNCHED();
+    MT_TRY(mt::exclusive_scan(m.tmp, m.flags, m.rank, (size_t)m.F, m.st));
+    hipLaunchKernelGGL(smp_face_scatter, mt::grid(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags, m.rank, m.fnext,
                        m.ctr);
-    VSA_HIP_TRY(hipGetLastError());
+    MT_LAUNCHED();
     int32_t* t = m.fcur;
     m.fcur = m.fnext;
     m.fnext = t;
@@ -800,8 +693,7 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
     if (pre) {
       // the last round: read the faces left and the accepted collapses back (F <= target now)
       long long fa[2];
-      VSA_HIP_TRY(hipMemcpyAsync(fa, m.ctr + CTR_F, sizeof(fa), hipMemcpyDeviceToHost, m.st));
-      VSA_HIP_TRY(hipStreamSynchronize(m.st));
+      MT_TRY(mt::read_counters(m.st, m.ctr + CTR_F, fa, 2));
       if (fa[0] < 0 || fa[0] > target || fa[1] < 1 || fa[1] > W) return VSA_ERR_UNSUPPORTED;
       collapses += fa[1];
       m.F = fa[0];
@@ -809,25 +701,24 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
       collapses += W;
       m.F -= R;
     }
-    SMP_TRY(stage_close(m, 5));
+    MT_TRY(m.timer.close(5));
   }
   // output: the referenced vertices in ascending index, faces in order
-  SMP_TRY(stage_open(m));
+  MT_TRY(m.timer.open());
   const long long n3 = 3 * m.F;
   VSA_HIP_TRY(hipMemsetAsync(m.flags, 0, 4 * (size_t)V, m.st));
-  hipLaunchKernelGGL(smp_mark_used, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.flags);
-  VSA_HIP_TRY(hipGetLastError());
-  SMP_TRY(smp_scan(m, m.flags, m.rank, V));
-  hipLaunchKernelGGL(smp_out_verts, grid_of(V), dim3(SMP_BLOCK), 0, m.st, m.P, V, m.flags, m.rank, out_verts, m.ctr);
-  VSA_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(smp_mark_used, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.flags);
+  MT_LAUNCHED();
+  MT_TRY(mt::exclusive_scan(m.tmp, m.flags, m.rank, (size_t)V, m.st));
+  hipLaunchKernelGGL(smp_out_verts, mt::grid(V), dim3(SMP_BLOCK), 0, m.st, m.P, V, m.flags, m.rank, out_verts, m.ctr);
+  MT_LAUNCHED();
   if (n3 > 0) {
-    hipLaunchKernelGGL(smp_out_faces, grid_of(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.rank, out_faces);
-    VSA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(smp_out_faces, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.rank, out_faces);
+    MT_LAUNCHED();
   }
   long long vout = 0;
-  VSA_HIP_TRY(hipMemcpyAsync(&vout, m.ctr + CTR_V, sizeof(vout), hipMemcpyDeviceToHost, m.st));
-  VSA_HIP_TRY(hipStreamSynchronize(m.st));
-  SMP_TRY(stage_close(m, 5));
+  MT_TRY(mt::read_counters(m.st, m.ctr + CTR_V, &vout));
+  MT_TRY(m.timer.close(5));
   stats[0] = rounds;
   stats[1] = collapses;
   stats[2] = stalled;
@@ -842,46 +733,37 @@ extern "C" int vsa_simplify(const float* verts, long long nr_verts, const int32_
                             long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
                             int32_t* out_faces, long long* stats, float* stage_ms, void* stream) {
   if (!verts || !faces || !workspace || !out_verts || !out_faces || !stats || target_faces < 0) return VSA_ERR_ARG;
-  int rc = smp_check(nr_verts, nr_faces);
-  if (rc != VSA_OK) return rc;
+  MT_TRY(mt::check_vf(nr_verts, nr_faces));
   Smp m;
-  rc = smp_layout(nr_verts, nr_faces, &m.l);
-  if (rc != VSA_OK) return rc;
+  MT_TRY(mt::abi_status(smp_layout(nr_verts, nr_faces, &m.l)));
   if (workspace_bytes < (long long)m.l.total) return VSA_ERR_ARG;
+  char* ws = static_cast<char*>(workspace);
+  const SmpLayout& l = m.l;
   m.st = (hipStream_t)stream;
-  m.ws = static_cast<char*>(workspace);
+  m.tmp = {ws + l.tmp, l.tmp_bytes};
   m.V = nr_verts;
   m.F = nr_faces;
-  m.s = 1;
-  while ((1ll << m.s) < nr_verts) ++m.s;
-  m.P = reinterpret_cast<float*>(m.ws + m.l.pos);
-  m.Q = reinterpret_cast<double*>(m.ws + m.l.Q);
-  m.vflag = reinterpret_cast<unsigned*>(m.ws + m.l.vflag);
-  m.vstart = reinterpret_cast<int32_t*>(m.ws + m.l.vstart);
-  m.vend = reinterpret_cast<int32_t*>(m.ws + m.l.vend);
-  m.m1 = reinterpret_cast<u64*>(m.ws + m.l.m1);
-  m.m2 = reinterpret_cast<u64*>(m.ws + m.l.m2);
-  m.fcur = reinterpret_cast<int32_t*>(m.ws + m.l.fa);
-  m.fnext = reinterpret_cast<int32_t*>(m.ws + m.l.fb);
-  m.A = reinterpret_cast<u64*>(m.ws + m.l.A);
-  m.B = reinterpret_cast<u64*>(m.ws + m.l.B);
-  m.flags = reinterpret_cast<int32_t*>(m.ws + m.l.flags);
-  m.rank = reinterpret_cast<int32_t*>(m.ws + m.l.rank);
-  m.ehead = reinterpret_cast<int32_t*>(m.ws + m.l.ehead);
-  m.ekey = reinterpret_cast<u64*>(m.ws + m.l.ekey);
-  m.vfk = reinterpret_cast<uint32_t*>(m.ws + m.l.vfk);
-  m.vff = reinterpret_cast<uint32_t*>(m.ws + m.l.vff);
-  m.ctr = reinterpret_cast<long long*>(m.ws + m.l.ctr);
-  m.stage_ms = stage_ms;
-  if (stage_ms) {
-    for (int k = 0; k < 6; ++k) stage_ms[k] = 0.f;
-    VSA_HIP_TRY(hipEventCreate(&m.ev[0]));
-    VSA_HIP_TRY(hipEventCreate(&m.ev[1]));
-  }
-  rc = run(m, verts, faces, target_faces, out_verts, out_faces, stats);
-  if (stage_ms) {
-    (void)hipEventDestroy(m.ev[0]);
-    (void)hipEventDestroy(m.ev[1]);
-  }
+  m.s = mt::bits_of(nr_verts);
+  m.P = mt::at<float>(ws, l.pos);
+  m.Q = mt::at<double>(ws, l.Q);
+  m.vflag = mt::at<unsigned>(ws, l.vflag);
+  m.vstart = mt::at<int32_t>(ws, l.vstart);
+  m.vend = mt::at<int32_t>(ws, l.vend);
+  m.m1 = mt::at<u64>(ws, l.m1);
+  m.m2 = mt::at<u64>(ws, l.m2);
+  m.fcur = mt::at<int32_t>(ws, l.fa);
+  m.fnext = mt::at<int32_t>(ws, l.fb);
+  m.A = mt::at<u64>(ws, l.A);
+  m.B = mt::at<u64>(ws, l.B);
+  m.flags = mt::at<int32_t>(ws, l.flags);
+  m.rank = mt::at<int32_t>(ws, l.rank);
+  m.ehead = mt::at<int32_t>(ws, l.ehead);
+  m.ekey = mt::at<u64>(ws, l.ekey);
+  m.vfk = mt::at<uint32_t>(ws, l.vfk);
+  m.vff = mt::at<uint32_t>(ws, l.vff);
+  m.ctr = mt::at<long long>(ws, l.ctr);
+  MT_TRY(m.timer.create(stage_ms, 6, m.st));
+  const int rc = run(m, verts, faces, target_faces, out_verts, out_faces, stats);
+  m.timer.destroy();
   return rc;
 }

@@ -2,8 +2,12 @@
 /root/reference/volsurfs_py/methods/volsurfs.py:82-117, 511) and synthetic
 nested shells for tests / bench (datasets are not available offline;
 SURVEY.md §8d "Synthetic inputs")."""
+import os
+
 import numpy as np
 import torch
+
+from . import _lib
 
 
 class TensorMesh:
@@ -18,6 +22,38 @@ class TensorMesh:
 
     def get_faces_uvs(self):
         return self.faces_uvs
+
+
+def check_mesh(mesh, what, refuse_degenerate=False):
+    """(vertices f32 [V, 3], faces i32 [F, 3]) of a mesh stage's argument, contiguous on cuda, finite and in range;
+    `what` names the caller in the messages.  With `refuse_degenerate`, no face may name a vertex twice."""
+    V, F = mesh.vertices, mesh.faces
+    if not (V.is_cuda and F.is_cuda):
+        raise ValueError(f"{what}: the mesh must be on cuda, got {V.device} / {F.device}")
+    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError(f"{what}: expected vertices [V, 3] and faces [F, 3], got {tuple(V.shape)} / {tuple(F.shape)}")
+    V = V.to(torch.float32).contiguous()
+    F = F.to(torch.int32).contiguous()
+    if F.shape[0] == 0:
+        return V, F
+    if not bool(torch.isfinite(V).all()):
+        raise _lib.VolsurfsHipError(f"{what}: the vertices hold NaN or inf")
+    lo, hi = torch.aminmax(F)
+    if int(lo) < 0 or int(hi) >= V.shape[0]:
+        raise _lib.VolsurfsHipError(f"{what}: face indices out of range [0, {V.shape[0]}): min {int(lo)}, max {int(hi)}")
+    if refuse_degenerate and bool(((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 2] == F[:, 0])).any()):
+        raise _lib.VolsurfsHipError(f"{what}: a face names one vertex twice")
+    return V, F
+
+
+def level_files(meshes_dir, obj=False):
+    """The `<level>.ply` names of a directory (with `obj`, `<level>.obj` too) in ascending level: inner to outer."""
+    ext = (".ply", ".obj") if obj else (".ply",)
+    names = [n for n in os.listdir(meshes_dir) if n.endswith(ext)]
+    names.sort(key=lambda x: float(x[:-4]))
+    if not names:
+        raise FileNotFoundError(f"no {' / '.join('<level>' + e for e in ext)} meshes in {meshes_dir}")
+    return names
 
 
 def icosphere(subdiv=2, radius=1.0):

@@ -16,8 +16,7 @@ import torch
 
 from . import _lib
 from .isosurface import _uvless
-from .mesh import TensorMesh, load_ply, save_ply
-from .simplify import _level_files
+from .mesh import TensorMesh, check_mesh, level_files, load_ply, save_ply
 
 STAGES = ("edges", "sort", "hook", "roots", "number", "areas", "threshold", "mask", "compact")
 MODE_ALL, MODE_MASK, MODE_CLUSTERS = 0, 1, 2
@@ -25,38 +24,7 @@ MODE_ALL, MODE_MASK, MODE_CLUSTERS = 0, 1, 2
 
 def workspace_bytes(nr_verts, nr_faces):
     """Device workspace of one clustering or one filter of a mesh with `nr_verts` vertices and `nr_faces` faces."""
-    n = _lib.lib().vsa_mesh_clusters_workspace_bytes(int(nr_verts), int(nr_faces))
-    if n < 0:
-        raise _lib.VolsurfsHipError(f"vsa_mesh_clusters_workspace_bytes failed with status {n}")
-    return int(n)
-
-
-def _check(mesh, what):
-    """(vertices f32 [V, 3], faces i32 [F, 3]) contiguous on cuda, finite and in range.  A face may name a vertex twice."""
-    V, F = mesh.vertices, mesh.faces
-    if not (V.is_cuda and F.is_cuda):
-        raise ValueError(f"{what}: the mesh must be on cuda, got {V.device} / {F.device}")
-    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError(f"{what}: expected vertices [V, 3] and faces [F, 3], got {tuple(V.shape)} / {tuple(F.shape)}")
-    V = V.to(torch.float32).contiguous()
-    F = F.to(torch.int32).contiguous()
-    if F.shape[0] == 0:
-        return V, F
-    if not bool(torch.isfinite(V).all()):
-        raise _lib.VolsurfsHipError(f"{what}: the vertices hold NaN or inf")
-    lo, hi = torch.aminmax(F)
-    if int(lo) < 0 or int(hi) >= V.shape[0]:
-        raise _lib.VolsurfsHipError(f"{what}: face indices out of range [0, {V.shape[0]}): min {int(lo)}, max {int(hi)}")
-    return V, F
-
-
-def _stage_array(stage_ms):
-    return (ctypes.c_float * len(STAGES))() if stage_ms is not None else None
-
-
-def _stage_update(stage_ms, ms):
-    if ms is not None:
-        stage_ms.update({k: float(ms[i]) for i, k in enumerate(STAGES)})
+    return _lib.workspace_bytes("vsa_mesh_clusters_workspace_bytes", int(nr_verts), int(nr_faces))
 
 
 @torch.no_grad()
@@ -65,7 +33,7 @@ def cluster_connected_triangles(mesh, stage_ms=None):
     undirected edge (the same pair of vertex indices); a cluster is a connected component, numbered in ascending order
     of its smallest face.  Returns (triangle_clusters [F] i32, cluster_n_triangles [C] i32, cluster_area [C] f64) on
     the device.  `stage_ms` (a dict) receives the device ms per stage."""
-    V, F = _check(mesh, "cluster_connected_triangles")
+    V, F = check_mesh(mesh, "cluster_connected_triangles")
     nv, nf = int(V.shape[0]), int(F.shape[0])
     dev = V.device
     if nf == 0:
@@ -76,11 +44,11 @@ def cluster_connected_triangles(mesh, stage_ms=None):
     counts = torch.empty(nf, dtype=torch.int32, device=dev)
     areas = torch.empty(nf, dtype=torch.float64, device=dev)
     C = ctypes.c_longlong(0)
-    ms = _stage_array(stage_ms)
+    ms = _lib.stage_array(STAGES, stage_ms)
     _lib.call("vsa_mesh_clusters", V, nv, F, nf, ws, ws.numel(), clusters, counts, areas,
               ctypes.cast(ctypes.pointer(C), ctypes.c_void_p),
               ctypes.cast(ms, ctypes.c_void_p) if ms is not None else None, _lib.stream_ptr())
-    _stage_update(stage_ms, ms)
+    _lib.stage_update(STAGES, stage_ms, ms)
     return clusters, counts[:C.value].clone(), areas[:C.value].clone()
 
 
@@ -96,12 +64,12 @@ def _filter(V, F, mode, keep_mask=None, cluster_to_keep=1, min_cluster_faces=0, 
     vmap = torch.empty(nv, dtype=torch.int32, device=dev)
     fmap = torch.empty(nf, dtype=torch.int32, device=dev)
     stats = (ctypes.c_longlong * 6)()
-    ms = _stage_array(stage_ms)
+    ms = _lib.stage_array(STAGES, stage_ms)
     _lib.call("vsa_mesh_filter", V, nv, F, nf, int(mode), keep_mask, int(cluster_to_keep), int(min_cluster_faces),
               bool(drop_unreferenced), bool(drop_degenerate), ws, ws.numel(), out_v, out_f, vmap, fmap,
               ctypes.cast(stats, ctypes.c_void_p), ctypes.cast(ms, ctypes.c_void_p) if ms is not None else None,
               _lib.stream_ptr())
-    _stage_update(stage_ms, ms)
+    _lib.stage_update(STAGES, stage_ms, ms)
     vout, fout, C, thr, kept, passed = (int(x) for x in stats)
     st = {"clusters": C, "threshold": thr, "clusters_kept": kept, "faces_in": nf, "faces_out": fout,
           "vertices_in": nv, "vertices_out": vout, "faces_passed": passed}
@@ -151,7 +119,7 @@ def _unchanged(mesh, V, F):
 def remove_triangles_by_mask(mesh, mask):
     """Open3D's `remove_triangles_by_mask`: the faces with mask[f] True are removed, the others keep their order;
     the vertices stay as they are.  `mask` [F] bool."""
-    V, F = _check(mesh, "remove_triangles_by_mask")
+    V, F = check_mesh(mesh, "remove_triangles_by_mask")
     mask = torch.as_tensor(mask, device=F.device).reshape(-1)
     if mask.shape[0] != F.shape[0]:
         raise ValueError(f"remove_triangles_by_mask: a mask of {mask.shape[0]} for {F.shape[0]} faces")
@@ -165,7 +133,7 @@ def remove_triangles_by_mask(mesh, mask):
 def remove_unreferenced_vertices(mesh):
     """Open3D's `remove_unreferenced_vertices`: the vertices a face names, in their order and with their bits; the
     faces renumbered."""
-    V, F = _check(mesh, "remove_unreferenced_vertices")
+    V, F = check_mesh(mesh, "remove_unreferenced_vertices")
     if F.shape[0] == 0 or V.shape[0] == 0:
         return _rebuild(mesh, V[:0].clone(), F.clone(), torch.zeros(0, dtype=torch.int32, device=F.device))
     v, f, _, fmap, _ = _filter(V, F, MODE_ALL, drop_unreferenced=True)
@@ -175,7 +143,7 @@ def remove_unreferenced_vertices(mesh):
 def remove_degenerate_triangles(mesh):
     """Open3D's `remove_degenerate_triangles`: the faces that name a vertex twice are removed, the others keep their
     order; the vertices stay as they are."""
-    V, F = _check(mesh, "remove_degenerate_triangles")
+    V, F = check_mesh(mesh, "remove_degenerate_triangles")
     if F.shape[0] == 0 or V.shape[0] == 0:
         return _unchanged(mesh, V, F)
     v, f, _, fmap, _ = _filter(V, F, MODE_ALL, drop_degenerate=True)
@@ -201,7 +169,7 @@ def post_process_mesh(mesh, cluster_to_keep=1000, min_cluster_faces=50, vertex_c
         raise ValueError(f"cluster_to_keep must be at least 1, got {cluster_to_keep}")
     if int(min_cluster_faces) < 0:
         raise ValueError(f"min_cluster_faces must not be negative, got {min_cluster_faces}")
-    V, F = _check(mesh, "post_process_mesh")
+    V, F = check_mesh(mesh, "post_process_mesh")
     colors = None
     if vertex_colors is not None:
         colors = torch.as_tensor(vertex_colors, device=V.device).to(torch.float32)
@@ -229,7 +197,7 @@ def clean_meshes(meshes_dir, out_dir, cluster_to_keep=1000, min_cluster_faces=50
     `<level>.ply` of `meshes_dir` through `post_process_mesh`, written under the same name into `out_dir`, with its
     texcoords when the file had them.  Returns the paths, inner to outer; `simplify.simplify_meshes` and
     `mesh.load_meshes_indexed_from_path` take `out_dir` as they take `meshes/`."""
-    names = _level_files(meshes_dir)
+    names = level_files(meshes_dir)
     os.makedirs(out_dir, exist_ok=True)
     paths = []
     for n in names:

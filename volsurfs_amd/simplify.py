@@ -14,17 +14,14 @@ import torch
 
 from . import _lib
 from .isosurface import _uvless
-from .mesh import TensorMesh, load_ply, save_ply
+from .mesh import TensorMesh, check_mesh, level_files, load_ply, save_ply
 
 STAGES = ("init", "edges", "cost", "select", "collapse", "compact")
 
 
 def workspace_bytes(nr_verts, nr_faces):
     """Device workspace of one simplification of a mesh with `nr_verts` vertices and `nr_faces` faces."""
-    n = _lib.lib().vsa_simplify_workspace_bytes(int(nr_verts), int(nr_faces))
-    if n < 0:
-        raise _lib.VolsurfsHipError(f"vsa_simplify_workspace_bytes failed with status {n}")
-    return int(n)
+    return _lib.workspace_bytes("vsa_simplify_workspace_bytes", int(nr_verts), int(nr_faces))
 
 
 def target_faces(nr_faces, ratio):
@@ -36,24 +33,7 @@ def _check(mesh, ratio):
     ratio = float(ratio)
     if not 0.0 < ratio <= 1.0:
         raise ValueError(f"target_nr_faces_ratio must lie in (0, 1], got {ratio}")
-    V, F = mesh.vertices, mesh.faces
-    if not (V.is_cuda and F.is_cuda):
-        raise ValueError(f"simplify_mesh: the mesh must be on cuda, got {V.device} / {F.device}")
-    if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError(f"simplify_mesh: expected vertices [V, 3] and faces [F, 3], got {tuple(V.shape)} / "
-                         f"{tuple(F.shape)}")
-    V = V.to(torch.float32).contiguous()
-    F = F.to(torch.int32).contiguous()
-    if F.shape[0] == 0:
-        return V, F, ratio
-    if not bool(torch.isfinite(V).all()):
-        raise _lib.VolsurfsHipError("simplify_mesh: the vertices hold NaN or inf")
-    lo, hi = torch.aminmax(F)
-    if int(lo) < 0 or int(hi) >= V.shape[0]:
-        raise _lib.VolsurfsHipError(f"simplify_mesh: face indices out of range [0, {V.shape[0]}): "
-                                    f"min {int(lo)}, max {int(hi)}")
-    if bool(((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 2] == F[:, 0])).any()):
-        raise _lib.VolsurfsHipError("simplify_mesh: a face names one vertex twice")
+    V, F = check_mesh(mesh, "simplify_mesh", refuse_degenerate=True)
     return V, F, ratio
 
 
@@ -65,12 +45,11 @@ def _simplify(V, F, target, stage_ms=None):
     out_v = torch.empty(nv, 3, device=V.device)
     out_f = torch.empty(nf, 3, dtype=torch.int32, device=V.device)
     stats = (ctypes.c_longlong * 5)()
-    ms = (ctypes.c_float * len(STAGES))() if stage_ms is not None else None
+    ms = _lib.stage_array(STAGES, stage_ms)
     _lib.call("vsa_simplify", V, nv, F, nf, int(target), ws, ws.numel(), out_v, out_f,
               ctypes.cast(stats, ctypes.c_void_p), ctypes.cast(ms, ctypes.c_void_p) if ms is not None else None,
               _lib.stream_ptr())
-    if ms is not None:
-        stage_ms.update({k: float(ms[i]) for i, k in enumerate(STAGES)})
+    _lib.stage_update(STAGES, stage_ms, ms)
     rounds, collapses, stalled, vout, fout = (int(x) for x in stats)
     st = {"rounds": rounds, "collapses": collapses, "stalled": bool(stalled), "faces_in": nf, "faces_out": fout,
           "target": int(target)}
@@ -94,20 +73,12 @@ def simplify_mesh(mesh, target_nr_faces_ratio=0.1, return_stats=False):
     return (out, st) if return_stats else out
 
 
-def _level_files(meshes_dir):
-    names = [n for n in os.listdir(meshes_dir) if n.endswith(".ply")]
-    names.sort(key=lambda x: float(x[:-4]))
-    if not names:
-        raise FileNotFoundError(f"no <level>.ply meshes in {meshes_dir}")
-    return names
-
-
 def simplify_meshes(meshes_dir, out_dir, target_nr_faces_ratio=0.025, device="cuda"):
     """The baker's `--simplify_meshes` (baker.py:682-724): every `<level>.ply` of `meshes_dir` simplified on its own
     to `target_nr_faces_ratio` of its faces, written under the same name into `out_dir` (the reference's
     `meshes_simplified/`) without texcoords.  Returns the paths, inner to outer; `mesh.load_meshes_indexed_from_path`
     reads them back in that order."""
-    names = _level_files(meshes_dir)
+    names = level_files(meshes_dir)
     os.makedirs(out_dir, exist_ok=True)
     paths = []
     for n in names:

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from . import mesh_clean
-from .mesh import TensorMesh, load_mesh, save_obj, save_ply
+from .mesh import TensorMesh, check_mesh, load_mesh, save_obj, save_ply
 from .raytrace import RayTracer
 
 TILES = ("8x8", "row")
@@ -102,7 +102,7 @@ def visible_face_mask(mesh, counts, min_hits=1, rings=1):
     rings = int(rings)
     if not 0 <= rings <= 16:
         raise ValueError(f"rings must be in 0..16, got {rings}")
-    V, F = mesh_clean._check(mesh, "visible_face_mask")
+    V, F = check_mesh(mesh, "visible_face_mask")
     counts = torch.as_tensor(counts, device=F.device).reshape(-1)
     if counts.shape[0] != F.shape[0]:
         raise ValueError(f"visible_face_mask: {counts.shape[0]} counts for {F.shape[0]} faces")
@@ -129,7 +129,7 @@ def remove_invisible_faces(meshes, cameras, min_hits=1, rings=1, supersample=1, 
     counts = face_view_counts(meshes, cameras, supersample=supersample)
     out, colors_out, stats = [], [], []
     for k, (m, c) in enumerate(zip(meshes, counts)):
-        V, F = mesh_clean._check(m, "remove_invisible_faces")
+        V, F = check_mesh(m, "remove_invisible_faces")
         colors = None
         if vertex_colors is not None:
             colors = torch.as_tensor(vertex_colors[k], device=V.device).to(torch.float32)
