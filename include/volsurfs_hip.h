@@ -1613,6 +1613,84 @@ int vsa_face_view_counts_tile(int tile);
 int vsa_face_ring_dilate(const int32_t* faces, long long nr_faces, long long nr_verts, uint8_t* keep,
                          int rings, uint8_t* vert_scratch, void* stream);
 
+/* ---- Mesh distance (no counterpart in the reference; csrc/mesh_distance.hip, csrc/closest_walk.h) ----
+ * The closest point of a mesh to a query point, an area-weighted surface sampler, and the two fused into the
+ * statistics of a sampled surface-to-surface distance.  The reference has no such stage: the rule below is this
+ * library's own, restated in tests/mesh_distance_restated.py and UNPINNED.
+ * qnodes / tris / mesh_roots / mesh_frames / max_depth as vsa_trace_q takes them (q16 nodes, leaf-ordered records
+ * v0.xyz, id | e1.xyz, - | e2.xyz, -).
+ *   closest point per point p and record (fp32, in the order written, no contraction): a = p - v0; d1 = e1.a, d2 = e2.a;
+ *                 b = a - e1; d3 = e1.b, d4 = e2.b; c = a - e2; d5 = e1.c, d6 = e2.c (x.y = (x0 y0 + x1 y1) + x2 y2);
+ *                 vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.  The first region that holds, in
+ *                 Ericson's order, gives the weights (u, v) of v1 and v2:
+ *                   A   d1 <= 0 and d2 <= 0                                        (0, 0)
+ *                   B   d3 >= 0 and d4 <= d3                                       (1, 0)
+ *                   AB  vc <= 0, d1 >= 0, d3 <= 0, d1 - d3 > 0                     (d1 / (d1 - d3), 0)
+ *                   C   d6 >= 0 and d5 <= d6                                       (0, 1)
+ *                   AC  vb <= 0, d2 >= 0, d6 <= 0, d2 - d6 > 0                     (0, d2 / (d2 - d6))
+ *                   BC  va <= 0, s = d4 - d3 >= 0, t = d5 - d6 >= 0, s + t > 0     v = s / (s + t), u = 1 - v
+ *                   in  (va + vb) + vc > 0                                         (vb, vc) * (1 / ((va + vb) + vc))
+ *                   otherwise (0, 0).  The positive denominators are the handling of zero-area records: a record
+ *                 with a zero edge falls through to the next region, e1 = e2 = 0 ends in A (the point v0).
+ *                 r = (a - u e1) - v e2 per component; d2 = r.r.
+ *   closest triangle  the minimum over (d2, original face id) of all records of the mesh: tri_test's tie rule.  A
+ *                 query with a NaN coordinate has no closest triangle: slot -1, dist +inf.
+ *   walk          one query per lane over the q16 nodes, a child pruned when a lower bound of its box's squared
+ *                 distance exceeds the best d2 so far.  The bound (grid gap x step per axis, squared, summed, scaled by
+ *                 1 - 2^-18; the boxes' one-unit margin) never exceeds the fp32 d2 of a triangle inside the box for
+ *                 queries within ~60 mesh extents of the mesh, the domain of vsa_trace_q: there the result is that of
+ *                 brute force over all records, bit for bit.  Beyond it a nearer triangle may be missed.
+ * vsa_closest_point_q: points [N, 3] f32 -> dist [K, N] f32 = sqrtf(d2), slot [K, N] i32 (index into tris), bary
+ *   [K, N, 2] f32 = (u, v) or NULL.  One launch, grid.y = mesh.  No atomics.
+ * vsa_closest_point_q_stats: the same walk with counters (measurement): counters [device] 3 long long = node visits,
+ *   triangle tests, queries, summed over the K meshes; nothing else is written.
+ * vsa_surface_area_prefix: area_prefix [nr_slots] i64 = the inclusive prefix of the integer weights of the records
+ *   [first_slot, first_slot + nr_slots).  area = 0.5 sqrt((nx nx + ny ny) + nz nz), n = e1 x e2, in fp64 on the fp32
+ *   edges; weight = floor(area 2^k) with 2^k the power of two that puts the largest area in [2^30, 2^31) (a step of at
+ *   most 2^-30 of the largest area; the total stays below 2^62); a zero or non-finite area weighs 0; when no area is
+ *   positive every record weighs 1.  Integers: the prefix is exact whatever the scan's shape.  workspace =
+ *   vsa_surface_area_prefix_workspace_bytes(nr_slots) bytes.
+ * vsa_surface_sample: sample i of n: a Pcg32 stream keyed by (seed, i) (state = splitmix64's finaliser of seed +
+ *   0x9E3779B97F4A7C15 (i + 1), one output discarded) draws xi, u, v in [0, 1); position = floor(((i + xi) / n) total) in
+ *   fp64, clamped to total - 1; the record is the first whose prefix exceeds the position (a weight-0 record is never
+ *   chosen); u + v > 1 folds to (1 - u, 1 - v); point = (v0 + u e1) + v e2 in fp32.  points [n, 3] f32, slot [n] i32
+ *   (index into tris) or NULL, bary [n, 2] f32 or NULL.  A function of (tris, n, seed): the same bytes on every call.
+ * vsa_surface_distance: the statistics of the distances from n samples of the source records to the destination mesh
+ *   (one tree: its root, its frame of 6 floats [host], its depth), fused: the device functions of the two entry points
+ *   above, no sample and no distance written.  stats [device] 12 64-bit words: the bits of the smallest and of the
+ *   largest fp32 distance (integer atomics on the bits, which order as the non-negative values do), sum d and sum d^2
+ *   as fp64 (every wave adds its 64 lanes by a fixed tree into partials [ceil(n / 64), 2] f64; a second kernel adds
+ *   the pairs in wave order in a shape fixed by the wave count: 1024 lanes each add a run of consecutive waves, one lane
+ *   adds the 1024 run sums in order), within[j] = #{d <= thresholds[j]} (integer atomics), j < 8.  thresholds [host].  No float
+ *   atomics: the same inputs give the same bytes.
+ * vsa_closest_walk_config(keep_bounds): process-wide; a stack entry can carry its child's bound and be dropped on the
+ *   pop when the best d2 has passed it (a second LDS word per entry), or hold the node only, which is then fetched and
+ *   its children tested.  1 (default): bounds with the 24-entry stack (max_depth < 24), node only with the 48-entry one;
+ *   0: node only; 2: bounds always.  The results do not depend on it; tools/mesh_distance_bench.py measures 0 and 2.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (bary, and slot of vsa_surface_sample, may be NULL; thresholds when
+ *   nr_thresholds = 0), nr_meshes outside 1..16, nr_points / nr_slots / nr_samples < 1, a negative first_slot or root,
+ *   max_depth >= 48, nr_thresholds outside 0..8, a negative or NaN threshold; a workspace smaller than asked for.
+ *   VSA_ERR_UNSUPPORTED: slots beyond 2^31 - 1, more than 2^31 - 1 waves (and from the query, a failed rocPRIM size
+ *   query: no device). */
+int vsa_closest_point_q(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots,
+                        const float* mesh_frames, int nr_meshes, int max_depth, const float* points,
+                        long long nr_points, float* dist, int32_t* slot, float* bary, void* stream);
+int vsa_closest_point_q_stats(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots,
+                              const float* mesh_frames, int nr_meshes, int max_depth, const float* points,
+                              long long nr_points, long long* counters, void* stream);
+int vsa_closest_walk_config(int keep_bounds);
+long long vsa_surface_area_prefix_workspace_bytes(long long nr_slots);
+int vsa_surface_area_prefix(const float* tris, long long first_slot, long long nr_slots, void* workspace,
+                            long long workspace_bytes, long long* area_prefix, void* stream);
+int vsa_surface_sample(const float* tris, long long first_slot, long long nr_slots, const long long* area_prefix,
+                       long long nr_samples, unsigned long long seed, float* points, int32_t* slot, float* bary,
+                       void* stream);
+int vsa_surface_distance(const float* src_tris, long long src_first_slot, long long src_nr_slots,
+                         const long long* src_area_prefix, const uint32_t* dst_qnodes, const float* dst_tris,
+                         int dst_root, const float* dst_frame, int dst_max_depth, long long nr_samples,
+                         unsigned long long seed, const float* thresholds, int nr_thresholds,
+                         unsigned long long* stats, double* partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

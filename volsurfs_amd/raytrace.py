@@ -313,6 +313,65 @@ class RayTracer:
         from .visibility import tracer_face_view_counts
         return tracer_face_view_counts(self, cameras, supersample, t_min)
 
+    def _closest_args(self, points, what):
+        if self.node_format != "q16":
+            raise _lib.VolsurfsHipError(
+                f'{what} walks the quantised nodes: the tracer was built with node_format="{self.node_format}", '
+                'build it with node_format="q16"')
+        if self.max_depth >= 48:
+            raise _lib.VolsurfsHipError(f"tree depth {self.max_depth} >= 48, deeper than the traversal stack")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise _lib.VolsurfsHipError(f"{what}: expected points [N, 3] with N >= 1, got "
+                                        f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points)}")
+        return _lib.check_f32(points.contiguous(), points.shape[0], 3)
+
+    def closest_all(self, points):
+        """The closest point of every shell to every query point, one launch (vsa_closest_point_q: the closest-point walk
+        of the q16 nodes, the result of brute force over all triangles bit for bit; queries within ~60 mesh extents).
+        points [N, 3] f32 -> {dist [K, N] f32, face [K, N] i64 (original face ids), slot [K, N] i32 (global index into
+        self.tris), bary [K, N, 2] f32 (the weights of the face's second and third vertex)}.  No host sync."""
+        points = self._closest_args(points, "closest_all")
+        K, N = self.nr_meshes, points.shape[0]
+        dist = torch.empty(K, N, device=points.device)
+        slot = torch.empty(K, N, dtype=torch.int32, device=points.device)
+        bary = torch.empty(K, N, 2, device=points.device)
+        _lib.call("vsa_closest_point_q", self.qnodes, self.tris, self._roots, self._frames, K, self.max_depth, points, N,
+                  dist, slot, bary, _lib.stream_ptr())
+        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+
+    def closest(self, points, mesh_id=0):
+        """`closest_all` for one shell: dist [N], face [N], slot [N], bary [N, 2]."""
+        points = self._closest_args(points, "closest")
+        if not 0 <= int(mesh_id) < self.nr_meshes:
+            raise _lib.VolsurfsHipError(f"closest: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
+        N = points.shape[0]
+        dist = torch.empty(N, device=points.device)
+        slot = torch.empty(N, dtype=torch.int32, device=points.device)
+        bary = torch.empty(N, 2, device=points.device)
+        root = (ctypes.c_int32 * 1)(self.roots[mesh_id])
+        _lib.call("vsa_closest_point_q", self.qnodes, self.tris, root, self._frame_ptr(mesh_id), 1, self.max_depth,
+                  points, N, dist, slot, bary, _lib.stream_ptr())
+        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+
+    def _slot_faces(self, slot):
+        """Original face ids of triangle slots (-1 stays -1: a query with a NaN coordinate has no closest face)."""
+        face = self.slot_face_id[slot.clamp_min(0).long()].long()
+        return torch.where(slot >= 0, face, torch.full_like(face, -1))
+
+    def _frame_ptr(self, mesh_id):
+        """Host pointer to the six floats of one shell's quantisation frame."""
+        return ctypes.c_void_p(ctypes.addressof(self._frames) + 24 * int(mesh_id))
+
+    def closest_stats(self, points):
+        """{node_visits, tri_tests, queries} of one `closest_all` of these points, summed over the K shells
+        (vsa_closest_point_q_stats: the same walk with counters).  Synchronises; measurement only."""
+        points = self._closest_args(points, "closest_stats")
+        st = torch.zeros(3, dtype=torch.int64, device=points.device)
+        _lib.call("vsa_closest_point_q_stats", self.qnodes, self.tris, self._roots, self._frames, self.nr_meshes,
+                  self.max_depth, points, points.shape[0], st, _lib.stream_ptr())
+        v = st.cpu().tolist()
+        return {"node_visits": v[0], "tri_tests": v[1], "queries": v[2]}
+
     def sah_cost(self):
         """Per-mesh SAH cost of the trees, from the fp32 nodes (measurement; copies them to the host):
         1 (the root's visit) + sum over every child box of area / root area x (1 for an inner node, its triangle
