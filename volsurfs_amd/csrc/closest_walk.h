@@ -1,7 +1,8 @@
 // The closest-point walk of the quantised (q16) BVH nodes, and the surface sampler, shared by the kernels of
 // mesh_distance.hip: the unfused entry points (points from memory, records to memory) and the fused launch (samples made
 // in registers, statistics reduced in the wave).  One text, so that all of them give the same closest point and the
-// same sample bit for bit.  The rule is this library's own (the reference has no such stage): include/volsurfs_hip.h
+// same sample bit for bit.  The nodes, their grid, the stack's shape and the host side of the tree arguments are the
+// ray walk's (trace_walk.h).  The rule is this library's own (the reference has no such stage): include/volsurfs_hip.h
 // "Mesh distance"; tests/mesh_distance_restated.py restates it in numpy, operation for operation.
 #pragma once
 #include "trace_walk.h"
@@ -15,6 +16,16 @@ struct Closest {
   int slot;         // index into the leaf-ordered triangle array, -1 = none (a NaN query)
   int id;           // original face id (tie break)
 };
+
+// "None yet": every triangle with a d2 that is not NaN beats it.
+__device__ __forceinline__ Closest no_closest() {
+  Closest c;
+  c.d2 = INFINITY;
+  c.u = c.v = 0.f;
+  c.slot = -1;
+  c.id = 0x7fffffff;
+  return c;
+}
 
 // Closest point of the triangle record (v0, e1, e2) to p: Ericson's seven regions (Real-Time Collision Detection
 // 5.1.5) on the record's edges, fp32, fixed order.  Every quantity is computed for every region and the regions are

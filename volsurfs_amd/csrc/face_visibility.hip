@@ -48,22 +48,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void face_view_counts_kernel(
   const RayOut r = pinhole_ray(c2w_all + 12ll * view, kinv_all + 9ll * view, x, y);
   const float ox = r.ox, oy = r.oy, oz = r.oz, dx = r.dx, dy = r.dy, dz = r.dz;
 
-  const float* fr = frames.f[mesh];
-  QRay qr;
-  {
-    const float gx = (ox - fr[0]) / fr[3] + 1.0f, gy = (oy - fr[1]) / fr[4] + 1.0f,
-                gz = (oz - fr[2]) / fr[5] + 1.0f;
-    const float ix = 1.0f / (dx / fr[3]), iy = 1.0f / (dy / fr[4]), iz = 1.0f / (dz / fr[5]);
-    qr.ix = f32x2_t{ix, ix}, qr.iy = f32x2_t{iy, iy}, qr.iz = f32x2_t{iz, iz};
-    qr.cx = f32x2_t{-(gx * ix), -(gx * ix)};
-    qr.cy = f32x2_t{-(gy * iy), -(gy * iy)};
-    qr.cz = f32x2_t{-(gz * iz), -(gz * iz)};
-  }
-  Hit best;
-  best.t = INFINITY;
-  best.u = best.v = 0.f;
-  best.slot = -1;
-  best.id = 0x7fffffff;
+  const QRay qr = make_qray(frames.f[mesh], ox, oy, oz, dx, dy, dz);
+  Hit best = no_hit();
   int cur = alive ? roots.root[mesh] : TRACE_EMPTY;
   int sp = 0;
   q_walk<STACK, false>(qnodes, tris, qr, ox, oy, oz, dx, dy, dz, t_min, cur, sp, best, s_stack, lane, 0);
@@ -129,10 +115,9 @@ extern "C" int vsa_face_view_counts(const uint32_t* qnodes, const float* tris, c
                                     const float* intrinsics_inv_all, int nr_views, int height, int width,
                                     int supersample, float t_min, const long long* face_base, uint32_t* counts,
                                     void* stream) {
-  if (!qnodes || !tris || !mesh_roots || !mesh_frames || !c2w_all || !intrinsics_inv_all || !face_base || !counts)
-    return VSA_ERR_ARG;
-  if (nr_meshes < 1 || nr_meshes > VSA_MAX_SHELLS || nr_views < 1 || height < 1 || width < 1) return VSA_ERR_ARG;
-  if (supersample < 1 || supersample > 8 || max_depth >= TRACE_STACK) return VSA_ERR_ARG;
+  if (const int rc = check_qtree(qnodes, tris, mesh_roots, mesh_frames, nr_meshes, max_depth, VSA_ERR_ARG)) return rc;
+  if (!c2w_all || !intrinsics_inv_all || !face_base || !counts) return VSA_ERR_ARG;
+  if (nr_views < 1 || height < 1 || width < 1 || supersample < 1 || supersample > 8) return VSA_ERR_ARG;
   // a u32 count holds every sample of every view: V H W s^2 < 2^32 (each factor checked before the next product)
   long long samples = (long long)nr_views * height;
   if (samples >= (1ll << 32)) return VSA_ERR_ARG;
@@ -140,13 +125,10 @@ extern "C" int vsa_face_view_counts(const uint32_t* qnodes, const float* tris, c
   if (samples >= (1ll << 32)) return VSA_ERR_ARG;
   samples *= supersample * supersample;
   if (samples >= (1ll << 32)) return VSA_ERR_ARG;
-  Roots r;
-  Frames fr;
+  const QTree t = make_qtree(qnodes, tris, mesh_roots, mesh_frames, nr_meshes);
   FaceBases fb;
   for (int i = 0; i < VSA_MAX_SHELLS; ++i) {
-    r.root[i] = i < nr_meshes ? mesh_roots[i] : 0;
     fb.base[i] = i < nr_meshes ? face_base[i] : 0;
-    for (int j = 0; j < 6; ++j) fr.f[i][j] = i < nr_meshes ? mesh_frames[6 * i + j] : 1.0f;
     if (fb.base[i] < 0) return VSA_ERR_ARG;
   }
   const int tile = face_view_tile();
@@ -156,20 +138,13 @@ extern "C" int vsa_face_view_counts(const uint32_t* qnodes, const float* tris, c
   const long long tiles = tiles_x * tiles_y;          // <= samples of a view
   if (tiles * nr_views > 0x7fffffffll) return VSA_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)(tiles * nr_views), nr_meshes), block(TRACE_BLOCK);
-  const uint4* qn = reinterpret_cast<const uint4*>(qnodes);
-  const float4* tr = reinterpret_cast<const float4*>(tris);
-#define FACE_VIEW_LAUNCH(ST, TL)                                                                                       \
-  hipLaunchKernelGGL((face_view_counts_kernel<ST, TL>), grid, block, 0, (hipStream_t)stream, qn, tr, r, fr, fb, c2w_all, \
-                     intrinsics_inv_all, (int)tiles_x, (int)tiles, (int)sh, (int)sw, supersample, t_min, counts)
-  // (the traversal stack never exceeds the tree depth: the 24-entry stack of vsa_trace_q for the usual shallow trees)
-  if (max_depth < 24) {
-    if (tile == TILE_8X8) FACE_VIEW_LAUNCH(24, TILE_8X8);
-    else FACE_VIEW_LAUNCH(24, TILE_ROW);
-  } else {
-    if (tile == TILE_8X8) FACE_VIEW_LAUNCH(TRACE_STACK, TILE_8X8);
-    else FACE_VIEW_LAUNCH(TRACE_STACK, TILE_ROW);
-  }
-#undef FACE_VIEW_LAUNCH
+  with_stack(max_depth, [&](auto st) {
+    with_choice<TILE_8X8, TILE_ROW>(tile == TILE_8X8, [&](auto tl) {
+      hipLaunchKernelGGL((face_view_counts_kernel<decltype(st)::value, decltype(tl)::value>), grid, block, 0,
+                         (hipStream_t)stream, t.qnodes, t.tris, t.roots, t.frames, fb, c2w_all, intrinsics_inv_all,
+                         (int)tiles_x, (int)tiles, (int)sh, (int)sw, supersample, t_min, counts);
+    });
+  });
   VSA_RETURN_LAUNCH_STATUS();
 }
 

@@ -28,11 +28,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void closest_point_kernel(
   float px = 0.f, py = 0.f, pz = 0.f;
   if (alive) px = points[3 * i], py = points[3 * i + 1], pz = points[3 * i + 2];
   const QPoint q = closest_qpoint(frames.f[mesh], px, py, pz);
-  Closest best;
-  best.d2 = INFINITY;
-  best.u = best.v = 0.f;
-  best.slot = -1;
-  best.id = 0x7fffffff;
+  Closest best = no_closest();
   int visits = 0, tests = 0;
   closest_walk<STACK, BOUNDS, COUNT>(qnodes, tris, q, px, py, pz, alive ? roots.root[mesh] : TRACE_EMPTY, best, s_node, s_bound,
                              lane, &visits, &tests);
@@ -132,11 +128,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void surface_distance_kernel(
     px = s.x, py = s.y, pz = s.z;
   }
   const QPoint q = closest_qpoint(frames.f[0], px, py, pz);
-  Closest best;
-  best.d2 = INFINITY;
-  best.u = best.v = 0.f;
-  best.slot = -1;
-  best.id = 0x7fffffff;
+  Closest best = no_closest();
   closest_walk<STACK, BOUNDS>(qnodes, tris, q, px, py, pz, alive ? roots.root[0] : TRACE_EMPTY, best, s_node, s_bound, lane);
   const float d = sqrtf(best.d2);
 
@@ -227,40 +219,25 @@ static int closest_point_launch(const uint32_t* qnodes, const float* tris, const
                                 const float* mesh_frames, int nr_meshes, int max_depth, const float* points,
                                 long long nr_points, float* dist, int32_t* slot, float* bary, long long* counters,
                                 void* stream) {
-  if (!qnodes || !tris || !mesh_roots || !mesh_frames || !points) return VSA_ERR_ARG;
+  if (const int rc = check_qtree(qnodes, tris, mesh_roots, mesh_frames, nr_meshes, max_depth, VSA_ERR_ARG)) return rc;
+  if (!points || nr_points < 1) return VSA_ERR_ARG;
   if (counters ? false : (!dist || !slot)) return VSA_ERR_ARG;
-  if (nr_meshes < 1 || nr_meshes > VSA_MAX_SHELLS || nr_points < 1 || max_depth >= TRACE_STACK) return VSA_ERR_ARG;
   const long long waves = (nr_points + TRACE_BLOCK - 1) / TRACE_BLOCK;
   if (waves > MAX_GRID) return VSA_ERR_UNSUPPORTED;
-  Roots r;
-  Frames fr;
-  for (int i = 0; i < VSA_MAX_SHELLS; ++i) {
-    r.root[i] = i < nr_meshes ? mesh_roots[i] : 0;
-    for (int j = 0; j < 6; ++j) fr.f[i][j] = i < nr_meshes ? mesh_frames[6 * i + j] : 1.0f;
-  }
+  const QTree t = make_qtree(qnodes, tris, mesh_roots, mesh_frames, nr_meshes);
   const dim3 grid((unsigned)waves, nr_meshes), block(TRACE_BLOCK);
-  const uint4* qn = reinterpret_cast<const uint4*>(qnodes);
-  const float4* tr = reinterpret_cast<const float4*>(tris);
   unsigned long long* ct = reinterpret_cast<unsigned long long*>(counters);
-#define CLOSEST_LAUNCH_B(ST, BD, CT)                                                                                   \
-  hipLaunchKernelGGL((closest_point_kernel<ST, BD, CT>), grid, block, 0, (hipStream_t)stream, qn, tr, r, fr, points, \
-                     nr_points, dist, slot, bary, ct)
-#define CLOSEST_LAUNCH(ST, CT)                  \
-  do {                                          \
-    if (walk_bounds(max_depth)) CLOSEST_LAUNCH_B(ST, true, CT); \
-    else CLOSEST_LAUNCH_B(ST, false, CT);       \
-  } while (0)
+  if (counters) VSA_HIP_TRY(hipMemsetAsync(counters, 0, 3 * sizeof(long long), (hipStream_t)stream));
   // (the stack never exceeds the tree depth: 24 entries for the usual shallow trees, as vsa_trace_q)
-  if (counters) {
-    VSA_HIP_TRY(hipMemsetAsync(counters, 0, 3 * sizeof(long long), (hipStream_t)stream));
-    if (max_depth < 24) CLOSEST_LAUNCH(24, true);
-    else CLOSEST_LAUNCH(TRACE_STACK, true);
-  } else {
-    if (max_depth < 24) CLOSEST_LAUNCH(24, false);
-    else CLOSEST_LAUNCH(TRACE_STACK, false);
-  }
-#undef CLOSEST_LAUNCH
-#undef CLOSEST_LAUNCH_B
+  with_stack(max_depth, [&](auto st) {
+    with_flag(walk_bounds(max_depth), [&](auto bd) {
+      with_flag(counters != nullptr, [&](auto cn) {
+        hipLaunchKernelGGL((closest_point_kernel<decltype(st)::value, decltype(bd)::value, decltype(cn)::value>), grid,
+                           block, 0, (hipStream_t)stream, t.qnodes, t.tris, t.roots, t.frames, points, nr_points, dist,
+                           slot, bary, ct);
+      });
+    });
+  });
   VSA_RETURN_LAUNCH_STATUS();
 }
 
@@ -332,10 +309,9 @@ extern "C" int vsa_surface_distance(const float* src_tris, long long src_first_s
                                     int dst_root, const float* dst_frame, int dst_max_depth, long long nr_samples,
                                     unsigned long long seed, const float* thresholds, int nr_thresholds,
                                     unsigned long long* stats, double* partials, void* stream) {
-  if (!src_tris || !src_area_prefix || !dst_qnodes || !dst_tris || !dst_frame || !stats || !partials)
-    return VSA_ERR_ARG;
-  if (src_first_slot < 0 || src_nr_slots < 1 || nr_samples < 1 || dst_root < 0 || dst_max_depth >= TRACE_STACK)
-    return VSA_ERR_ARG;
+  if (const int rc = check_qtree(dst_qnodes, dst_tris, &dst_root, dst_frame, 1, dst_max_depth, VSA_ERR_ARG)) return rc;
+  if (!src_tris || !src_area_prefix || !stats || !partials) return VSA_ERR_ARG;
+  if (src_first_slot < 0 || src_nr_slots < 1 || nr_samples < 1 || dst_root < 0) return VSA_ERR_ARG;
   if (nr_thresholds < 0 || nr_thresholds > 8 || (nr_thresholds > 0 && !thresholds)) return VSA_ERR_ARG;
   Thresholds th = {};
   for (int j = 0; j < nr_thresholds; ++j) {
@@ -345,29 +321,17 @@ extern "C" int vsa_surface_distance(const float* src_tris, long long src_first_s
   const long long waves = (nr_samples + TRACE_BLOCK - 1) / TRACE_BLOCK;
   if (src_nr_slots > 0x7fffffffll || src_first_slot > 0x7fffffffll - src_nr_slots || waves > MAX_GRID)
     return VSA_ERR_UNSUPPORTED;
-  Roots r = {};
-  Frames fr;
-  r.root[0] = dst_root;
-  for (int i = 0; i < VSA_MAX_SHELLS; ++i)
-    for (int j = 0; j < 6; ++j) fr.f[i][j] = i == 0 ? dst_frame[j] : 1.0f;
+  const QTree t = make_qtree(dst_qnodes, dst_tris, &dst_root, dst_frame, 1);
   const hipStream_t st = (hipStream_t)stream;
   const float4* sr = reinterpret_cast<const float4*>(src_tris);
-  const uint4* qn = reinterpret_cast<const uint4*>(dst_qnodes);
-  const float4* tr = reinterpret_cast<const float4*>(dst_tris);
   hipLaunchKernelGGL(distance_init_kernel, dim3(1), dim3(64), 0, st, stats);
-#define DISTANCE_LAUNCH_B(ST, BD)                                                                                  \
-  hipLaunchKernelGGL((surface_distance_kernel<ST, BD>), dim3((unsigned)waves), dim3(TRACE_BLOCK), 0, st, sr,      \
-                     src_first_slot, src_nr_slots, src_area_prefix, qn, tr, r, fr, nr_samples, seed, th, nr_thresholds, \
-                     stats, partials)
-#define DISTANCE_LAUNCH(ST)                     \
-  do {                                          \
-    if (walk_bounds(dst_max_depth)) DISTANCE_LAUNCH_B(ST, true); \
-    else DISTANCE_LAUNCH_B(ST, false);          \
-  } while (0)
-  if (dst_max_depth < 24) DISTANCE_LAUNCH(24);
-  else DISTANCE_LAUNCH(TRACE_STACK);
-#undef DISTANCE_LAUNCH
-#undef DISTANCE_LAUNCH_B
+  with_stack(dst_max_depth, [&](auto sk) {
+    with_flag(walk_bounds(dst_max_depth), [&](auto bd) {
+      hipLaunchKernelGGL((surface_distance_kernel<decltype(sk)::value, decltype(bd)::value>), dim3((unsigned)waves),
+                         dim3(TRACE_BLOCK), 0, st, sr, src_first_slot, src_nr_slots, src_area_prefix, t.qnodes, t.tris,
+                         t.roots, t.frames, nr_samples, seed, th, nr_thresholds, stats, partials);
+    });
+  });
   hipLaunchKernelGGL(distance_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, st, reinterpret_cast<const double2*>(partials), waves,
                      stats);
   VSA_RETURN_LAUNCH_STATUS();

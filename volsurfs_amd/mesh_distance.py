@@ -63,10 +63,7 @@ def _resolve(mesh, what):
         return RayTracer([mesh], builder="device"), 0
     if isinstance(mesh, (tuple, list)) and len(mesh) == 2 and isinstance(mesh[0], RayTracer):
         tracer, mesh_id = mesh[0], int(mesh[1])
-        if tracer.node_format != "q16":
-            raise _lib.VolsurfsHipError(
-                f'{what} walks the quantised nodes: the tracer was built with node_format="{tracer.node_format}", '
-                'build it with node_format="q16"')
+        tracer.require_q16(what, walk=False)     # (a source is only sampled; the walk's entry points check the depth)
         if not 0 <= mesh_id < tracer.nr_meshes:
             raise ValueError(f"{what}: mesh_id {mesh_id} outside 0..{tracer.nr_meshes - 1}")
         return tracer, mesh_id
@@ -153,9 +150,10 @@ def _surface_distance(src, dst, n, seed, th):
     stats = torch.empty(12, dtype=torch.int64, device=dev)
     partials = torch.empty(2 * ((n + 63) // 64), dtype=torch.float64, device=dev)
     tau = (ctypes.c_float * max(len(th), 1))(*th)
-    _lib.call("vsa_surface_distance", ts.tris, ts.mesh_tri_offset[ms], ts.mesh_nr_tris[ms], prefix, td.qnodes, td.tris,
-              td.roots[md], td._frame_ptr(md), td.max_depth, n, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
-              tau, len(th), stats, partials, _lib.stream_ptr())
+    qnodes, tris, root, frame, _, depth = td.q16_tree_args(md)
+    _lib.call("vsa_surface_distance", ts.tris, ts.mesh_tri_offset[ms], ts.mesh_nr_tris[ms], prefix, qnodes, tris, root[0],
+              frame, depth, n, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), tau, len(th), stats, partials,
+              _lib.stream_ptr())
     w = stats.cpu().numpy()                                   # the one blocking read
     lo, hi = w[0:2].astype(np.uint32).view(np.float32)
     s1, s2 = w[2:4].view(np.float64)

@@ -15,6 +15,12 @@ import torch
 from . import _lib
 
 
+def _rays(rays_o, rays_d):
+    """(N, rays_o, rays_d): the rays as checked contiguous f32 [N, 3] tensors."""
+    N = rays_o.shape[0]
+    return N, _lib.check_f32(rays_o.contiguous(), N, 3), _lib.check_f32(rays_d.contiguous(), N, 3)
+
+
 class RayTracer:
     BUILDERS = ("host", "device", "ploc")
     DEVICE_BUILDERS = ("device", "ploc")
@@ -51,7 +57,6 @@ class RayTracer:
         if builder in self.DEVICE_BUILDERS:
             self._build_on_device(tensor_meshes, leaf_size, self.PLOC_RADIUS if ploc_radius is None else ploc_radius)
             return
-        node_base = tri_base = 0
         # The K shells' trees are independent host builds (binned SAH, csrc/bvh_build.cpp, one thread each): built side by
         # side on a thread pool — ctypes drops the GIL inside the call — 7 x 1.31 M triangles (configs[4]) take the time of one
         # shell (2.1 s) instead of 15 s.  Handles are collected in mesh order: the layout below is the sequential build's.
@@ -74,16 +79,13 @@ class RayTracer:
         for rc, h in built:
             if rc != 0:
                 raise _lib.VolsurfsHipError(f"vsa_bvh_build failed with status {rc}")
+        sizes = []
         for _, h in built:
             self._bvh.append(h)
             nn, nt, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
             L.vsa_bvh_sizes(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
-            self._layout.append((node_base, nn.value, tri_base, nt.value))
-            self.mesh_tri_offset.append(tri_base)
-            self.mesh_nr_tris.append(nt.value)
-            self.max_depth = max(self.max_depth, md.value)
-            node_base += nn.value
-            tri_base += nt.value
+            sizes.append((nn.value, nt.value, md.value))
+        self._record_shells(sizes)
         dev = tensor_meshes[0].vertices.device
         self.device = dev
         nodes, qnodes, tris, frames = self._export()
@@ -93,8 +95,21 @@ class RayTracer:
         self.tris = torch.from_numpy(tris).to(dev)
         # original face id of every leaf-ordered triangle slot (for uv tables etc.)
         self.slot_face_id = torch.from_numpy(tris[:, 3].copy().view(np.int32)).to(dev)
+
+    def _record_shells(self, sizes):
+        """The shells' (nr_nodes, nr_tris, depth), in mesh order, into the layout of the concatenated arrays: `_layout`,
+        `mesh_tri_offset`, `mesh_nr_tris`, `max_depth` and the roots.  Returns the totals (nr_nodes, nr_tris)."""
+        node_base = tri_base = 0
+        for nn, nt, md in sizes:
+            self._layout.append((node_base, nn, tri_base, nt))
+            self.mesh_tri_offset.append(tri_base)
+            self.mesh_nr_tris.append(nt)
+            self.max_depth = max(self.max_depth, md)
+            node_base += nn
+            tri_base += nt
         self.roots = [lay[0] for lay in self._layout]
         self._roots = (ctypes.c_int32 * self.nr_meshes)(*self.roots)
+        return node_base, tri_base
 
     def _build_on_device(self, tensor_meshes, leaf_size, radius):
         """The K trees built on the GPU (vsa_bvh_dev_build, or vsa_bvh_dev_build_ploc at `radius`) one after another
@@ -123,7 +138,7 @@ class RayTracer:
                 if rc != 0:
                     raise _lib.VolsurfsHipError(f"{name} failed with status {rc}")
                 self._bvh.append(h)
-            node_base = tri_base = 0
+            sizes = []
             for h in self._bvh:
                 nn, nt, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
                 rc = L.vsa_bvh_dev_sizes(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
@@ -133,23 +148,17 @@ class RayTracer:
                         'build this mesh with builder="host"')
                 if rc != 0:
                     raise _lib.VolsurfsHipError(f"vsa_bvh_dev_sizes failed with status {rc}")
-                self._layout.append((node_base, nn.value, tri_base, nt.value))
-                self.mesh_tri_offset.append(tri_base)
-                self.mesh_nr_tris.append(nt.value)
-                self.max_depth = max(self.max_depth, md.value)
-                node_base += nn.value
-                tri_base += nt.value
+                sizes.append((nn.value, nt.value, md.value))
         except Exception:
             self._destroy()
             raise
+        node_base, tri_base = self._record_shells(sizes)
         self.device = dev
         self.nodes = torch.empty(node_base, 16, dtype=torch.float32, device=dev)
         self.qnodes = torch.empty(node_base, 8, dtype=torch.int32, device=dev)
         self.tris = torch.empty(tri_base, 12, dtype=torch.float32, device=dev)
         self._export_device()
         self.slot_face_id = self.tris[:, 3].contiguous().view(torch.int32)
-        self.roots = [lay[0] for lay in self._layout]
-        self._roots = (ctypes.c_int32 * self.nr_meshes)(*self.roots)
 
     def _export_device(self):
         """Both node formats and the triangles of the device-built trees, written in place into self.nodes /
@@ -234,9 +243,7 @@ class RayTracer:
     def trace_all(self, rays_o, rays_d, t_min=0.0, out=None):
         """All K shells, one launch.  Returns hit_t [K,N] f32, hit_slot [K,N]
         i32 (global index into self.tris, -1 = miss), hit_uv [K,N,2] f32 (written into `out` = that triple when given)."""
-        N = rays_o.shape[0]
-        rays_o = _lib.check_f32(rays_o.contiguous(), N, 3)
-        rays_d = _lib.check_f32(rays_d.contiguous(), N, 3)
+        N, rays_o, rays_d = _rays(rays_o, rays_d)
         K = self.nr_meshes
         if out is not None:
             hit_t, hit_slot, hit_uv = out
@@ -253,9 +260,8 @@ class RayTracer:
         # feedback has nothing to learn from random rays (profiles/NOTEBOOK.md round 5)
         rpw = self.narrow_rays_per_wave(N, K) if self.node_format == "q16" else 64
         if rpw < 64:
-            _lib.call("vsa_trace_q_narrow", self.qnodes, self.tris, self._roots, self._frames, K,
-                      self.max_depth, rays_o, rays_d, N, float(t_min), hit_t, hit_slot, hit_uv, int(rpw),
-                      _lib.stream_ptr())
+            _lib.call("vsa_trace_q_narrow", *self.q16_tree_args(), rays_o, rays_d, N, float(t_min), hit_t, hit_slot,
+                      hit_uv, int(rpw), _lib.stream_ptr())
         elif self.node_format == "q16" and self.cost_feedback and self.max_depth < 48:
             if self._fb is None or self._fb[1] < N or self._fb[0].device != rays_o.device:   # grows only
                 fn = _lib.lib().vsa_trace_feedback_bytes
@@ -266,12 +272,10 @@ class RayTracer:
                 self._fb = [torch.zeros(nbytes, dtype=torch.uint8, device=rays_o.device), N, nbytes]
             # phase 2: the read / written halves alternate through a word in the buffer, flipped on the
             # device in front of every launch, so a captured graph alternates them on every replay too
-            _lib.call("vsa_trace_q_fb", self.qnodes, self.tris, self._roots, self._frames, K,
-                      self.max_depth, rays_o, rays_d, N, float(t_min), hit_t, hit_slot, hit_uv,
+            _lib.call("vsa_trace_q_fb", *self.q16_tree_args(), rays_o, rays_d, N, float(t_min), hit_t, hit_slot, hit_uv,
                       self._fb[0], ctypes.c_longlong(self._fb[2]), 2, _lib.stream_ptr())
         elif self.node_format == "q16":
-            _lib.call("vsa_trace_q", self.qnodes, self.tris, self._roots, self._frames, K,
-                      self.max_depth, rays_o, rays_d, N, float(t_min), hit_t, hit_slot, hit_uv,
+            _lib.call("vsa_trace_q", *self.q16_tree_args(), rays_o, rays_d, N, float(t_min), hit_t, hit_slot, hit_uv,
                       _lib.stream_ptr())
         else:
             _lib.call("vsa_trace", self.nodes, self.tris, self._roots, K, self.max_depth, rays_o,
@@ -297,12 +301,9 @@ class RayTracer:
     def walk_stats(self, rays_o, rays_d, t_min=0.0):
         """{lane_visits, tri_tests, wave_trips, waves, max_wave_trips} of one traversal of these rays
         (vsa_trace_q_stats: the same walk with counters; q16 nodes).  Synchronises; measurement only."""
-        N = rays_o.shape[0]
-        rays_o = _lib.check_f32(rays_o.contiguous(), N, 3)
-        rays_d = _lib.check_f32(rays_d.contiguous(), N, 3)
+        N, rays_o, rays_d = _rays(rays_o, rays_d)
         st = torch.zeros(5, dtype=torch.int64, device=rays_o.device)
-        _lib.call("vsa_trace_q_stats", self.qnodes, self.tris, self._roots, self._frames, self.nr_meshes,
-                  self.max_depth, rays_o, rays_d, N, float(t_min), st, _lib.stream_ptr())
+        _lib.call("vsa_trace_q_stats", *self.q16_tree_args(), rays_o, rays_d, N, float(t_min), st, _lib.stream_ptr())
         v = st.cpu().tolist()
         return dict(zip(("lane_visits", "tri_tests", "wave_trips", "waves", "max_wave_trips"), v))
 
@@ -313,13 +314,25 @@ class RayTracer:
         from .visibility import tracer_face_view_counts
         return tracer_face_view_counts(self, cameras, supersample, t_min)
 
-    def _closest_args(self, points, what):
+    def q16_tree_args(self, mesh_id=None):
+        """The leading arguments of the q16 entry points (qnodes, tris, mesh_roots, mesh_frames, nr_meshes, max_depth):
+        of all K shells, or of shell `mesh_id` alone as a tracer of one shell."""
+        if mesh_id is None:
+            return self.qnodes, self.tris, self._roots, self._frames, self.nr_meshes, self.max_depth
+        return (self.qnodes, self.tris, (ctypes.c_int32 * 1)(self.roots[mesh_id]), self._frame_ptr(mesh_id), 1,
+                self.max_depth)
+
+    def require_q16(self, what, walk=True):
+        """Raises unless `what` can use this tracer's quantised nodes and (walk) walk them with the traversal stack."""
         if self.node_format != "q16":
             raise _lib.VolsurfsHipError(
                 f'{what} walks the quantised nodes: the tracer was built with node_format="{self.node_format}", '
                 'build it with node_format="q16"')
-        if self.max_depth >= 48:
+        if walk and self.max_depth >= 48:
             raise _lib.VolsurfsHipError(f"tree depth {self.max_depth} >= 48, deeper than the traversal stack")
+
+    def _closest_args(self, points, what):
+        self.require_q16(what)
         if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
             raise _lib.VolsurfsHipError(f"{what}: expected points [N, 3] with N >= 1, got "
                                         f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points)}")
@@ -335,8 +348,7 @@ class RayTracer:
         dist = torch.empty(K, N, device=points.device)
         slot = torch.empty(K, N, dtype=torch.int32, device=points.device)
         bary = torch.empty(K, N, 2, device=points.device)
-        _lib.call("vsa_closest_point_q", self.qnodes, self.tris, self._roots, self._frames, K, self.max_depth, points, N,
-                  dist, slot, bary, _lib.stream_ptr())
+        _lib.call("vsa_closest_point_q", *self.q16_tree_args(), points, N, dist, slot, bary, _lib.stream_ptr())
         return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
 
     def closest(self, points, mesh_id=0):
@@ -348,9 +360,7 @@ class RayTracer:
         dist = torch.empty(N, device=points.device)
         slot = torch.empty(N, dtype=torch.int32, device=points.device)
         bary = torch.empty(N, 2, device=points.device)
-        root = (ctypes.c_int32 * 1)(self.roots[mesh_id])
-        _lib.call("vsa_closest_point_q", self.qnodes, self.tris, root, self._frame_ptr(mesh_id), 1, self.max_depth,
-                  points, N, dist, slot, bary, _lib.stream_ptr())
+        _lib.call("vsa_closest_point_q", *self.q16_tree_args(mesh_id), points, N, dist, slot, bary, _lib.stream_ptr())
         return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
 
     def _slot_faces(self, slot):
@@ -367,8 +377,7 @@ class RayTracer:
         (vsa_closest_point_q_stats: the same walk with counters).  Synchronises; measurement only."""
         points = self._closest_args(points, "closest_stats")
         st = torch.zeros(3, dtype=torch.int64, device=points.device)
-        _lib.call("vsa_closest_point_q_stats", self.qnodes, self.tris, self._roots, self._frames, self.nr_meshes,
-                  self.max_depth, points, points.shape[0], st, _lib.stream_ptr())
+        _lib.call("vsa_closest_point_q_stats", *self.q16_tree_args(), points, points.shape[0], st, _lib.stream_ptr())
         v = st.cpu().tolist()
         return {"node_visits": v[0], "tri_tests": v[1], "queries": v[2]}
 
@@ -403,9 +412,7 @@ class RayTracer:
 
     def trace(self, rays_o, rays_d, mesh_id=0, t_min=0.0):
         """raytracelib-shaped single-mesh trace (volsurfs.py:480-501)."""
-        N = rays_o.shape[0]
-        rays_o = _lib.check_f32(rays_o.contiguous(), N, 3)
-        rays_d = _lib.check_f32(rays_d.contiguous(), N, 3)
+        N, rays_o, rays_d = _rays(rays_o, rays_d)
         dev = rays_o.device
         hit_t = torch.empty(1, N, device=dev)
         hit_slot = torch.empty(1, N, dtype=torch.int32, device=dev)

@@ -50,15 +50,10 @@ def _stack_cameras(cameras, device):
 def tracer_face_view_counts(tracer, cameras, supersample=1, t_min=0.0, nr_faces=None):
     """`RayTracer.face_view_counts`: the counts of the tracer's shells, a list of K int64 [F_k] tensors.  `nr_faces`:
     the shells' face counts (default: the tracer's triangle counts)."""
-    if tracer.node_format != "q16":
-        raise _lib.VolsurfsHipError(
-            f'face_view_counts walks the quantised nodes: the tracer was built with node_format="{tracer.node_format}", '
-            'build it with node_format="q16"')
+    tracer.require_q16("face_view_counts")
     s = int(supersample)
     if not 1 <= s <= 8:
         raise ValueError(f"supersample must be in 1..8, got {supersample}")
-    if tracer.max_depth >= 48:
-        raise _lib.VolsurfsHipError(f"tree depth {tracer.max_depth} >= 48, deeper than the traversal stack")
     dev = tracer.device
     c2w, kinv, H, W = _stack_cameras(cameras, dev)
     V = int(c2w.shape[0])
@@ -74,8 +69,8 @@ def tracer_face_view_counts(tracer, cameras, supersample=1, t_min=0.0, nr_faces=
         total += n
     counts = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)         # (u32 on the device)
     face_base = (ctypes.c_longlong * tracer.nr_meshes)(*base)
-    _lib.call("vsa_face_view_counts", tracer.qnodes, tracer.tris, tracer._roots, tracer._frames, tracer.nr_meshes,
-              tracer.max_depth, c2w, kinv, V, H, W, s, float(t_min), face_base, counts, _lib.stream_ptr())
+    _lib.call("vsa_face_view_counts", *tracer.q16_tree_args(), c2w, kinv, V, H, W, s, float(t_min), face_base, counts,
+              _lib.stream_ptr())
     wide = counts.to(torch.int64) & 0xFFFFFFFF
     return [wide[b:b + n].clone() for b, n in zip(base, nr_faces)]
 
