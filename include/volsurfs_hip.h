@@ -1691,6 +1691,62 @@ int vsa_surface_distance(const float* src_tris, long long src_first_slot, long l
                          unsigned long long seed, const float* thresholds, int nr_thresholds,
                          unsigned long long* stats, double* partials, void* stream);
 
+/* ---- Mesh signed distance (no counterpart in the reference; csrc/mesh_sdf.hip, csrc/closest_walk.h) ----
+ * The distance of "Mesh distance" with a sign: negative inside a closed mesh whose faces wind outward (as
+ * marching cubes and icosphere wind them).  The sign is that of r . N, N the angle-weighted pseudonormal of the closest
+ * feature (Baerentzen & Aanaes 2005).  The reference has no such stage: the rule below is this library's own, restated
+ * in tests/mesh_sdf_restated.py and UNPINNED.  The sign means inside / outside for closed, consistently oriented
+ * meshes; for any other mesh it is whatever the rule gives.
+ *   region        the region of the closest record that "Mesh distance" chose, as a code: A 0, B 1, C 2 (the vertices
+ *                 v0, v1, v2), AB 3, AC 4, BC 5 (the edges), in 6; "otherwise" is A.  It comes out of the same chain of
+ *                 tests as (u, v), never from (u, v) afterwards; r = (a - u e1) - v e2 is the residual formed there.
+ *   face normal   n_f = (e1 x e2) / |e1 x e2| with e1 = v1 - v0, e2 = v2 - v0, the cross product (a.y b.z - a.z b.y, ..),
+ *                 |n| = sqrt((nx nx + ny ny) + nz nz), every operation in fp64 on the fp32 vertices; 0 when |n| is not
+ *                 positive and finite (a zero-area face contributes nothing anywhere).
+ *   pseudonormal  in:     n_f.
+ *                 edge:   the sum of n_f over every face corner whose undirected edge key (min, max vertex) is the
+ *                         edge's, in ascending face id: one face on a boundary, two on a manifold edge, or more.
+ *                 vertex: the sum over the (vertex, face) ring of the vertex, in ascending face id, of alpha n_f, alpha =
+ *                         atan2(|a x b|, a . b) of the two edges a, b that leave the vertex in that face (at the first
+ *                         corner that names it), a . b = (a0 b0 + a1 b1) + a2 b2.
+ *                 Sums in fp64 from 0, each stored rounded to fp32.
+ *   sign          s = r . N = (r0 N0 + r1 N1) + r2 N2 in fp32; the signed distance is -sqrtf(d2) when s < 0, else
+ *                 +sqrtf(d2): a point on the surface gets +0, a NaN query keeps slot -1 and +inf.
+ * vsa_mesh_pseudonormals: vertices [V, 3] f32, faces [F, 3] i32 (indices in [0, V): the caller checks) -> table
+ *   [F, 7, 3] f32, row f = original face id, entry = region code.  Vertex rings and sorted edges of csrc/mesh_topology.hip,
+ *   one thread per vertex / per sorted face corner, no float atomics: the same inputs give the same bytes.  workspace =
+ *   vsa_mesh_pseudonormals_workspace_bytes(V, F) bytes.
+ * vsa_signed_distance_q: vsa_closest_point_q with the tables: table [sum F_k, 7, 3] f32 (the meshes' tables one after
+ *   the other), table_face_base [host, nr_meshes] = the first row of each mesh.  The same outputs, dist signed; |dist|,
+ *   slot and bary are vsa_closest_point_q's bits.
+ * vsa_mesh_sdf_grid: grid [nx, ny, nz] f32 (C order) = clamp(signed distance at (x[i], y[j], z[k]), -band, band) to ONE
+ *   mesh (its root, its frame of 6 floats [host], its first table row).  x / y / z are device arrays of the axis values
+ *   themselves.  band = +inf: the whole field, one wave per 4 x 4 x 4 brick of lattice points, nothing else.  A finite
+ *   band: one lane per brick first takes d_c at the brick's centre (per axis the mean of the brick's first and last
+ *   value) and rho = the distance from the centre to the brick's farthest lattice point; a brick with |d_c| > band +
+ *   (4/3) rho is FAR and filled with copysignf(band, d_c) (the distance is 1-Lipschitz: every point of it has |d| >=
+ *   |d_c| - rho > band and lies on the centre's side), the others are compacted in ascending brick order (flags,
+ *   exclusive scan, scatter) and walked.  brick_counts [host, 2] = near, far bricks, through one blocking read of the
+ *   stream (none with band = +inf).  workspace = vsa_mesh_sdf_grid_workspace_bytes(nx, ny, nz) bytes (may be NULL with
+ *   band = +inf).
+ * The walk's stack form follows vsa_closest_walk_config.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (bary may be NULL), V, F, nr_points or an axis length < 1,
+ *   nr_meshes outside 1..16, max_depth >= 48, a negative root or table row, band <= 0 or NaN; a workspace smaller than
+ *   asked for.  VSA_ERR_UNSUPPORTED: 3 F + 3 beyond int32, more than 2^31 - 1 waves or bricks (and from the queries, a
+ *   failed rocPRIM size query: no device). */
+long long vsa_mesh_pseudonormals_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_mesh_pseudonormals(const float* vertices, long long nr_verts, const int32_t* faces, long long nr_faces,
+                           void* workspace, long long workspace_bytes, float* table, void* stream);
+int vsa_signed_distance_q(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots,
+                          const float* mesh_frames, int nr_meshes, int max_depth, const float* table,
+                          const long long* table_face_base, const float* points, long long nr_points, float* dist,
+                          int32_t* slot, float* bary, void* stream);
+long long vsa_mesh_sdf_grid_workspace_bytes(int nx, int ny, int nz);
+int vsa_mesh_sdf_grid(const uint32_t* qnodes, const float* tris, int root, const float* frame, int max_depth,
+                      const float* table, long long table_face_base, const float* x, const float* y, const float* z,
+                      int nx, int ny, int nz, float band, float* grid, void* workspace, long long workspace_bytes,
+                      long long* brick_counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,13 +9,22 @@
 // (pcg32.h uses the HIP runtime's intrinsics: after common.h)
 #include "pcg32.h"
 
+// Does a stack entry of the walk carry its bound at this tree depth?  The process-wide choice of
+// vsa_closest_walk_config (csrc/mesh_distance.hip), for every unit that launches the walk.
+bool closest_walk_bounds(int max_depth);
+
 namespace {
 
 struct Closest {
   float d2, u, v;   // squared distance; weights of v1 and v2
   int slot;         // index into the leaf-ordered triangle array, -1 = none (a NaN query)
   int id;           // original face id (tie break)
+  int region;       // the region of the record that holds the closest point (CR_*)
 };
+
+// The region closest_on_triangle chose: the vertices v0 / v1 / v2, the edges v0 v1 / v0 v2 / v1 v2, the interior.  (The
+// sliver whose three areas all rounded away ends at v0: CR_A.)  Only the signed distance reads it (csrc/mesh_sdf.hip).
+enum { CR_A = 0, CR_B = 1, CR_C = 2, CR_AB = 3, CR_AC = 4, CR_BC = 5, CR_IN = 6, CR_REGIONS = 7 };
 
 // "None yet": every triangle with a d2 that is not NaN beats it.
 __device__ __forceinline__ Closest no_closest() {
@@ -24,6 +33,7 @@ __device__ __forceinline__ Closest no_closest() {
   c.u = c.v = 0.f;
   c.slot = -1;
   c.id = 0x7fffffff;
+  c.region = CR_A;
   return c;
 }
 
@@ -33,7 +43,8 @@ __device__ __forceinline__ Closest no_closest() {
 // takes the same values.  An edge region also asks for a positive denominator: a record with a zero edge falls through
 // to the next region instead of dividing 0 by 0, and e1 = e2 = 0 ends in region A (u = v = 0: the point v0).
 __device__ __forceinline__ void closest_on_triangle(const float4 v0, const float4 e1, const float4 e2, float px,
-                                                    float py, float pz, float& d2_out, float& u_out, float& v_out) {
+                                                    float py, float pz, float& d2_out, float& u_out, float& v_out,
+                                                    int& region_out) {
   const float ax = px - v0.x, ay = py - v0.y, az = pz - v0.z;
   const float d1 = dot3(e1.x, e1.y, e1.z, ax, ay, az);
   const float d2 = dot3(e2.x, e2.y, e2.z, ax, ay, az);
@@ -51,22 +62,24 @@ __device__ __forceinline__ void closest_on_triangle(const float4 v0, const float
   const float den_bc = t43 + t56;
   const float sum = (va + vb) + vc;
   float u, v;
+  int region = CR_A;
   if (d1 <= 0.0f && d2 <= 0.0f) {                                    // A
     u = 0.0f, v = 0.0f;
   } else if (d3 >= 0.0f && d4 <= d3) {                               // B
-    u = 1.0f, v = 0.0f;
+    u = 1.0f, v = 0.0f, region = CR_B;
   } else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f && den_ab > 0.0f) {   // AB
-    u = d1 / den_ab, v = 0.0f;
+    u = d1 / den_ab, v = 0.0f, region = CR_AB;
   } else if (d6 >= 0.0f && d5 <= d6) {                               // C
-    u = 0.0f, v = 1.0f;
+    u = 0.0f, v = 1.0f, region = CR_C;
   } else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f && den_ac > 0.0f) {   // AC
-    u = 0.0f, v = d2 / den_ac;
+    u = 0.0f, v = d2 / den_ac, region = CR_AC;
   } else if (va <= 0.0f && t43 >= 0.0f && t56 >= 0.0f && den_bc > 0.0f) { // BC
     v = t43 / den_bc;
     u = 1.0f - v;
+    region = CR_BC;
   } else if (sum > 0.0f) {                                           // interior
     const float inv = 1.0f / sum;
-    u = vb * inv, v = vc * inv;
+    u = vb * inv, v = vc * inv, region = CR_IN;
   } else {                                                           // (a sliver whose three areas all rounded away)
     u = 0.0f, v = 0.0f;
   }
@@ -76,13 +89,15 @@ __device__ __forceinline__ void closest_on_triangle(const float4 v0, const float
   d2_out = dot3(rx, ry, rz, rx, ry, rz);
   u_out = u;
   v_out = v;
+  region_out = region;
 }
 
 // The minimum over (d2, original face id): tri_test's tie rule.  A NaN d2 never wins.
 __device__ __forceinline__ void closest_tri(const float4 v0, const float4 e1, const float4 e2, float px, float py,
                                             float pz, int slot, Closest& best) {
   float d2, u, v;
-  closest_on_triangle(v0, e1, e2, px, py, pz, d2, u, v);
+  int region;
+  closest_on_triangle(v0, e1, e2, px, py, pz, d2, u, v, region);
   const int id = __float_as_int(v0.w);
   if (d2 < best.d2 || (d2 == best.d2 && id < best.id)) {
     best.d2 = d2;
@@ -90,6 +105,7 @@ __device__ __forceinline__ void closest_tri(const float4 v0, const float4 e1, co
     best.v = v;
     best.slot = slot;
     best.id = id;
+    best.region = region;
   }
 }
 

@@ -211,9 +211,10 @@ int& walk_mode() {
   static int mode = 1;
   return mode;
 }
-bool walk_bounds(int max_depth) { return walk_mode() == 2 || (walk_mode() == 1 && max_depth < 24); }
 
 }  // namespace
+
+bool closest_walk_bounds(int max_depth) { return walk_mode() == 2 || (walk_mode() == 1 && max_depth < 24); }
 
 static int closest_point_launch(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots,
                                 const float* mesh_frames, int nr_meshes, int max_depth, const float* points,
@@ -230,7 +231,7 @@ static int closest_point_launch(const uint32_t* qnodes, const float* tris, const
   if (counters) VSA_HIP_TRY(hipMemsetAsync(counters, 0, 3 * sizeof(long long), (hipStream_t)stream));
   // (the stack never exceeds the tree depth: 24 entries for the usual shallow trees, as vsa_trace_q)
   with_stack(max_depth, [&](auto st) {
-    with_flag(walk_bounds(max_depth), [&](auto bd) {
+    with_flag(closest_walk_bounds(max_depth), [&](auto bd) {
       with_flag(counters != nullptr, [&](auto cn) {
         hipLaunchKernelGGL((closest_point_kernel<decltype(st)::value, decltype(bd)::value, decltype(cn)::value>), grid,
                            block, 0, (hipStream_t)stream, t.qnodes, t.tris, t.roots, t.frames, points, nr_points, dist,
@@ -326,7 +327,7 @@ extern "C" int vsa_surface_distance(const float* src_tris, long long src_first_s
   const float4* sr = reinterpret_cast<const float4*>(src_tris);
   hipLaunchKernelGGL(distance_init_kernel, dim3(1), dim3(64), 0, st, stats);
   with_stack(dst_max_depth, [&](auto sk) {
-    with_flag(walk_bounds(dst_max_depth), [&](auto bd) {
+    with_flag(closest_walk_bounds(dst_max_depth), [&](auto bd) {
       hipLaunchKernelGGL((surface_distance_kernel<decltype(sk)::value, decltype(bd)::value>), dim3((unsigned)waves),
                          dim3(TRACE_BLOCK), 0, st, sr, src_first_slot, src_nr_slots, src_area_prefix, t.qnodes, t.tris,
                          t.roots, t.frames, nr_samples, seed, th, nr_thresholds, stats, partials);

@@ -47,6 +47,8 @@ class RayTracer:
         # q16 only: launch order from the previous call's measured cost (vsa_trace_q_fb; identical hits)
         self.cost_feedback = os.environ.get("VSA_TRACE_FEEDBACK", "1") != "0"
         self._fb = None
+        self._meshes = list(tensor_meshes)          # (the pseudonormal tables of signed_distance* are built from them)
+        self._pn = None
         self.nr_meshes = len(tensor_meshes)
         if not 1 <= self.nr_meshes <= 16:
             raise _lib.VolsurfsHipError("RayTracer supports 1..16 meshes")
@@ -209,6 +211,7 @@ class RayTracer:
         if len(tensor_meshes) != self.nr_meshes:
             raise _lib.VolsurfsHipError("refit needs the meshes the tracer was built on")
         L = _lib.lib()
+        self._meshes, self._pn = list(tensor_meshes), None       # the tables belonged to the old geometry
         if self.builder in self.DEVICE_BUILDERS:
             st = _lib.stream_ptr()
             for h, m in zip(self._bvh, tensor_meshes):
@@ -361,6 +364,48 @@ class RayTracer:
         slot = torch.empty(N, dtype=torch.int32, device=points.device)
         bary = torch.empty(N, 2, device=points.device)
         _lib.call("vsa_closest_point_q", *self.q16_tree_args(mesh_id), points, N, dist, slot, bary, _lib.stream_ptr())
+        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+
+    def pseudonormal_tables(self):
+        """(table [sum F_k, 7, 3] f32, face_base [K] host long long): the pseudonormals of every face of every shell
+        (vsa_mesh_pseudonormals; `mesh_sdf.pseudonormals` per mesh, one after the other) and each shell's first row.
+        Built on first use from the tracer's meshes and kept; `refit` drops them."""
+        if self._pn is None:
+            from .mesh_sdf import pseudonormals
+            tables = [pseudonormals(m, device=self.device) for m in self._meshes]
+            base = np.cumsum([0] + [t.shape[0] for t in tables[:-1]])
+            self._pn = (torch.cat(tables) if len(tables) > 1 else tables[0],
+                        (ctypes.c_longlong * self.nr_meshes)(*[int(b) for b in base]))
+        return self._pn
+
+    def signed_distance_all(self, points):
+        """`closest_all` with `dist` signed (vsa_signed_distance_q; include/volsurfs_hip.h "Mesh signed distance",
+        DESIGN §29): negative inside a closed shell whose faces wind outward, by the angle-weighted pseudonormal of
+        the closest feature.  |dist|, face, slot and bary are `closest_all`'s bits; a point on the surface gets +0.
+        The sign means inside / outside for closed, consistently oriented shells only; for any other mesh it is
+        whatever the rule gives.  No host sync once the tables exist."""
+        points = self._closest_args(points, "signed_distance_all")
+        table, base = self.pseudonormal_tables()
+        K, N = self.nr_meshes, points.shape[0]
+        dist = torch.empty(K, N, device=points.device)
+        slot = torch.empty(K, N, dtype=torch.int32, device=points.device)
+        bary = torch.empty(K, N, 2, device=points.device)
+        _lib.call("vsa_signed_distance_q", *self.q16_tree_args(), table, base, points, N, dist, slot, bary,
+                  _lib.stream_ptr())
+        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+
+    def signed_distance(self, points, mesh_id=0):
+        """`signed_distance_all` for one shell: dist [N] (signed), face [N], slot [N], bary [N, 2]."""
+        points = self._closest_args(points, "signed_distance")
+        if not 0 <= int(mesh_id) < self.nr_meshes:
+            raise _lib.VolsurfsHipError(f"signed_distance: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
+        table, base = self.pseudonormal_tables()
+        N = points.shape[0]
+        dist = torch.empty(N, device=points.device)
+        slot = torch.empty(N, dtype=torch.int32, device=points.device)
+        bary = torch.empty(N, 2, device=points.device)
+        _lib.call("vsa_signed_distance_q", *self.q16_tree_args(mesh_id), table,
+                  (ctypes.c_longlong * 1)(base[int(mesh_id)]), points, N, dist, slot, bary, _lib.stream_ptr())
         return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
 
     def _slot_faces(self, slot):
