@@ -1747,6 +1747,27 @@ int vsa_mesh_sdf_grid(const uint32_t* qnodes, const float* tris, int root, const
                       int nx, int ny, int nz, float band, float* grid, void* workspace, long long workspace_bytes,
                       long long* brick_counts, void* stream);
 
+/* ---- Image preparation (the reference's loader, mvdatasets, is absent; csrc/image_prepare.hip) ----
+ * A split's decoded image bytes to the float stacks `TensorReel`, `render_and_eval` and the bakers read, in one launch:
+ * alpha over a background colour, box subsampling by an integer factor s, and the mask.  The rule is this library's own,
+ * restated in tests/datasets_restated.py and UNPINNED.
+ *   src  [C, H0, W0, ch] u8, ch in {1, 3, 4} (grey, RGB, RGBA; ch = 4 is read a dword per texel: src 4-byte aligned)
+ *   mask [C, H0, W0] u8 or NULL;  bg [host, 3] f32;  1 <= s <= 16;  H = H0 / s, W = W0 / s (the remainder rows and
+ *   columns at the bottom and the right are dropped)
+ *   rgb  [C, H, W, 3] f32;  out_mask [C, H, W] f32, or NULL when there is neither a mask nor an alpha channel
+ * Per output pixel, over its n = s s source texels k (a_k the alpha byte, 255 when ch is 1 or 3; c_k the colour bytes,
+ * replicated for ch = 1), with integer sums A = sum a_k, P_c = sum c_k a_k, M = sum mask_k (all below 2^24):
+ *   alpha = fl(float(A) / float(255 n)),  prem_c = fl(float(P_c) / float(65025 n))     (correctly rounded divisions)
+ *   rgb_c = fl(prem_c + fl(fl(1 - alpha) bg_c))                                         (no fused multiply-add)
+ *   out_mask = fl(float(M) / float(255 n)) with a mask, else alpha (ch = 4)
+ * so that an opaque texel at s = 1 gives fl(c / 255), a transparent one gives bg, and subsampling averages
+ * premultiplied colour (a transparent texel's colour bytes never count).
+ * VSA_ERR_ARG (before any HIP call): s outside 1..16, ch not 1 / 3 / 4, a negative size, a NULL src / bg / rgb with
+ *   something to do, out_mask without a mask or an alpha channel, a mask without out_mask, a misaligned RGBA src.
+ *   VSA_ERR_UNSUPPORTED: more than 2^31 - 1 blocks (C H ceil(W / 256)). */
+int vsa_images_prepare(const uint8_t* src, const uint8_t* mask, int C, int H0, int W0, int ch, int s, const float* bg,
+                       float* rgb, float* out_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
