@@ -1747,6 +1747,85 @@ int vsa_mesh_sdf_grid(const uint32_t* qnodes, const float* tris, int root, const
                       int nx, int ny, int nz, float band, float* grid, void* workspace, long long workspace_bytes,
                       long long* brick_counts, void* stream);
 
+/* ---- Mesh winding number (no counterpart in the reference; csrc/mesh_winding.hip, csrc/winding_walk.h) ----
+ * A sign for meshes that are not closed: the generalised winding number w(q) = sum over the faces of Omega_f(q) / 4 pi
+ * (Jacobson et al. 2013), about 1 inside and about 0 outside, with the far field of Barill et al. 2018 at order 0.  The
+ * reference has no such stage: the rule below is this library's own and UNPINNED; the exact sum is restated in float64
+ * in tests/mesh_sdf_restated.py (winding_number).
+ *   exact term    for a triangle record (v0, e1, e2) and the query q: a = v0 - q, b = a + e1, c = a + e2,
+ *                 Omega = 2 atan2f(a . (b x c), den), den = (((|a| |b|) |c| + (a . b) |c|) + (b . c) |a|) + (c . a) |b|,
+ *                 in fp32: x . y = (x0 y0 + x1 y1) + x2 y2, |x| = sqrtf(x . x), b x c = (b1 c2 - b2 c1, b2 c0 - b0 c2,
+ *                 b0 c1 - b1 c0), no fused multiply-add.  atan2f(0, 0) = 0: a query on a vertex, and a face without
+ *                 area, contribute 0.
+ *   moments       every subtree of the q16 tree carries N = sum 1/2 e1 x e2, the area-weighted centroid p = sum (area
+ *                 centroid) / sum area (area = |1/2 e1 x e2|, centroid = v0 + (e1 + e2) / 3) and a radius r: no vertex
+ *                 of the subtree is farther than r from p.  The sums are fp64 on the fp32 records, a leaf's triangles in
+ *                 slot order, an inner subtree child 0 plus child 1; each is stored once, rounded to fp32.  r of a leaf
+ *                 is the largest distance (fp64) from the stored p to a vertex (v0, v0 + e1, v0 + e2), r of an inner
+ *                 subtree the largest |p - p_c| + r_c over its children; both times 1 + 10^-6, rounded up.  A subtree
+ *                 without area has N as summed (0 for faces without area), p = the first vertex of its first record
+ *                 (inner: its first child's p) and its r.
+ *   table         a leaf has no node of its own (it is a code in its parent's child word), so the table has one entry
+ *                 per CHILD SLOT of every inner node, entry 2 n + c for child c of node n (node indices as in qnodes,
+ *                 all meshes), then one per mesh root: entry 2 nr_nodes + m.  An entry is 8 floats, 32 bytes: N.xyz, r,
+ *                 p.xyz, 0: the two 16-byte loads of a visit, aligned.  A missing child's entry is all 0.
+ *   walk          depth first from the root's entry, child 0 before child 1.  With d = p - q, L = sqrtf(d . d): when
+ *                 L > beta r (strict) and (d . d) L > 0 the subtree adds (d . N) / ((d . d) L) and is not opened; otherwise an inner node's
+ *                 children are judged in turn and a leaf's triangles add their Omega in slot order.  One fp32
+ *                 accumulator from 0 in that order; w = the sum times fl(1 / 4 pi).  beta = +inf: no subtree is far,
+ *                 every leaf is summed.  The same tree, point and beta give the same bytes on every call, whichever
+ *                 other points share the launch.  A NaN query gives NaN.
+ * vsa_mesh_winding_moments: the table [2 nr_nodes + nr_meshes, 8] f32 of all the meshes of a tracer (qnodes [nr_nodes,
+ *   8] u32, tris [nr_tris, 12] f32, mesh_roots [host, nr_meshes]).  Bottom up without parent pointers in the nodes: one
+ *   pass writes parent[child], then a thread per child slot that holds a leaf (or nothing) writes its entry and climbs;
+ *   at each inner node an integer arrival counter decides: the first arriver leaves, the second (after a device-scope
+ *   fence) combines child 0 then child 1 and goes on.  No thread waits for another; no float atomics: two builds give
+ *   the same bytes, for any builder's node order.  workspace = vsa_mesh_winding_moments_workspace_bytes(nr_nodes,
+ *   nr_meshes) bytes.
+ * vsa_winding_number_q: w [nr_meshes, nr_points] f32 of points [nr_points, 3] f32; moment_roots [host, nr_meshes] = each
+ *   mesh's root entry.  One lane per point, one-wave workgroups, the stack of entries in LDS ([24 or 48][64] by
+ *   max_depth), no scratch.  vsa_winding_number_q_stats: the same walk, counters [3] i64 (device) = entries judged,
+ *   exact triangle terms, queries.
+ * vsa_signed_distance_w_q: vsa_closest_point_q's outputs with the sign from w: dist = -sqrtf(d2) when w > 1/2, else
+ *   +sqrtf(d2); |dist|, slot and bary are vsa_closest_point_q's bits.  A NaN query keeps slot -1 and +inf.
+ * vsa_mesh_sdf_grid_w: vsa_mesh_sdf_grid with this sign, for ONE mesh (its root, frame and root entry): grid = the point
+ *   query at (x[i], y[j], z[k]) clamped to [-band, band], bit for bit, with or without a band.  A finite band: one lane
+ *   per brick takes the UNSIGNED distance d_c at the brick's centre; a brick with d_c > band + (4/3) rho is FAR, skips
+ *   the closest-point walk and writes -band where its point's OWN w > 1/2, else +band (w crosses 1/2 away from the
+ *   surface, on the membrane that closes a hole: a far brick can hold both signs); the others walk both.  brick_counts
+ *   [host, 2] = near, far bricks, through one blocking read of the stream (none with band = +inf).  workspace =
+ *   vsa_mesh_sdf_grid_w_workspace_bytes(nx, ny, nz) bytes (may be NULL with band = +inf).
+ * vsa_mesh_edge_census: counts [host, 3] = the undirected edges with one face (boundary), with more than two
+ *   (non-manifold), and with two faces that traverse them in the same direction (inconsistent winding), over the faces
+ *   with a positive finite area (vsa_mesh_pseudonormals' rule), from the sorted edge keys of csrc/mesh_topology.hip.
+ *   One blocking read.  workspace = vsa_mesh_edge_census_workspace_bytes(V, F) bytes.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (bary may be NULL), nr_nodes, nr_tris, nr_points, V, F or an axis
+ *   length < 1, nr_meshes outside 1..16, max_depth >= 48, a root outside [0, nr_nodes), a negative root or root entry,
+ *   beta <= 1 or NaN, band <= 0 or NaN, a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED: 2 nr_nodes + 16 or
+ *   3 F + 3 beyond int32, nr_tris >= 2^27, more than 2^31 - 1 waves or bricks. */
+long long vsa_mesh_winding_moments_workspace_bytes(long long nr_nodes, int nr_meshes);
+int vsa_mesh_winding_moments(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots, int nr_meshes,
+                             long long nr_nodes, long long nr_tris, void* workspace, long long workspace_bytes,
+                             float* moments, void* stream);
+int vsa_winding_number_q(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots, int nr_meshes,
+                         int max_depth, const float* moments, const long long* moment_roots, float beta,
+                         const float* points, long long nr_points, float* w, void* stream);
+int vsa_winding_number_q_stats(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots, int nr_meshes,
+                               int max_depth, const float* moments, const long long* moment_roots, float beta,
+                               const float* points, long long nr_points, long long* counters, void* stream);
+int vsa_signed_distance_w_q(const uint32_t* qnodes, const float* tris, const int32_t* mesh_roots,
+                            const float* mesh_frames, int nr_meshes, int max_depth, const float* moments,
+                            const long long* moment_roots, float beta, const float* points, long long nr_points,
+                            float* dist, int32_t* slot, float* bary, void* stream);
+long long vsa_mesh_sdf_grid_w_workspace_bytes(int nx, int ny, int nz);
+int vsa_mesh_sdf_grid_w(const uint32_t* qnodes, const float* tris, int root, const float* frame, int max_depth,
+                        const float* moments, long long moment_root, float beta, const float* x, const float* y,
+                        const float* z, int nx, int ny, int nz, float band, float* grid, void* workspace,
+                        long long workspace_bytes, long long* brick_counts, void* stream);
+long long vsa_mesh_edge_census_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_mesh_edge_census(const float* vertices, long long nr_verts, const int32_t* faces, long long nr_faces,
+                         void* workspace, long long workspace_bytes, long long* counts, void* stream);
+
 /* ---- Image preparation (the reference's loader, mvdatasets, is absent; csrc/image_prepare.hip) ----
  * A split's decoded image bytes to the float stacks `TensorReel`, `render_and_eval` and the bakers read, in one launch:
  * alpha over a background colour, box subsampling by an integer factor s, and the mask.  The rule is this library's own,

@@ -7,6 +7,14 @@ angle-weighted pseudonormal of the closest feature (Baerentzen & Aanaes 2005): n
 wind outward, as `marching_cubes` and `icosphere` wind them.  The sign means inside / outside for closed, consistently
 oriented meshes only; for any other mesh it is whatever the rule gives.
 
+Every entry point below takes `sign="pseudonormal"` (the default: the rule above), `"winding"` or `"auto"`, and `beta`.
+With `"winding"` a point is inside iff the generalised winding number of the mesh there exceeds 1/2
+(`mesh_winding.winding_number(points, mesh, beta)`; "Mesh winding number"), for faces that wind outward:
+that also means something for open, self-intersecting and inconsistently wound meshes.  Across a hole the level sets
+close with the w = 1/2 membrane; the field jumps from -d to +d there, so all K shells of `offset_shells` cross it within
+one cell, in level order: nested, but crowded.  `"auto"` takes the winding number iff `mesh_winding.edge_census` finds a
+boundary, a non-manifold or an inconsistently wound edge.  An unknown value raises ValueError.
+
 A mesh is a cuda `TensorMesh` or a pair `(RayTracer, mesh_id)`, as in `mesh_distance`.
 
 * `pseudonormals` — the table [F, 7, 3] of a mesh (csrc/mesh_sdf.hip: vsa_mesh_pseudonormals).
@@ -49,17 +57,19 @@ def pseudonormals(mesh, device=None):
 
 
 @torch.no_grad()
-def signed_distance(points, mesh):
+def signed_distance(points, mesh, sign="pseudonormal", beta=2.0):
     """{dist [N] (signed: negative inside), face [N], slot [N], bary [N, 2]} of the closest point of `mesh` to each of
-    points [N, 3] f32 (cuda): `mesh_distance.closest_points` with the sign (`RayTracer.signed_distance`)."""
+    points [N, 3] f32 (cuda): `mesh_distance.closest_points` with the sign (`RayTracer.signed_distance`).
+    sign="winding": inside iff the winding number exceeds 1/2 (the module's text); "auto": by the edge census."""
     tracer, mesh_id = _resolve(mesh, "signed_distance")
-    return tracer.signed_distance(points, mesh_id)
+    return tracer.signed_distance(points, mesh_id, sign=sign, beta=beta)
 
 
 @torch.no_grad()
-def contains(points, mesh):
-    """[N] bool: is the point inside the mesh (signed distance < 0; a point on the surface is not)."""
-    return signed_distance(points, mesh)["dist"] < 0
+def contains(points, mesh, sign="pseudonormal", beta=2.0):
+    """[N] bool: is the point inside the mesh (signed distance < 0; a point on the surface is not).  sign="winding":
+    inside iff the winding number exceeds 1/2, whether the mesh is closed or not."""
+    return signed_distance(points, mesh, sign=sign, beta=beta)["dist"] < 0
 
 
 def _axis(n, r, device):
@@ -67,12 +77,14 @@ def _axis(n, r, device):
     return torch.linspace(-r, r, n, dtype=torch.float32).to(device)
 
 
-def _grid(handle, x, y, z, band):
+def _grid(handle, x, y, z, band, sign="pseudonormal", beta=2.0):
     tracer, mesh_id = handle
     tracer.require_q16("mesh_to_sdf_grid")
     band = math.inf if band is None else float(band)
     if not band > 0.0:
         raise ValueError(f"mesh_to_sdf_grid: band must be > 0 (None: the whole field), got {band}")
+    if tracer.sign_rule(sign, [mesh_id]) == "winding":
+        return _grid_w(tracer, mesh_id, x, y, z, band, tracer._check_beta(beta))
     table, base = tracer.pseudonormal_tables()
     x, y, z = (_lib.check_f32(a.contiguous(), a.shape[0]) for a in (x, y, z))
     nx, ny, nz = x.shape[0], y.shape[0], z.shape[0]
@@ -86,35 +98,56 @@ def _grid(handle, x, y, z, band):
     return grid, {"near_bricks": int(counts[0]), "far_bricks": int(counts[1])}
 
 
+def _grid_w(tracer, mesh_id, x, y, z, band, beta):
+    """`_grid` with the winding sign (vsa_mesh_sdf_grid_w)."""
+    table, entries = tracer.winding_moments()
+    x, y, z = (_lib.check_f32(a.contiguous(), a.shape[0]) for a in (x, y, z))
+    nx, ny, nz = x.shape[0], y.shape[0], z.shape[0]
+    nbytes = _lib.workspace_bytes("vsa_mesh_sdf_grid_w_workspace_bytes", nx, ny, nz) if band < math.inf else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=tracer.device) if nbytes else None
+    grid = torch.empty(nx, ny, nz, device=tracer.device)
+    counts = (ctypes.c_longlong * 2)()
+    qnodes, tris, root, frame, _, depth = tracer.q16_tree_args(mesh_id)
+    _lib.call("vsa_mesh_sdf_grid_w", qnodes, tris, root[0], frame, depth, table, int(entries[mesh_id]), beta, x, y, z,
+              nx, ny, nz, band, grid, ws, nbytes, ctypes.cast(counts, ctypes.c_void_p), _lib.stream_ptr())
+    return grid, {"near_bricks": int(counts[0]), "far_bricks": int(counts[1])}
+
+
 @torch.no_grad()
-def sdf_grid(mesh, x, y, z, band=None):
+def sdf_grid(mesh, x, y, z, band=None, sign="pseudonormal", beta=2.0):
     """(grid [nx, ny, nz] f32, {near_bricks, far_bricks}): clamp(signed distance to `mesh` at (x[i], y[j], z[k]), -band,
-    band) for three device axis arrays (vsa_mesh_sdf_grid).  band None: the whole field."""
-    return _grid(_resolve(mesh, "sdf_grid"), x, y, z, band)
+    band) for three device axis arrays (vsa_mesh_sdf_grid; sign="winding": vsa_mesh_sdf_grid_w, bit for bit the point
+    query with that sign).  band None: the whole field."""
+    return _grid(_resolve(mesh, "sdf_grid"), x, y, z, band, sign, beta)
 
 
 @torch.no_grad()
-def mesh_to_sdf_grid(mesh, nr_points_per_dim, scene_radius=1.0, band=None):
+def mesh_to_sdf_grid(mesh, nr_points_per_dim, scene_radius=1.0, band=None, sign="pseudonormal", beta=2.0):
     """(grid [n, n, n] f32, {near_bricks, far_bricks}): the signed distance to `mesh` on `sample_grid`'s lattice of
     radius `scene_radius`, bit for bit `sample_grid(lambda p: signed_distance(p, mesh)["dist"], n, scene_radius)`
     clamped to [-band, band] (None: not clamped).  A wave walks a 4 x 4 x 4 brick of lattice points; with a band, bricks
     farther from the surface than the band plus their own radius are filled with +-band from one query at their centre
-    (far_bricks) and only the others are walked (near_bricks).  One blocking read with a band, none without."""
+    (far_bricks) and only the others are walked (near_bricks).  One blocking read with a band, none without.
+    sign="winding": the same contract with `signed_distance(p, mesh, sign="winding", beta=beta)`; bricks are classified
+    on the unsigned distance, and a far brick still takes the winding number at each of its points (it crosses 1/2 away
+    from the surface, on the membrane that closes a hole), so only the closest-point walk is saved there."""
     handle = _resolve(mesh, "mesh_to_sdf_grid")
     n = int(nr_points_per_dim)
     if n < 2:
         raise ValueError(f"mesh_to_sdf_grid: nr_points_per_dim must be >= 2, got {n}")
     axis = _axis(n, float(scene_radius), handle[0].device)
-    return _grid(handle, axis, axis, axis, band)
+    return _grid(handle, axis, axis, axis, band, sign, beta)
 
 
 @torch.no_grad()
 def offset_shells(mesh, nr_meshes, delta_surfs=0.0025, extract_level_set=0.0, nr_points_per_dim=512, scene_radius=1.0,
-                  band=None):
+                  band=None, sign="pseudonormal", beta=2.0):
     """(meshes, levels), inner to outer: the level sets `level_set_values(nr_meshes, delta_surfs, extract_level_set)`
     of the signed distance to `mesh`, from one banded grid and one K-level `marching_cubes` call.  The band is
     max |level| + 2 |spacing| (|spacing| the lattice cell's diagonal) unless given; a band that does not exceed every
-    |level| by a cell's diagonal cannot hold the level's crossings and raises."""
+    |level| by a cell's diagonal cannot hold the level's crossings and raises.  sign="winding" (or "auto" on a mesh
+    that is not closed): shells from an open mesh; they close across its holes along the w = 1/2 membrane, where all K
+    of them lie within one cell of each other."""
     levels = sorted(level_set_values(nr_meshes, delta_surfs, extract_level_set))
     if len(levels) > MAX_LEVELS:
         raise _lib.VolsurfsHipError(f"offset_shells: at most {MAX_LEVELS} levels, got {len(levels)}")
@@ -126,34 +159,35 @@ def offset_shells(mesh, nr_meshes, delta_surfs=0.0025, extract_level_set=0.0, nr
     if not band >= top + diag:
         raise ValueError(f"offset_shells: a band of {band} cannot hold the level {top} on a lattice whose cells are "
                          f"{diag} across (it takes at least {top + diag})")
-    grid, _ = mesh_to_sdf_grid(mesh, n, r, band)
+    grid, _ = mesh_to_sdf_grid(mesh, n, r, band, sign, beta)
     return marching_cubes(grid, levels, origin, spacing), levels
 
 
 def offset_meshes(mesh_path, out_dir, nr_meshes, delta_surfs=0.0025, extract_level_set=0.0, nr_points_per_dim=512,
-                  scene_radius=1.0):
+                  scene_radius=1.0, sign="pseudonormal", beta=2.0):
     """`offset_shells` of the PLY / OBJ at `mesh_path`, written as `<out_dir>/meshes/<level>.ply` (`save_level_sets`):
     the layout `simplify_meshes`, `compute_meshes_atlas` and `VolSurfs.from_meshes_path` continue from.  Returns
     (paths, levels)."""
     mesh = load_mesh(mesh_path)
     meshes, levels = offset_shells(TensorMesh(mesh.vertices, mesh.faces, None, device=mesh.vertices.device), nr_meshes,
-                                   delta_surfs, extract_level_set, nr_points_per_dim, scene_radius)
+                                   delta_surfs, extract_level_set, nr_points_per_dim, scene_radius, sign=sign, beta=beta)
     return save_level_sets(meshes, levels, os.path.join(out_dir, "meshes")), levels
 
 
 @torch.no_grad()
-def shell_nesting(meshes, n=1_000_000, seed=0):
+def shell_nesting(meshes, n=1_000_000, seed=0, sign="pseudonormal", beta=2.0):
     """Is every shell inside the next one?  For each consecutive pair (k, k + 1): n samples of shell k
     (`sample_surface(shell k, n, seed)`) and their signed distance d to shell k + 1; a list of K - 1 dicts {pair,
     outside = the number of samples with d >= 0 (not inside), clearance = -max d (the smallest depth of a sample below
     shell k + 1; negative when a sample is outside)}.  `meshes`: a list of TensorMeshes (one tracer is built for all of
-    them) or a RayTracer.  The signed companion of `mesh_distance.shell_clearance`."""
+    them) or a RayTracer.  The signed companion of `mesh_distance.shell_clearance`.  sign="winding": inside means a
+    winding number above 1/2, for shells that are not closed."""
     n = _check_n(n, "shell_nesting")
     tracer = meshes if isinstance(meshes, RayTracer) else RayTracer(list(meshes), builder="device")
     out = []
     for k in range(tracer.nr_meshes - 1):
         points, _, _ = sample_surface(_resolve((tracer, k), "shell_nesting"), n, seed)
-        d = tracer.signed_distance(points, k + 1)["dist"]
+        d = tracer.signed_distance(points, k + 1, sign=sign, beta=beta)["dist"]
         outside, top = torch.stack([(d >= 0).sum().double(), d.max().double()]).cpu().tolist()
         out.append({"pair": (k, k + 1), "outside": int(outside), "clearance": -top})
     return out

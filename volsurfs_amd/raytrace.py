@@ -49,6 +49,8 @@ class RayTracer:
         self._fb = None
         self._meshes = list(tensor_meshes)          # (the pseudonormal tables of signed_distance* are built from them)
         self._pn = None
+        self._wm = None                             # (the winding moments of winding_number* / sign="winding")
+        self._census = None
         self.nr_meshes = len(tensor_meshes)
         if not 1 <= self.nr_meshes <= 16:
             raise _lib.VolsurfsHipError("RayTracer supports 1..16 meshes")
@@ -212,6 +214,7 @@ class RayTracer:
             raise _lib.VolsurfsHipError("refit needs the meshes the tracer was built on")
         L = _lib.lib()
         self._meshes, self._pn = list(tensor_meshes), None       # the tables belonged to the old geometry
+        self._wm = self._census = None
         if self.builder in self.DEVICE_BUILDERS:
             st = _lib.stream_ptr()
             for h, m in zip(self._bvh, tensor_meshes):
@@ -378,13 +381,122 @@ class RayTracer:
                         (ctypes.c_longlong * self.nr_meshes)(*[int(b) for b in base]))
         return self._pn
 
-    def signed_distance_all(self, points):
-        """`closest_all` with `dist` signed (vsa_signed_distance_q; include/volsurfs_hip.h "Mesh signed distance",
-        DESIGN §29): negative inside a closed shell whose faces wind outward, by the angle-weighted pseudonormal of
-        the closest feature.  |dist|, face, slot and bary are `closest_all`'s bits; a point on the surface gets +0.
-        The sign means inside / outside for closed, consistently oriented shells only; for any other mesh it is
-        whatever the rule gives.  No host sync once the tables exist."""
+    SIGNS = ("pseudonormal", "winding", "auto")
+
+    def winding_moments(self):
+        """(table [2 nr_nodes + K, 8] f32, root_entry [K] host long long): per subtree of every shell's q16 tree the
+        area vector N = sum 1/2 e1 x e2, the area-weighted centroid and a radius about it (vsa_mesh_winding_moments;
+        include/volsurfs_hip.h "Mesh winding number"): entry 2 n + c for child c of node n, then one per
+        shell root; an entry is N.xyz, r, p.xyz, 0.  Built on first use and kept; `refit` drops it.  The same tracer
+        gives the same bytes."""
+        if self._wm is None:
+            self.require_q16("winding_moments")
+            nn, nt, K = self.qnodes.shape[0], self.tris.shape[0], self.nr_meshes
+            nbytes = _lib.workspace_bytes("vsa_mesh_winding_moments_workspace_bytes", nn, K)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            table = torch.empty(2 * nn + K, 8, device=self.device)
+            _lib.call("vsa_mesh_winding_moments", self.qnodes, self.tris, self._roots, K, nn, nt, ws, nbytes, table,
+                      _lib.stream_ptr())
+            self._wm = (table, (ctypes.c_longlong * K)(*[2 * nn + k for k in range(K)]))
+        return self._wm
+
+    def edge_census(self, mesh_id=0):
+        """{boundary, non_manifold, inconsistent} of shell `mesh_id` (`mesh_winding.edge_census`), kept until `refit`."""
+        if self._census is None:
+            self._census = [None] * self.nr_meshes
+        if self._census[mesh_id] is None:
+            from .mesh_winding import edge_census
+            self._census[mesh_id] = edge_census(self._meshes[mesh_id], device=self.device)
+        return self._census[mesh_id]
+
+    def sign_rule(self, sign, mesh_ids=None):
+        """"pseudonormal" or "winding": what `sign` means for these shells (all of them by default).  "auto" is the
+        winding number iff the edge census of one of them finds a boundary, a non-manifold or an inconsistently wound
+        edge.  Anything else raises ValueError."""
+        if sign not in self.SIGNS:
+            raise ValueError(f"sign must be one of {self.SIGNS}, got {sign!r}")
+        if sign != "auto":
+            return sign
+        ids = range(self.nr_meshes) if mesh_ids is None else mesh_ids
+        return "winding" if any(any(self.edge_census(k).values()) for k in ids) else "pseudonormal"
+
+    @staticmethod
+    def _check_beta(beta):
+        beta = float(beta)
+        if not beta > 1.0:
+            raise ValueError(f"beta must be > 1 (math.inf: every leaf is summed exactly), got {beta}")
+        return beta
+
+    def _winding_roots(self, mesh_id):
+        """(moments table, mesh_roots, moment_roots, nr_meshes) of all shells, or of shell `mesh_id` alone."""
+        table, entries = self.winding_moments()
+        if mesh_id is None:
+            return table, self._roots, entries, self.nr_meshes
+        return table, (ctypes.c_int32 * 1)(self.roots[mesh_id]), (ctypes.c_longlong * 1)(entries[mesh_id]), 1
+
+    def _winding(self, points, mesh_id, beta, what):
+        points = self._closest_args(points, what)
+        beta = self._check_beta(beta)
+        if mesh_id is not None and not 0 <= int(mesh_id) < self.nr_meshes:
+            raise _lib.VolsurfsHipError(f"{what}: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
+        table, roots, entries, K = self._winding_roots(mesh_id)
+        N = points.shape[0]
+        w = torch.empty((K, N) if mesh_id is None else (N,), device=points.device)
+        _lib.call("vsa_winding_number_q", self.qnodes, self.tris, roots, K, self.max_depth, table, entries, beta, points,
+                  N, w, _lib.stream_ptr())
+        return w
+
+    def winding_number_all(self, points, beta=2.0):
+        """w [K, N] f32: the generalised winding number of every shell at points [N, 3] f32, one launch
+        (vsa_winding_number_q): about 1 inside and about 0 outside for outward-wound faces, in between
+        across a hole, the multiplicity where parts overlap.  Returned raw: threshold it as you see fit (the signed
+        queries use w > 1/2).  Subtrees farther than beta times their radius are taken by their area vector (Barill
+        et al. 2018, order 0); beta must be > 1, math.inf sums every triangle exactly.  A NaN query gives NaN.  No
+        host sync once the moments exist."""
+        return self._winding(points, None, beta, "winding_number_all")
+
+    def winding_number(self, points, mesh_id=0, beta=2.0):
+        """`winding_number_all` for one shell: w [N]."""
+        return self._winding(points, int(mesh_id), beta, "winding_number")
+
+    def winding_stats(self, points, beta=2.0):
+        """{node_visits, tri_terms, queries} of one `winding_number_all` of these points, summed over the K shells
+        (vsa_winding_number_q_stats: the same walk with counters).  Synchronises; measurement only."""
+        points = self._closest_args(points, "winding_stats")
+        table, roots, entries, K = self._winding_roots(None)
+        st = torch.zeros(3, dtype=torch.int64, device=points.device)
+        _lib.call("vsa_winding_number_q_stats", self.qnodes, self.tris, roots, K, self.max_depth, table, entries,
+                  self._check_beta(beta), points, points.shape[0], st, _lib.stream_ptr())
+        v = st.cpu().tolist()
+        return {"node_visits": v[0], "tri_terms": v[1], "queries": v[2]}
+
+    def _signed_w(self, points, mesh_id, beta):
+        beta = self._check_beta(beta)
+        table, _, entries, K = self._winding_roots(mesh_id)
+        N = points.shape[0]
+        shape = (K, N) if mesh_id is None else (N,)
+        dist = torch.empty(shape, device=points.device)
+        slot = torch.empty(shape, dtype=torch.int32, device=points.device)
+        bary = torch.empty(*shape, 2, device=points.device)
+        _lib.call("vsa_signed_distance_w_q", *self.q16_tree_args(mesh_id), table, entries, beta, points, N, dist, slot,
+                  bary, _lib.stream_ptr())
+        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+
+    def signed_distance_all(self, points, sign="pseudonormal", beta=2.0):
+        """`closest_all` with `dist` signed; |dist|, face, slot and bary are `closest_all`'s bits.
+        sign="pseudonormal" (default; vsa_signed_distance_q; include/volsurfs_hip.h "Mesh signed distance", DESIGN
+        §29): negative inside a closed shell whose faces wind outward, by the angle-weighted pseudonormal of the
+        closest feature; a point on the surface gets +0.  It means inside / outside for closed, consistently oriented
+        shells only; for any other mesh it is whatever the rule gives.
+        sign="winding" (vsa_signed_distance_w_q; "Mesh winding number"): negative iff the winding number
+        `winding_number_all(points, beta)` exceeds 1/2, for outward-wound faces.  It also holds for open,
+        self-intersecting and inconsistently wound meshes: across a hole the level sets close with the w = 1/2
+        membrane, where the field jumps from -d to +d.
+        sign="auto": the winding number iff `edge_census` finds anything on a shell, else the pseudonormal.
+        No host sync once the tables exist."""
         points = self._closest_args(points, "signed_distance_all")
+        if self.sign_rule(sign) == "winding":
+            return self._signed_w(points, None, beta)
         table, base = self.pseudonormal_tables()
         K, N = self.nr_meshes, points.shape[0]
         dist = torch.empty(K, N, device=points.device)
@@ -394,11 +506,13 @@ class RayTracer:
                   _lib.stream_ptr())
         return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
 
-    def signed_distance(self, points, mesh_id=0):
+    def signed_distance(self, points, mesh_id=0, sign="pseudonormal", beta=2.0):
         """`signed_distance_all` for one shell: dist [N] (signed), face [N], slot [N], bary [N, 2]."""
         points = self._closest_args(points, "signed_distance")
         if not 0 <= int(mesh_id) < self.nr_meshes:
             raise _lib.VolsurfsHipError(f"signed_distance: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
+        if self.sign_rule(sign, [int(mesh_id)]) == "winding":
+            return self._signed_w(points, int(mesh_id), beta)
         table, base = self.pseudonormal_tables()
         N = points.shape[0]
         dist = torch.empty(N, device=points.device)
