@@ -107,19 +107,26 @@ def encode(values, x, scale_list, random_shift, window=None):
     return out
 
 
-def encode_backward(g_out, x, scale_list, random_shift, capacity, window=None, F=2):
-    """d loss / d values [L, capacity, F] (fp64 accumulation) for d loss / d out = g_out [N, L*F]."""
+def vertex_weights(x, scale_list, random_shift, capacity, window=None):
+    """Per level and simplex vertex: (l, k, idx [N] int64, w [N] fp32) — the table entry and the fp32
+    weight bary_k * window_l that `encode` multiplies its value by."""
     N, D = x.shape
-    L = len(scale_list)
     sf = scale_factors(scale_list, D)
-    g = np.zeros((L, capacity, F), np.float64)
-    for l in range(L):
+    for l in range(len(scale_list)):
         rem0, rank, bary = simplex(x.astype(f32), random_shift[l], sf[l])
         wl = f32(1.0) if window is None else f32(window[l])
         for k in range(D + 1):
-            idx = vertex_index(rem0, rank, k, capacity)
-            w = (bary[:, k] * wl).astype(f32)
-            np.add.at(g[l], idx, (g_out[:, l * F:(l + 1) * F] * w[:, None]).astype(np.float64))
+            yield l, k, vertex_index(rem0, rank, k, capacity), (bary[:, k] * wl).astype(f32)
+
+
+def encode_backward(g_out, x, scale_list, random_shift, capacity, window=None, F=2, dtype=f32):
+    """d loss / d values [L, capacity, F] (fp64 accumulation) for d loss / d out = g_out [N, L*F].
+    dtype: the precision of the products g * w (fp32 as the kernels form them; np.float64 for the exact
+    products of the fp32 weights and gradients)."""
+    g = np.zeros((len(scale_list), capacity, F), np.float64)
+    for l, k, idx, w in vertex_weights(x, scale_list, random_shift, capacity, window):
+        prod = g_out[:, l * F:(l + 1) * F].astype(dtype) * w[:, None].astype(dtype)
+        np.add.at(g[l], idx, prod.astype(np.float64))
     return g
 
 

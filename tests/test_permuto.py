@@ -190,3 +190,77 @@ def test_hip_permuto_grouped_launch_equals_the_encoders_one_by_one(sizes):
             scale = float(gb.abs().max())
             np.testing.assert_allclose(ga.cpu().numpy(), gb.cpu().numpy(), rtol=1e-4, atol=1e-5 * scale)
             e.encoder.lattice_values.grad = None
+
+
+@pytest.mark.gpu
+def test_hip_permuto_lds_table_gradient_holds_a_float64_bound_over_a_wide_dynamic_range():
+    """permuto_bwd_lds_kernel (all ten levels on the LDS path, five chunks of 1024 points) against the float64
+    sum of the exact products of the oracle's fp32 weights and the gradients, for a gradient with one element
+    1.0 among +-[1, 2) 2^-16 .. 2^-34 — the case that separates an exact fixed-point conversion from one that
+    rounds small negative contributions (tests/test_grid_table_grad.py derives the bound).
+
+    Per table float, with u = 2^-24: a workgroup owns (level, chunk c), scales by its OWN max|g| over the
+    chunk's two columns of that level, 2^(E_c-1) <= max < 2^E_c, and its count bits are the smallest cb with
+    2^cb >= (D + 1) 1024, i.e. 12 for D = 3: quantum q_c = 2^(E_c + 12 - 62).
+        sum_c (n_c / 2) q_c      every contribution rounded to the nearest quantum of its chunk
+        + (2 + P) u A'           the fp32 product, a chunk's sum rounded to float, P float atomicAdds of the
+                                 chunks' sums (P = chunks with a contribution, A' = A + the line above)
+        + 2^-53 A'               the int64 -> double conversion before the float rounding
+    A contribution that finds no slot within 16 probes would go to memory by a float atomic of its own; the
+    scales here keep a chunk's distinct vertices below a quarter of the 4096 slots (asserted), where the
+    multiplicative slot hash leaves no run of 16 taken slots."""
+    from volsurfs_amd.encodings import PermutoEncoding
+    import grid_table_grad_restated as R
+    D, L, C, N, CHUNK = 3, 10, 1 << 12, 5000, 1024
+    rng = np.random.default_rng(11)
+    scales = np.geomspace(1.0, 0.05, L)
+    shift = (rng.standard_normal((L, D)) * 10).astype(np.float32)
+    x = rng.random((N, D), dtype=np.float32)
+    go = R.dynamic_range_gradient(N, 2 * L, 3).numpy()
+    enc = PermutoEncoding(D, C, L, 2, scales)
+    with torch.no_grad():
+        enc.random_shift_per_level.copy_(torch.from_numpy(shift))
+    out = enc(torch.from_numpy(x).cuda(), None)
+    enc.lattice_values.grad = None
+    out.backward(torch.from_numpy(go).cuda())
+    got = enc.lattice_values.grad.cpu().numpy().astype(np.float64)
+
+    S = P.encode_backward(go, x, scales, shift, C, None, dtype=np.float64)
+    cb = R.count_bits((D + 1) * CHUNK)
+    assert cb == 12
+    A, quant, n = np.zeros_like(S), np.zeros_like(S), np.zeros(S.shape, np.int64)
+    chunks = np.zeros(S.shape, np.int64)
+    chunk_of = np.arange(N) // CHUNK
+    nchunks = chunk_of.max() + 1
+    distinct = np.zeros((L, nchunks), np.int64)
+    seen = [[set() for _ in range(nchunks)] for _ in range(L)]
+    hit = np.zeros((nchunks,) + S.shape, bool)
+    for l, k, idx, w in P.vertex_weights(x, scales, shift, C, None):
+        for f in range(2):
+            c = w.astype(np.float64) * go[:, 2 * l + f].astype(np.float64)
+            nz = c != 0
+            np.add.at(A[l, :, f], idx[nz], np.abs(c[nz]))
+            np.add.at(n[l, :, f], idx[nz], 1)
+            for ch in range(nchunks):
+                rows = nz & (chunk_of == ch)
+                m = np.abs(go[chunk_of == ch, 2 * l:2 * l + 2]).max()
+                q = 2.0 ** (int(np.frexp(m)[1]) + cb - 62)
+                np.add.at(quant[l, :, f], idx[rows], 0.5 * q)
+                hit[ch, l, idx[rows], f] = True
+        for ch in range(nchunks):
+            seen[l][ch].update(idx[chunk_of == ch].tolist())
+    for l in range(L):
+        for ch in range(nchunks):
+            distinct[l, ch] = len(seen[l][ch])
+    assert distinct.max() <= 1024, distinct.max()
+    Pn = hit.sum(0)
+    A1 = A + quant
+    bound = quant + (2 + Pn) * 2.0 ** -24 * A1 + 2.0 ** -53 * A1
+    err = np.abs(got - S)
+    ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), 0.0)
+    worst = np.unravel_index(np.argmax(ratio), ratio.shape)
+    print("permuto LDS: %d floats with contributions, worst error / bound = %.3g at %s (error %.3g, bound %.3g, n %d)"
+          % ((n > 0).sum(), ratio[worst], worst, err[worst], bound[worst], n[worst]))
+    assert (n > 0).sum() > 1000 and Pn.max() == nchunks
+    assert (got[n == 0] == 0).all()
+    assert (err <= bound).all(), "%d table floats beyond the bound, worst %.3g x" % ((err > bound).sum(), ratio[worst])

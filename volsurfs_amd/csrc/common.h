@@ -35,6 +35,23 @@ __device__ __forceinline__ float vsa_pin_f32(float x) {
   return x;
 }
 
+// round(v) as a two's-complement 64-bit integer for finite |v| < 2^62, from two native 32-bit
+// conversions (the float -> int64 conversion itself is a ~30-instruction software sequence).  The
+// MAGNITUDE is split, a = |rint(v)| = hi * 2^32 + lo: hi = floor(a / 2^32) is exact (a power-of-two
+// scaling), and lo = a - hi * 2^32 in [0, 2^32) is exact because it keeps only low bits of a's 24
+// significant ones.  The 64-bit integer is negated for v < 0.  (Splitting the SIGNED value instead put
+// lo of a small negative v at 2^32 - |v|, where floats are 256 apart: negative contributions below 2^31
+// quanta were rounded to multiples of 256 quanta, and those above -128 became -1.)
+// The fixed-point table-gradient accumulators of grid_encode.hip and permuto_encode.hip use it; a
+// non-finite v has no fixed-point value and is kept out of them by the callers.
+__device__ __forceinline__ unsigned long long vsa_fixed62(float v) {
+  const float a = fabsf(rintf(v));
+  const float hi = floorf(a * 2.3283064365386963e-10f);
+  const float lo = a - hi * 4294967296.0f;
+  const unsigned long long m = ((unsigned long long)(unsigned)hi << 32) + (unsigned long long)(unsigned)lo;
+  return v < 0.f ? 0ull - m : m;
+}
+
 static inline int vsa_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Compute units of the current device (grid size of the persistent kernels).

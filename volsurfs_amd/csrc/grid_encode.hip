@@ -197,13 +197,22 @@ __global__ __launch_bounds__(256) void grid_encode_bwd_kernel(vsa_grid_plan plan
 // spare — against 26 ms of atomics.  The LDS accumulators are 64-bit FIXED POINT (ds_add_u64:
 // LDS float atomics are ~20x slower on gfx950, tools/ubench/lds_atomics.hip; first version of this
 // kernel with ds_add_f32: 27.7 ms), scaled by a power of two from max|g| so that
-// 8 B contributions cannot overflow: resolution 2^-38 of the level's largest gradient, i.e. finer
-// than the fp32 sums it replaces for any level within 2^-14 of that, and independent of the summation order (bit-reproducible).
+// 8 B contributions cannot overflow: a quantum of 2^(count_bits - 62) of the largest gradient OF ALL
+// LEVELS (2^-38 at 2 M samples), every contribution rounded to the nearest quantum whatever its sign
+// (vsa_fixed62, common.h) — finer than the fp32 sums it replaces for any level within 2^-14 of that
+// maximum — and independent of the summation order (bit-reproducible).
 // g_lm: the output gradient re-laid level-major [L][B] float2 (grid_transpose_kernel, which also
 // reduces max|g|) so that a workgroup streams its level's gradients contiguously.
 constexpr int GS_SLICE_LOG2 = 13;
 constexpr int GS_SLICE = 1 << GS_SLICE_LOG2;
 constexpr int GS_THREADS = 1024;
+
+// (the float -> 62-bit fixed-point conversion: vsa_fixed62, common.h)
+// A NON-FINITE gradient has no fixed-point value.  Corner weights are finite, so a contribution is
+// non-finite exactly when its gradient is: such a feature of a sample is added straight to the output
+// floats of its 2^D entries, as the plain kernel above propagates it, and enters the fixed-point sums
+// as zero.  The transposer raises max_bits[1] when it meets one (max|g| itself is over the finite ones).
+__device__ __forceinline__ bool grid_nonfinite(float v) { return !(fabsf(v) < INFINITY); }
 
 // A workgroup re-lays GT_ROWS samples x L levels through LDS: rows are read as they lie (contiguous
 // per sample), and every level's GT_ROWS gradients leave as one contiguous 512-byte run (written
@@ -222,9 +231,9 @@ __global__ __launch_bounds__(256) void grid_transpose_kernel(const float* __rest
     const float* gp = g_out + (b0 + r) * g_stride + 2 * l;
     const float2 g = make_float2(gp[0], gp[1]);
     s_tile[l][r] = g;
-    float mm = fmaxf(fabsf(g.x), fabsf(g.y));
-    if (!(mm < INFINITY)) mm = 0.f;
-    m = fmaxf(m, mm);
+    const float ax = grid_nonfinite(g.x) ? 0.f : fabsf(g.x), ay = grid_nonfinite(g.y) ? 0.f : fabsf(g.y);
+    if (grid_nonfinite(g.x) || grid_nonfinite(g.y)) max_bits[1] = 1u;      // (every writer stores the same word)
+    m = fmaxf(m, fmaxf(ax, ay));
   }
   __syncthreads();
   for (int idx = threadIdx.x; idx < L * GT_ROWS; idx += 256) {
@@ -249,16 +258,6 @@ __global__ __launch_bounds__(256) void grid_transpose_kernel(const float* __rest
 // and whenever 64 are queued the wave adds them with ONE fully active atomic pair.
 constexpr int GS_QUEUE = 128;                      // ring entries per wave (a corner adds <= 64)
 
-// round(v) as a two's-complement 64-bit integer for |v| < 2^62, from two native 32-bit
-// conversions (the float -> int64 conversion itself is a ~30-instruction software sequence):
-// v = hi * 2^32 + lo with hi = floor(v / 2^32) exact (a power-of-two scaling), lo in [0, 2^32)
-__device__ __forceinline__ unsigned long long fixed62(float v) {
-  const float r = rintf(v);
-  const float hi = floorf(r * 2.3283064365386963e-10f);
-  const float lo = r - hi * 4294967296.0f;            // exact: r has 24 significant bits
-  return ((unsigned long long)(unsigned)(int)hi << 32) + (unsigned long long)(unsigned)lo;
-}
-
 template <int D>
 __global__ __launch_bounds__(GS_THREADS) void grid_encode_bwd_sliced_kernel(
     vsa_grid_plan plan, const float* __restrict__ x, const float2* __restrict__ g_lm,
@@ -268,9 +267,9 @@ __global__ __launch_bounds__(GS_THREADS) void grid_encode_bwd_sliced_kernel(
   const GridLevel g = grid_level(plan, l);
   if ((unsigned)slice << GS_SLICE_LOG2 >= g.size) return;
   const float gmax = __uint_as_float(max_bits[0]);
-  if (!(gmax > 0.f)) return;                         // no gradient at all
+  if (!(gmax > 0.f) && max_bits[1] == 0u) return;    // no gradient at all
   int e;
-  frexpf(gmax, &e);                                  // gmax < 2^e
+  frexpf(gmax, &e);                                  // gmax < 2^e (e = 0 when only non-finite gradients exist)
   const float scale = ldexpf(1.0f, 62 - count_bits - e);
   for (int i = threadIdx.x; i < 2 * GS_SLICE; i += GS_THREADS) s_acc[i] = 0ull;
   __syncthreads();
@@ -283,8 +282,8 @@ __global__ __launch_bounds__(GS_THREADS) void grid_encode_bwd_sliced_kernel(
       const int pos = (q_head + lane) & (GS_QUEUE - 1);
       const unsigned ent = s_q[3 * pos];
       const float vx = __uint_as_float(s_q[3 * pos + 1]), vy = __uint_as_float(s_q[3 * pos + 2]);
-      atomicAdd(s_acc + 2 * ent, fixed62(vx * scale));
-      atomicAdd(s_acc + 2 * ent + 1, fixed62(vy * scale));
+      atomicAdd(s_acc + 2 * ent, vsa_fixed62(vx * scale));
+      atomicAdd(s_acc + 2 * ent + 1, vsa_fixed62(vy * scale));
     }
     __builtin_amdgcn_wave_barrier();
     q_head = (q_head + n) & (GS_QUEUE - 1);
@@ -328,10 +327,28 @@ __global__ __launch_bounds__(GS_THREADS) void grid_encode_bwd_sliced_kernel(
     load_samples(base + GS_STEP + (long long)lane * GS_PER, go_n, x_n);
 #pragma unroll 1
     for (int j = 0; j < GS_PER; ++j) {
-      const float2 go = go_c[j];
+      float2 go = go_c[j];
       const bool active = go.x != 0.f || go.y != 0.f;
       if (!__ballot(active)) continue;
       const GridCell<D> cell = grid_cell<D>(g, x_c[j]);
+      if (__ballot(grid_nonfinite(go.x) || grid_nonfinite(go.y))) {      // rare: inf / nan goes straight to the output
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          const float gf = f ? go.y : go.x;
+          if (!grid_nonfinite(gf)) continue;
+#pragma unroll 1
+          for (int corner = 0; corner < (1 << D); ++corner) {
+            unsigned c[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) c[d] = cell.c[d] + ((corner >> d) & 1);
+            const unsigned idx = grid_index<D>(g, c);
+            if ((idx >> GS_SLICE_LOG2) == (unsigned)slice)               // (each entry belongs to one slice, each sample to one chunk)
+              atomicAdd(g_tables + 2 * (long long)(g.offset + idx) + f, corner_weight<D>(cell, corner) * gf);
+          }
+          if (f) go.y = 0.f;
+          else go.x = 0.f;
+        }
+      }
 #pragma unroll
       for (int corner = 0; corner < (1 << D); ++corner) {
         unsigned idx = 0;
@@ -468,7 +485,7 @@ template <int D>
 __global__ __launch_bounds__(GB_SAMPLES) void grid_bin_scatter_kernel(
     vsa_grid_plan plan, const float* __restrict__ x, const float2* __restrict__ g_lm, int B,
     unsigned long long* __restrict__ cursors, unsigned short* __restrict__ rec_idx,
-    float* __restrict__ rec_x, float* __restrict__ rec_y) {
+    float* __restrict__ rec_x, float* __restrict__ rec_y, float* __restrict__ g_tables) {
   constexpr int NC = 1 << D;
   extern __shared__ unsigned s_raw[];
   unsigned* s_cnt = s_raw;                              // [32] contributions per slice in this trip
@@ -499,6 +516,20 @@ __global__ __launch_bounds__(GB_SAMPLES) void grid_bin_scatter_kernel(
       for (int corner = 0; corner < NC; ++corner) {
         w[corner] = corner_weight<D>(cell, corner);
         rank[corner] = atomicAdd(&s_cnt[idx[corner] >> GS_SLICE_LOG2], 1u);
+      }
+      // rare: inf / nan goes straight to the output; its records stay (the bins were sized by
+      // grid_bin_count from the same `active`) and carry zeros
+      if (grid_nonfinite(go.x) || grid_nonfinite(go.y)) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          const float gf = f ? go.y : go.x;
+          if (!grid_nonfinite(gf)) continue;
+#pragma unroll
+          for (int corner = 0; corner < NC; ++corner)
+            atomicAdd(g_tables + 2 * (long long)(g.offset + idx[corner]) + f, w[corner] * gf);
+          if (f) go.y = 0.f;
+          else go.x = 0.f;
+        }
       }
     }
     __syncthreads();
@@ -592,8 +623,8 @@ __global__ __launch_bounds__(GS_THREADS) void grid_bin_accumulate_kernel(
       const unsigned long long ru = base + u;
       const bool ok = ru >= r0 && ru < r1;
       if (ok) {
-        sx += fixed62(vx[u] * scale);
-        sy += fixed62(vy[u] * scale);
+        sx += vsa_fixed62(vx[u] * scale);
+        sy += vsa_fixed62(vy[u] * scale);
       }
       // last record of a run of equal entries inside this lane's stretch
       const bool next_ok = u + 1 < GB_RPL && ru + 1 >= r0 && ru + 1 < r1;
@@ -865,10 +896,10 @@ extern "C" int vsa_grid_encode_bwd_binned_ld(const vsa_grid_plan* plan, const fl
   hipLaunchKernelGGL(grid_bin_scan_kernel, dim3(1), dim3(1024), 0, st, counts, nbins, offsets, cursors);
   if (plan->n_dims == 2) {
     hipLaunchKernelGGL(grid_bin_scatter_kernel<2>, grid, dim3(GB_SAMPLES), lds_sc, st, *plan, x, g_lm, nr_points,
-                       cursors, rec_idx, rec_x, rec_y);
+                       cursors, rec_idx, rec_x, rec_y, grad_tables);
   } else {
     hipLaunchKernelGGL(grid_bin_scatter_kernel<3>, grid, dim3(GB_SAMPLES), lds_sc, st, *plan, x, g_lm, nr_points,
-                       cursors, rec_idx, rec_x, rec_y);
+                       cursors, rec_idx, rec_x, rec_y, grad_tables);
   }
   // an entry receives at most 2^D corners of every sample
   long long worst = B << plan->n_dims;

@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void permuto_bwd_kernel(vsa_permuto_plan plan_
 // serialised at the memory side.  Here a workgroup owns (level, chunk of PL_CHUNK points: 1 024 —
 // with 4 096 the ten levels of a 10 k-point batch were 30 workgroups, the slowest 51 us): it adds
 // the chunk's contributions into an open-addressing table in LDS (keys claimed with ds_cmpst,
-// values 64-bit FIXED POINT as in grid_encode.hip: ds_add_u64 is ~16x faster than ds_add_f32 on
+// values 64-bit FIXED POINT as in grid_encode.hip (vsa_fixed62, common.h): ds_add_u64 is ~16x faster than ds_add_f32 on
 // gfx950, and integer sums make the result independent of the order inside the chunk), and then
 // flushes each distinct vertex ONCE.  The power-of-two scale comes from the chunk's own max|g|
 // (first pass over the chunk's gradient column).  A contribution that finds neither its key nor a
@@ -231,13 +231,6 @@ constexpr int PL_PROBES = 16;
 #endif
 constexpr int PL_CHUNK = PL_CHUNK_POINTS;  // points per workgroup
 constexpr unsigned PL_EMPTY = 0xffffffffu;
-
-__device__ __forceinline__ unsigned long long pl_fixed62(float v) {      // as grid_encode.hip's fixed62
-  const float r = rintf(v);
-  const float hi = floorf(r * 2.3283064365386963e-10f);
-  const float lo = r - hi * 4294967296.0f;
-  return ((unsigned long long)(unsigned)(int)hi << 32) + (unsigned long long)(unsigned)lo;
-}
 
 template <int D, bool DEV>
 __global__ __launch_bounds__(PL_THREADS) void permuto_bwd_lds_kernel(vsa_permuto_plan plan_val,
@@ -320,7 +313,7 @@ __global__ __launch_bounds__(PL_THREADS) void permuto_bwd_lds_kernel(vsa_permuto
         }
         slot = (slot + 1) & (PL_SLOTS - 1);
       }
-      if (found >= 0) atomicAdd(&s_val[2 * found + f], pl_fixed62((go * w) * scale));
+      if (found >= 0) atomicAdd(&s_val[2 * found + f], vsa_fixed62((go * w) * scale));
       else atomicAdd(tab + 2ll * idx + f, go * w);
     }
   }
