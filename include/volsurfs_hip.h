@@ -1826,6 +1826,65 @@ long long vsa_mesh_edge_census_workspace_bytes(long long nr_verts, long long nr_
 int vsa_mesh_edge_census(const float* vertices, long long nr_verts, const int32_t* faces, long long nr_faces,
                          void* workspace, long long workspace_bytes, long long* counts, void* stream);
 
+/* ---- Mesh repair (no counterpart in the reference; csrc/mesh_repair.hip) ----
+ * Welding the vertices that are one point and winding every edge-connected component consistently, outward.  The rules
+ * are this library's own and UNPINNED, restated in tests/mesh_repair_restated.py.
+ *   grouping      rep[i] = the lowest index whose row of three 32-bit words equals row i: three stable radix sorts of
+ *                 (word, index), last word first, from iota; the head of a run of equal rows is its lowest index.
+ * vsa_mesh_weld: verts [V, 3] f32 and faces [F, 3] i32 (device) to out_verts [V, 3] (the first stats[0] rows written),
+ *   out_faces [F, 3] (the first stats[1] rows), out_vertex_map [V] i32 (old -> new), out_face_map [F] i32 (old -> new,
+ *   -1: dropped) and stats [host, 4] = vertices out, faces out, degenerate faces dropped, duplicate faces dropped.
+ *   tol = 0       two vertices are one iff their three coordinates have equal bits after -0.0 -> +0.0; a vertex with a
+ *                 NaN coordinate merges with nothing.  Rows = the coordinate bits, grouped.
+ *   tol > 0       two vertices are in one cluster iff a chain of vertices links them whose consecutive members are within
+ *                 tol: d2 = ((dx dx + dy dy) + dz dz) <= tol tol in fp64 from the fp32 coordinates, no fused
+ *                 multiply-add.  The cell of a vertex is floor(p / tol) per axis in fp64, 21 bits each (offset 2^20),
+ *                 packed into 63 bits; (cell, vertex) is sorted; a lane per vertex searches its 27 neighbouring cells
+ *                 and hooks itself to every lower vertex within tol (the union-find of csrc/mesh_topology.h: the root
+ *                 is the lowest vertex whatever the order).  A vertex with a NaN has no cell and stays alone; a cell
+ *                 index outside [-2^20, 2^20) gives VSA_ERR_UNSUPPORTED (counted on the device, seen at the read).
+ *                 n vertices in one cell cost n^2 distance tests.
+ *   output        a representative (the lowest vertex of its cluster) keeps its own bits: nothing is averaged.  New
+ *                 indices ascend with the representative's old index.  Faces are remapped; with drop_degenerate a face
+ *                 that names a vertex twice goes; with drop_duplicates a face that stays so far and whose sorted
+ *                 triple equals a lower face's goes (the grouping over the sorted triples of all faces).  The others
+ *                 keep their order and winding.  Vertices no face names stay.
+ *   One blocking read.  stage_ms [host, 4] or NULL: group, vertices, duplicates, faces.
+ * vsa_mesh_orient: faces [F, 3] to out_faces [F, 3], out_flipped [F] u8, out_component [F] i32 and stats [host, 5] =
+ *   components, faces flipped, components that are not orientable, undecided components, their faces.  faces_uvs
+ *   [F, 3, 2] f32 or NULL: the per-corner UVs, written to out_faces_uvs with the flipped faces' corners swapped.
+ *   constraints   an undirected edge named by exactly two different faces of positive finite area (vsa_mesh_edge_census'
+ *                 faces and manifold edges) ties them: par = 1 iff both traverse it in the same direction.  Node
+ *                 2 f + s means face f kept (s = 0) or flipped (s = 1); 2 f is joined with 2 g + par and 2 f + 1 with
+ *                 2 g + 1 - par in a union-find over 2 F nodes whose roots are minima.  component[f] = root(2 f) >> 1
+ *                 (the lowest face of the component), the relative flip = root(2 f) & 1; root(2 f) = root(2 f + 1):
+ *                 the component is not orientable and keeps its faces as they are.
+ *   outward       per orientable component, fp64 sums of fixed shape over its faces in ascending order (chunks of 2048
+ *                 sorted positions, then the chunks of a component; no float atomics), a face without a finite area
+ *                 adding nothing: with N = 1/2 (v1 - v0) x (v2 - v0) after the relative flip, A = |N| and c = ((v0 + v1)
+ *                 + v2) / 3: cbar = sum A c / sum A (0 without area); S = sum (Nx dx + Ny dy) + Nz dz, d = c - cbar;
+ *                 U = sum A (|c|_1 + |cbar|_1).  S is three times the signed volume of a closed component and positive
+ *                 for a sheet whose normals point away from its centroid.  Decided iff |S| > 2^-20 U; a decided
+ *                 component with S < 0 (outward = 1; S > 0 with outward = 0) is flipped whole, an undecided one keeps
+ *                 the relative orientation.  flipped = relative flip xor the component's; a flipped face is
+ *                 (v0, v2, v1).
+ *   One blocking read.  stage_ms [host, 5] or NULL: edges, hook, roots, sums, flip.
+ * workspace = vsa_mesh_weld_workspace_bytes(V, F) / vsa_mesh_orient_workspace_bytes(V, F) bytes, the caller's.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (faces_uvs, out_faces_uvs without faces_uvs, and stage_ms may be
+ *   NULL), V or F < 1, tol negative, NaN or infinite, a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED: V >= 2^31
+ *   or 3 F + 3 (orient: 6 F + 3) >= 2^31, a cell index out of range (and from the queries, a failed rocPRIM size query:
+ *   no device). */
+long long vsa_mesh_weld_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_mesh_weld(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, double tol,
+                  int drop_degenerate, int drop_duplicates, void* workspace, long long workspace_bytes,
+                  float* out_verts, int32_t* out_faces, int32_t* out_vertex_map, int32_t* out_face_map,
+                  long long* stats, float* stage_ms, void* stream);
+long long vsa_mesh_orient_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_mesh_orient(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, int outward,
+                    const float* faces_uvs, void* workspace, long long workspace_bytes, int32_t* out_faces,
+                    float* out_faces_uvs, uint8_t* out_flipped, int32_t* out_component, long long* stats,
+                    float* stage_ms, void* stream);
+
 /* ---- Image preparation (the reference's loader, mvdatasets, is absent; csrc/image_prepare.hip) ----
  * A split's decoded image bytes to the float stacks `TensorReel`, `render_and_eval` and the bakers read, in one launch:
  * alpha over a background colour, box subsampling by an integer factor s, and the mask.  The rule is this library's own,

@@ -141,13 +141,21 @@ def mesh_to_sdf_grid(mesh, nr_points_per_dim, scene_radius=1.0, band=None, sign=
 
 @torch.no_grad()
 def offset_shells(mesh, nr_meshes, delta_surfs=0.0025, extract_level_set=0.0, nr_points_per_dim=512, scene_radius=1.0,
-                  band=None, sign="pseudonormal", beta=2.0):
+                  band=None, sign="pseudonormal", beta=2.0, repair=False, return_report=False):
     """(meshes, levels), inner to outer: the level sets `level_set_values(nr_meshes, delta_surfs, extract_level_set)`
     of the signed distance to `mesh`, from one banded grid and one K-level `marching_cubes` call.  The band is
     max |level| + 2 |spacing| (|spacing| the lattice cell's diagonal) unless given; a band that does not exceed every
     |level| by a cell's diagonal cannot hold the level's crossings and raises.  sign="winding" (or "auto" on a mesh
     that is not closed): shells from an open mesh; they close across its holes along the w = 1/2 membrane, where all K
-    of them lie within one cell of each other."""
+    of them lie within one cell of each other.  `repair`: the mesh (a TensorMesh) goes through
+    `mesh_repair.repair_mesh` first, so that a soup or a mis-wound mesh takes the sign it would have taken clean;
+    `return_report` adds that report (None without `repair`) as a third element."""
+    report = None
+    if repair:
+        from .mesh_repair import repair_mesh
+        if isinstance(mesh, tuple):
+            raise TypeError("offset_shells: repair=True takes a TensorMesh, not a (RayTracer, mesh_id) pair")
+        mesh, report = repair_mesh(mesh)
     levels = sorted(level_set_values(nr_meshes, delta_surfs, extract_level_set))
     if len(levels) > MAX_LEVELS:
         raise _lib.VolsurfsHipError(f"offset_shells: at most {MAX_LEVELS} levels, got {len(levels)}")
@@ -160,18 +168,21 @@ def offset_shells(mesh, nr_meshes, delta_surfs=0.0025, extract_level_set=0.0, nr
         raise ValueError(f"offset_shells: a band of {band} cannot hold the level {top} on a lattice whose cells are "
                          f"{diag} across (it takes at least {top + diag})")
     grid, _ = mesh_to_sdf_grid(mesh, n, r, band, sign, beta)
-    return marching_cubes(grid, levels, origin, spacing), levels
+    meshes = marching_cubes(grid, levels, origin, spacing)
+    return (meshes, levels, report) if return_report else (meshes, levels)
 
 
 def offset_meshes(mesh_path, out_dir, nr_meshes, delta_surfs=0.0025, extract_level_set=0.0, nr_points_per_dim=512,
-                  scene_radius=1.0, sign="pseudonormal", beta=2.0):
+                  scene_radius=1.0, sign="pseudonormal", beta=2.0, repair=False, return_report=False):
     """`offset_shells` of the PLY / OBJ at `mesh_path`, written as `<out_dir>/meshes/<level>.ply` (`save_level_sets`):
     the layout `simplify_meshes`, `compute_meshes_atlas` and `VolSurfs.from_meshes_path` continue from.  Returns
-    (paths, levels)."""
+    (paths, levels); `repair` and `return_report` as in `offset_shells`."""
     mesh = load_mesh(mesh_path)
-    meshes, levels = offset_shells(TensorMesh(mesh.vertices, mesh.faces, None, device=mesh.vertices.device), nr_meshes,
-                                   delta_surfs, extract_level_set, nr_points_per_dim, scene_radius, sign=sign, beta=beta)
-    return save_level_sets(meshes, levels, os.path.join(out_dir, "meshes")), levels
+    meshes, levels, report = offset_shells(TensorMesh(mesh.vertices, mesh.faces, None, device=mesh.vertices.device),
+                                           nr_meshes, delta_surfs, extract_level_set, nr_points_per_dim, scene_radius,
+                                           sign=sign, beta=beta, repair=repair, return_report=True)
+    paths = save_level_sets(meshes, levels, os.path.join(out_dir, "meshes"))
+    return (paths, levels, report) if return_report else (paths, levels)
 
 
 @torch.no_grad()
