@@ -1906,6 +1906,71 @@ int vsa_mesh_orient(const float* verts, long long nr_verts, const int32_t* faces
 int vsa_images_prepare(const uint8_t* src, const uint8_t* mask, int C, int H0, int W0, int ch, int s, const float* bg,
                        float* rgb, float* out_mask, void* stream);
 
+/* ---- Mesh crossings (no counterpart in the reference; csrc/mesh_cross.hip, csrc/cross_walk.h) ----
+ * Which faces of two meshes cross -- pass through one another -- and which faces of one mesh cross each other.  Exact in
+ * the sense that every face pair is decided by one restated rule, not sampled.  The reference has no such stage: the
+ * rule below is this library's own, restated in tests/mesh_intersect_restated.py and UNPINNED.
+ *   inputs        two triangles A = (A0, A1, A2), B = (B0, B1, B2): the fp32 bits of the meshes' VERTEX ARRAYS converted
+ *                 to fp64 (not the tree's records v0, e1, e2: their rounded edges would give a vertex two faces share
+ *                 different bits in each, and the rule leans on shared vertices being bit-equal).
+ *   arithmetic    fp64, in the order written, no contraction.  orient(a, b, c, d) = det[a - d; b - d; c - d] along its
+ *                 first row: p = a - d, q = b - d, r = c - d;  m0 = q.y r.z - q.z r.y,  m1 = q.x r.z - q.z r.x,
+ *                 m2 = q.x r.y - q.y r.x;  orient = (p.x m0 - p.y m1) + p.z m2.
+ *   determinants  sB[i] = orient(B0, B1, B2, A_i) (the side of A's vertex i of B's plane), sA[j] = orient(A0, A1, A2,
+ *                 B_j), e[i][j] = orient(A_i, A_{i+1}, B_j, B_{j+1}), indices mod 3: fifteen, each computed once.
+ *   crossing      edge i of A pierces B iff sB[i] and sB[i+1] are strictly opposite (one < 0, the other > 0) and
+ *                 e[i][0..2] are all >= 0 or all <= 0; edge j of B pierces A iff sA[j], sA[j+1] are strictly opposite
+ *                 and e[0..2][j] are all >= 0 or all <= 0.  A and B cross iff one of the six edges pierces and none of
+ *                 the six sides is NaN.  Signs only: a determinant whose sign no live condition reads may be skipped.
+ *   it follows    a vertex two faces share by equal bits has side exactly 0, so faces that share an edge never cross and
+ *                 faces that share one vertex cross only when the opposite edge of one goes through the other; no index
+ *                 is compared, so a triangle soup gives what its welded mesh gives; coplanar pairs, touching without
+ *                 passing through, duplicate faces and zero-area faces are not crossings; a face with a NaN coordinate
+ *                 crosses nothing (without the clause on the sides, the edge between its two other vertices could).
+ *   segment       the piercing point of edge p q against the other triangle's plane is p + t (q - p) per component,
+ *                 t = s_p / (s_p - s_q).  The pair's segment is the point of the first and of the last piercing edge in
+ *                 the order A's edges 0, 1, 2, B's edges 0, 1, 2.  Generically exactly two edges pierce; where a third
+ *                 does (an edge through an edge), first and last may be the same point.
+ *   walk          one lane per query face, one wave per workgroup, an LDS stack; a child of the tree mesh's q16 node is
+ *                 entered iff its u16 box overlaps (closed) the box of the query triangle in the tree's grid, g = (x -
+ *                 lo) / step + 1 of the fp32 minimum and maximum of the three vertices.  The boxes' outward margin of at
+ *                 least one unit covers the three roundings of g (below 2^-6 of a unit wherever g is compared with a u16
+ *                 coordinate, at any distance): no crossing pair is missed, and the result is that of brute force over
+ *                 all pairs.  At a leaf: slot -> the record's face id -> tree_faces row -> tree_vertices, then the rule.
+ *   self mode     (self_mode = 1: the query arrays are the tree's) face i against itself is skipped; a pair is evaluated
+ *                 with the lower face id as A whichever lane finds it; count_query[i] = the number of partners of face
+ *                 i; only pairs with j > i are emitted (offsets and total count those).
+ * qnodes / tris / max_depth as vsa_trace_q takes them; root, frame [host, 6 floats]: the tree mesh's.  query_order [Fq]
+ * i32 or NULL: lane i takes query face query_order[i] (a permutation that puts nearby faces into one wave; the results
+ * do not depend on it).  A face with a vertex index outside its vertex array, and a record whose id is outside 0 .. Ft -
+ * 1, cross nothing; nothing outside the arrays is read.
+ * vsa_mesh_cross_count: count_query [Fq] i32 = the tree faces each query face crosses; count_tree [Ft] i32 = the query
+ *   faces that cross each tree face (one integer atomicAdd per crossing; NULL and unused in self mode); offsets [Fq] i32
+ *   = the exclusive scan (rocPRIM) of the pairs each query face emits; total [device, 1] i64 = their sum (integer
+ *   atomics), the one word a caller reads back.
+ * vsa_mesh_cross_emit: the same walk with those offsets and nr_pairs = that total (>= 1): the pairs (query face, tree
+ *   face) as 64-bit keys at the query's offset, sorted ascending by a radix sort (csrc/mesh_topology.hip) -> pairs
+ *   [nr_pairs, 2] i64, segments [nr_pairs, 2, 3] f64 (or NULL) carried along.  A slot the walk leaves unwritten (offsets
+ *   that are not this input's) comes out as (2^32 - 1, 2^32 - 1) at the end; nothing beyond nr_pairs is written.
+ * workspace = vsa_mesh_cross_workspace_bytes(nr_query_faces, nr_pairs (0 for the count pass), segments != 0) bytes.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (query_order, segments, and count_tree in self mode may be NULL),
+ *   root < 0, max_depth >= 48, a vertex or face count < 1, self_mode outside 0..1 or with counts that differ, nr_pairs <
+ *   1 (emit) or < 0 (query); a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED: 3 F + 3 or V beyond 2^31 - 1,
+ *   nr_pairs beyond 2^31 - 1 (and from the query, a failed rocPRIM size query: no device). */
+long long vsa_mesh_cross_workspace_bytes(long long nr_query_faces, long long nr_pairs, int segments);
+int vsa_mesh_cross_count(const uint32_t* qnodes, const float* tris, int root, const float* frame, int max_depth,
+                         const float* tree_vertices, long long nr_tree_verts, const int32_t* tree_faces,
+                         long long nr_tree_faces, const float* query_vertices, long long nr_query_verts,
+                         const int32_t* query_faces, long long nr_query_faces, const int32_t* query_order,
+                         int self_mode, int32_t* count_query, int32_t* count_tree, int32_t* offsets, long long* total,
+                         void* workspace, long long workspace_bytes, void* stream);
+int vsa_mesh_cross_emit(const uint32_t* qnodes, const float* tris, int root, const float* frame, int max_depth,
+                        const float* tree_vertices, long long nr_tree_verts, const int32_t* tree_faces,
+                        long long nr_tree_faces, const float* query_vertices, long long nr_query_verts,
+                        const int32_t* query_faces, long long nr_query_faces, const int32_t* query_order,
+                        int self_mode, const int32_t* offsets, long long nr_pairs, long long* pairs, double* segments,
+                        void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

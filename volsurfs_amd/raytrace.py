@@ -540,6 +540,14 @@ class RayTracer:
         v = st.cpu().tolist()
         return {"node_visits": v[0], "tri_tests": v[1], "queries": v[2]}
 
+    def crossings(self, mesh, mesh_id=0, segments=False):
+        """Which faces of `mesh` (a cuda TensorMesh, or (RayTracer, mesh_id)) cross which faces of shell `mesh_id`:
+        `mesh_intersect.mesh_crossings(mesh, (self, mesh_id), segments)` -- a `Crossings` of (face of mesh, face of the
+        shell) pairs decided by the fp64 rule of DESIGN §33 over a box-overlap walk of the shell's q16 tree
+        (vsa_mesh_cross_count / vsa_mesh_cross_emit).  One blocking read."""
+        from .mesh_intersect import mesh_crossings
+        return mesh_crossings(mesh, (self, int(mesh_id)), segments)
+
     def sah_cost(self):
         """Per-mesh SAH cost of the trees, from the fp32 nodes (measurement; copies them to the host):
         1 (the root's visit) + sum over every child box of area / root area x (1 for an inner node, its triangle
