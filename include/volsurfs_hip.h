@@ -1971,6 +1971,51 @@ int vsa_mesh_cross_emit(const uint32_t* qnodes, const float* tris, int root, con
                         int self_mode, const int32_t* offsets, long long nr_pairs, long long* pairs, double* segments,
                         void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Shell untangling (no counterpart in the reference; csrc/shell_untangle.hip) ----
+ * Move the vertices of a shell M until it lies on one side of a fixed shell X and none of its faces crosses X.  Faces,
+ * UVs, vertex count and order are untouched.  The reference has no such stage: the rule below is this library's own,
+ * restated in tests/shell_untangle_restated.py and UNPINNED.
+ *   state         every vertex of M carries an integer level, 0 at round 0.  side s = +1 (M moves outward: it is to
+ *                 lie outside X) or -1 (inward).
+ *   project       for every vertex p of M, referenced by a face or not: the query of vsa_signed_distance_q against X
+ *                 (moments = NULL; the pseudonormal sign) or of vsa_signed_distance_w_q (moments, moment_root, beta: the
+ *                 winding sign) gives the signed dist, the residual r = p - closest point and the table's entry n of
+ *                 the closest feature.  m = margin * 2^min(level, max_level) (fp32, exact).  The vertex is VIOLATED iff
+ *                 it has a closest record and s dist < m (fp32; a NaN never is).  A violated vertex moves to p + t g per
+ *                 component, a multiply then an add without contraction: t = s (1.25f m) - dist;  g = r / |dist|,
+ *                 negated when dist < 0, if |dist| > 0, else g = n / sqrt(dot3(n, n)).  A g with a non-finite component
+ *                 leaves the vertex where it is: it counts as stuck, not as moved.  (1.25: a step that lands exactly on
+ *                 the margin flickers on the last ulp.)
+ *   count         the crossing face pairs P of M's faces against X: vsa_mesh_cross_count with M as the query mesh,
+ *                 after the project step.
+ *   stop          moved == 0 and P == 0: the pair has converged.
+ *   escalate      otherwise every vertex of every face of M with a non-zero count gets level += 1, once per round
+ *                 however many of its faces cross; the next round follows.
+ * vsa_shell_untangle_project: one lane per vertex, one wave per workgroup, the closest-point walk of X's q16 tree with an
+ *   LDS stack; vertices [nr_verts, 3] f32 are M's, moved IN PLACE; dist, slot and weights never reach memory.  state
+ *   [device, 4] i64: word 0 = moved, word 1 = stuck, word 2 = the bits of the largest |t| of a moved vertex (a non-negative
+ *   float: integer atomicMax), all three cleared by this call and written with one integer atomic per wave; word 3 is not
+ *   touched (hand &state[3] to vsa_mesh_cross_count as its `total`, and one read of 32 bytes ends the round).  round = 0
+ *   also clears the workspace: levels 0, stamps -1.  table / table_face_base: X's pseudonormals, needed with either sign
+ *   (a vertex on X moves along n).  side: +1 or -1.
+ * vsa_shell_untangle_escalate: one lane per face of M; count_query [nr_faces] i32 is the count pass's.  A crossing face
+ *   raises the stamp of its three vertices to `round` (integer atomicMax); the lane that raised it adds 1 to the level.
+ *   A face with an index outside 0 .. nr_verts - 1 is skipped.  `round` must increase from call to call.
+ * workspace = vsa_shell_untangle_workspace_bytes(nr_verts) bytes, kept by the caller across the rounds of one pair: the
+ *   levels [nr_verts] i32 at offset 0, then the stamps.
+ * No float atomics; the same inputs give the same bytes.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (moments may be NULL), root < 0, max_depth >= 48, a count < 1, side
+ *   not +-1, margin not a positive finite number, max_level outside 0 .. 30, round < 0, moments with moment_root < 0 or
+ *   beta <= 1, a workspace smaller than asked for.  VSA_ERR_UNSUPPORTED: nr_verts or 3 nr_faces + 3 beyond 2^31 - 1. */
+long long vsa_shell_untangle_workspace_bytes(long long nr_verts);
+int vsa_shell_untangle_project(const uint32_t* qnodes, const float* tris, int root, const float* frame, int max_depth,
+                               const float* table, long long table_face_base, const float* moments,
+                               long long moment_root, float beta, float* vertices, long long nr_verts, int side,
+                               float margin, int max_level, int round, void* workspace, long long workspace_bytes,
+                               long long* state, void* stream);
+int vsa_shell_untangle_escalate(const int32_t* count_query, const int32_t* faces, long long nr_faces,
+                                long long nr_verts, int round, void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

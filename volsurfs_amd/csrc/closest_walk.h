@@ -201,6 +201,40 @@ __device__ __forceinline__ void closest_walk(const uint4* __restrict__ qnodes, c
   }
 }
 
+// ---- the sign by the pseudonormal (csrc/mesh_sdf.hip; csrc/shell_untangle.hip moves vertices along the same r and N)
+
+constexpr int PN_FLOATS = 3 * CR_REGIONS;     // a face's row of the pseudonormal table [F, 7, 3]
+
+// The residual r = p - closest point of a walk's result (best.slot >= 0), as closest_on_triangle forms it: from the
+// same record and weights, the same bits.
+__device__ __forceinline__ void closest_residual(const float4* __restrict__ tris, const Closest& best, float px,
+                                                 float py, float pz, float& rx, float& ry, float& rz) {
+  const long long s = best.slot;
+  const float4 v0 = tris[3 * s], e1 = tris[3 * s + 1], e2 = tris[3 * s + 2];
+  const float ax = px - v0.x, ay = py - v0.y, az = pz - v0.z;
+  rx = (ax - best.u * e1.x) - best.v * e2.x;
+  ry = (ay - best.u * e1.y) - best.v * e2.y;
+  rz = (az - best.u * e1.z) - best.v * e2.z;
+}
+
+// The table's entry of the closest feature: (face, region) of a walk's result, `base` the mesh's first row.
+__device__ __forceinline__ const float* closest_pseudonormal(const float* __restrict__ table, long long base,
+                                                             const Closest& best) {
+  return table + (base + best.id) * PN_FLOATS + 3 * best.region;
+}
+
+// The walk's distance with the sign of r . N: r the residual, N the table's entry of (face, region).  No closest
+// record (a NaN query): +inf.
+__device__ __forceinline__ float signed_distance(const float4* __restrict__ tris, const float* __restrict__ table,
+                                                 long long base, const Closest& best, float px, float py, float pz) {
+  const float d = sqrtf(best.d2);
+  if (best.slot < 0) return d;
+  float rx, ry, rz;
+  closest_residual(tris, best, px, py, pz, rx, ry, rz);
+  const float* n = closest_pseudonormal(table, base, best);
+  return dot3(rx, ry, rz, n[0], n[1], n[2]) < 0.0f ? -d : d;
+}
+
 // ---- the surface sampler
 
 // fp64 area of a record: 0.5 sqrt((nx nx + ny ny) + nz nz), n = e1 x e2, every operation in fp64 on the fp32 edges.

@@ -10,7 +10,7 @@
 //   and sorted edges are mesh_topology's; one thread per vertex walks its ring in order, one thread per face corner the
 //   run of its edge key in order; fp64 sums, stored as fp32.  No float atomics: the same bytes on every call.
 // vsa_signed_distance_q: vsa_closest_point_q with `dist` signed: one record and one table fetch and a dot product
-//   after the walk.
+//   after the walk (closest_walk.h: signed_distance, shared with csrc/shell_untangle.hip).
 // vsa_mesh_sdf_grid: the field on a lattice given by its three axes, clamped to a band.  A wave is a 4 x 4 x 4 brick of
 //   lattice points.  With a finite band one lane per brick first asks at the brick's centre: a brick farther from the
 //   surface than the band plus its own radius is filled with +-band, the others are compacted in order (flags, scan,
@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr int PN_FLOATS = 3 * CR_REGIONS;     // a face's row of the table
 constexpr int SDF_BRICK = 4;                  // a wave: SDF_BRICK^3 = 64 lattice points
 constexpr long long MAX_GRID = 0x7fffffffll;
 
@@ -143,22 +142,6 @@ int pn_layout(long long V, long long F, PnLayout* l) {
 struct TableBase {
   long long face[VSA_MAX_SHELLS];   // first row of each mesh's faces in the table
 };
-
-// The walk's distance with the sign of r . N: r the residual as closest_on_triangle forms it, from the same record
-// and weights (the same bits), N the table's entry of (face, region).  No closest record (a NaN query): +inf.
-__device__ __forceinline__ float signed_distance(const float4* __restrict__ tris, const float* __restrict__ table,
-                                                 long long base, const Closest& best, float px, float py, float pz) {
-  const float d = sqrtf(best.d2);
-  if (best.slot < 0) return d;
-  const long long s = best.slot;
-  const float4 v0 = tris[3 * s], e1 = tris[3 * s + 1], e2 = tris[3 * s + 2];
-  const float ax = px - v0.x, ay = py - v0.y, az = pz - v0.z;
-  const float rx = (ax - best.u * e1.x) - best.v * e2.x;
-  const float ry = (ay - best.u * e1.y) - best.v * e2.y;
-  const float rz = (az - best.u * e1.z) - best.v * e2.z;
-  const float* n = table + (base + best.id) * PN_FLOATS + 3 * best.region;
-  return dot3(rx, ry, rz, n[0], n[1], n[2]) < 0.0f ? -d : d;
-}
 
 template <int STACK, bool BOUNDS>
 __global__ __launch_bounds__(TRACE_BLOCK) void signed_distance_kernel(

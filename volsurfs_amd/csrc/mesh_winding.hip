@@ -203,12 +203,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) void winding_number_kernel(
   if (alive) w[(long long)mesh * nr_points + i] = wn;
 }
 
-// The walk's distance, negative iff w > 1/2.  No closest record (a NaN query): +inf (w is NaN there).
-__device__ __forceinline__ float signed_by_winding(const Closest& best, float wn) {
-  const float d = sqrtf(best.d2);
-  return wn > 0.5f ? -d : d;
-}
-
 template <int STACK, bool BOUNDS>
 __global__ __launch_bounds__(TRACE_BLOCK) void signed_distance_w_kernel(
     const uint4* __restrict__ qnodes, const float4* __restrict__ tris, Roots roots, Frames frames,

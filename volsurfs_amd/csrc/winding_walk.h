@@ -95,4 +95,10 @@ __device__ __forceinline__ float winding_walk(const uint4* __restrict__ qnodes, 
   return acc * WN_INV_4PI;
 }
 
+// The closest-point walk's distance, negative iff w > 1/2.  No closest record (a NaN query): +inf (w is NaN there).
+__device__ __forceinline__ float signed_by_winding(const Closest& best, float wn) {
+  const float d = sqrtf(best.d2);
+  return wn > 0.5f ? -d : d;
+}
+
 }  // namespace

@@ -548,6 +548,16 @@ class RayTracer:
         from .mesh_intersect import mesh_crossings
         return mesh_crossings(mesh, (self, int(mesh_id)), segments)
 
+    def untangle(self, mesh_id, against, side, margin=1e-3, max_rounds=16, max_level=6, sign="pseudonormal", beta=2.0,
+                 log=None):
+        """Move the vertices of shell `mesh_id` until it clears shell `against` on `side` (+1: outside it, -1: inside
+        it): one pair of `shell_untangle.untangle_shells` (vsa_shell_untangle_project / _escalate around the crossing
+        count pass; include/volsurfs_hip.h "Shell untangling").  The shell's mesh is replaced by a new
+        TensorMesh with the same faces and UVs and the tracer is `refit`.  Returns an `UntangleReport`; one blocking
+        read per round."""
+        from .shell_untangle import untangle_pair
+        return untangle_pair(self, mesh_id, against, side, margin, max_rounds, max_level, sign, beta, log)
+
     def sah_cost(self):
         """Per-mesh SAH cost of the trees, from the fp32 nodes (measurement; copies them to the host):
         1 (the root's visit) + sum over every child box of area / root area x (1 for an inner node, its triangle
