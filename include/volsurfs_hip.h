@@ -2016,6 +2016,67 @@ int vsa_shell_untangle_project(const uint32_t* qnodes, const float* tris, int ro
 int vsa_shell_untangle_escalate(const int32_t* count_query, const int32_t* faces, long long nr_faces,
                                 long long nr_verts, int round, void* workspace, long long workspace_bytes, void* stream);
 
+/* ---- Shell rasterization (no counterpart in the reference's tree; csrc/shell_raster.hip) ----
+ * The hit records of vsa_trace_q for every sample of one camera, from screen-space bins instead of BVH walks: the same
+ * pinhole ray (csrc/pinhole.h) and the same triangle test (csrc/trace_walk.h tri_test: smallest t, ties to the smallest
+ * original face id, a hit iff t > t_min) over, per 8 x 8-sample tile, a list that holds every triangle one of the
+ * tile's rays can pass.  The closest hit does not depend on the order or the length of such a list, so the records
+ * equal the trace's bit for bit.  The bin rule below is this library's own, restated in tests/rasterize_restated.py and
+ * UNPINNED.  No nodes are read: any builder, either node format.
+ *   tris          the tracer's leaf-ordered records [nr_slots, 12] f32 (v0.xyz, id | e1.xyz, - | e2.xyz, -);
+ *                 mesh_tri_offset / mesh_nr_tris [host, nr_meshes] i32: shell k owns slots offset .. offset + nr - 1.
+ *   camera        c2w [3, 4] = [R | t], intrinsics K [3, 3] and intrinsics_inv [3, 3], f32 on the device; any pinhole K
+ *                 (skew and an off-centre principal point included).  Rays come from intrinsics_inv, boxes from K.
+ *   samples       the grid of vsa_face_view_counts: sample (i, j) of pixel (col, row) goes through x = col + (i + 0.5f)
+ *                 / s, y = row + (j + 0.5f) / s; s = 1 is the unjittered ray of vsa_camera_rays bit for bit.  Sample
+ *                 (X, Y) = (col s + i, row s + j) of the (s H) x (s W) grid belongs to tile (X / 8, Y / 8).
+ *   bin rule      fp32, in the order written, no contraction.  Per slot: a = v0, b = v0 + e1, c = v0 + e2; per vertex
+ *                 w = v - t, p = ((R0i w0 + R1i w1) + R2i w2) for i = x, y, z (p = R^T w).  z_g = 1e-4f max(1, |t.x|,
+ *                 |t.y|, |t.z|).
+ *                 dropped      a vertex coordinate is not finite: in no list (tri_test accepts nothing on NaN).
+ *                 behind       all three p.z < -z_g: in no list.  (A hit has camera z = t d_z > 0 for t > t_min >= 0.)
+ *                 straddling   neither behind nor in front, or a projection that is not finite or has h.w <= 0: the
+ *                              face goes to EVERY tile of its shell.  It is kept once, in a list per shell that every
+ *                              tile's wave walks after its own, not copied into the tiles' lists.
+ *                 in front     all three p.z > z_g.  h = K p (rows as (Ki0 p.x + Ki1 p.y) + Ki2 p.z), u = h.x / h.w,
+ *                              v = h.y / h.w in pixels.  The box of the three (u, v), grown by ONE PIXEL on every side,
+ *                              in samples: X0 = floor((min u - 1) s), X1 = floor((max u + 1) s), Y likewise; off the
+ *                              image (X1 < 0, X0 > s W - 1, ...) it is in no list, else clamped to [0, s W - 1] x
+ *                              [0, s H - 1] in float, converted, and the face is in the list of every tile from
+ *                              (X0 / 8, Y0 / 8) to (X1 / 8, Y1 / 8).
+ *                 The pixel is part of the rule: tri_test is inexact and accepts rays just outside the exact triangle
+ *                 (measured: at most 1.9e-6 pixels outside the unexpanded box; DESIGN 35 has the argument).
+ *   stats         [host, 4] long long: faces behind, faces straddling, faces binned (in front, in at least one tile's
+ *                 list), pairs = the (tile, slot) entries of all tiles' lists (straddling faces not among them).
+ * vsa_shell_raster_setup: the setup pass (one lane per slot: class, box, one integer atomic per tile touched), a scan
+ *   of the (shell, tile) counters, and one blocking read of `stats`.  t_min is only checked.
+ * vsa_shell_raster_draw: the fill pass (one integer atomic per pair; the order inside a list is the schedule's and does
+ *   not matter) and the raster pass (one wave per (shell, tile), one lane per sample, lanes past the image edge masked;
+ *   no stack, no LDS, no scratch).  Same arguments and workspace as the setup call before it; pairs [device, nr_pairs]
+ *   i32 is the caller's, nr_pairs = stats[3] (pairs may be NULL when it is 0).  May be repeated after one setup.
+ *   hit_t [K, N] f32 (0 for a miss), hit_slot [K, N] i32 (global slot, -1 = miss), hit_uv [K, N, 2] f32, as vsa_trace_q
+ *   writes them; N = H W s^2, pixel-major, a pixel's samples consecutive, j outer, i inner.  rays_d [N, 3] f32 or NULL:
+ *   the samples' directions (the origin is t).  stage_ms [host, 2] or NULL: device ms of the fill and the raster pass
+ *   (synchronises).
+ * workspace = vsa_shell_raster_workspace_bytes(nr_slots, nr_meshes, height, width, supersample) bytes, the caller's:
+ *   20 bytes per slot and 12 per (shell, tile) plus the scan's storage.
+ * Integer atomics only; the same inputs give the same bytes.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer (rays_d, stage_ms and, with nr_pairs = 0, pairs may be NULL),
+ *   nr_slots < 1, nr_meshes outside 1 .. 16, a slot range outside 0 .. nr_slots, height or width < 1, supersample outside
+ *   1 .. 8, t_min < 0 or not finite, H W s^2 >= 2^31, nr_pairs < 0, a workspace smaller than asked for.
+ *   VSA_ERR_UNSUPPORTED: more than 2^31 - 1 pairs (setup: after the read; faces that each cover the whole image make
+ *   F x tiles pairs), or K x tiles + 1 beyond 2^31 - 1. */
+long long vsa_shell_raster_workspace_bytes(long long nr_slots, int nr_meshes, int height, int width, int supersample);
+int vsa_shell_raster_setup(const float* tris, long long nr_slots, const int32_t* mesh_tri_offset,
+                           const int32_t* mesh_nr_tris, int nr_meshes, const float* c2w, const float* intrinsics,
+                           const float* intrinsics_inv, int height, int width, int supersample, float t_min,
+                           void* workspace, long long workspace_bytes, long long* stats, void* stream);
+int vsa_shell_raster_draw(const float* tris, long long nr_slots, const int32_t* mesh_tri_offset,
+                          const int32_t* mesh_nr_tris, int nr_meshes, const float* c2w, const float* intrinsics,
+                          const float* intrinsics_inv, int height, int width, int supersample, float t_min,
+                          const void* workspace, long long workspace_bytes, long long nr_pairs, int32_t* pairs,
+                          float* hit_t, int32_t* hit_slot, float* hit_uv, float* rays_d, float* stage_ms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -571,9 +571,10 @@ class VolSurfs(torch.nn.Module):
             idx = torch.nonzero_static(mask, size=mask.numel(), fill_value=0)
             return VolSurfs._TraceAhead(rays_o, rays_d, hit, idx, mask.sum(1))
 
-    def render_rays(self, rays_o, rays_d, iter_nr=None, return_samples=True, ahead=None, **kwargs):
+    def render_rays(self, rays_o, rays_d, iter_nr=None, return_samples=True, ahead=None, hits=None, **kwargs):
         """volsurfs.py:423-761: returns {"renders": {"ray_traced": {...}}, "samples_3d",
-        "samples_grad"} with the reference's keys, shapes and dtypes."""
+        "samples_grad"} with the reference's keys, shapes and dtypes.  hits: these rays' (hit_t, hit_slot, hit_uv)
+        when the caller already has them (`RayTracer.rasterize`); the traversal is skipped."""
         N, K = rays_o.shape[0], self.nr_meshes
         if N > self.max_rays:
             raise _lib.VolsurfsHipError(f"{N} rays > max_rays={self.max_rays}; use render()")
@@ -583,7 +584,9 @@ class VolSurfs(torch.nn.Module):
             prof.start("meshes_raytracing")
         if ahead is not None and (ahead.rays_o.data_ptr() != rays_o.data_ptr() or ahead.rays_o.shape != rays_o.shape):
             ahead = None                                                       # not this batch's: trace now
-        if ahead is not None:
+        if hits is not None:
+            hit_t, hit_slot, hit_uv = hits
+        elif ahead is not None:
             ahead.join()
             hit_t, hit_slot, hit_uv = ahead.hit_t, ahead.hit_slot, ahead.hit_uv
         else:
@@ -663,15 +666,44 @@ class VolSurfs(torch.nn.Module):
         outs = []
         for a in range(0, rays_o.shape[0], chunk):
             o, d = rays_o[a:a + chunk].contiguous(), rays_d[a:a + chunk].contiguous()
-            hit_t, hit_slot, hit_uv = self._trace_now(o, d)
-            tex_uv = self.baked.tex_uv_only(hit_slot, hit_uv, self.face_uvs)
-            rgb_k, alpha_k, normals, _ = self.baked.shade(hit_slot, tex_uv, d, self.raytracer.tris,
-                                                          want_normals=True)
-            bg = self.bg_color if self.bg_color is not None else torch.ones(1, 3, device=o.device)
-            out = composite_dense(rgb_k, alpha_k, bg)
-            out["surfs_normals"] = normals
-            outs.append(out)
+            _, hit_slot, hit_uv = self._trace_now(o, d)
+            outs.append(self._shade_baked(hit_slot, hit_uv, d))
         return outs[0] if len(outs) == 1 else {k: torch.cat([o_[k] for o_ in outs], 0) for k in outs[0]}
+
+    def _shade_baked(self, hit_slot, hit_uv, rays_d):
+        """What follows the hits in a baked render: per-hit uv -> shade -> composite."""
+        tex_uv = self.baked.tex_uv_only(hit_slot, hit_uv, self.face_uvs)
+        rgb_k, alpha_k, normals, _ = self.baked.shade(hit_slot, tex_uv, rays_d, self.raytracer.tris,
+                                                      want_normals=True)
+        bg = self.bg_color if self.bg_color is not None else torch.ones(1, 3, device=rays_d.device)
+        out = composite_dense(rgb_k, alpha_k, bg)
+        out["surfs_normals"] = normals
+        return out
+
+    @torch.no_grad()
+    def render_baked_camera(self, camera, supersample=1, hits="trace"):
+        """`render_baked` from the camera down: the `ray_traced` dict per pixel, [H * W, C], the mean over the pixel's
+        s^2 samples when supersample = s > 1.
+        hits="trace" (default): `get_camera_rays` (jittered when s > 1, as BaseRenderer.render draws them) +
+        `trace_all`.  hits="raster": `RayTracer.rasterize` -- no ray-generation launch, no ray in memory, no BVH walk;
+        the s^2 samples lie on the s x s grid of `face_view_counts`.  At s = 1 the two give the same bytes in every
+        buffer.  Measured: the raster path is faster for simplified shells seen from outside (a few faces
+        per 8 x 8 tile; 1.3x, 2x at s = 2); the trace is faster, by far, for dense meshes (tens of faces per tile) and
+        for a camera inside a shell."""
+        from .rasterize import camera_hits, check_hits_mode
+        s = int(supersample)
+        if not 1 <= s <= 8:
+            raise ValueError(f"supersample must be in 1..8, got {supersample}")
+        if check_hits_mode(hits) == "raster":
+            _, rays_d, (_, hit_slot, hit_uv) = camera_hits(self.raytracer, camera, s)
+            out = self._shade_baked(hit_slot, hit_uv, rays_d)
+        else:
+            from .camera import get_camera_rays
+            rays_o, rays_d, _ = get_camera_rays(camera, s * s, s > 1)
+            out = self.render_baked(rays_o, rays_d)
+        if s > 1:
+            out = {k: v.reshape(-1, s * s, *v.shape[1:]).float().mean(1) for k, v in out.items()}
+        return out
 
     # -- fused training path: the same forward + mean-L1 + backward as `forward(...)` followed by
     # `loss.backward()`, as ONE sequence of C-ABI launches on the current stream (no autograd
@@ -852,17 +884,32 @@ class VolSurfs(torch.nn.Module):
         return path
 
     @torch.no_grad()
-    def render_camera(self, camera, nr_rays_per_pixel=1, jitter_pixels=False, chunk=None):
+    def render_camera(self, camera, nr_rays_per_pixel=1, jitter_pixels=False, chunk=None, hits="trace"):
         """base_method.py:366-541 from the camera down: device ray generation (`ray_gen`,
-        :386-402) then the chunked render, reshaped to [H, W, C] images."""
-        from .camera import get_camera_rays
-        rays_o, rays_d, _ = get_camera_rays(camera, nr_rays_per_pixel, jitter_pixels)
-        full = self.render(rays_o, rays_d, nr_rays_per_pixel, chunk)
+        :386-402) then the chunked render, reshaped to [H, W, C] images.
+        hits="trace" (default): `get_camera_rays` + the traversal.  hits="raster": the hits and directions of the
+        whole frame from `RayTracer.rasterize` (no ray-generation launch, no BVH walk), then the same chunked render.
+        It needs jitter_pixels=False and nr_rays_per_pixel = s^2, s in 1..8, and raises ValueError otherwise.  At one
+        ray per pixel the two give the same bytes in every buffer.  With more they give DIFFERENT images: unjittered,
+        `get_camera_rays` sends all of a pixel's rays through its centre, the raster path puts them on the s x s grid
+        of `face_view_counts` -- a real supersample, the better image.  Measured: the raster path is
+        faster for simplified shells seen from outside (a few faces per 8 x 8 tile), the trace for dense meshes and for
+        a camera inside a shell."""
+        from .rasterize import camera_hits, check_hits_mode, grid_side
+        if check_hits_mode(hits) == "raster":
+            if jitter_pixels:
+                raise ValueError('hits="raster" samples a fixed grid: it cannot jitter (jitter_pixels=False)')
+            rays_o, rays_d, frame_hits = camera_hits(self.raytracer, camera, grid_side(nr_rays_per_pixel))
+        else:
+            from .camera import get_camera_rays
+            rays_o, rays_d, _ = get_camera_rays(camera, nr_rays_per_pixel, jitter_pixels)
+            frame_hits = None
+        full = self.render(rays_o, rays_d, nr_rays_per_pixel, chunk, hits=frame_hits)
         return {k: None if v is None else v.reshape(camera.height, camera.width, *v.shape[1:])
                 for k, v in full.items()}
 
     @torch.no_grad()
-    def render(self, rays_o, rays_d, nr_rays_per_pixel=1, chunk=None):
+    def render(self, rays_o, rays_d, nr_rays_per_pixel=1, chunk=None, hits=None):
         """base_method.py:366-541: chunked full-frame render, supersample mean over
         nr_rays_per_pixel; buffers stay on the device.  chunk: rays per render_rays call — the
         reference's test_rays_batch_size is 16 384; the default here is what this method's buffers
@@ -871,7 +918,9 @@ class VolSurfs(torch.nn.Module):
         chunk = int(chunk) if chunk else self.max_rays
         outs = []
         for a in range(0, rays_o.shape[0], chunk):
-            r = self.render_rays(rays_o[a:a + chunk], rays_d[a:a + chunk], return_samples=False)
+            # (hits: the rays' hit records when the caller has them -- render_camera(hits="raster"))
+            part = None if hits is None else tuple(h[:, a:a + chunk].contiguous() for h in hits)
+            r = self.render_rays(rays_o[a:a + chunk], rays_d[a:a + chunk], return_samples=False, hits=part)
             outs.append(r["renders"]["ray_traced"])
         # keys a configuration does not produce are None (surfs_uvs on the legacy branch)
         # (one chunk: the buffers as they are - `torch.cat` of a single tensor is a copy, and the output

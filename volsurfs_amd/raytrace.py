@@ -320,6 +320,20 @@ class RayTracer:
         from .visibility import tracer_face_view_counts
         return tracer_face_view_counts(self, cameras, supersample, t_min)
 
+    raster_stats = None         # the `rasterize.RasterStats` of the last `rasterize` call
+
+    def rasterize(self, camera, supersample=1, t_min=0.0, out=None, want_dirs=False):
+        """`trace_all`'s (hit_t, hit_slot, hit_uv), bit for bit, for every sample of one camera, by screen-space bins
+        instead of BVH walks (vsa_shell_raster_setup / _draw; include/volsurfs_hip.h "Shell rasterization", DESIGN
+        §35): N = H W s^2 samples, pixel-major, a pixel's s x s samples consecutive (j outer, i inner), sample (i, j)
+        through (col + (i + 0.5) / s, row + (j + 0.5) / s) as in `face_view_counts`; s = 1 is the unjittered rays of
+        `get_camera_rays`.  No ray is written or read and no node is walked: any builder, either node format.
+        `out` as `trace_all` takes it; want_dirs adds rays_d [N, 3] to the result (the origin is the camera centre).
+        t_min must be >= 0.  One blocking read (the pair list is sized from it); `raster_stats` has the call's
+        (behind, straddling, binned, pairs)."""
+        from .rasterize import tracer_rasterize
+        return tracer_rasterize(self, camera, supersample, t_min, out, want_dirs)
+
     def q16_tree_args(self, mesh_id=None):
         """The leading arguments of the q16 entry points (qnodes, tris, mesh_roots, mesh_frames, nr_meshes, max_depth):
         of all K shells, or of shell `mesh_id` alone as a tracer of one shell."""

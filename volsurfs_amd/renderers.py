@@ -201,3 +201,9 @@ class VolsurfsRenderer(BaseRenderer):
     @torch.no_grad()
     def render_rays(self, rays_o, rays_d, verbose=False) -> dict:
         return {"renders": {"ray_traced": self.method.render_baked(rays_o, rays_d)}}
+
+    @torch.no_grad()
+    def render_baked_camera(self, camera, supersample=1, hits="trace"):
+        """The method's `render_baked_camera`: the `ray_traced` dict per pixel, on the device; hits="raster" takes
+        the frame's hits from `RayTracer.rasterize` instead of `get_camera_rays` + `trace_all`."""
+        return self.method.render_baked_camera(camera, supersample=supersample, hits=hits)

@@ -342,6 +342,8 @@ class BakedScene:
     # VolSurfs' own methods, so that a loaded scene and a baked method render through one path
     _trace_now = VolSurfs._trace_now
     render_baked = VolSurfs.render_baked
+    _shade_baked = VolSurfs._shade_baked
+    render_baked_camera = VolSurfs.render_baked_camera
 
     def render_rays(self, rays_o, rays_d, chunk=1 << 20):
         return self.render_baked(rays_o, rays_d, chunk=chunk)
