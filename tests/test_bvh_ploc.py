@@ -1,18 +1,15 @@
 """A2 on the GPU, SAH quality: the PLOC builder (csrc/bvh_ploc.hip, RayTracer(builder="ploc")).
 
 The traversal's closest hit is the minimum over (t, original face id) and the boxes only prune, so the PLOC tree is
-pinned against the brute-force oracle and against the host tree with no tolerances, like the LBVH
-(tests/test_bvh_device.py, whose helpers this file reuses).  Its SAH cost is held against both other trees."""
+pinned against the brute-force oracle and against the host tree with no tolerances, like the LBVH: by the cases of
+tests/bvh_builder_cases.py, which take the builder as an argument.  What holds for PLOC alone is here: its entry point's
+argument checks, the radius, and its SAH cost, held against both other trees."""
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import raytrace as oracle_rt
-from tests.test_bvh_device import _assert_same_hits, _check_structure, _face_ids, _perturbed_spheres
-from tests.test_raytrace import _chain_mesh, _rays
-from volsurfs_amd.mesh import icosphere
+from tests import bvh_builder_cases as cases
 
 
 # ---------------------------------------------------------------------------------------------- no GPU needed
@@ -36,13 +33,7 @@ def test_ploc_entry_point_rejects_bad_arguments_before_touching_the_device():
 
 
 def test_ploc_builder_needs_the_meshes_on_the_gpu():
-    from volsurfs_amd import _lib
-    from volsurfs_amd.mesh import TensorMesh
-    from volsurfs_amd.raytrace import RayTracer
-    assert "ploc" in RayTracer.BUILDERS
-    v, f = icosphere(1, 0.3)
-    with pytest.raises(_lib.VolsurfsHipError, match='builder="ploc" needs the meshes on the GPU'):
-        RayTracer([TensorMesh(v, f, device="cpu")], builder="ploc")
+    cases.builder_needs_the_meshes_on_the_gpu("ploc")
 
 
 # ---------------------------------------------------------------------------------------------- GPU
@@ -51,81 +42,18 @@ def test_ploc_builder_needs_the_meshes_on_the_gpu():
 @pytest.mark.parametrize("fmt", ["q16", "f32"])
 @pytest.mark.parametrize("subdiv,n", [(0, 1000), (2, 4096), (4, 4096), (5, 2000)])
 def test_ploc_tree_bit_exact_vs_bruteforce(subdiv, n, fmt):
-    from volsurfs_amd.mesh import TensorMesh
-    from volsurfs_amd.raytrace import RayTracer
-    meshes_np = _perturbed_spheres(subdiv)
-    rt = RayTracer([TensorMesh(v, f) for v, f in meshes_np], node_format=fmt, builder="ploc")
-    assert rt.builder == "ploc"
-    o, d = _rays(n, subdiv)
-    oc, dc = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
-    hit_t, hit_slot, hit_uv = rt.trace_all(oc, dc)
-    face_id = _face_ids(rt, hit_slot).cpu().numpy()
-    for k, (v, f) in enumerate(meshes_np):
-        ref = oracle_rt.trace_bruteforce(v, f, o, d)
-        assert (ref["tri"] >= 0).sum() > n // 20
-        assert np.array_equal(face_id[k], ref["tri"])
-        assert np.array_equal(hit_t[k].cpu().numpy(), ref["t"])
-        m = ref["tri"] >= 0
-        assert np.array_equal(hit_uv[k].cpu().numpy()[m], ref["uv"][m])
-        res = rt.trace(oc, dc, mesh_id=k)
-        att = oracle_rt.hit_attributes(v, f, o, d, ref)
-        assert res["any_hit"] == att["any_hit"]
-        assert np.array_equal(res["is_hit"].cpu().numpy(), att["is_hit"])
-        assert np.array_equal(res["triangles_id"].cpu().numpy(), att["triangles_id"])
-        np.testing.assert_allclose(res["positions"].cpu().numpy(), att["positions"], atol=1e-6)
-        np.testing.assert_allclose(res["normals"].cpu().numpy(), att["normals"], atol=1e-6)
-        np.testing.assert_allclose(res["barycentric"].cpu().numpy(), att["barycentric"], atol=1e-6)
+    cases.tree_bit_exact_vs_bruteforce("ploc", subdiv, n, fmt)
 
 
 @pytest.mark.gpu
 def test_ploc_tree_equals_host_tree_on_every_traversal_form():
-    from volsurfs_amd.camera import pinhole_rays
-    from volsurfs_amd.mesh import nested_shells
-    from volsurfs_amd.raytrace import RayTracer
-    meshes = nested_shells(K=5, subdiv=6)
-    host, dev = RayTracer(meshes), RayTracer(meshes, builder="ploc")
-    assert dev.builder == "ploc" and dev.mesh_nr_tris == host.mesh_nr_tris and dev.mesh_tri_offset == host.mesh_tri_offset
-    o, d = pinhole_rays(800, 800, focal=1111.1, cam_pos=(0, 0, -1.5))
-    ref = [x.clone() for x in host.trace_all(o, d)]
-    assert (ref[1] >= 0).sum().item() > 500000
-    for _ in range(2):                                   # cost feedback: no order yet / measured on the same rays
-        _assert_same_hits(dev.trace_all(o, d), ref, dev, host)
-    dev.cost_feedback = False
-    _assert_same_hits(dev.trace_all(o, d), ref, dev, host)
-    dev.cost_feedback = True
-    # narrow waves, and the cooperative finish of a small launch (a slice of the frame through its centre)
-    n = 9000
-    os_, ds_ = o[320000:320000 + n].contiguous(), d[320000:320000 + n].contiguous()
-    ref_s = [x.clone() for x in host.trace_all(os_, ds_)]
-    dev.NARROW_BELOW, dev.NARROW_RPW = 1 << 30, 16
-    assert dev.narrow_rays_per_wave(n, 5) == 16
-    _assert_same_hits(dev.trace_all(os_, ds_), ref_s, dev, host)
-    dev.NARROW_BELOW = 0
-    try:
-        RayTracer.coop_config(1, 64, 8192)             # every small launch finishes cooperatively at once
-        for _ in range(2):
-            _assert_same_hits(dev.trace_all(os_, ds_), ref_s, dev, host)
-    finally:
-        RayTracer.coop_config()
-    assert (ref_s[1] >= 0).sum().item() > n
-
-
-def _shell_depth(mesh, leaf_size):
-    from volsurfs_amd.raytrace import RayTracer
-    return RayTracer([mesh], leaf_size=leaf_size, builder="ploc").max_depth
+    cases.tree_equals_host_tree_on_every_traversal_form("ploc")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("leaf_size", [1, 4, 8])
 def test_ploc_tree_structure(leaf_size):
-    from volsurfs_amd.mesh import TensorMesh
-    from volsurfs_amd.raytrace import RayTracer
-    meshes_np = _perturbed_spheres(4, k=2, seed=7) + [icosphere(2, 0.5)]
-    rt = RayTracer([TensorMesh(v, f) for v, f in meshes_np], leaf_size=leaf_size, builder="ploc")
-    # (the tracer keeps the deepest shell's depth: each shell's own comes from a build of that shell alone)
-    rt._dev_depth = [_shell_depth(TensorMesh(v, f), leaf_size) for v, f in meshes_np]
-    assert rt.max_depth == max(rt._dev_depth)
-    _check_structure(rt, meshes_np, leaf_size)
+    cases.tree_structure("ploc", leaf_size)
 
 
 @pytest.mark.gpu
@@ -134,12 +62,7 @@ def test_ploc_build_is_deterministic(radius):
     from volsurfs_amd.mesh import nested_shells
     from volsurfs_amd.raytrace import RayTracer
     meshes = nested_shells(K=3, subdiv=5, noise=0.05)
-    a = RayTracer(meshes, builder="ploc", ploc_radius=radius)
-    b = RayTracer(meshes, builder="ploc", ploc_radius=radius)
-    assert a._layout == b._layout and a.max_depth == b.max_depth
-    assert torch.equal(a.nodes.view(torch.int32), b.nodes.view(torch.int32))
-    assert torch.equal(a.qnodes, b.qnodes) and torch.equal(a.tris.view(torch.int32), b.tris.view(torch.int32))
-    assert list(a._frames) == list(b._frames)
+    a = cases.assert_deterministic(meshes, builder="ploc", ploc_radius=radius)
     # and it is not the LBVH (at radius 1 only neighbours merge: the leaf order is the Morton order, the tree is not)
     lbvh = RayTracer(meshes, builder="device")
     assert not (a.nodes.shape == lbvh.nodes.shape and torch.equal(a.nodes.view(torch.int32), lbvh.nodes.view(torch.int32)))
@@ -148,78 +71,7 @@ def test_ploc_build_is_deterministic(radius):
 @pytest.mark.gpu
 @pytest.mark.parametrize("fmt", ["q16", "f32"])
 def test_ploc_tree_edge_cases(fmt):
-    from volsurfs_amd import _lib
-    from volsurfs_amd.mesh import TensorMesh
-    from volsurfs_amd.raytrace import RayTracer
-    # one face (the wrapped root), two faces
-    one = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.array([[0, 1, 2]], np.int32))
-    two = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0.5]], np.float32), np.array([[0, 1, 2], [1, 3, 2]], np.int32))
-    for leaf_size in (1, 4):
-        meshes_np = [one, two]
-        rt = RayTracer([TensorMesh(v, f) for v, f in meshes_np], leaf_size=leaf_size, node_format=fmt, builder="ploc")
-        rt._dev_depth = [0, 0 if leaf_size >= 2 else 1]
-        _check_structure(rt, meshes_np, leaf_size)
-        g = np.random.default_rng(3)
-        o = np.concatenate([g.random((500, 2)) * 1.4 - 0.2, -np.ones((500, 1))], 1).astype(np.float32)
-        d = np.tile(np.array([[0, 0, 1]], np.float32), (500, 1))
-        t, s, uv = rt.trace_all(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
-        fid = _face_ids(rt, s).cpu().numpy()
-        for k, (v, f) in enumerate(meshes_np):
-            ref = oracle_rt.trace_bruteforce(v, f, o, d)
-            assert (ref["tri"] >= 0).sum() > 100
-            assert np.array_equal(fid[k], ref["tri"]) and np.array_equal(t[k].cpu().numpy(), ref["t"])
-    # every triangle with the same centroid: all Morton codes equal, the clustering goes by area alone
-    g = np.random.default_rng(4)
-    nt = 3000
-    a = g.standard_normal((nt, 3)).astype(np.float32) * 0.3
-    q = a * g.uniform(-1, 1, (nt, 3)).astype(np.float32)          # |q| <= |a| per axis: box centre 0 for every face
-    v = np.concatenate([a, -a, q]).astype(np.float32)
-    f = np.stack([np.arange(nt), np.arange(nt) + nt, np.arange(nt) + 2 * nt], 1).astype(np.int32)
-    rt = RayTracer([TensorMesh(v, f)], node_format=fmt, builder="ploc")
-    rt._dev_depth = [rt.max_depth]
-    _check_structure(rt, [(v, f)], 4)
-    o, d = _rays(2000, 5)
-    t, s, uv = rt.trace_all(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
-    ref = oracle_rt.trace_bruteforce(v, f, o, d)
-    assert (ref["tri"] >= 0).sum() > 200
-    assert np.array_equal(_face_ids(rt, s)[0].cpu().numpy(), ref["tri"]) and np.array_equal(t[0].cpu().numpy(), ref["t"])
-    # identical boxes: every area ties, and the tie order pairs neighbours (a balanced tree, not a chain)
-    v = np.tile(np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), (1000, 1))
-    f = np.arange(3000, dtype=np.int32).reshape(1000, 3)
-    rt = RayTracer([TensorMesh(v, f)], node_format=fmt, builder="ploc")
-    rt._dev_depth = [rt.max_depth]
-    _check_structure(rt, [(v, f)], 4)
-    assert rt.max_depth <= 10                                   # 1000 triangles paired level by level
-    # the chain mesh (deep for the host's SAH): PLOC builds it below the traversal stack, or refuses it naming "host"
-    v, f = _chain_mesh()
-    v2, f2 = icosphere(3, 0.4)
-    try:
-        rt = RayTracer([TensorMesh(v, f), TensorMesh(v2, f2)], node_format=fmt, builder="ploc")
-    except _lib.VolsurfsHipError as e:
-        assert 'builder="host"' in str(e) and ">= 48" in str(e)
-        print("chain mesh:", e)
-        return
-    print("chain mesh: depth", rt.max_depth)
-    assert rt.max_depth < 48
-    g = np.random.default_rng(1)
-    n = 6000
-    i = g.integers(0, 20, n)
-    tgt = np.stack([3.0 ** -i, np.zeros(n), np.zeros(n)], 1) + (0.2 * 3.0 ** -i)[:, None] * g.standard_normal((n, 3))
-    o = np.tile(np.array([[0.2, 0.05, -2.0]]), (n, 1)) + 0.01 * g.standard_normal((n, 3))
-    d = tgt - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    o, d = o.astype(np.float32), d.astype(np.float32)
-    hit_t, hit_slot, hit_uv = rt.trace_all(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
-    face_id = _face_ids(rt, hit_slot).cpu().numpy()
-    for k, (vv, ff) in enumerate([(v, f), (v2, f2)]):
-        ref = oracle_rt.trace_bruteforce(vv, ff, o, d)
-        # the well-conditioned hits of tests/test_raytrace.py::test_trace_deep_bvh_takes_the_48_entry_stack_bit_exact
-        ok = np.ones(n, bool) if k else ((ref["tri"] // 64 < 12) & (face_id[k] // 64 < 12))
-        assert ok.mean() > 0.5
-        assert np.array_equal(face_id[k][ok], ref["tri"][ok])
-        assert np.array_equal(hit_t[k].cpu().numpy()[ok], ref["t"][ok])
-        m = (ref["tri"] >= 0) & ok
-        assert np.array_equal(hit_uv[k].cpu().numpy()[m], ref["uv"][m])
+    cases.tree_edge_cases("ploc", fmt)
 
 
 # The bound of every shell's PLOC / host SAH ratio below.  Measured on MI355X at the default radius 8:
@@ -247,76 +99,14 @@ def test_ploc_tree_sah_cost_beats_the_lbvh_and_nears_the_host_tree(stress):
 @pytest.mark.gpu
 @pytest.mark.parametrize("fmt", ["q16", "f32"])
 def test_ploc_refit_after_the_vertices_moved_is_bit_exact_and_keeps_the_slots(fmt):
-    from volsurfs_amd.mesh import TensorMesh
-    from volsurfs_amd.raytrace import RayTracer
-    g = np.random.default_rng(5)
-    base = [icosphere(4, 0.3 + 0.03 * k) for k in range(3)]
-    rt = RayTracer([TensorMesh(v, f) for v, f in base], node_format=fmt, builder="ploc")
-    slots_before = rt.slot_face_id.clone()
-    o, d = _rays(5000, 9)
-    oc, dc = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
-    rt.trace_all(oc, dc)                                    # leaves a cost-feedback state behind
-    shear = np.array([[1.0, 0.15, 0.0], [0.0, 1.0, 0.1], [0.05, 0.0, 1.0]], np.float32)
-    moved = [(((v * (1 + 0.06 * g.standard_normal((v.shape[0], 1)))) @ shear).astype(np.float32), f) for v, f in base]
-    rt.refit([TensorMesh(v, f) for v, f in moved])
-    assert rt._fb is None
-    assert torch.equal(rt.slot_face_id, slots_before)
-    fresh = RayTracer([TensorMesh(v, f) for v, f in moved], node_format=fmt, builder="ploc")
-    for _ in range(2):
-        hit_t, hit_slot, hit_uv = rt.trace_all(oc, dc)
-    ft, fs, fu = fresh.trace_all(oc, dc)
-    face_id = _face_ids(rt, hit_slot).cpu().numpy()
-    assert np.array_equal(face_id, _face_ids(fresh, fs).cpu().numpy()) and torch.equal(hit_t, ft)
-    assert torch.equal(hit_uv, fu)
-    for k, (v, f) in enumerate(moved):
-        ref = oracle_rt.trace_bruteforce(v, f, o, d)
-        assert (ref["tri"] >= 0).sum() > 250
-        assert np.array_equal(face_id[k], ref["tri"])
-        assert np.array_equal(hit_t[k].cpu().numpy(), ref["t"])
-        m = ref["tri"] >= 0
-        assert np.array_equal(hit_uv[k].cpu().numpy()[m], ref["uv"][m])
-    rt._dev_depth = [_shell_depth(TensorMesh(v, f), 4) for v, f in base]
-    _check_structure(rt, moved, 4)
-    with pytest.raises(Exception):
-        rt.refit([TensorMesh(v[:-1], f) for v, f in moved])          # another vertex count: refused
+    cases.refit_after_the_vertices_moved_is_bit_exact_and_keeps_the_slots("ploc", fmt)
 
 
 @pytest.mark.gpu
 def test_volsurfs_with_the_ploc_tree_renders_the_host_trees_pixels():
-    from volsurfs_amd.camera import pinhole_rays
-    from volsurfs_amd.mesh import nested_shells
-    from volsurfs_amd.methods import VolSurfs
-    o, d = pinhole_rays(64, 64, focal=110.0)
-    gt = torch.rand(o.shape[0], 3, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    out = []
-    for builder in ("host", "ploc"):
-        m = VolSurfs(nested_shells(K=2, subdiv=3), max_rays=4096, textures_res=(256, 128, 64, 32), bvh_builder=builder)
-        assert m.raytracer.builder == builder
-        g = torch.Generator().manual_seed(0)
-        with torch.no_grad():
-            m.bank.tables.copy_((torch.rand(m.bank.tables.shape, generator=g) * 2 - 1).cuda())
-        m.bank.refresh_half_params()
-        m.grad_scale = float(o.shape[0])
-        rgb = m.render_rays(o, d)["renders"]["ray_traced"]["rgb"]
-        (rgb.float() - gt).abs().mean().backward()
-        out.append((rgb.detach().clone(), m.bank.tables.grad.clone(), m.bank.weights.grad.clone()))
-    (rgb_h, gt_h, gw_h), (rgb_p, gt_p, gw_p) = out
-    assert torch.equal(rgb_h, rgb_p)
-    # the f16 gradient chain accumulates in triangle-slot order, which differs between the trees: the LBVH test's bound
-    for name, a, b in (("tables", gt_p, gt_h), ("weights", gw_p, gw_h)):
-        assert b.abs().max() > 0
-        rel = float((a - b).abs().max() / b.abs().max())
-        cos = float(torch.nn.functional.cosine_similarity(a.flatten(), b.flatten(), dim=0))
-        print(f"{name}: max error {rel:.2e} of the largest entry, cos {cos:.7f}")
-        assert rel <= 5e-3 and cos > 0.99999, (name, rel, cos)
+    cases.volsurfs_with_the_tree_renders_the_host_trees_pixels("ploc")
 
 
 @pytest.mark.gpu
 def test_pipeline_step_with_the_ploc_tree_equals_the_host_trees():
-    from volsurfs_amd.pipeline import KShellPipeline
-    res = []
-    for builder in ("host", "ploc"):
-        p = KShellPipeline.synthetic(K=2, subdiv=2, res=64, bvh_builder=builder)
-        assert p.tracer.builder == builder
-        res.append(p.step().detach().clone())
-    assert torch.equal(res[0], res[1])
+    cases.pipeline_step_with_the_tree_equals_the_host_trees("ploc")

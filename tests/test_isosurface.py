@@ -350,7 +350,7 @@ def test_empty_and_invalid_inputs():
 
 @pytest.mark.gpu
 def test_end_to_end_files_raytracer_and_volsurfs(tmp_path):
-    from tests.test_bvh_device import _assert_same_hits
+    from tests.bvh_builder_cases import assert_same_hits as _assert_same_hits
     from volsurfs_amd.camera import pinhole_rays
     from volsurfs_amd.mesh import load_meshes_indexed_from_path
     from volsurfs_amd.methods import VolSurfs

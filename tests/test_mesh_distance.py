@@ -231,6 +231,46 @@ def test_equals_brute_force(builder, leaf_size):
     assert st["tri_tests"] < st["queries"] * (80 + 320 + 1280) / 3          # the walk prunes
 
 
+def _same_bits(a, b):
+    """torch.equal on the bits: a float result with a NaN (the NaN query's) equals itself, and -0 is not +0."""
+    if a.is_floating_point():
+        a, b = a.view(torch.int32), b.view(torch.int32)
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a, b)
+
+
+@gpu
+@pytest.mark.parametrize("builder", ["device", "ploc"])
+def test_single_shell_queries_equal_their_row_of_the_all_shell_query(builder):
+    """closest, signed_distance and winding_number of shell k are row k of their *_all form, every key, bit for bit:
+    257 queries (four full waves and one lane of a fifth, where a [K, N] / [N] mix-up shows), one with a NaN."""
+    from volsurfs_amd.mesh import icosphere
+    from volsurfs_amd.raytrace import RayTracer
+    K, N = 3, 257
+    tracer = RayTracer([_mesh(*icosphere(2, 0.30 + 0.04 * k)) for k in range(K)], builder=builder)
+    assert tracer.mesh_nr_tris == [320] * K
+    pts = np.random.default_rng(29).uniform(-0.6, 0.6, (N, 3)).astype(np.float32)
+    pts[100, 1] = np.nan
+    q = torch.from_numpy(pts).cuda()
+    every = tracer.closest_all(q)
+    assert every["dist"].shape == (K, N) and every["bary"].shape == (K, N, 2) and bool((every["slot"][:, 100] == -1).all())
+    signed = {s: tracer.signed_distance_all(q, sign=s) for s in ("pseudonormal", "winding")}
+    wind = {b: tracer.winding_number_all(q, beta=b) for b in (2.0, math.inf)}
+    assert wind[2.0].shape == (K, N) and bool(wind[2.0][:, 100].isnan().all())
+    for k in range(K):
+        pairs = [("closest", tracer.closest(q, k), every)]
+        pairs += [(s, tracer.signed_distance(q, k, sign=s), signed[s]) for s in signed]
+        for what, one, rows in pairs:
+            assert sorted(one) == sorted(rows) == ["bary", "dist", "face", "slot"]
+            for key in rows:
+                assert _same_bits(one[key], rows[key][k]), (what, k, key)
+        for b in wind:
+            assert _same_bits(tracer.winding_number(q, k, beta=b), wind[b][k]), (b, k)
+    for bad in (-1, K):
+        for call in (tracer.closest, tracer.signed_distance, tracer.winding_number):
+            with pytest.raises(_lib.VolsurfsHipError):
+                call(q, bad)
+
+
 @gpu
 def test_non_convex_shells_equal_brute_force():
     """Lobed shells; half of the queries at radii between the lobes' troughs and crests, i.e. inside the concavities."""

@@ -366,6 +366,23 @@ def test_shells_built_side_by_side_equal_the_sequential_build(monkeypatch):
         assert torch.equal(a.slot_face_id, b.slot_face_id)
 
 
+def test_a_host_build_that_fails_part_way_destroys_the_trees_already_built(monkeypatch):
+    """Three shells, the second with a face index past its vertices (vsa_bvh_build refuses it): the constructor raises
+    and the trees of the other two are destroyed, as the device builders do.  Runs without a GPU."""
+    from volsurfs_amd import _lib
+    from volsurfs_amd.mesh import TensorMesh, icosphere
+    from volsurfs_amd.raytrace import RayTracer
+    v, f = icosphere(1, 0.3)
+    bad = f.copy()
+    bad[5, 1] = v.shape[0]
+    L = _lib.lib()
+    destroy, destroyed = L.vsa_bvh_destroy, []
+    monkeypatch.setattr(L, "vsa_bvh_destroy", lambda h: destroyed.append(h.value) or destroy(h))
+    with pytest.raises(_lib.VolsurfsHipError, match="vsa_bvh_build failed"):
+        RayTracer([TensorMesh(v, x, device="cpu") for x in (f, bad, f)])
+    assert len(destroyed) == 2 and all(destroyed) and destroyed[0] != destroyed[1]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("rays_per_wave", [32, 16, 5])
 def test_narrow_waves_return_the_same_hits_bit_for_bit(rays_per_wave):

@@ -447,7 +447,7 @@ def _lobed_fn(pts):
 
 @pytest.mark.gpu
 def test_end_to_end_files_raytracer_and_volsurfs(tmp_path):
-    from tests.test_bvh_device import _assert_same_hits
+    from tests.bvh_builder_cases import assert_same_hits as _assert_same_hits
     from tests.test_isosurface import _lobed_fn as lobed
     from volsurfs_amd import isosurface as iso
     from volsurfs_amd.camera import pinhole_rays

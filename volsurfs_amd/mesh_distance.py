@@ -226,7 +226,7 @@ def shell_clearance(meshes, n=1_000_000, seed=0):
     (shell k -> k + 1), in (k + 1 -> k)}.  A `min` near 0 means the two shells touch or cross.  `meshes`: a list of
     TensorMeshes (one tracer is built for all of them) or a RayTracer."""
     n = _check_n(n, "shell_clearance")
-    tracer = meshes if isinstance(meshes, RayTracer) else RayTracer(list(meshes), builder="device")
+    tracer = RayTracer.over(meshes)
     handles = [_resolve((tracer, k), "shell_clearance") for k in range(tracer.nr_meshes)]
     return [{"pair": (k, k + 1), "out": _surface_distance(handles[k], handles[k + 1], n, seed, []),
              "in": _surface_distance(handles[k + 1], handles[k], n, seed, [])} for k in range(tracer.nr_meshes - 1)]

@@ -151,16 +151,12 @@ def crossing_stats(a, b):
     return _stats(ca, cb, total)
 
 
-def _tracer(meshes):
-    return meshes if isinstance(meshes, RayTracer) else RayTracer(list(meshes), builder="device")
-
-
 @torch.no_grad()
 def shell_crossings(meshes):
     """For each consecutive pair of shells (k, k + 1): {pair, pairs = the crossing face pairs, faces_inner = the faces
     of shell k that cross shell k + 1, faces_outer = the reverse}, from the count pass.  `meshes`: a list of
     TensorMeshes (one tracer is built for all of them) or a RayTracer."""
-    tracer = _tracer(meshes)
+    tracer = RayTracer.over(meshes)
     out = []
     for k in range(tracer.nr_meshes - 1):
         pairs, inner, outer = crossing_stats((tracer, k), (tracer, k + 1))
@@ -182,7 +178,7 @@ def shells_nested(meshes, sign="pseudonormal"):
     the self-crossings of either shell (`self_crossings`); for a shell k + 1 that is not closed the sign is whatever
     `sign` gives and "inside" means no more than that."""
     from .mesh_clean import cluster_connected_triangles
-    tracer = _tracer(meshes)
+    tracer = RayTracer.over(meshes)
     tracer.sign_rule(sign)
     out = []
     for k in range(tracer.nr_meshes - 1):

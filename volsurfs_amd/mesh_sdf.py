@@ -194,7 +194,7 @@ def shell_nesting(meshes, n=1_000_000, seed=0, sign="pseudonormal", beta=2.0):
     them) or a RayTracer.  The signed companion of `mesh_distance.shell_clearance`.  sign="winding": inside means a
     winding number above 1/2, for shells that are not closed."""
     n = _check_n(n, "shell_nesting")
-    tracer = meshes if isinstance(meshes, RayTracer) else RayTracer(list(meshes), builder="device")
+    tracer = RayTracer.over(meshes)
     out = []
     for k in range(tracer.nr_meshes - 1):
         points, _, _ = sample_surface(_resolve((tracer, k), "shell_nesting"), n, seed)

@@ -95,12 +95,9 @@ def rasterize_shells(meshes, camera, supersample=1, t_min=0.0, out=None, want_di
     """`RayTracer.rasterize` from a list of K cuda TensorMeshes.  `tracer`: a RayTracer of these meshes (default: one
     is built on the device)."""
     meshes = list(meshes)
-    if tracer is None:
-        if any(m.vertices.device.type != "cuda" for m in meshes):
-            raise _lib.VolsurfsHipError("rasterize_shells needs the meshes on the GPU")
-        tracer = RayTracer(meshes, builder="device")
-    elif tracer.nr_meshes != len(meshes):
-        raise ValueError(f"a tracer of {tracer.nr_meshes} shells for {len(meshes)} meshes")
+    if tracer is None and any(m.vertices.device.type != "cuda" for m in meshes):
+        raise _lib.VolsurfsHipError("rasterize_shells needs the meshes on the GPU")
+    tracer = RayTracer.over(meshes if tracer is None else tracer, len(meshes))
     return tracer_rasterize(tracer, camera, supersample, t_min, out, want_dirs)
 
 

@@ -2,8 +2,8 @@
 "Secondary boundaries").
 
 Mirrors `raytracelib.RayTracer(list[TensorMesh])` / `.trace(rays_o, rays_d,
-mesh_id=int) -> dict` as called at
-/root/reference/volsurfs_py/methods/volsurfs.py:128 and :476-501, and adds
+mesh_id=int) -> dict` as called at the reference's
+volsurfs_py/methods/volsurfs.py:128 and :476-501, and adds
 `trace_all` (all K shells in one launch, no host sync) used by the fused path.
 """
 import ctypes
@@ -21,6 +21,159 @@ def _rays(rays_o, rays_d):
     return N, _lib.check_f32(rays_o.contiguous(), N, 3), _lib.check_f32(rays_d.contiguous(), N, 3)
 
 
+def _sizes(fn, h):
+    """(status, (nr_nodes, nr_tris, depth)) of one tree handle, from vsa_bvh_sizes / vsa_bvh_dev_sizes."""
+    nn, nt, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = fn(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
+    return rc, (nn.value, nt.value, md.value)
+
+
+class _HostTrees:
+    """The shells' binned-SAH trees, built on the CPU from host copies of the meshes (csrc/bvh_build.cpp)."""
+
+    def __init__(self):
+        self.handles = []
+
+    def build(self, meshes, leaf_size, radius):
+        """Builds every shell's tree; returns their (nr_nodes, nr_tris, depth) in mesh order."""
+        L = _lib.lib()
+        arrays = [(np.ascontiguousarray(m.vertices.detach().cpu().numpy(), np.float32),
+                   np.ascontiguousarray(m.faces.detach().cpu().numpy(), np.int32)) for m in meshes]
+        made = self.handles = []        # every tree as it is made: what destroy frees if the build fails part-way
+
+        def build_one(vf):
+            v, f = vf
+            h = ctypes.c_void_p()
+            rc = L.vsa_bvh_build(v.ctypes.data_as(ctypes.c_void_p), f.ctypes.data_as(ctypes.c_void_p),
+                                 ctypes.c_int(v.shape[0]), ctypes.c_int(f.shape[0]),
+                                 ctypes.c_int(leaf_size), ctypes.byref(h))
+            if h.value:
+                made.append(h)
+            return rc, h
+        # The shells' trees are independent builds, one thread each: built side by side on a thread pool (ctypes drops
+        # the GIL inside the call), 7 x 1.31 M triangles (configs[4]) take the time of one shell (2.1 s) instead of
+        # 15 s.  Handles are collected in mesh order: the layout is the sequential build's.
+        if len(arrays) > 1 and sum(f.shape[0] for _, f in arrays) >= 100000 and os.environ.get("VSA_BVH_THREADS", "1") != "0":
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=min(len(arrays), os.cpu_count() or 1)) as pool:
+                built = list(pool.map(build_one, arrays))
+        else:
+            built = [build_one(vf) for vf in arrays]
+        for rc, _ in built:
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_build failed with status {rc}")
+        self.handles = [h for _, h in built]                        # (in mesh order)
+        return [_sizes(L.vsa_bvh_sizes, h)[1] for h in self.handles]
+
+    def export(self, layout, nodes, qnodes, tris, frames):
+        """Both node formats and the triangles into the concatenated arrays (staged through numpy: they may live on
+        the GPU), the K quantisation frames into the host array `frames`."""
+        L = _lib.lib()
+        h_nodes = np.empty(tuple(nodes.shape), np.float32)
+        h_qnodes = np.empty(tuple(qnodes.shape), np.uint32)
+        h_tris = np.empty(tuple(tris.shape), np.float32)
+        for i, (h, (nb, nn, tb, nt)) in enumerate(zip(self.handles, layout)):
+            rc = L.vsa_bvh_export(h, h_nodes[nb:nb + nn].ctypes.data_as(ctypes.c_void_p),
+                                  h_tris[tb:tb + nt].ctypes.data_as(ctypes.c_void_p), ctypes.c_int(nb),
+                                  ctypes.c_int(tb))
+            rc2 = L.vsa_bvh_export_q(h, h_qnodes[nb:nb + nn].ctypes.data_as(ctypes.c_void_p),
+                                     h_tris[tb:tb + nt].ctypes.data_as(ctypes.c_void_p), ctypes.c_int(nb),
+                                     ctypes.c_int(tb), ctypes.c_void_p(ctypes.addressof(frames) + 24 * i))
+            if rc != 0 or rc2 != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_export failed with status {rc} / {rc2}")
+        nodes.copy_(torch.from_numpy(h_nodes))
+        qnodes.copy_(torch.from_numpy(h_qnodes.view(np.int32)))
+        tris.copy_(torch.from_numpy(h_tris))
+
+    def refit(self, meshes):
+        L = _lib.lib()
+        for h, m in zip(self.handles, meshes):
+            v = np.ascontiguousarray(m.vertices.detach().cpu().numpy(), np.float32)
+            rc = L.vsa_bvh_refit(h, v.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(v.shape[0]))
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_refit failed with status {rc} (vertex count changed?)")
+
+    def destroy(self):
+        for h in self.handles:
+            _lib.lib().vsa_bvh_destroy(h)
+        self.handles = []
+
+
+class _DeviceTrees:
+    """The shells' trees built on the GPU from the meshes' device tensors, no host copy: the Karras LBVH
+    (builder="device", csrc/bvh_device.hip) or PLOC clustering (builder="ploc", csrc/bvh_ploc.hip)."""
+
+    def __init__(self, builder):
+        self.builder = builder
+        self.handles = []
+
+    def build(self, meshes, leaf_size, radius):
+        """Issues every shell's build (vsa_bvh_dev_build, or vsa_bvh_dev_build_ploc at `radius`) on the current stream,
+        then reads the sizes: one synchronisation per shell.  Returns their (nr_nodes, nr_tris, depth) in mesh order."""
+        L = _lib.lib()
+        dev = self.device = meshes[0].vertices.device
+        if dev.type != "cuda":
+            raise _lib.VolsurfsHipError(f'builder="{self.builder}" needs the meshes on the GPU')
+        st = _lib.stream_ptr()
+        name, rule = ("vsa_bvh_dev_build_ploc", (radius,)) if self.builder == "ploc" else ("vsa_bvh_dev_build", ())
+        inputs = []             # (alive until the sizes calls have synchronised the builds that read them)
+        for m in meshes:
+            v = m.vertices.detach().to(dev, torch.float32).contiguous()
+            f = m.faces.detach().to(dev, torch.int32).contiguous()
+            inputs.append((v, f))
+            h = ctypes.c_void_p()
+            rc = getattr(L, name)(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, *rule, st,
+                                  ctypes.byref(h))
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"{name} failed with status {rc}")
+            self.handles.append(h)
+        sizes = []
+        for h in self.handles:
+            rc, size = _sizes(L.vsa_bvh_dev_sizes, h)
+            if rc == -2 and size[2] >= 48:
+                raise _lib.VolsurfsHipError(
+                    f'builder="{self.builder}": tree depth {size[2]} >= 48, deeper than the traversal stack; '
+                    'build this mesh with builder="host"')
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_dev_sizes failed with status {rc}")
+            sizes.append(size)
+        return sizes
+
+    def export(self, layout, nodes, qnodes, tris, frames):
+        """Both node formats and the triangles written in place into the concatenated device arrays, the K
+        quantisation frames into the host array `frames`."""
+        L = _lib.lib()
+        st = _lib.stream_ptr()
+        for i, (h, (nb, nn, tb, nt)) in enumerate(zip(self.handles, layout)):
+            rc = L.vsa_bvh_dev_export(h, nodes[nb].data_ptr(), qnodes[nb].data_ptr(), tris[tb].data_ptr(), nb, tb,
+                                      ctypes.addressof(frames) + 24 * i, st)
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_dev_export failed with status {rc}")
+
+    def refit(self, meshes):
+        L = _lib.lib()
+        st = _lib.stream_ptr()
+        for h, m in zip(self.handles, meshes):
+            v = m.vertices.detach().to(self.device, torch.float32).contiguous()
+            rc = L.vsa_bvh_dev_refit(h, v.data_ptr(), v.shape[0], st)
+            if rc != 0:
+                raise _lib.VolsurfsHipError(f"vsa_bvh_dev_refit failed with status {rc} (vertex count changed?)")
+
+    def destroy(self):
+        for h in self.handles:
+            _lib.lib().vsa_bvh_dev_destroy(h)
+        self.handles = []
+
+
+def _trees(builder):
+    """The one place that knows which builder is which."""
+    if builder == "host":
+        return _HostTrees()
+    if builder in RayTracer.DEVICE_BUILDERS:
+        return _DeviceTrees(builder)
+    raise _lib.VolsurfsHipError(f"unknown builder {builder!r} (expected one of {RayTracer.BUILDERS})")
+
+
 class RayTracer:
     BUILDERS = ("host", "device", "ploc")
     DEVICE_BUILDERS = ("device", "ploc")
@@ -36,215 +189,85 @@ class RayTracer:
         node_format: "q16" (default; binary 32-byte quantised nodes, vsa_trace_q / vsa_trace_q_fb) or
         "f32" (binary 64-byte fp32 nodes, vsa_trace); also selected by VSA_TRACE_NODES.  Both give
         identical hits; the quantised format assumes ray origins within ~60 mesh extents of the mesh
-        (include/volsurfs_hip.h).  (The 4-wide nodes, the budgeted three-pass walk and the persistent-lane
-        kernel of round 3 — bit-exact, measured slower: profiles/NOTEBOOK.md A9.4 — left the library in round 5.)"""
-        if builder not in self.BUILDERS:
-            raise _lib.VolsurfsHipError(f"unknown builder {builder!r} (expected one of {self.BUILDERS})")
+        (include/volsurfs_hip.h)."""
+        self._trees = _trees(builder)               # (the builder's handles, kept for refit)
         self.builder = builder
         self.node_format = node_format or os.environ.get("VSA_TRACE_NODES", "q16")
         if self.node_format not in ("q16", "f32"):
             raise _lib.VolsurfsHipError(f"unknown node_format {self.node_format}")
         # q16 only: launch order from the previous call's measured cost (vsa_trace_q_fb; identical hits)
         self.cost_feedback = os.environ.get("VSA_TRACE_FEEDBACK", "1") != "0"
-        self._fb = None
-        self._meshes = list(tensor_meshes)          # (the pseudonormal tables of signed_distance* are built from them)
-        self._pn = None
-        self._wm = None                             # (the winding moments of winding_number* / sign="winding")
-        self._census = None
-        self.nr_meshes = len(tensor_meshes)
-        if not 1 <= self.nr_meshes <= 16:
+        self._meshes = list(tensor_meshes)
+        self._drop_geometry_state()
+        K = self.nr_meshes = len(tensor_meshes)
+        if not 1 <= K <= 16:
             raise _lib.VolsurfsHipError("RayTracer supports 1..16 meshes")
-        L = _lib.lib()
-        self._bvh, self._layout = [], []            # builder handles (kept for refit) and (node_base, nr_nodes, tri_base, nr_tris)
-        self.mesh_tri_offset, self.mesh_nr_tris = [], []
-        self.max_depth = 0
-        if builder in self.DEVICE_BUILDERS:
-            self._build_on_device(tensor_meshes, leaf_size, self.PLOC_RADIUS if ploc_radius is None else ploc_radius)
-            return
-        # The K shells' trees are independent host builds (binned SAH, csrc/bvh_build.cpp, one thread each): built side by
-        # side on a thread pool — ctypes drops the GIL inside the call — 7 x 1.31 M triangles (configs[4]) take the time of one
-        # shell (2.1 s) instead of 15 s.  Handles are collected in mesh order: the layout below is the sequential build's.
-        arrays = [(np.ascontiguousarray(m.vertices.detach().cpu().numpy(), np.float32),
-                   np.ascontiguousarray(m.faces.detach().cpu().numpy(), np.int32)) for m in tensor_meshes]
-
-        def build_one(vf):
-            v, f = vf
-            h = ctypes.c_void_p()
-            rc = L.vsa_bvh_build(v.ctypes.data_as(ctypes.c_void_p), f.ctypes.data_as(ctypes.c_void_p),
-                                 ctypes.c_int(v.shape[0]), ctypes.c_int(f.shape[0]),
-                                 ctypes.c_int(leaf_size), ctypes.byref(h))
-            return rc, h
-        if self.nr_meshes > 1 and sum(f.shape[0] for _, f in arrays) >= 100000 and os.environ.get("VSA_BVH_THREADS", "1") != "0":
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=min(self.nr_meshes, os.cpu_count() or 1)) as pool:
-                built = list(pool.map(build_one, arrays))
-        else:
-            built = [build_one(vf) for vf in arrays]
-        for rc, h in built:
-            if rc != 0:
-                raise _lib.VolsurfsHipError(f"vsa_bvh_build failed with status {rc}")
-        sizes = []
-        for _, h in built:
-            self._bvh.append(h)
-            nn, nt, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            L.vsa_bvh_sizes(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
-            sizes.append((nn.value, nt.value, md.value))
-        self._record_shells(sizes)
-        dev = tensor_meshes[0].vertices.device
-        self.device = dev
-        nodes, qnodes, tris, frames = self._export()
-        self.nodes = torch.from_numpy(nodes).to(dev)
-        self.qnodes = torch.from_numpy(qnodes.view(np.int32)).to(dev)
-        self._frames = (ctypes.c_float * (6 * self.nr_meshes))(*frames.tolist())
-        self.tris = torch.from_numpy(tris).to(dev)
+        try:
+            sizes = self._trees.build(self._meshes, leaf_size, self.PLOC_RADIUS if ploc_radius is None else ploc_radius)
+        except Exception:
+            self._trees.destroy()
+            raise
+        nr_nodes, nr_tris = self._record_shells(sizes)
+        dev = self.device = tensor_meshes[0].vertices.device
+        self.nodes = torch.empty(nr_nodes, 16, dtype=torch.float32, device=dev)
+        self.qnodes = torch.empty(nr_nodes, 8, dtype=torch.int32, device=dev)
+        self.tris = torch.empty(nr_tris, 12, dtype=torch.float32, device=dev)
+        self._frames = (ctypes.c_float * (6 * K))()         # the K quantisation frames (host)
+        self._trees.export(self._layout, self.nodes, self.qnodes, self.tris, self._frames)
         # original face id of every leaf-ordered triangle slot (for uv tables etc.)
-        self.slot_face_id = torch.from_numpy(tris[:, 3].copy().view(np.int32)).to(dev)
+        self.slot_face_id = self.tris[:, 3].contiguous().view(torch.int32)
 
     def _record_shells(self, sizes):
-        """The shells' (nr_nodes, nr_tris, depth), in mesh order, into the layout of the concatenated arrays: `_layout`,
-        `mesh_tri_offset`, `mesh_nr_tris`, `max_depth` and the roots.  Returns the totals (nr_nodes, nr_tris)."""
+        """The shells' (nr_nodes, nr_tris, depth), in mesh order, into the layout of the concatenated arrays: `_layout`
+        ((node_base, nr_nodes, tri_base, nr_tris) per shell), `mesh_tri_offset`, `mesh_nr_tris`, `max_depth` and the
+        roots.  Returns the totals (nr_nodes, nr_tris)."""
+        self._layout, self.max_depth = [], 0
         node_base = tri_base = 0
         for nn, nt, md in sizes:
             self._layout.append((node_base, nn, tri_base, nt))
-            self.mesh_tri_offset.append(tri_base)
-            self.mesh_nr_tris.append(nt)
             self.max_depth = max(self.max_depth, md)
             node_base += nn
             tri_base += nt
+        self.mesh_tri_offset = [lay[2] for lay in self._layout]
+        self.mesh_nr_tris = [lay[3] for lay in self._layout]
         self.roots = [lay[0] for lay in self._layout]
         self._roots = (ctypes.c_int32 * self.nr_meshes)(*self.roots)
         return node_base, tri_base
 
-    def _build_on_device(self, tensor_meshes, leaf_size, radius):
-        """The K trees built on the GPU (vsa_bvh_dev_build, or vsa_bvh_dev_build_ploc at `radius`) one after another
-        on the current stream from the meshes' device tensors, one synchronisation per shell to read its sizes, then
-        exported straight into the concatenated device arrays."""
-        L = _lib.lib()
-        dev = tensor_meshes[0].vertices.device
-        if dev.type != "cuda":
-            raise _lib.VolsurfsHipError(f'builder="{self.builder}" needs the meshes on the GPU')
-        st = _lib.stream_ptr()
-        inputs = []             # (alive until the sizes calls have synchronised the builds that read them)
-        try:
-            for m in tensor_meshes:
-                v = m.vertices.detach().to(dev, torch.float32).contiguous()
-                f = m.faces.detach().to(dev, torch.int32).contiguous()
-                inputs.append((v, f))
-                h = ctypes.c_void_p()
-                if self.builder == "ploc":
-                    name = "vsa_bvh_dev_build_ploc"
-                    rc = L.vsa_bvh_dev_build_ploc(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, radius,
-                                                  st, ctypes.byref(h))
-                else:
-                    name = "vsa_bvh_dev_build"
-                    rc = L.vsa_bvh_dev_build(v.data_ptr(), f.data_ptr(), v.shape[0], f.shape[0], leaf_size, st,
-                                             ctypes.byref(h))
-                if rc != 0:
-                    raise _lib.VolsurfsHipError(f"{name} failed with status {rc}")
-                self._bvh.append(h)
-            sizes = []
-            for h in self._bvh:
-                nn, nt, md = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-                rc = L.vsa_bvh_dev_sizes(h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(md))
-                if rc == -2 and md.value >= 48:
-                    raise _lib.VolsurfsHipError(
-                        f'builder="{self.builder}": tree depth {md.value} >= 48, deeper than the traversal stack; '
-                        'build this mesh with builder="host"')
-                if rc != 0:
-                    raise _lib.VolsurfsHipError(f"vsa_bvh_dev_sizes failed with status {rc}")
-                sizes.append((nn.value, nt.value, md.value))
-        except Exception:
-            self._destroy()
-            raise
-        node_base, tri_base = self._record_shells(sizes)
-        self.device = dev
-        self.nodes = torch.empty(node_base, 16, dtype=torch.float32, device=dev)
-        self.qnodes = torch.empty(node_base, 8, dtype=torch.int32, device=dev)
-        self.tris = torch.empty(tri_base, 12, dtype=torch.float32, device=dev)
-        self._export_device()
-        self.slot_face_id = self.tris[:, 3].contiguous().view(torch.int32)
-
-    def _export_device(self):
-        """Both node formats and the triangles of the device-built trees, written in place into self.nodes /
-        self.qnodes / self.tris; the K quantisation frames into self._frames (host)."""
-        L = _lib.lib()
-        frames = (ctypes.c_float * (6 * self.nr_meshes))()
-        st = _lib.stream_ptr()
-        for i, (h, (nb, nn, tb, nt)) in enumerate(zip(self._bvh, self._layout)):
-            rc = L.vsa_bvh_dev_export(h, self.nodes[nb].data_ptr(), self.qnodes[nb].data_ptr(), self.tris[tb].data_ptr(),
-                                      nb, tb, ctypes.addressof(frames) + 24 * i, st)
-            if rc != 0:
-                raise _lib.VolsurfsHipError(f"vsa_bvh_dev_export failed with status {rc}")
-        self._frames = frames
-
-    def _destroy(self):
-        L = _lib.lib()
-        for h in self._bvh:
-            (L.vsa_bvh_dev_destroy if self.builder in self.DEVICE_BUILDERS else L.vsa_bvh_destroy)(h)
-        self._bvh = []
-
-    def _export(self):
-        """Concatenated fp32 nodes [*,16], quantised nodes [*,8] u32, triangles [*,12] and the K
-        quantisation frames [K*6] of the builder handles."""
-        L = _lib.lib()
-        n_nodes = sum(lay[1] for lay in self._layout)
-        n_tris = sum(lay[3] for lay in self._layout)
-        nodes = np.empty((n_nodes, 16), np.float32)
-        qnodes = np.empty((n_nodes, 8), np.uint32)
-        tris = np.empty((n_tris, 12), np.float32)
-        frames = np.empty(6 * self.nr_meshes, np.float32)
-        for i, (h, (nb, nn, tb, nt)) in enumerate(zip(self._bvh, self._layout)):
-            rc = L.vsa_bvh_export(h, nodes[nb:nb + nn].ctypes.data_as(ctypes.c_void_p),
-                                  tris[tb:tb + nt].ctypes.data_as(ctypes.c_void_p), ctypes.c_int(nb),
-                                  ctypes.c_int(tb))
-            rc2 = L.vsa_bvh_export_q(h, qnodes[nb:nb + nn].ctypes.data_as(ctypes.c_void_p),
-                                     tris[tb:tb + nt].ctypes.data_as(ctypes.c_void_p), ctypes.c_int(nb),
-                                     ctypes.c_int(tb), frames[6 * i:6 * i + 6].ctypes.data_as(ctypes.c_void_p))
-            if rc != 0 or rc2 != 0:
-                raise _lib.VolsurfsHipError(f"vsa_bvh_export failed with status {rc} / {rc2}")
-        return nodes, qnodes, tris, frames
+    def _drop_geometry_state(self):
+        """Forget what belongs to the meshes' geometry, each rebuilt on first use: the cost feedback's measured launch
+        order (`_fb`), the pseudonormal tables (`_pn`), the winding moments (`_wm`) and the edge census (`_census`)."""
+        self._fb = self._pn = self._wm = self._census = None
 
     def refit(self, tensor_meshes):
         """The shells' vertices moved (same faces): recompute triangle records and boxes bottom-up in the
-        existing trees (vsa_bvh_refit) and overwrite the device arrays in place — no SAH rebuild, triangle
+        existing trees (vsa_bvh_refit / vsa_bvh_dev_refit) and overwrite the arrays in place — no rebuild, triangle
         slots (and with them `slot_face_id` and any per-slot uv table) unchanged.  Hits through the
-        refitted trees are bit-identical to a rebuild's (tests/test_raytrace.py::test_refit_*).
+        refitted trees are bit-identical to a rebuild's (tests/test_raytrace.py::test_refit_*,
+        tests/test_bvh_device.py::test_device_refit_*, tests/test_bvh_ploc.py::test_ploc_refit_*).
         SURVEY §8f row 1; replaces re-running RayTracer(tensor_meshes) (volsurfs.py:82-128)."""
         if len(tensor_meshes) != self.nr_meshes:
             raise _lib.VolsurfsHipError("refit needs the meshes the tracer was built on")
-        L = _lib.lib()
-        self._meshes, self._pn = list(tensor_meshes), None       # the tables belonged to the old geometry
-        self._wm = self._census = None
-        if self.builder in self.DEVICE_BUILDERS:
-            st = _lib.stream_ptr()
-            for h, m in zip(self._bvh, tensor_meshes):
-                v = m.vertices.detach().to(self.device, torch.float32).contiguous()
-                rc = L.vsa_bvh_dev_refit(h, v.data_ptr(), v.shape[0], st)
-                if rc != 0:
-                    raise _lib.VolsurfsHipError(f"vsa_bvh_dev_refit failed with status {rc} (vertex count changed?)")
-            self._export_device()
-            self._fb = None
-            return self
-        for h, m in zip(self._bvh, tensor_meshes):
-            v = np.ascontiguousarray(m.vertices.detach().cpu().numpy(), np.float32)
-            rc = L.vsa_bvh_refit(h, v.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(v.shape[0]))
-            if rc != 0:
-                raise _lib.VolsurfsHipError(f"vsa_bvh_refit failed with status {rc} (vertex count changed?)")
-        nodes, qnodes, tris, frames = self._export()
-        self.nodes.copy_(torch.from_numpy(nodes))
-        self.qnodes.copy_(torch.from_numpy(qnodes.view(np.int32)))
-        self.tris.copy_(torch.from_numpy(tris))
-        self._frames = (ctypes.c_float * (6 * self.nr_meshes))(*frames.tolist())
-        self._fb = None        # the measured launch order belonged to the old geometry
+        self._meshes = list(tensor_meshes)
+        self._drop_geometry_state()
+        self._trees.refit(self._meshes)
+        self._trees.export(self._layout, self.nodes, self.qnodes, self.tris, self._frames)
         return self
 
     def __del__(self):
         try:
-            if getattr(self, "_bvh", None):
-                self._destroy()
+            self._trees.destroy()
         except Exception:
             pass
-        self._bvh = []
+
+    @classmethod
+    def over(cls, meshes, nr_shells=None, builder="device"):
+        """`meshes` itself when it is a RayTracer, else a tracer built over this list of meshes with `builder`.
+        nr_shells: the number of shells it must have (ValueError)."""
+        tracer = meshes if isinstance(meshes, cls) else cls(list(meshes), builder=builder)
+        if nr_shells is not None and tracer.nr_meshes != nr_shells:
+            raise ValueError(f"a tracer of {tracer.nr_meshes} shells for {nr_shells} meshes")
+        return tracer
 
     def trace_all(self, rays_o, rays_d, t_min=0.0, out=None):
         """All K shells, one launch.  Returns hit_t [K,N] f32, hit_slot [K,N]
@@ -304,14 +327,19 @@ class RayTracer:
     def narrow_rays_per_wave(self, N, K):
         return self.NARROW_RPW if N * K < self.NARROW_BELOW else 64
 
+    @staticmethod
+    def _counted(name, counters, device, *args):
+        """{counter: value} of one `name(*args, counters, stream)`: a walk with int64 counters.  Synchronises."""
+        st = torch.zeros(len(counters), dtype=torch.int64, device=device)
+        _lib.call(name, *args, st, _lib.stream_ptr())
+        return dict(zip(counters, st.cpu().tolist()))
+
     def walk_stats(self, rays_o, rays_d, t_min=0.0):
         """{lane_visits, tri_tests, wave_trips, waves, max_wave_trips} of one traversal of these rays
         (vsa_trace_q_stats: the same walk with counters; q16 nodes).  Synchronises; measurement only."""
         N, rays_o, rays_d = _rays(rays_o, rays_d)
-        st = torch.zeros(5, dtype=torch.int64, device=rays_o.device)
-        _lib.call("vsa_trace_q_stats", *self.q16_tree_args(), rays_o, rays_d, N, float(t_min), st, _lib.stream_ptr())
-        v = st.cpu().tolist()
-        return dict(zip(("lane_visits", "tri_tests", "wave_trips", "waves", "max_wave_trips"), v))
+        return self._counted("vsa_trace_q_stats", ("lane_visits", "tri_tests", "wave_trips", "waves", "max_wave_trips"),
+                             rays_o.device, *self.q16_tree_args(), rays_o, rays_d, N, float(t_min))
 
     def face_view_counts(self, cameras, supersample=1, t_min=0.0):
         """Per shell, how many samples of how many views had each face as the shell's closest hit: a list of K int64
@@ -334,13 +362,17 @@ class RayTracer:
         from .rasterize import tracer_rasterize
         return tracer_rasterize(self, camera, supersample, t_min, out, want_dirs)
 
+    def _shells(self, mesh_id=None):
+        """(mesh_roots, mesh_frames, nr_meshes) of all K shells, or of shell `mesh_id` alone as a tracer of one shell."""
+        if mesh_id is None:
+            return self._roots, self._frames, self.nr_meshes
+        frame = ctypes.c_void_p(ctypes.addressof(self._frames) + 24 * int(mesh_id))   # (six floats per shell, host)
+        return (ctypes.c_int32 * 1)(self.roots[mesh_id]), frame, 1
+
     def q16_tree_args(self, mesh_id=None):
         """The leading arguments of the q16 entry points (qnodes, tris, mesh_roots, mesh_frames, nr_meshes, max_depth):
         of all K shells, or of shell `mesh_id` alone as a tracer of one shell."""
-        if mesh_id is None:
-            return self.qnodes, self.tris, self._roots, self._frames, self.nr_meshes, self.max_depth
-        return (self.qnodes, self.tris, (ctypes.c_int32 * 1)(self.roots[mesh_id]), self._frame_ptr(mesh_id), 1,
-                self.max_depth)
+        return (self.qnodes, self.tris, *self._shells(mesh_id), self.max_depth)
 
     def require_q16(self, what, walk=True):
         """Raises unless `what` can use this tracer's quantised nodes and (walk) walk them with the traversal stack."""
@@ -351,37 +383,47 @@ class RayTracer:
         if walk and self.max_depth >= 48:
             raise _lib.VolsurfsHipError(f"tree depth {self.max_depth} >= 48, deeper than the traversal stack")
 
-    def _closest_args(self, points, what):
+    def _points(self, points, what):
+        """The query points of `what` as a checked contiguous f32 [N, 3] tensor; raises without q16 nodes."""
         self.require_q16(what)
         if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
             raise _lib.VolsurfsHipError(f"{what}: expected points [N, 3] with N >= 1, got "
                                         f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points)}")
         return _lib.check_f32(points.contiguous(), points.shape[0], 3)
 
+    def _check_mesh_id(self, mesh_id, what):
+        if mesh_id is not None and not 0 <= mesh_id < self.nr_meshes:
+            raise _lib.VolsurfsHipError(f"{what}: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
+
+    def _table_args(self, rule, mesh_id):
+        """(table, first row per shell) of the sign rule's table, the pseudonormals or the winding moments: of all K
+        shells, or of shell `mesh_id` alone."""
+        table, base = self.winding_moments() if rule == "winding" else self.pseudonormal_tables()
+        return table, base if mesh_id is None else (ctypes.c_longlong * 1)(base[mesh_id])
+
+    def _closest(self, name, points, mesh_id, *table_args):
+        """{dist, face, slot, bary} of one closest-point entry point (vsa_closest_point_q, vsa_signed_distance_q or
+        vsa_signed_distance_w_q with its table arguments) for all K shells ([K, N] results; mesh_id None) or one ([N])."""
+        N = points.shape[0]
+        shape = (self.nr_meshes, N) if mesh_id is None else (N,)
+        dist = torch.empty(shape, device=points.device)
+        slot = torch.empty(shape, dtype=torch.int32, device=points.device)
+        bary = torch.empty(*shape, 2, device=points.device)
+        _lib.call(name, *self.q16_tree_args(mesh_id), *table_args, points, N, dist, slot, bary, _lib.stream_ptr())
+        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+
     def closest_all(self, points):
         """The closest point of every shell to every query point, one launch (vsa_closest_point_q: the closest-point walk
         of the q16 nodes, the result of brute force over all triangles bit for bit; queries within ~60 mesh extents).
         points [N, 3] f32 -> {dist [K, N] f32, face [K, N] i64 (original face ids), slot [K, N] i32 (global index into
         self.tris), bary [K, N, 2] f32 (the weights of the face's second and third vertex)}.  No host sync."""
-        points = self._closest_args(points, "closest_all")
-        K, N = self.nr_meshes, points.shape[0]
-        dist = torch.empty(K, N, device=points.device)
-        slot = torch.empty(K, N, dtype=torch.int32, device=points.device)
-        bary = torch.empty(K, N, 2, device=points.device)
-        _lib.call("vsa_closest_point_q", *self.q16_tree_args(), points, N, dist, slot, bary, _lib.stream_ptr())
-        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+        return self._closest("vsa_closest_point_q", self._points(points, "closest_all"), None)
 
     def closest(self, points, mesh_id=0):
         """`closest_all` for one shell: dist [N], face [N], slot [N], bary [N, 2]."""
-        points = self._closest_args(points, "closest")
-        if not 0 <= int(mesh_id) < self.nr_meshes:
-            raise _lib.VolsurfsHipError(f"closest: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
-        N = points.shape[0]
-        dist = torch.empty(N, device=points.device)
-        slot = torch.empty(N, dtype=torch.int32, device=points.device)
-        bary = torch.empty(N, 2, device=points.device)
-        _lib.call("vsa_closest_point_q", *self.q16_tree_args(mesh_id), points, N, dist, slot, bary, _lib.stream_ptr())
-        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+        points, mesh_id = self._points(points, "closest"), int(mesh_id)
+        self._check_mesh_id(mesh_id, "closest")
+        return self._closest("vsa_closest_point_q", points, mesh_id)
 
     def pseudonormal_tables(self):
         """(table [sum F_k, 7, 3] f32, face_base [K] host long long): the pseudonormals of every face of every shell
@@ -423,12 +465,16 @@ class RayTracer:
             self._census[mesh_id] = edge_census(self._meshes[mesh_id], device=self.device)
         return self._census[mesh_id]
 
+    @classmethod
+    def _check_sign(cls, sign):
+        if sign not in cls.SIGNS:
+            raise ValueError(f"sign must be one of {cls.SIGNS}, got {sign!r}")
+
     def sign_rule(self, sign, mesh_ids=None):
         """"pseudonormal" or "winding": what `sign` means for these shells (all of them by default).  "auto" is the
         winding number iff the edge census of one of them finds a boundary, a non-manifold or an inconsistently wound
         edge.  Anything else raises ValueError."""
-        if sign not in self.SIGNS:
-            raise ValueError(f"sign must be one of {self.SIGNS}, got {sign!r}")
+        self._check_sign(sign)
         if sign != "auto":
             return sign
         ids = range(self.nr_meshes) if mesh_ids is None else mesh_ids
@@ -441,23 +487,20 @@ class RayTracer:
             raise ValueError(f"beta must be > 1 (math.inf: every leaf is summed exactly), got {beta}")
         return beta
 
-    def _winding_roots(self, mesh_id):
-        """(moments table, mesh_roots, moment_roots, nr_meshes) of all shells, or of shell `mesh_id` alone."""
-        table, entries = self.winding_moments()
-        if mesh_id is None:
-            return table, self._roots, entries, self.nr_meshes
-        return table, (ctypes.c_int32 * 1)(self.roots[mesh_id]), (ctypes.c_longlong * 1)(entries[mesh_id]), 1
+    def _winding_args(self, what, points, mesh_id, beta):
+        """(checked points, the arguments of vsa_winding_number_q / _stats in front of them: qnodes, tris, mesh_roots,
+        nr_meshes, max_depth, moments, moment_roots, beta), for all K shells or for shell `mesh_id`."""
+        points, beta = self._points(points, what), self._check_beta(beta)
+        self._check_mesh_id(mesh_id, what)
+        roots, _, K = self._shells(mesh_id)
+        return points, (self.qnodes, self.tris, roots, K, self.max_depth, *self._table_args("winding", mesh_id), beta)
 
-    def _winding(self, points, mesh_id, beta, what):
-        points = self._closest_args(points, what)
-        beta = self._check_beta(beta)
-        if mesh_id is not None and not 0 <= int(mesh_id) < self.nr_meshes:
-            raise _lib.VolsurfsHipError(f"{what}: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
-        table, roots, entries, K = self._winding_roots(mesh_id)
+    def _winding(self, what, points, mesh_id, beta):
+        """w [K, N] of all K shells, or w [N] of shell `mesh_id`."""
+        points, args = self._winding_args(what, points, mesh_id, beta)
         N = points.shape[0]
-        w = torch.empty((K, N) if mesh_id is None else (N,), device=points.device)
-        _lib.call("vsa_winding_number_q", self.qnodes, self.tris, roots, K, self.max_depth, table, entries, beta, points,
-                  N, w, _lib.stream_ptr())
+        w = torch.empty((self.nr_meshes, N) if mesh_id is None else (N,), device=points.device)
+        _lib.call("vsa_winding_number_q", *args, points, N, w, _lib.stream_ptr())
         return w
 
     def winding_number_all(self, points, beta=2.0):
@@ -467,34 +510,28 @@ class RayTracer:
         queries use w > 1/2).  Subtrees farther than beta times their radius are taken by their area vector (Barill
         et al. 2018, order 0); beta must be > 1, math.inf sums every triangle exactly.  A NaN query gives NaN.  No
         host sync once the moments exist."""
-        return self._winding(points, None, beta, "winding_number_all")
+        return self._winding("winding_number_all", points, None, beta)
 
     def winding_number(self, points, mesh_id=0, beta=2.0):
         """`winding_number_all` for one shell: w [N]."""
-        return self._winding(points, int(mesh_id), beta, "winding_number")
+        return self._winding("winding_number", points, int(mesh_id), beta)
 
     def winding_stats(self, points, beta=2.0):
         """{node_visits, tri_terms, queries} of one `winding_number_all` of these points, summed over the K shells
         (vsa_winding_number_q_stats: the same walk with counters).  Synchronises; measurement only."""
-        points = self._closest_args(points, "winding_stats")
-        table, roots, entries, K = self._winding_roots(None)
-        st = torch.zeros(3, dtype=torch.int64, device=points.device)
-        _lib.call("vsa_winding_number_q_stats", self.qnodes, self.tris, roots, K, self.max_depth, table, entries,
-                  self._check_beta(beta), points, points.shape[0], st, _lib.stream_ptr())
-        v = st.cpu().tolist()
-        return {"node_visits": v[0], "tri_terms": v[1], "queries": v[2]}
+        points, args = self._winding_args("winding_stats", points, None, beta)
+        return self._counted("vsa_winding_number_q_stats", ("node_visits", "tri_terms", "queries"), points.device, *args,
+                             points, points.shape[0])
 
-    def _signed_w(self, points, mesh_id, beta):
-        beta = self._check_beta(beta)
-        table, _, entries, K = self._winding_roots(mesh_id)
-        N = points.shape[0]
-        shape = (K, N) if mesh_id is None else (N,)
-        dist = torch.empty(shape, device=points.device)
-        slot = torch.empty(shape, dtype=torch.int32, device=points.device)
-        bary = torch.empty(*shape, 2, device=points.device)
-        _lib.call("vsa_signed_distance_w_q", *self.q16_tree_args(mesh_id), table, entries, beta, points, N, dist, slot,
-                  bary, _lib.stream_ptr())
-        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+    def _signed(self, what, points, mesh_id, sign, beta):
+        """`_closest` signed by what `sign` means for these shells; beta is checked where the winding number uses it."""
+        points = self._points(points, what)
+        self._check_sign(sign)
+        self._check_mesh_id(mesh_id, what)
+        if self.sign_rule(sign, None if mesh_id is None else [mesh_id]) == "winding":
+            beta = self._check_beta(beta)
+            return self._closest("vsa_signed_distance_w_q", points, mesh_id, *self._table_args("winding", mesh_id), beta)
+        return self._closest("vsa_signed_distance_q", points, mesh_id, *self._table_args("pseudonormal", mesh_id))
 
     def signed_distance_all(self, points, sign="pseudonormal", beta=2.0):
         """`closest_all` with `dist` signed; |dist|, face, slot and bary are `closest_all`'s bits.
@@ -508,51 +545,23 @@ class RayTracer:
         membrane, where the field jumps from -d to +d.
         sign="auto": the winding number iff `edge_census` finds anything on a shell, else the pseudonormal.
         No host sync once the tables exist."""
-        points = self._closest_args(points, "signed_distance_all")
-        if self.sign_rule(sign) == "winding":
-            return self._signed_w(points, None, beta)
-        table, base = self.pseudonormal_tables()
-        K, N = self.nr_meshes, points.shape[0]
-        dist = torch.empty(K, N, device=points.device)
-        slot = torch.empty(K, N, dtype=torch.int32, device=points.device)
-        bary = torch.empty(K, N, 2, device=points.device)
-        _lib.call("vsa_signed_distance_q", *self.q16_tree_args(), table, base, points, N, dist, slot, bary,
-                  _lib.stream_ptr())
-        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+        return self._signed("signed_distance_all", points, None, sign, beta)
 
     def signed_distance(self, points, mesh_id=0, sign="pseudonormal", beta=2.0):
         """`signed_distance_all` for one shell: dist [N] (signed), face [N], slot [N], bary [N, 2]."""
-        points = self._closest_args(points, "signed_distance")
-        if not 0 <= int(mesh_id) < self.nr_meshes:
-            raise _lib.VolsurfsHipError(f"signed_distance: mesh_id {mesh_id} outside 0..{self.nr_meshes - 1}")
-        if self.sign_rule(sign, [int(mesh_id)]) == "winding":
-            return self._signed_w(points, int(mesh_id), beta)
-        table, base = self.pseudonormal_tables()
-        N = points.shape[0]
-        dist = torch.empty(N, device=points.device)
-        slot = torch.empty(N, dtype=torch.int32, device=points.device)
-        bary = torch.empty(N, 2, device=points.device)
-        _lib.call("vsa_signed_distance_q", *self.q16_tree_args(mesh_id), table,
-                  (ctypes.c_longlong * 1)(base[int(mesh_id)]), points, N, dist, slot, bary, _lib.stream_ptr())
-        return {"dist": dist, "face": self._slot_faces(slot), "slot": slot, "bary": bary}
+        return self._signed("signed_distance", points, int(mesh_id), sign, beta)
 
     def _slot_faces(self, slot):
         """Original face ids of triangle slots (-1 stays -1: a query with a NaN coordinate has no closest face)."""
         face = self.slot_face_id[slot.clamp_min(0).long()].long()
         return torch.where(slot >= 0, face, torch.full_like(face, -1))
 
-    def _frame_ptr(self, mesh_id):
-        """Host pointer to the six floats of one shell's quantisation frame."""
-        return ctypes.c_void_p(ctypes.addressof(self._frames) + 24 * int(mesh_id))
-
     def closest_stats(self, points):
         """{node_visits, tri_tests, queries} of one `closest_all` of these points, summed over the K shells
         (vsa_closest_point_q_stats: the same walk with counters).  Synchronises; measurement only."""
-        points = self._closest_args(points, "closest_stats")
-        st = torch.zeros(3, dtype=torch.int64, device=points.device)
-        _lib.call("vsa_closest_point_q_stats", *self.q16_tree_args(), points, points.shape[0], st, _lib.stream_ptr())
-        v = st.cpu().tolist()
-        return {"node_visits": v[0], "tri_tests": v[1], "queries": v[2]}
+        points = self._points(points, "closest_stats")
+        return self._counted("vsa_closest_point_q_stats", ("node_visits", "tri_tests", "queries"), points.device,
+                             *self.q16_tree_args(), points, points.shape[0])
 
     def crossings(self, mesh, mesh_id=0, segments=False):
         """Which faces of `mesh` (a cuda TensorMesh, or (RayTracer, mesh_id)) cross which faces of shell `mesh_id`:

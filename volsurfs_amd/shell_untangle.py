@@ -180,7 +180,7 @@ def untangle_shells(meshes, anchor=None, margin=1e-3, max_rounds=16, max_level=6
         for k, m in enumerate(meshes):
             if not (m.vertices.is_cuda and m.faces.is_cuda):
                 raise ValueError(f"untangle_shells: shell {k} must be on cuda, got {m.vertices.device}")
-    tracer = meshes if is_tracer else RayTracer(meshes, builder="device")
+    tracer = RayTracer.over(meshes)
     reports = [None] * K
     kw = dict(margin=margin, max_rounds=max_rounds, max_level=max_level, sign=sign, beta=beta)
     for k, against, side in ([(k, k - 1, 1) for k in range(anchor + 1, K)] +

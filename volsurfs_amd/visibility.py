@@ -82,10 +82,7 @@ def face_view_counts(meshes, cameras, supersample=1, t_min=0.0, tracer=None):
     tensors on the device: the number of samples, over all views, whose closest hit (t > t_min; ties to the smallest face)
     on shell k was face f.  `tracer`: a RayTracer of these meshes with q16 nodes (default: one is built on the device)."""
     meshes = list(meshes)
-    if tracer is None:
-        tracer = RayTracer(meshes, builder="device")
-    elif tracer.nr_meshes != len(meshes):
-        raise ValueError(f"a tracer of {tracer.nr_meshes} shells for {len(meshes)} meshes")
+    tracer = RayTracer.over(meshes if tracer is None else tracer, len(meshes))
     return tracer_face_view_counts(tracer, cameras, supersample, t_min, [int(m.faces.shape[0]) for m in meshes])
 
 
