@@ -1283,6 +1283,41 @@ long long vsa_simplify_workspace_bytes(long long nr_verts, long long nr_faces);
 int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
                  long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
                  int32_t* out_faces, long long* stats, float* stage_ms, void* stream);
+/* Guarded simplification: vsa_simplify with G = nr_guards guard meshes that the simplified mesh must not
+ * newly cross -- a shell's neighbours in a stack (volsurfs_amd/simplify.py:simplify_shells).  Every rule above holds
+ * unchanged; one condition is appended to `candidate`:
+ *   guard         for every face at a or b that does not contain both (the faces the flip rule enumerates), taken in
+ *                 its corner order with the moved vertex at the fp32 position p: that triangle, as A, must not cross
+ *                 any face of any guard mesh, as B.  "Cross" is the rule of "Mesh crossings" below (tri_cross of
+ *                 csrc/cross_walk.h): fp64 determinants of the fp32 bits; touching, coplanar, zero-area and NaN faces
+ *                 cross nothing; a guard face with an index outside its vertex array is no face.
+ * A candidate that fails gets the key UINT64_MAX like any other non-candidate; selection, acceptance order and
+ * stalling are unchanged.  Winners share no face and no vertex and no winner's endpoint lies in another's ring, so the
+ * faces one winner creates are untouched by the others: judging each candidate alone is exact for the mesh after the
+ * round.  Faces of the input that already cross a guard are not judged: they go only when a collapse removes or
+ * replaces them.  The verdict is an OR over all (new face, guard face) pairs: it does not depend on a guard's tree,
+ * its builder or the order of the guards, and with guards that reject nothing the output is vsa_simplify's bit for
+ * bit.  tests/simplify_guarded_restated.py restates the rule; the kernels are held to it bit for bit.
+ *   guards        [host] arrays of nr_guards (1..4) entries, guard g: guard_qnodes[g], guard_tris[g] = the device
+ *                 arrays of a q16 tree that holds the guard (vsa_bvh_quantize's nodes and the triangle records whose
+ *                 v0.w is the face id), guard_roots[g] its root node, guard_frames[6 g .. 6 g + 6) its grid (lo, step),
+ *                 guard_max_depths[g] its depth (< 48), guard_vertices[g] [V_g, 3] f32 and guard_faces[g] [F_g, 3]
+ *                 i32 the guard mesh on the device, guard_nr_verts[g] = V_g, guard_nr_faces[g] = F_g, both >= 1.
+ *   stats         [host] 6 long long: the five of vsa_simplify, then guard_rejected = the number of (round, edge)
+ *                 verdicts the guard turned down (one integer atomicAdd per wave).
+ *   stage_ms      [host] 7 floats or NULL: init, edges, cost, guard, select, collapse, compact.
+ *   workspace     vsa_simplify_guarded_workspace_bytes(V, F) = vsa_simplify_workspace_bytes(V, F): the guard stage
+ *                 places the vertex again as the collapse does and keeps no buffer of its own.
+ * No blocking read is added to a round.  VSA_ERR_ARG, before any HIP call: nr_guards outside 1..4, a NULL guard array
+ * or guard pointer, a negative root, a depth >= 48, V_g or F_g < 1, and every case of vsa_simplify. */
+long long vsa_simplify_guarded_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_simplify_guarded(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                         long long target_faces, int nr_guards, const uint32_t* const* guard_qnodes,
+                         const float* const* guard_tris, const int32_t* guard_roots, const float* guard_frames,
+                         const int32_t* guard_max_depths, const float* const* guard_vertices,
+                         const long long* guard_nr_verts, const int32_t* const* guard_faces,
+                         const long long* guard_nr_faces, void* workspace, long long workspace_bytes,
+                         float* out_verts, int32_t* out_faces, long long* stats, float* stage_ms, void* stream);
 
 /* ------------------------------------------------------------------------
  * UV atlas (csrc/atlas.hip): box-projection charts of one uv-less, consistently wound triangle mesh, packed into one

@@ -9,6 +9,9 @@
 //             (vstart / vend over the sorted slots): the ring of faces of every vertex.
 //   cost:     one lane per edge: placement, cost and the validity rules over the rings of both endpoints -> the
 //             64-bit key (cost bits << 32 | edge id) or UINT64_MAX.
+//   guard:    (vsa_simplify_guarded only) one lane per edge that is still a candidate: every face the collapse would
+//             create, as triangle A, walks each guard mesh's q16 tree by box overlap (cross_walk.h) and meets the
+//             faces of the leaves it reaches under the exact crossing rule; one crossing clears the edge's key.
 //   select:   m1 (64-bit atomicMin over edges), m2 (64-bit atomicMin over faces), the winners' flags, a scan, the
 //             winners' keys compacted in edge-id order, and {W, faces they remove} read by the host.  Only when the
 //             winners would remove more than the faces still to remove are their keys sorted and a scan of their
@@ -21,6 +24,7 @@
 
 #include <cstdint>
 
+#include "cross_walk.h"
 #include "mesh_topology.h"
 
 #define SMP_BLOCK MT_BLOCK
@@ -37,7 +41,10 @@
 #define CTR_F 3
 #define CTR_ACC 4
 #define CTR_V 5
+#define CTR_G 6          // (round, edge) verdicts the guard turned down; read with CTR_V
 #define CTR_N 8
+
+#define SMP_MAX_GUARDS 4
 
 using mt::u64;
 
@@ -363,6 +370,102 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_cost(const float* __restrict__ 
   ekey[e] = key;
 }
 
+// ------------------------------------------------------------------------------------------------ guard
+
+// One guard mesh: its q16 tree as cross_walk reads it, and the grid of that tree.
+struct SmpGuard {
+  const uint4* qnodes;
+  const float4* tris;
+  int root;
+  float frame[6];
+  CrossMesh mesh;
+};
+
+struct SmpGuards {
+  int n, max_depth;
+  SmpGuard g[SMP_MAX_GUARDS];
+};
+
+// One lane per edge id, one wave per block.  A lane whose edge is still a candidate places the new vertex as
+// smp_collapse will (recomputed: 2 x 80 bytes of Q, 2 x 12 of P and 2 x 4 of flags read per candidate, against a
+// 12-byte store per edge in smp_cost, a 12-byte load here and 36 bytes per face of workspace for a position buffer --
+// and smp_cost, which the unguarded entry shares, stays as it is), then takes the surviving faces of a's ring and of
+// b's ring one at a time.  cross_walk loops on wave ballots, so the wave stays together: the loop over the faces runs
+// to the wave's longest ring, and a lane with no face left, or with its verdict already in, walks from TRACE_EMPTY.
+template <int STACK>
+__global__ __launch_bounds__(TRACE_BLOCK) void smp_guard(const float* __restrict__ P, const double* __restrict__ Q,
+                                                        const unsigned* __restrict__ vflag,
+                                                        const int32_t* __restrict__ faces,
+                                                        const u64* __restrict__ sorted,
+                                                        const int32_t* __restrict__ ehead,
+                                                        const uint32_t* __restrict__ vff,
+                                                        const int32_t* __restrict__ vstart,
+                                                        const int32_t* __restrict__ vend, int s,
+                                                        long long* __restrict__ ctr, u64* __restrict__ ekey,
+                                                        SmpGuards G) {
+  __shared__ int s_node[STACK][TRACE_BLOCK];
+  const int lane = threadIdx.x;
+  const long long e = (long long)blockIdx.x * TRACE_BLOCK + lane;
+  const bool live = e < ctr[CTR_E] && ekey[e] != SMP_NONE;
+  int a = 0, b = 0, ring = 2, j = 0;
+  float p[3] = {0.f, 0.f, 0.f};
+  if (live) {
+    const u64 hk = sorted[ehead[e]];
+    a = (int)(hk >> s), b = (int)(hk & ((1ull << s) - 1));
+    double cost;
+    smp_place(Q, P, vflag, a, b, p, &cost);
+    ring = 0;
+    j = vstart[a];
+  }
+  bool rejected = false;
+  for (;;) {
+    // the lane's next face at a without b, then at b without a
+    int id[3] = {0, 0, 0}, m = 0;
+    bool have = false;
+    if (!rejected) {
+      while (ring < 2) {
+        if (j >= (ring == 0 ? vend[a] : vend[b])) {
+          ++ring;
+          j = vstart[b];
+          continue;
+        }
+        const long long f = vff[j++];
+        const int other = ring == 0 ? b : a;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) id[c] = faces[3 * f + c];
+        if (id[0] == other || id[1] == other || id[2] == other) continue;
+        m = ring == 0 ? a : b;
+        have = true;
+        break;
+      }
+    }
+    if (__builtin_amdgcn_ballot_w64(have) == 0) break;
+    // the face in its corner order, the moved vertex at p
+    CrossTri T;
+    float x[3], y[3], z[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const bool moved = !have || id[c] == m;
+      const long long v = moved ? 0 : id[c];
+      x[c] = moved ? p[0] : P[3 * v];
+      y[c] = moved ? p[1] : P[3 * v + 1];
+      z[c] = moved ? p[2] : P[3 * v + 2];
+      T.x[c] = (double)x[c], T.y[c] = (double)y[c], T.z[c] = (double)z[c];
+    }
+    for (int g = 0; g < G.n; ++g) {
+      const SmpGuard& gd = G.g[g];
+      const CrossBox qb = cross_qbox(gd.frame, x, y, z);
+      cross_walk<STACK, false, false, false>(gd.qnodes, gd.tris, gd.mesh, T, qb, 0,
+                                             have && !rejected ? gd.root : TRACE_EMPTY, s_node, lane,
+                                             [&](int, const double*) { rejected = true; });
+    }
+  }
+  if (rejected) ekey[e] = SMP_NONE;
+  const unsigned long long turned_down = __builtin_amdgcn_ballot_w64(rejected);
+  if (lane == 0 && turned_down)
+    atomicAdd((unsigned long long*)(ctr + CTR_G), (unsigned long long)__popcll(turned_down));
+}
+
 // ------------------------------------------------------------------------------------------------ select
 
 __global__ __launch_bounds__(SMP_BLOCK) void smp_m1(const u64* __restrict__ ekey, const u64* __restrict__ sorted,
@@ -603,9 +706,12 @@ int build_rings(Smp& m) {
   return mt::vertex_rings(m.fcur, m.F, m.V, m.s, kin, m.vfk, kin + 3 * m.F, m.vff, m.vstart, m.vend, m.tmp, m.st);
 }
 
-int run(Smp& m, const float* verts, const int32_t* faces, long long target, float* out_verts, int32_t* out_faces,
-        long long* stats) {
+// The rounds.  `guards`: null (vsa_simplify) or the guard meshes of vsa_simplify_guarded, whose stage sits between cost
+// and select and moves the later stages' timer slots up by one; stats then has a sixth entry.
+int run(Smp& m, const float* verts, const int32_t* faces, long long target, const SmpGuards* guards, float* out_verts,
+        int32_t* out_faces, long long* stats) {
   const long long V = m.V;
+  const int later = guards ? 1 : 0;
   long long rounds = 0, collapses = 0, stalled = 0;
   MT_TRY(m.timer.open());
   VSA_HIP_TRY(hipMemcpyAsync(m.P, verts, 12 * (size_t)V, hipMemcpyDeviceToDevice, m.st));
@@ -634,6 +740,17 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
                        m.vstart, m.vend, n3, m.s, m.ctr, m.ekey);
     MT_LAUNCHED();
     MT_TRY(m.timer.close(2));
+    // guard
+    if (guards) {
+      MT_TRY(m.timer.open());
+      const dim3 grid((unsigned)((n3 + TRACE_BLOCK - 1) / TRACE_BLOCK)), block(TRACE_BLOCK);
+      with_stack(guards->max_depth, [&](auto sk) {
+        hipLaunchKernelGGL((smp_guard<decltype(sk)::value>), grid, block, 0, m.st, m.P, m.Q, m.vflag, m.fcur, m.B,
+                           m.ehead, m.vff, m.vstart, m.vend, m.s, m.ctr, m.ekey, *guards);
+      });
+      MT_LAUNCHED();
+      MT_TRY(m.timer.close(3));
+    }
     // select
     MT_TRY(m.timer.open());
     VSA_HIP_TRY(hipMemsetAsync(m.m1, 0xFF, 8 * (size_t)V, m.st));
@@ -657,7 +774,7 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
     const long long W = wr[0], R = wr[1], need = m.F - target;
     if (W < 0 || W > m.F) return VSA_ERR_UNSUPPORTED;
     if (W == 0) {
-      MT_TRY(m.timer.close(3));
+      MT_TRY(m.timer.close(3 + later));
       stalled = 1;
       break;
     }
@@ -671,13 +788,13 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
       list = wsorted;
       pre = m.rank;
     }
-    MT_TRY(m.timer.close(3));
+    MT_TRY(m.timer.close(3 + later));
     // collapse
     MT_TRY(m.timer.open());
     hipLaunchKernelGGL(smp_collapse, mt::grid(W), dim3(SMP_BLOCK), 0, m.st, list, W, pre, need, m.B, m.ehead, m.s,
                        m.vflag, m.vff, m.vstart, m.vend, m.P, m.Q, m.fcur, m.ctr);
     MT_LAUNCHED();
-    MT_TRY(m.timer.close(4));
+    MT_TRY(m.timer.close(4 + later));
     // compact
     MT_TRY(m.timer.open());
     hipLaunchKernelGGL(smp_face_alive, mt::grid(m.F), dim3(SMP_BLOCK), 0, m.st, m.fcur, m.F, m.flags);
@@ -701,7 +818,7 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
       collapses += W;
       m.F -= R;
     }
-    MT_TRY(m.timer.close(5));
+    MT_TRY(m.timer.close(5 + later));
   }
   // output: the referenced vertices in ascending index, faces in order
   MT_TRY(m.timer.open());
@@ -716,22 +833,26 @@ int run(Smp& m, const float* verts, const int32_t* faces, long long target, floa
     hipLaunchKernelGGL(smp_out_faces, mt::grid(n3), dim3(SMP_BLOCK), 0, m.st, m.fcur, n3, m.rank, out_faces);
     MT_LAUNCHED();
   }
-  long long vout = 0;
-  MT_TRY(mt::read_counters(m.st, m.ctr + CTR_V, &vout));
-  MT_TRY(m.timer.close(5));
+  long long vg[2];
+  MT_TRY(mt::read_counters(m.st, m.ctr + CTR_V, vg, 2));
+  MT_TRY(m.timer.close(5 + later));
   stats[0] = rounds;
   stats[1] = collapses;
   stats[2] = stalled;
-  stats[3] = vout;
+  stats[3] = vg[0];
   stats[4] = m.F;
+  if (guards) stats[5] = vg[1];
   return VSA_OK;
 }
 
 }  // namespace
 
-extern "C" int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
-                            long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
-                            int32_t* out_faces, long long* stats, float* stage_ms, void* stream) {
+namespace {
+
+// Binds the workspace and runs: the body both entry points share.
+int simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, long long target_faces,
+             const SmpGuards* guards, void* workspace, long long workspace_bytes, float* out_verts, int32_t* out_faces,
+             long long* stats, float* stage_ms, void* stream) {
   if (!verts || !faces || !workspace || !out_verts || !out_faces || !stats || target_faces < 0) return VSA_ERR_ARG;
   MT_TRY(mt::check_vf(nr_verts, nr_faces));
   Smp m;
@@ -762,8 +883,54 @@ extern "C" int vsa_simplify(const float* verts, long long nr_verts, const int32_
   m.vfk = mt::at<uint32_t>(ws, l.vfk);
   m.vff = mt::at<uint32_t>(ws, l.vff);
   m.ctr = mt::at<long long>(ws, l.ctr);
-  MT_TRY(m.timer.create(stage_ms, 6, m.st));
-  const int rc = run(m, verts, faces, target_faces, out_verts, out_faces, stats);
+  MT_TRY(m.timer.create(stage_ms, guards ? 7 : 6, m.st));
+  const int rc = run(m, verts, faces, target_faces, guards, out_verts, out_faces, stats);
   m.timer.destroy();
   return rc;
+}
+
+}  // namespace
+
+extern "C" int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                            long long target_faces, void* workspace, long long workspace_bytes, float* out_verts,
+                            int32_t* out_faces, long long* stats, float* stage_ms, void* stream) {
+  return simplify(verts, nr_verts, faces, nr_faces, target_faces, nullptr, workspace, workspace_bytes, out_verts,
+                  out_faces, stats, stage_ms, stream);
+}
+
+// The guard stage reads the rounds' own buffers and writes the keys in place: the workspace is vsa_simplify's.
+extern "C" long long vsa_simplify_guarded_workspace_bytes(long long nr_verts, long long nr_faces) {
+  return vsa_simplify_workspace_bytes(nr_verts, nr_faces);
+}
+
+extern "C" int vsa_simplify_guarded(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                                    long long target_faces, int nr_guards, const uint32_t* const* guard_qnodes,
+                                    const float* const* guard_tris, const int32_t* guard_roots,
+                                    const float* guard_frames, const int32_t* guard_max_depths,
+                                    const float* const* guard_vertices, const long long* guard_nr_verts,
+                                    const int32_t* const* guard_faces, const long long* guard_nr_faces,
+                                    void* workspace, long long workspace_bytes, float* out_verts, int32_t* out_faces,
+                                    long long* stats, float* stage_ms, void* stream) {
+  if (nr_guards < 1 || nr_guards > SMP_MAX_GUARDS) return VSA_ERR_ARG;
+  if (!guard_qnodes || !guard_tris || !guard_roots || !guard_frames || !guard_max_depths || !guard_vertices ||
+      !guard_nr_verts || !guard_faces || !guard_nr_faces)
+    return VSA_ERR_ARG;
+  SmpGuards G = {};
+  G.n = nr_guards;
+  for (int g = 0; g < nr_guards; ++g) {
+    MT_TRY(check_qtree(guard_qnodes[g], guard_tris[g], guard_roots + g, guard_frames + 6 * g, 1, guard_max_depths[g],
+                       VSA_ERR_ARG));
+    if (guard_roots[g] < 0 || !guard_vertices[g] || !guard_faces[g]) return VSA_ERR_ARG;
+    if (guard_nr_verts[g] < 1 || guard_nr_faces[g] < 1) return VSA_ERR_ARG;
+    if (guard_nr_verts[g] > 0x7fffffffll || guard_nr_faces[g] > 0x7fffffffll / 3 - 1) return VSA_ERR_UNSUPPORTED;
+    SmpGuard& d = G.g[g];
+    d.qnodes = reinterpret_cast<const uint4*>(guard_qnodes[g]);
+    d.tris = reinterpret_cast<const float4*>(guard_tris[g]);
+    d.root = guard_roots[g];
+    for (int k = 0; k < 6; ++k) d.frame[k] = guard_frames[6 * g + k];
+    d.mesh = CrossMesh{guard_vertices[g], guard_faces[g], guard_nr_verts[g], guard_nr_faces[g]};
+    G.max_depth = guard_max_depths[g] > G.max_depth ? guard_max_depths[g] : G.max_depth;
+  }
+  return simplify(verts, nr_verts, faces, nr_faces, target_faces, &G, workspace, workspace_bytes, out_verts, out_faces,
+                  stats, stage_ms, stream);
 }
