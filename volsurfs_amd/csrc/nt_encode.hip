@@ -377,7 +377,11 @@ __device__ __forceinline__ void enc_bwd_piece(
     int acc[NF][4];
 #pragma unroll
     for (int f = 0; f < NF; ++f) acc[f][0] = acc[f][1] = acc[f][2] = acc[f][3] = 0;
-    unsigned cur_cx = 0xffffffffu, cur_cy = 0xffffffffu;
+    // "no cell yet" is a cx no texel centre can have.  (It was 0xffffffff, which IS a cell: column -1, where the
+    // apron texels left of a texture land once the level is finer than the texture, scale > R.  The both-feature
+    // dense levels take this path at any scale, and every contribution of such a texel was dropped.)
+    constexpr unsigned NO_CELL = 0x80000000u;
+    unsigned cur_cx = NO_CELL, cur_cy = 0u;
 #pragma unroll
     for (int u = 0; u < ENC_UNROLL; ++u) {
       const int slot = s0 + u;
@@ -415,7 +419,7 @@ __device__ __forceinline__ void enc_bwd_piece(
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[f][k] += v[f][k];
         } else {
-          if (cur_cx != 0xffffffffu) {
+          if (cur_cx != NO_CELL) {
 #pragma unroll
             for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -430,7 +434,7 @@ __device__ __forceinline__ void enc_bwd_piece(
         }
       }
     }
-    if (MERGE && cur_cx != 0xffffffffu) {
+    if (MERGE && cur_cx != NO_CELL) {
 #pragma unroll
       for (int f = 0; f < NF; ++f)
 #pragma unroll
