@@ -3,7 +3,12 @@
 The reference builds `apex.optimizers.FusedAdam(param_groups, amsgrad=False, betas=(0.9, 0.99),
 eps=1e-15, weight_decay=0.0, lr=...)` (/root/reference/volsurfs_py/methods/base_method.py:87-94)
 and calls `.step()` once per iteration (trainer.py:278) — the same update as
-`torch.optim.Adam`, against which tests/test_optim.py pins this class at 1e-6.
+`torch.optim.Adam`.  tests/test_adam_step.py pins the kernel and this file's classes BIT FOR BIT to a
+float32 restatement of the documented operation order (tests/adam_restated.py: every path of the kernel,
+40-step trajectories through FusedAdam, its side-stream step and ShardedFusedAdam), and that restatement
+to torch.optim.Adam in float64 through a derived rounding bound;
+tests/test_optim.py::test_fused_adam_matches_torch_adam compares the class with torch.optim.Adam in fp32
+at 1e-6.
 
 `vsa_adam_step` (csrc/adam.hip) updates ALL tensors of a parameter group in one launch and
 fuses two passes the surrounding loop otherwise makes over the same memory: the refresh of a
@@ -26,6 +31,14 @@ class AdamTensor(ctypes.Structure):
 
 
 class FusedAdam(torch.optim.Optimizer):
+    """Adam(betas, eps, no weight decay, no amsgrad) over contiguous CUDA float32 parameters, one launch per group.
+
+    half_copies: {parameter: f16 tensor of its shape} — the kernel writes half(p') beside every p' it stores.
+    It stores nothing for a group of 4 consecutive elements (counted from the tensor's start) whose gradient and
+    both moments are all zero (csrc/adam.hip: the idle skip), so a copy must hold half(param) BEFORE the first
+    step: the optimiser does not initialise the entries that never receive a gradient
+    (tests/test_adam_step.py::test_idle_groups_are_not_stored)."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.99), eps=1e-15, weight_decay=0.0,
                  amsgrad=False, half_copies=None):
         if weight_decay != 0.0 or amsgrad:
