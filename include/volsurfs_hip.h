@@ -2112,6 +2112,69 @@ int vsa_shell_raster_draw(const float* tris, long long nr_slots, const int32_t* 
                           const void* workspace, long long workspace_bytes, long long nr_pairs, int32_t* pairs,
                           float* hit_t, int32_t* hit_slot, float* hit_uv, float* rays_d, float* stage_ms, void* stream);
 
+/* ---- Mesh smoothing (no counterpart in the reference; csrc/mesh_smooth.hip) ----
+ * Taubin's lambda | mu fairing of one mesh: vertices move, and only vertices, so faces, UVs, vertex count and order are
+ * untouched.  With guard meshes the result crosses no guard face that the input did not cross.  The reference never
+ * smooths: the rule below is this library's own, restated in tests/mesh_smooth_restated.py and UNPINNED.  fp32 in the
+ * order written, no contraction; fp32 division is correctly rounded.  P [V, 3] f32, faces [F, 3] i32 with every index in
+ * 0 .. V - 1 (as vsa_simplify requires).
+ *   ring          of vertex v: the corner slots 3 f + c with faces[f, c] == v in ascending slot order (the order of the
+ *                 stage's (vertex, face) sort); a face that names v twice is in it twice.
+ *   boundary      v is a boundary vertex iff it is an endpoint of an undirected edge key (min, max of a corner and the
+ *                 next) that occurs exactly once among the 3 F keys.  With fix_boundary != 0 a boundary vertex never
+ *                 moves; a vertex with an empty ring never moves.
+ *   half-step     with weight w, for every vertex that may move: acc = 0; for each ring slot in order, componentwise,
+ *                 acc = (acc + P[a]) + P[b] with a = faces[f, (c + 1) % 3], b = faces[f, (c + 2) % 3]; cen = acc /
+ *                 (float)(2 slots); Q[v] = P[v] + w (cen - P[v]) (a subtract, a multiply, an add).  A Q[v] with a
+ *                 component that is not finite is dropped: the vertex keeps P[v] and counts as stuck.  Every vertex reads
+ *                 P and writes Q (Jacobi): src and dst are two buffers.
+ *   iteration     a half-step with lambda in (0, 1] (half = 0), then one with mu <= 0 (half = 1) on its result; mu = 0
+ *                 is plain Laplacian smoothing.
+ *   guard         once per iteration, P = the positions before it, Q after it; rounds r = 0, 1, ...:
+ *                 a face of the mesh is BAD iff one of its vertices differs in bits between Q and P and it crosses, as A,
+ *                 a face of a guard, as B, by the rule of "Mesh crossings" (tri_cross of csrc/cross_walk.h; a face with
+ *                 an index outside its vertex array is no face).  Every vertex of a bad face that still differs from P
+ *                 gets its bits of P back: reverted.  The rounds end with the first that reverts nothing; the reverted
+ *                 set only grows, so they end.  Afterwards every face that crosses a guard face has its three vertices
+ *                 where they were before the iteration: the crossing pairs with a guard are a subset of the input's.
+ *                 The verdict is an OR over (face, guard face) pairs: it does not depend on a guard's tree or builder.
+ * vsa_mesh_smooth_prepare: once per mesh: the rings, the sorted edge keys and the boundary flags into the workspace,
+ *   stamps -1.  The flags [V] i32 (0 / 1) are at offset 0 of the workspace.
+ * vsa_mesh_smooth_step: one half-step src -> dst, one lane per vertex, the ring summed by that lane alone in ring order.
+ *   half = 0 takes weight in (0, 1], half = 1 weight <= 0.  *state (device, i64) += the stuck vertices, one integer
+ *   atomic per wave; it is the caller's to clear.  No read, no synchronisation.
+ * vsa_mesh_smooth_guard: one lane per face, one wave per workgroup; before = P, after = Q.  A face with a vertex that
+ *   differs from P walks each guard's q16 tree (LDS stack) until its first crossing and then stamps its three vertices
+ *   with `round`.  The guard arrays are vsa_simplify_guarded's.  `round` must increase by one from call to call after
+ *   one prepare (across iterations too): the stamps are never cleared.  first_round = the `round` of this iteration's
+ *   first call: in a later round only a face with a vertex stamped in the round before is judged again (the others
+ *   have not changed since they were found clear), which changes no verdict.
+ * vsa_mesh_smooth_revert: one lane per vertex: a vertex stamped `round` whose bits in `after` differ from `before` gets
+ *   them back.  *state (device, i64) += the vertices restored, one integer atomic per wave; the caller reads it, the
+ *   one blocking read of a round.
+ * workspace = vsa_mesh_smooth_workspace_bytes(V, F) bytes, kept by the caller from prepare to the last call: 16 bytes
+ *   per vertex and 96 per face plus rocPRIM's temporary storage.
+ * No float atomics; the same inputs give the same bytes.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer, src == dst, V or F < 1, a workspace smaller than asked for, a
+ *   weight that is not finite, half = 0 with a weight outside (0, 1], half = 1 with a weight > 0, half not 0 or 1,
+ *   nr_guards outside 1 .. 4, a negative root, a depth >= 48, V_g or F_g < 1, round < 0, first_round < 0 or > round.  VSA_ERR_UNSUPPORTED: V >= 2^31
+ *   or 3 F + 3 >= 2^31 (of the mesh or of a guard), or a failed size query. */
+long long vsa_mesh_smooth_workspace_bytes(long long nr_verts, long long nr_faces);
+int vsa_mesh_smooth_prepare(const int32_t* faces, long long nr_verts, long long nr_faces, void* workspace,
+                            long long workspace_bytes, void* stream);
+int vsa_mesh_smooth_step(const float* src, float* dst, const int32_t* faces, long long nr_verts, long long nr_faces,
+                         int half, float weight, int fix_boundary, const void* workspace, long long workspace_bytes,
+                         long long* state, void* stream);
+int vsa_mesh_smooth_guard(const float* before, const float* after, const int32_t* faces, long long nr_verts,
+                          long long nr_faces, int nr_guards, const uint32_t* const* guard_qnodes,
+                          const float* const* guard_tris, const int32_t* guard_roots, const float* guard_frames,
+                          const int32_t* guard_max_depths, const float* const* guard_vertices,
+                          const long long* guard_nr_verts, const int32_t* const* guard_faces,
+                          const long long* guard_nr_faces, int first_round, int round, void* workspace,
+                          long long workspace_bytes, void* stream);
+int vsa_mesh_smooth_revert(const float* before, float* after, long long nr_verts, long long nr_faces, int round,
+                           const void* workspace, long long workspace_bytes, long long* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

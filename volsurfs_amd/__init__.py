@@ -6,4 +6,15 @@ HIP, C-ABI in include/volsurfs_hip.h).  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib"]
+_MESH_SMOOTH = ("smooth_mesh", "smooth_shells", "smooth_meshes", "SmoothReport")
+
+__all__ = ["_lib", *_MESH_SMOOTH]
+
+
+def __getattr__(name):
+    """The smoothing stage's names, imported on first use: importing the package alone still loads neither torch nor
+    the library."""
+    if name in _MESH_SMOOTH:
+        from . import mesh_smooth
+        return getattr(mesh_smooth, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

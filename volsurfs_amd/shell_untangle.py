@@ -200,12 +200,9 @@ def _ply_is_binary(path):
         return not f.readline().split()[1:2] == [b"ascii"]
 
 
-def untangle_meshes(meshes_dir, out_dir, **kw):
-    """`untangle_shells` of a `meshes*/` directory (`<level>.ply` / `.obj`, sorted by level as
-    `VolSurfs.from_meshes_path` sorts them) into `out_dir` under the same names and in the same formats: an OBJ keeps
-    its per-corner UVs, a PLY its wedge UVs, its vertex colours and its ascii / binary form.  Returns (report,
-    `check_shells(out_dir)`).  It can sit after `simplify_meshes`, or after `compute_meshes_atlas`: only vertices move,
-    so the atlas stays valid."""
+def _load_shell_dir(meshes_dir):
+    """(names, meshes, vertex colours or None) of a `meshes*/` directory (`<level>.ply` / `.obj`), sorted by level as
+    `VolSurfs.from_meshes_path` sorts them."""
     names = [n for n in os.listdir(meshes_dir) if n.endswith(".obj") or n.endswith(".ply")]
     names.sort(key=lambda x: float(x[:-4]))
     if not names:
@@ -219,7 +216,12 @@ def untangle_meshes(meshes_dir, out_dir, **kw):
             m, c = load_obj(path), None
         meshes.append(m)
         colors.append(c)
-    out, report = untangle_shells(meshes, **kw)
+    return names, meshes, colors
+
+
+def _save_shell_dir(meshes_dir, out_dir, names, out, colors):
+    """The meshes `out` into `out_dir` under the names and in the formats of `meshes_dir`: an OBJ keeps its per-corner
+    UVs, a PLY its wedge UVs, its vertex colours and its ascii / binary form."""
     os.makedirs(out_dir, exist_ok=True)
     for n, m, c in zip(names, out, colors):
         src, dst = os.path.join(meshes_dir, n), os.path.join(out_dir, n)
@@ -229,6 +231,17 @@ def untangle_meshes(meshes_dir, out_dir, **kw):
             uvs = m.faces_uvs if getattr(m, "has_uvs", True) else None
             save_ply(dst, TensorMesh(m.vertices, m.faces, uvs, device=m.vertices.device), binary=_ply_is_binary(src),
                      vertex_colors=c)
+
+
+def untangle_meshes(meshes_dir, out_dir, **kw):
+    """`untangle_shells` of a `meshes*/` directory (`<level>.ply` / `.obj`, sorted by level as
+    `VolSurfs.from_meshes_path` sorts them) into `out_dir` under the same names and in the same formats: an OBJ keeps
+    its per-corner UVs, a PLY its wedge UVs, its vertex colours and its ascii / binary form.  Returns (report,
+    `check_shells(out_dir)`).  It can sit after `simplify_meshes`, or after `compute_meshes_atlas`: only vertices move,
+    so the atlas stays valid."""
+    names, meshes, colors = _load_shell_dir(meshes_dir)
+    out, report = untangle_shells(meshes, **kw)
+    _save_shell_dir(meshes_dir, out_dir, names, out, colors)
     return report, check_shells(out_dir)
 
 
