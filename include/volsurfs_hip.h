@@ -1010,6 +1010,47 @@ int vsa_reel_next_rays_batch(const float* c2w_all, const float* intrinsics_inv_a
                              float* rays_o, float* rays_d, float* gt_rgb, float* gt_mask,
                              float* points_2d, void* stream);
 
+/* ---- Teacher distillation: virtual hemisphere cameras (trainer.py:132-166, 209-214 of the reference) ----
+ * `sample_cameras_on_hemisphere` lives in mvdatasets, an empty submodule: parity unpinned, the rule is this library's
+ * own (csrc/hemisphere_camera.h, restated in tests/distill_restated.py), fp32, + - * / sqrt only, in a fixed order:
+ *   camera c owns draws [32 c, 32 c + 32) of the call's PCG32 stream (rng_state, rng_inc): up to 16 candidate pairs
+ *   (a, b) = (2u - 1, 2v - 1), s = a a + b b; the first with s < 1 and min_height <= |1 - 2s| <= max_height gives the
+ *   direction (2a sqrt(1 - s), 2b sqrt(1 - s), |1 - 2s|) / its length, uniform by area over the band of heights; if
+ *   all 16 are refused (3e-10 of the cameras at [0, 0.95]): height (min_height + max_height) / 2, azimuth 0.
+ *   The third component is along the height axis up_sign * e[up_axis] (up_axis 0..2, up_sign +-1), the first and second
+ *   along the axes (up_axis + 1) % 3 and (up_axis + 2) % 3.  The centre is radius * direction; the pose looks at the
+ *   origin with the height axis as world up, columns x right, y down, z forward.
+ * Refused (VSA_ERR_ARG): radius not positive and finite, min_height < 0, min_height > max_height, max_height >= 1.
+ *
+ * vsa_hemisphere_cameras: the nr_cameras poses of a stream, c2w_out [C,3,4] (device), one lane per camera. */
+int vsa_hemisphere_cameras(int nr_cameras, float radius, int up_axis, int up_sign, float min_height, float max_height,
+                           uint64_t rng_state, uint64_t rng_inc, float* c2w_out, void* stream);
+
+/* One training batch from those cameras without a pose table: sample b draws (camera, col, row[, jx, jy]) as
+ * vsa_reel_next_rays_batch does, at stream position 32 nr_cameras + b (3 + 2 jitter_pixels), makes that camera's pose in
+ * registers and emits ONE ray through (col + jx, row + jy), (jx, jy) = (0.5, 0.5) unjittered.  All cameras share
+ * intrinsics_inv [3,3] (device).  camera_idx [B], rays_o / rays_d [B,3], points_2d [B,2] (may be NULL). */
+int vsa_virtual_rays_batch(const float* intrinsics_inv, int nr_cameras, int height, int width, float radius,
+                           int up_axis, int up_sign, float min_height, float max_height, int batch_size,
+                           int jitter_pixels, uint64_t rng_state, uint64_t rng_inc, int32_t* camera_idx,
+                           float* rays_o, float* rays_d, float* points_2d, void* stream);
+
+/* The mixed batch [virtual | real] of a distilled iteration in one launch.  Rays 0 .. nr_virtual - 1 are
+ * vsa_virtual_rays_batch(batch_size = nr_virtual)'s from the stream (virtual_rng_state, virtual_rng_inc), bit for bit;
+ * rays nr_virtual + b R + s are ray b R + s of vsa_reel_next_rays_batch(batch_size = nr_real) from (rng_state, rng_inc),
+ * bit for bit.  rays_o / rays_d [nr_virtual + nr_real R, 3]; gt_rgb [same, 3], gt_mask [same] and points_2d [same, 2]
+ * may be NULL.  Ground truth is per RAY here: the real half repeats its pixel's colour and mask for each of the R
+ * rays (mask 1 where mask_all is NULL); the virtual half's gt_rgb is left unwritten for the teacher, its mask is 1.
+ * virtual_camera_idx [nr_virtual], real_camera_idx [nr_real].  Either half may be empty. */
+int vsa_distill_rays_batch(const float* virtual_intrinsics_inv, int nr_virtual_cameras, float radius, int up_axis,
+                           int up_sign, float min_height, float max_height, int nr_virtual, int jitter_virtual,
+                           uint64_t virtual_rng_state, uint64_t virtual_rng_inc, const float* c2w_all,
+                           const float* intrinsics_inv_all, const float* rgb_all, const float* mask_all,
+                           int nr_cameras, int height, int width, int nr_real, int nr_rays_per_pixel,
+                           int jitter_pixels, uint64_t rng_state, uint64_t rng_inc, int32_t* virtual_camera_idx,
+                           int32_t* real_camera_idx, float* rays_o, float* rays_d, float* gt_rgb, float* gt_mask,
+                           float* points_2d, void* stream);
+
 /* ------------------------------------------------------------------------
  * The training iteration as ONE replayed HIP graph (round 6): device-side control block.
  *

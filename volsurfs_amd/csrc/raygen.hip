@@ -11,6 +11,7 @@
 // (camera rays) or per sampled pixel (reel), writes coalesced, 40 B of output per ray — an
 // HBM-write-bound kernel that costs microseconds next to the 3 ms render step.
 #include "common.h"
+#include "hemisphere_camera.h"
 #include "pcg32.h"
 #include "pinhole.h"
 
@@ -45,12 +46,62 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(
   store_ray(pinhole_ray(c2w, kinv, x, y), x, y, i, rays_o, rays_d, points_2d);
 }
 
+// sample b of a reel batch: three draws pick (camera, col, row) uniformly; its R rays follow (jittered: two
+// more draws each).  Ground truth is the picked pixel's value whatever the jitter: one row per sample, or
+// (GT_PER_RAY, the mixed batch) one row per ray.  Every batch kernel calls this one text.
+template <bool GT_PER_RAY>
+__device__ __forceinline__ void reel_sample(
+    const float* __restrict__ c2w_all, const float* __restrict__ kinv_all, const float* __restrict__ rgb_all,
+    const float* __restrict__ mask_all, int C, int H, int W, int R, int jitter, unsigned long long rng_state,
+    unsigned long long rng_inc, long long b, int* __restrict__ camera_idx, float* __restrict__ rays_o,
+    float* __restrict__ rays_d, float* __restrict__ gt_rgb, float* __restrict__ gt_mask,
+    float* __restrict__ points_2d) {
+  Pcg32 rng{rng_state, rng_inc};
+  rng.advance((unsigned long long)b * (unsigned long long)(3 + (jitter ? 2 * R : 0)));
+  const int cam = min((int)(rng.next_float() * (float)C), C - 1);
+  const int col = min((int)(rng.next_float() * (float)W), W - 1);
+  const int row = min((int)(rng.next_float() * (float)H), H - 1);
+  camera_idx[b] = cam;
+  const long long px = ((long long)cam * H + row) * W + col;
+  float rgb[3] = {0.f, 0.f, 0.f}, mask = 0.f;
+  if (gt_rgb) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = rgb_all[3 * px + c];
+  }
+  if (gt_mask) mask = mask_all ? mask_all[px] : 1.f;      // (only the mixed batch passes a mask buffer without masks)
+  if (!GT_PER_RAY) {
+    if (gt_rgb) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) gt_rgb[3 * b + c] = rgb[c];
+    }
+    if (gt_mask) gt_mask[b] = mask;
+  }
+  const float* c2w = c2w_all + 12ll * cam;
+  const float* kinv = kinv_all + 9ll * cam;
+  for (int s = 0; s < R; ++s) {
+    float jx = 0.5f, jy = 0.5f;
+    if (jitter) {
+      jx = rng.next_float();
+      jy = rng.next_float();
+    }
+    const float x = (float)col + jx, y = (float)row + jy;
+    const long long i = b * R + s;
+    store_ray(pinhole_ray(c2w, kinv, x, y), x, y, i, rays_o, rays_d, points_2d);
+    if (GT_PER_RAY) {
+      if (gt_rgb) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gt_rgb[3 * i + c] = rgb[c];
+      }
+      if (gt_mask) gt_mask[i] = mask;
+    }
+  }
+}
+
 struct ReelDummy {
   float o[3], d[3], rgb[3];
 };
 
-// sample b: three draws pick (camera, col, row) uniformly; its R rays follow (jittered: two
-// more draws each).  Ground truth is the picked pixel's value whatever the jitter.
+// one lane per sample (reel_sample)
 __global__ __launch_bounds__(256) void reel_rays_kernel(
     const float* __restrict__ c2w_all, const float* __restrict__ kinv_all,
     const float* __restrict__ rgb_all, const float* __restrict__ mask_all, int C, int H, int W,
@@ -81,29 +132,82 @@ __global__ __launch_bounds__(256) void reel_rays_kernel(
   } else if (b >= B) {
     return;
   }
+  reel_sample<false>(c2w_all, kinv_all, rgb_all, mask_all, C, H, W, R, jitter, rng_state, rng_inc, b, camera_idx,
+                     rays_o, rays_d, gt_rgb, gt_mask, points_2d);
+}
+
+// ---- teacher distillation (trainer.py:132-166): rays of virtual cameras on a hemisphere (hemisphere_camera.h)
+// one lane per camera: the poses a call's stream stands for, to memory (the Python API and the tests)
+__global__ __launch_bounds__(256) void hemisphere_cameras_kernel(HemiParams hp, unsigned long long rng_state,
+                                                                 unsigned long long rng_inc,
+                                                                 float* __restrict__ c2w_out) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= hp.nr_cameras) return;
+  float c2w[12];
+  hemisphere_camera(rng_state, rng_inc, c, hp, c2w);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) c2w_out[12ll * c + i] = c2w[i];
+}
+
+// sample b of a virtual batch: behind the cameras' part of the stream, three draws pick (camera, col, row), two more
+// the jitter; the camera's pose is made in registers and never stored.  One ray per sample.
+__device__ __forceinline__ void virtual_sample(const HemiParams& hp, const float* __restrict__ kinv, int H, int W,
+                                               int jitter, unsigned long long rng_state, unsigned long long rng_inc,
+                                               long long b, int* __restrict__ camera_idx, float* __restrict__ rays_o,
+                                               float* __restrict__ rays_d, float* __restrict__ points_2d) {
+  const int C = hp.nr_cameras;
   Pcg32 rng{rng_state, rng_inc};
-  rng.advance((unsigned long long)b * (unsigned long long)(3 + (jitter ? 2 * R : 0)));
+  rng.advance((unsigned long long)C * (unsigned long long)HEMI_CAM_STRIDE +
+              (unsigned long long)b * (unsigned long long)(3 + (jitter ? 2 : 0)));
   const int cam = min((int)(rng.next_float() * (float)C), C - 1);
   const int col = min((int)(rng.next_float() * (float)W), W - 1);
   const int row = min((int)(rng.next_float() * (float)H), H - 1);
+  float jx = 0.5f, jy = 0.5f;
+  if (jitter) {
+    jx = rng.next_float();
+    jy = rng.next_float();
+  }
   camera_idx[b] = cam;
-  const long long px = ((long long)cam * H + row) * W + col;
-  if (gt_rgb) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gt_rgb[3 * b + c] = rgb_all[3 * px + c];
+  float c2w[12];
+  hemisphere_camera(rng_state, rng_inc, cam, hp, c2w);
+  const float x = (float)col + jx, y = (float)row + jy;
+  store_ray(pinhole_ray(c2w, kinv, x, y), x, y, b, rays_o, rays_d, points_2d);
+}
+
+__global__ __launch_bounds__(256) void virtual_rays_kernel(
+    HemiParams hp, const float* __restrict__ kinv, int H, int W, int B, int jitter, unsigned long long rng_state,
+    unsigned long long rng_inc, int* __restrict__ camera_idx, float* __restrict__ rays_o, float* __restrict__ rays_d,
+    float* __restrict__ points_2d) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  virtual_sample(hp, kinv, H, W, jitter, rng_state, rng_inc, b, camera_idx, rays_o, rays_d, points_2d);
+}
+
+struct ReelArgs {      // what reel_sample reads, by value
+  const float *c2w_all, *kinv_all, *rgb_all, *mask_all;
+  int C, H, W, R, jitter;
+  unsigned long long rng_state, rng_inc;
+};
+
+// the mixed batch [virtual | real] of one iteration: lanes < n_v are virtual_rays_kernel's, the others reel_rays_kernel's
+// for sample b - n_v, writing behind the virtual rays (ground truth and mask per RAY; the virtual half's ground truth is
+// the teacher's to fill, its mask is one)
+__global__ __launch_bounds__(256) void distill_rays_kernel(
+    HemiParams hp, const float* __restrict__ kinv, int jitter_v, unsigned long long v_rng_state,
+    unsigned long long v_rng_inc, int n_v, ReelArgs ra, int n_r, int* __restrict__ camera_idx_v,
+    int* __restrict__ camera_idx_r, float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ gt_rgb,
+    float* __restrict__ gt_mask, float* __restrict__ points_2d) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (b < n_v) {
+    virtual_sample(hp, kinv, ra.H, ra.W, jitter_v, v_rng_state, v_rng_inc, b, camera_idx_v, rays_o, rays_d, points_2d);
+    if (gt_mask) gt_mask[b] = 1.0f;
+    return;
   }
-  if (gt_mask) gt_mask[b] = mask_all[px];
-  const float* c2w = c2w_all + 12ll * cam;
-  const float* kinv = kinv_all + 9ll * cam;
-  for (int s = 0; s < R; ++s) {
-    float jx = 0.5f, jy = 0.5f;
-    if (jitter) {
-      jx = rng.next_float();
-      jy = rng.next_float();
-    }
-    const float x = (float)col + jx, y = (float)row + jy;
-    store_ray(pinhole_ray(c2w, kinv, x, y), x, y, b * R + s, rays_o, rays_d, points_2d);
-  }
+  if (b - n_v >= n_r) return;
+  reel_sample<true>(ra.c2w_all, ra.kinv_all, ra.rgb_all, ra.mask_all, ra.C, ra.H, ra.W, ra.R, ra.jitter, ra.rng_state,
+                    ra.rng_inc, b - n_v, camera_idx_r, rays_o + 3ll * n_v, rays_d + 3ll * n_v,
+                    gt_rgb ? gt_rgb + 3ll * n_v : nullptr, gt_mask ? gt_mask + n_v : nullptr,
+                    points_2d ? points_2d + 2ll * n_v : nullptr);
 }
 
 // Pixel-tile order.  Full-frame rays arrive row-major (a 64-lane wave = a 64x1 strip of
@@ -243,6 +347,61 @@ extern "C" int vsa_reel_next_rays_batch_ctl(const float* c2w_all, const float* i
   hipLaunchKernelGGL(reel_rays_kernel, dim3(vsa_div_up(capacity, 256)), dim3(256), 0, (hipStream_t)stream, c2w_all,
                      intrinsics_inv_all, rgb_all, mask_all, nr_cameras, height, width, capacity, nr_rays_per_pixel,
                      jitter_pixels, 0ull, 0ull, camera_idx, rays_o, rays_d, gt_rgb, gt_mask, points_2d, ctl, dm);
+  VSA_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int vsa_hemisphere_cameras(int nr_cameras, float radius, int up_axis, int up_sign, float min_height,
+                                      float max_height, uint64_t rng_state, uint64_t rng_inc, float* c2w_out,
+                                      void* stream) {
+  const HemiParams hp{radius, min_height, max_height, up_axis, up_sign, nr_cameras};
+  if (nr_cameras < 0 || !hemi_params_ok(hp)) return VSA_ERR_ARG;
+  if (nr_cameras == 0) return VSA_OK;
+  if (!c2w_out) return VSA_ERR_ARG;
+  hipLaunchKernelGGL(hemisphere_cameras_kernel, dim3(vsa_div_up(nr_cameras, 256)), dim3(256), 0, (hipStream_t)stream,
+                     hp, (unsigned long long)rng_state, (unsigned long long)rng_inc, c2w_out);
+  VSA_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int vsa_virtual_rays_batch(const float* intrinsics_inv, int nr_cameras, int height, int width, float radius,
+                                      int up_axis, int up_sign, float min_height, float max_height, int batch_size,
+                                      int jitter_pixels, uint64_t rng_state, uint64_t rng_inc, int32_t* camera_idx,
+                                      float* rays_o, float* rays_d, float* points_2d, void* stream) {
+  const HemiParams hp{radius, min_height, max_height, up_axis, up_sign, nr_cameras};
+  if (batch_size < 0 || !hemi_params_ok(hp)) return VSA_ERR_ARG;
+  if (batch_size == 0) return VSA_OK;
+  if (nr_cameras < 1 || height < 1 || width < 1) return VSA_ERR_ARG;
+  if (!intrinsics_inv || !camera_idx || !rays_o || !rays_d) return VSA_ERR_ARG;
+  hipLaunchKernelGGL(virtual_rays_kernel, dim3(vsa_div_up(batch_size, 256)), dim3(256), 0, (hipStream_t)stream, hp,
+                     intrinsics_inv, height, width, batch_size, jitter_pixels, (unsigned long long)rng_state,
+                     (unsigned long long)rng_inc, camera_idx, rays_o, rays_d, points_2d);
+  VSA_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int vsa_distill_rays_batch(const float* virtual_intrinsics_inv, int nr_virtual_cameras, float radius,
+                                      int up_axis, int up_sign, float min_height, float max_height, int nr_virtual,
+                                      int jitter_virtual, uint64_t virtual_rng_state, uint64_t virtual_rng_inc,
+                                      const float* c2w_all, const float* intrinsics_inv_all, const float* rgb_all,
+                                      const float* mask_all, int nr_cameras, int height, int width, int nr_real,
+                                      int nr_rays_per_pixel, int jitter_pixels, uint64_t rng_state, uint64_t rng_inc,
+                                      int32_t* virtual_camera_idx, int32_t* real_camera_idx, float* rays_o,
+                                      float* rays_d, float* gt_rgb, float* gt_mask, float* points_2d, void* stream) {
+  const HemiParams hp{radius, min_height, max_height, up_axis, up_sign, nr_virtual_cameras};
+  if (nr_virtual < 0 || nr_real < 0 || nr_rays_per_pixel < 1 || !hemi_params_ok(hp)) return VSA_ERR_ARG;
+  const long long lanes = (long long)nr_virtual + nr_real;
+  if (lanes == 0) return VSA_OK;
+  if (height < 1 || width < 1 || !rays_o || !rays_d) return VSA_ERR_ARG;
+  if (nr_virtual > 0 && (nr_virtual_cameras < 1 || !virtual_intrinsics_inv || !virtual_camera_idx)) return VSA_ERR_ARG;
+  if (nr_real > 0) {
+    if (nr_cameras < 1 || !c2w_all || !intrinsics_inv_all || !real_camera_idx) return VSA_ERR_ARG;
+    if (gt_rgb && !rgb_all) return VSA_ERR_ARG;
+  }
+  if (lanes > 0x7fffffffll) return VSA_ERR_UNSUPPORTED;
+  const ReelArgs ra{c2w_all, intrinsics_inv_all, rgb_all, mask_all, nr_cameras, height, width, nr_rays_per_pixel,
+                    jitter_pixels, (unsigned long long)rng_state, (unsigned long long)rng_inc};
+  hipLaunchKernelGGL(distill_rays_kernel, dim3(vsa_div_up(lanes, 256)), dim3(256), 0, (hipStream_t)stream, hp,
+                     virtual_intrinsics_inv, jitter_virtual, (unsigned long long)virtual_rng_state,
+                     (unsigned long long)virtual_rng_inc, nr_virtual, ra, nr_real, virtual_camera_idx, real_camera_idx,
+                     rays_o, rays_d, gt_rgb, gt_mask, points_2d);
   VSA_RETURN_LAUNCH_STATUS();
 }
 

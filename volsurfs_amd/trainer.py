@@ -204,6 +204,61 @@ def train_step_from_reel(method, reel, nr_rays, jitter_pixels=True, nr_rays_per_
                       is_training_masked=is_training_masked, **kw)
 
 
+def train_step_distilled(method, virtual, reel, teacher_method, nr_rays, jitter_pixels=True, nr_rays_per_pixel=1,
+                         iter_nr=0, is_training_masked=False, **kw):
+    """trainer.py:123-235 with a teacher: half of the batch from `virtual` (camera.VirtualCameras: fresh hemisphere
+    cameras, always jittered, :138-159), coloured by `teacher_method` in eval mode under no_grad (:162-168), half from
+    the reel (:176-190, honouring `jitter_pixels` and `nr_rays_per_pixel`), trained on [teacher | real] (:209-214).
+    n_virtual = n_real = nr_rays // 2 (:157, :184).  The whole batch is one launch (camera.mixed_rays_batch); the
+    teacher's colours are written into its first rows.
+
+    The teacher is anything with `render(rays_o, rays_d, chunk=...) -> {"rgb": [n,3]}`: `chunk` is its
+    `hyper_params.test_rays_batch_size` (None without hyper_params), its `is_training` is False for the call and
+    restored afterwards, its `bg_color` is set to the student's first (:126-130) when the student has one.
+    The real half gets the mask rule of `train_step_from_reel`; gt_mask is None when the reel has no masks and training
+    is unmasked (so that `supports_fused_step` still takes the fused path), else [ones | mask].  No look-ahead."""
+    from . import _lib
+    from .camera import mixed_rays_batch
+    n = int(nr_rays) // 2
+    if n < 1:
+        raise _lib.VolsurfsHipError(f"train_step_distilled: nr_rays {nr_rays} < 2 leaves no ray per half")
+    need_mask = reel.masks is not None or bool(is_training_masked)
+    rays_o, rays_d, gt_rgb, gt_mask, _, _ = mixed_rays_batch(virtual, reel, n, n, jitter_pixels, nr_rays_per_pixel,
+                                                             with_mask=need_mask)
+    with torch.no_grad():
+        bg = getattr(method, "bg_color", None)
+        if bg is not None:
+            teacher_method.bg_color = bg.detach().reshape(1, 3)
+        was = getattr(teacher_method, "is_training", False)
+        teacher_method.is_training = False
+        try:
+            chunk = getattr(getattr(teacher_method, "hyper_params", None), "test_rays_batch_size", None)
+            gt_rgb[:n] = teacher_method.render(rays_o[:n], rays_d[:n], chunk=chunk)["rgb"]
+        finally:
+            teacher_method.is_training = was
+        if is_training_masked:
+            real_rgb, real_mask = gt_rgb[n:], gt_mask[n:]
+            real_rgb *= real_mask
+            if bg is not None:
+                real_rgb += (1 - real_mask) * bg.reshape(1, 3).to(real_rgb)
+    return train_step(method, rays_o, rays_d, gt_rgb, gt_mask, iter_nr, nr_rays=nr_rays,
+                      is_training_masked=is_training_masked, **kw)
+
+
+def load_teacher(teacher_checkpoints_path, hyper_params, bounding_primitive, bg_color=None):
+    """trainer.py:624-650: the NeRF teacher from the last checkpoint of `teacher_checkpoints_path`, in eval mode
+    (train=False: no optimiser).  `hyper_params` is a nerf.NeRFHyperParams — reading the teacher's hyper_params.cfg is
+    the caller's (configs are out of scope).  Raises when the directory holds no checkpoint."""
+    from . import _lib
+    from .nerf import NeRF
+    last = get_last_checkpoint_in_path(teacher_checkpoints_path)
+    if last is None:
+        raise _lib.VolsurfsHipError(f"load_teacher: no teacher checkpoints found in {teacher_checkpoints_path!r}")
+    return NeRF(train=False, hyper_params=hyper_params, load_checkpoints_path=teacher_checkpoints_path,
+                save_checkpoints_path=None, bounding_primitive=bounding_primitive, bg_color=bg_color,
+                start_iter_nr=int(last))
+
+
 class TrainingState:
     """utils/training.py's state carried through the callbacks (trainer.py:84-86)."""
 
@@ -215,12 +270,22 @@ class TrainingState:
 
 def train(train_data_tensor_reel, method, start_iter_nr=0, iter_finish_nr=0, callbacks=None,
           nr_training_rays=None, jitter_training_rays=True, nr_training_rays_per_pixel=1,
-          is_training_masked=False, target_nr_of_training_samples=None, world=1):
+          is_training_masked=False, target_nr_of_training_samples=None, world=1, teacher_method=None,
+          teacher_nr_cameras=100, teacher_camera_radius=None, teacher_up=(2, 1)):
     """The loop of trainer.py:57-440 around `train_step_from_reel`, with the reference's callback
     hooks (callbacks/callback.py:25-47: training_started / iter_started / iter_ended /
     training_ended, each called with phase=TrainingState).  Logging, checkpoints, test-loss
     estimates and evaluation renders of the reference loop are outside SURVEY §8 and belong to
-    the callbacks.  Returns the number of completed iterations."""
+    the callbacks.  Returns the number of completed iterations.
+
+    teacher_method (trainer.py:65, 132-166; None: nothing changes): each iteration is `train_step_distilled` — half
+    of the batch comes from `teacher_nr_cameras` fresh cameras on a hemisphere around the origin and is coloured by
+    the teacher, half from the reel.  Intrinsics, height and width of the virtual cameras are the reel's first
+    camera's (:95-97).  `teacher_camera_radius` None: the mean distance of the reel's camera centres from the origin,
+    read once before the loop (the reference passes mv_data.scene_radius, :98).  `teacher_up` = (up_axis, up_sign),
+    the hemisphere's height axis (camera.sample_cameras_on_hemisphere; +z, a Blender scene's up).  `nr_training_rays`
+    < 2 is refused.  The look-ahead of the legacy branch (train_step_from_reel) is off in this mode: the next batch
+    is drawn when its iteration starts."""
     def hook(name, **kw):
         for cb in (callbacks or []):
             fn = getattr(cb, name, None)
@@ -232,14 +297,29 @@ def train(train_data_tensor_reel, method, start_iter_nr=0, iter_finish_nr=0, cal
     nr_rays = nr_training_rays if nr_training_rays is not None else 512
     if getattr(method, "optimizer", None) is None:
         method.init_optim()
+    virtual = None
+    if teacher_method is not None:
+        from . import _lib
+        from .camera import VirtualCameras
+        reel = train_data_tensor_reel
+        if nr_rays < 2:
+            raise _lib.VolsurfsHipError(f"train: a teacher needs nr_training_rays >= 2 (one per half), got {nr_rays}")
+        radius = teacher_camera_radius
+        if radius is None:
+            radius = float(reel.c2w[:, :, 3].norm(dim=1).mean())
+        virtual = VirtualCameras(reel.intrinsics[0], reel.height, reel.width, radius, nr_cameras=teacher_nr_cameras,
+                                 up_axis=teacher_up[0], up_sign=teacher_up[1], device=reel.rgbs.device)
     hook("training_started")
     for _ in range(start_iter_nr, iter_finish_nr):
         hook("iter_started", phase=phase)
-        losses, nr_rays = train_step_from_reel(
-            method, train_data_tensor_reel, nr_rays, jitter_pixels=jitter_training_rays,
-            nr_rays_per_pixel=nr_training_rays_per_pixel, iter_nr=phase.iter_nr,
-            is_training_masked=is_training_masked, is_first_iter=phase.is_first_iter,
-            target_nr_of_training_samples=target_nr_of_training_samples, world=world)
+        kw = dict(jitter_pixels=jitter_training_rays, nr_rays_per_pixel=nr_training_rays_per_pixel,
+                  iter_nr=phase.iter_nr, is_training_masked=is_training_masked, is_first_iter=phase.is_first_iter,
+                  target_nr_of_training_samples=target_nr_of_training_samples, world=world)
+        if virtual is None:
+            losses, nr_rays = train_step_from_reel(method, train_data_tensor_reel, nr_rays, **kw)
+        else:
+            losses, nr_rays = train_step_distilled(method, virtual, train_data_tensor_reel, teacher_method, nr_rays,
+                                                   **kw)
         phase.loss_rgb = losses["loss"]
         method.is_training = False                                            # set_eval_mode (:324)
         hook("iter_ended", phase=phase, losses=losses, nr_rays=nr_rays)
