@@ -1344,13 +1344,17 @@ int vsa_simplify(const float* verts, long long nr_verts, const int32_t* faces, l
  *                 v0.w is the face id), guard_roots[g] its root node, guard_frames[6 g .. 6 g + 6) its grid (lo, step),
  *                 guard_max_depths[g] its depth (< 48), guard_vertices[g] [V_g, 3] f32 and guard_faces[g] [F_g, 3]
  *                 i32 the guard mesh on the device, guard_nr_verts[g] = V_g, guard_nr_faces[g] = F_g, both >= 1.
- *   stats         [host] 6 long long: the five of vsa_simplify, then guard_rejected = the number of (round, edge)
+ *                 This is the guard block (nr_guards and the nine arrays, in this order) of every entry point that
+ *                 takes guards: one check and one device struct (cross_guards_bind, CrossGuards of csrc/cross_walk.h).
+ *                 VSA_ERR_ARG: nr_guards outside 1..4, a NULL guard array or guard pointer, a negative root, a depth
+ *                 >= 48, V_g or F_g < 1; then VSA_ERR_UNSUPPORTED: V_g >= 2^31 or 3 F_g + 3 >= 2^31.
+ *   stats        [host] 6 long long: the five of vsa_simplify, then guard_rejected = the number of (round, edge)
  *                 verdicts the guard turned down (one integer atomicAdd per wave).
  *   stage_ms      [host] 7 floats or NULL: init, edges, cost, guard, select, collapse, compact.
  *   workspace     vsa_simplify_guarded_workspace_bytes(V, F) = vsa_simplify_workspace_bytes(V, F): the guard stage
  *                 places the vertex again as the collapse does and keeps no buffer of its own.
- * No blocking read is added to a round.  VSA_ERR_ARG, before any HIP call: nr_guards outside 1..4, a NULL guard array
- * or guard pointer, a negative root, a depth >= 48, V_g or F_g < 1, and every case of vsa_simplify. */
+ * No blocking read is added to a round.  VSA_ERR_ARG, before any HIP call: the guard block's cases, and every case of
+ * vsa_simplify. */
 long long vsa_simplify_guarded_workspace_bytes(long long nr_verts, long long nr_faces);
 int vsa_simplify_guarded(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
                          long long target_faces, int nr_guards, const uint32_t* const* guard_qnodes,
@@ -2186,7 +2190,7 @@ int vsa_shell_raster_draw(const float* tris, long long nr_slots, const int32_t* 
  *   atomic per wave; it is the caller's to clear.  No read, no synchronisation.
  * vsa_mesh_smooth_guard: one lane per face, one wave per workgroup; before = P, after = Q.  A face with a vertex that
  *   differs from P walks each guard's q16 tree (LDS stack) until its first crossing and then stamps its three vertices
- *   with `round`.  The guard arrays are vsa_simplify_guarded's.  `round` must increase by one from call to call after
+ *   with `round`.  The guard block is vsa_simplify_guarded's, arrays and errors.  `round` must increase by one from call to call after
  *   one prepare (across iterations too): the stamps are never cleared.  first_round = the `round` of this iteration's
  *   first call: in a later round only a face with a vertex stamped in the round before is judged again (the others
  *   have not changed since they were found clear), which changes no verdict.
@@ -2198,8 +2202,8 @@ int vsa_shell_raster_draw(const float* tris, long long nr_slots, const int32_t* 
  * No float atomics; the same inputs give the same bytes.
  * VSA_ERR_ARG (before any HIP call): a NULL pointer, src == dst, V or F < 1, a workspace smaller than asked for, a
  *   weight that is not finite, half = 0 with a weight outside (0, 1], half = 1 with a weight > 0, half not 0 or 1,
- *   nr_guards outside 1 .. 4, a negative root, a depth >= 48, V_g or F_g < 1, round < 0, first_round < 0 or > round.  VSA_ERR_UNSUPPORTED: V >= 2^31
- *   or 3 F + 3 >= 2^31 (of the mesh or of a guard), or a failed size query. */
+ *   the guard block's cases, round < 0, first_round < 0 or > round.  VSA_ERR_UNSUPPORTED: V >= 2^31 or 3 F + 3 >= 2^31
+ *   (of the mesh or of a guard), or a failed size query. */
 long long vsa_mesh_smooth_workspace_bytes(long long nr_verts, long long nr_faces);
 int vsa_mesh_smooth_prepare(const int32_t* faces, long long nr_verts, long long nr_faces, void* workspace,
                             long long workspace_bytes, void* stream);

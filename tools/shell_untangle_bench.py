@@ -47,8 +47,8 @@ def _baseline_pair(tracer, mesh_id, against, side, margin, max_rounds, max_level
     v = mesh.vertices.detach().to(dev, torch.float32).clone()
     f = mesh.faces.detach().to(dev, torch.int32).contiguous()
     level = torch.zeros(v.shape[0], dtype=torch.int64, device=dev)
-    tree = MI._tree((tracer, against), "baseline")
-    order = MI._leaf_order(tracer, mesh_id)
+    tree = MI.tree_of((tracer, against), "baseline")
+    order = MI.leaf_order(tracer, mesh_id)
     s, m0 = torch.tensor(float(side), device=dev), torch.tensor(margin, dtype=torch.float32, device=dev)
     rounds, converged = 0, False
     for _ in range(max_rounds):
@@ -67,7 +67,7 @@ def _baseline_pair(tracer, mesh_id, against, side, margin, max_rounds, max_level
         g = torch.where((dist < 0)[:, None], -g, g)
         moved = violated & torch.isfinite(g).all(1)
         v = torch.where(moved[:, None], v + t[:, None] * g, v).contiguous()
-        _, count_q, _, _, total = MI._cross(tree, (v, f, order), False, False, False)
+        _, count_q, _, _, total = MI.cross_passes(tree, (v, f, order), False, False, False)
         crossing = f[count_q > 0].flatten().long().unique()
         level[crossing] += 1
         rounds += 1
@@ -106,7 +106,8 @@ def main():
     from tools.simplify_bench import _fields
     from volsurfs_amd import _lib, isosurface as iso, mesh_intersect as MI
     from volsurfs_amd.raytrace import RayTracer
-    from volsurfs_amd.shell_untangle import _self_count, untangle_shells
+    from volsurfs_amd.shell_stack import self_crossing_count
+    from volsurfs_amd.shell_untangle import untangle_shells
     from volsurfs_amd.simplify import simplify_mesh
 
     kw = dict(margin=a.margin, max_rounds=a.max_rounds, max_level=a.max_level)
@@ -123,7 +124,7 @@ def main():
     tracer = fresh()
     result["tree_depth"] = tracer.max_depth
     result["before"] = {"crossings": [e["pairs"] for e in MI.shell_crossings(tracer)],
-                        "self_crossings": [int(_self_count(tracer, k).item()) for k in range(K)],
+                        "self_crossings": [int(self_crossing_count(tracer, k).item()) for k in range(K)],
                         "nested": MI.shells_nested(tracer)}
     log = {}
     out, reports = untangle_shells(tracer, log=log, **kw)

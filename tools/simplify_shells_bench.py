@@ -39,13 +39,14 @@ def _guarded_stack(meshes, ratio, stage_ms=None):
     """`simplify_shells`' K guarded calls alone (no report): the outputs; stage_ms (a list) takes one dict per shell."""
     from volsurfs_amd import simplify as smp
     from volsurfs_amd.raytrace import RayTracer
+    from volsurfs_amd.shell_stack import guard_block
     inputs = RayTracer(meshes, builder="device")
     done, out = [None] * K, [None] * K
     for k, names in smp.stack_order(K, K // 2):
         guards = [(inputs, g) if which == "in" else (done[g], 0) for which, g in names]
         V, F, r = smp._check(meshes[k], ratio)
         ms = {} if stage_ms is not None else None
-        v, f, _ = smp._simplify_guarded(V, F, smp.target_faces(F.shape[0], r), guards, ms)
+        v, f, _ = smp._simplify_guarded(V, F, smp.target_faces(F.shape[0], r), guard_block(guards, "bench"), ms)
         out[k] = smp._uvless(v, f)
         done[k] = RayTracer([out[k]], builder="device")
         if stage_ms is not None:
@@ -78,7 +79,8 @@ def main():
     from tools.simplify_bench import _fields
     from volsurfs_amd import isosurface as iso, mesh_intersect as MI
     from volsurfs_amd.raytrace import RayTracer
-    from volsurfs_amd.shell_untangle import _self_count, untangle_shells
+    from volsurfs_amd.shell_stack import self_crossing_count
+    from volsurfs_amd.shell_untangle import untangle_shells
     from volsurfs_amd.simplify import simplify_mesh, simplify_shells
 
     result = {"device": torch.cuda.get_device_name(0), "grid": a.n, "reps": a.reps, "delta_surfs": DELTA,
@@ -91,7 +93,7 @@ def main():
 
     def selfs(ms):
         t = RayTracer(ms, builder="device")
-        return [int(_self_count(t, k).item()) for k in range(K)]
+        return [int(self_crossing_count(t, k).item()) for k in range(K)]
 
     def note(what):
         print(f"[simplify_shells_bench] {what}", file=sys.stderr, flush=True)

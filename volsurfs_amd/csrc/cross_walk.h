@@ -1,7 +1,8 @@
 // Which faces of two meshes cross?  The triangle-triangle rule and the box-overlap walk of the quantised (q16) BVH
 // nodes, for the kernels of mesh_cross.hip (the count pass and the emit pass walk the same text, so that they find the
-// same pairs).  The nodes, their grid, the stack's shape and the host side of the tree arguments are the ray walk's
-// (trace_walk.h).  The rule is this library's own (the reference has no such stage): include/volsurfs_hip.h
+// same pairs) and for the guards of simplify.hip and mesh_smooth.hip (one guard block, one loop over it).  The nodes,
+// their grid, the stack's shape and the host side of the tree arguments are the ray walk's (trace_walk.h).
+// The rule is this library's own (the reference has no such stage): include/volsurfs_hip.h
 // "Mesh crossings"; tests/mesh_intersect_restated.py restates it in numpy, operation for operation.
 #pragma once
 #include "trace_walk.h"
@@ -199,6 +200,71 @@ __device__ __forceinline__ void cross_walk(const uint4* __restrict__ qnodes, con
       }
       cur = sp ? s_node[--sp][lane] : TRACE_EMPTY;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ guards
+// Up to CROSS_MAX_GUARDS meshes that a moving face must not cross: the guard block of vsa_simplify_guarded and
+// vsa_mesh_smooth_guard (include/volsurfs_hip.h states the arrays' contract once, at vsa_simplify_guarded).
+
+constexpr int CROSS_MAX_GUARDS = 4;
+
+// One guard mesh: its q16 tree as cross_walk reads it, and the grid of that tree.
+struct CrossGuard {
+  const uint4* qnodes;
+  const float4* tris;
+  int root;
+  float frame[6];
+  CrossMesh mesh;
+};
+
+struct CrossGuards {
+  int n, max_depth;
+  CrossGuard g[CROSS_MAX_GUARDS];
+};
+
+// The status of the guard arrays, in the order the entry points document, and the block for the kernels.
+inline int cross_guards_bind(int nr_guards, const uint32_t* const* guard_qnodes, const float* const* guard_tris,
+                             const int32_t* guard_roots, const float* guard_frames, const int32_t* guard_max_depths,
+                             const float* const* guard_vertices, const long long* guard_nr_verts,
+                             const int32_t* const* guard_faces, const long long* guard_nr_faces, CrossGuards* out) {
+  if (nr_guards < 1 || nr_guards > CROSS_MAX_GUARDS) return VSA_ERR_ARG;
+  if (!guard_qnodes || !guard_tris || !guard_roots || !guard_frames || !guard_max_depths || !guard_vertices ||
+      !guard_nr_verts || !guard_faces || !guard_nr_faces)
+    return VSA_ERR_ARG;
+  CrossGuards G = {};
+  G.n = nr_guards;
+  for (int g = 0; g < nr_guards; ++g) {
+    if (const int rc = check_qtree(guard_qnodes[g], guard_tris[g], guard_roots + g, guard_frames + 6 * g, 1,
+                                   guard_max_depths[g], VSA_ERR_ARG))
+      return rc;
+    if (guard_roots[g] < 0 || !guard_vertices[g] || !guard_faces[g]) return VSA_ERR_ARG;
+    if (guard_nr_verts[g] < 1 || guard_nr_faces[g] < 1) return VSA_ERR_ARG;
+    if (guard_nr_verts[g] > 0x7fffffffll || guard_nr_faces[g] > 0x7fffffffll / 3 - 1) return VSA_ERR_UNSUPPORTED;
+    CrossGuard& d = G.g[g];
+    d.qnodes = reinterpret_cast<const uint4*>(guard_qnodes[g]);
+    d.tris = reinterpret_cast<const float4*>(guard_tris[g]);
+    d.root = guard_roots[g];
+    for (int k = 0; k < 6; ++k) d.frame[k] = guard_frames[6 * g + k];
+    d.mesh = CrossMesh{guard_vertices[g], guard_faces[g], guard_nr_verts[g], guard_nr_faces[g]};
+    G.max_depth = guard_max_depths[g] > G.max_depth ? guard_max_depths[g] : G.max_depth;
+  }
+  *out = G;
+  return VSA_OK;
+}
+
+// Does the face T (fp32 corners x, y, z) cross a face of a guard?  Sets `hit`, the lane's verdict, and never clears
+// it.  cross_walk loops on wave ballots, so every lane enters the walk of every guard: a lane that is not `live`, or
+// that has its verdict (from an earlier face too), walks from TRACE_EMPTY.
+template <int STACK>
+__device__ __forceinline__ void cross_guards_hit(const CrossGuards& G, const CrossTri& T, const float* x,
+                                                 const float* y, const float* z, bool live, bool& hit,
+                                                 int (*s_node)[TRACE_BLOCK], int lane) {
+  for (int g = 0; g < G.n; ++g) {
+    const CrossGuard& gd = G.g[g];
+    const CrossBox qb = cross_qbox(gd.frame, x, y, z);
+    cross_walk<STACK, false, false, false>(gd.qnodes, gd.tris, gd.mesh, T, qb, 0, live && !hit ? gd.root : TRACE_EMPTY,
+                                           s_node, lane, [&](int, const double*) { hit = true; });
   }
 }
 

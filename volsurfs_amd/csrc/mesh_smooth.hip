@@ -9,10 +9,11 @@
 //   atomics: the order is the contract.  Every vertex reads src and writes dst (Jacobi).  stuck leaves as one integer
 //   atomic per wave.  The unguarded path is 2 x iterations of these launches and nothing else.
 // vsa_mesh_smooth_guard: msm_guard, one lane per face of the moving mesh, one wave per workgroup.  A face with a vertex
-//   whose bits differ from P walks each guard's q16 tree (cross_walk.h: LDS stack, the wave kept together by ballots, no
-//   scratch); after its first crossing it walks no further guard -- a verdict, not a count -- and stamps its three
-//   vertices with the round number (racing stores of one value).  After an iteration's first round only a face with a
-//   vertex stamped in the round before can have a new verdict: the others are as they were when they were found clear.
+//   whose bits differ from P walks each guard's q16 tree (cross_guards_hit of cross_walk.h, vsa_simplify_guarded's
+//   guard block and loop: LDS stack, the wave kept together by ballots, no scratch); after its first crossing it walks
+//   no further guard -- a verdict, not a count -- and stamps its three vertices with the round number (racing stores
+//   of one value).  After an iteration's first round only a face with a vertex stamped in the round before can have a
+//   new verdict: the others are as they were when they were found clear.
 // vsa_mesh_smooth_revert: msm_revert, one lane per vertex.  A vertex stamped this round and still different from P is
 //   restored; the newly reverted count leaves as one integer atomic per wave.
 // Integers and a fixed fp32 order throughout: the same inputs give the same bytes.
@@ -20,8 +21,6 @@
 #include "mesh_topology.h"
 
 namespace {
-
-constexpr int MSM_MAX_GUARDS = 4;
 
 struct MsmLayout {
   size_t boundary, stamp, vstart, vend, vff, kin, kout, vin, keys, sorted, tmp, tmp_bytes, total;
@@ -120,23 +119,9 @@ __global__ __launch_bounds__(MT_BLOCK) void msm_step(const float* __restrict__ P
   if ((threadIdx.x & 63) == 0 && held) atomicAdd(state, (unsigned long long)__popcll(held));
 }
 
-// One guard mesh: its q16 tree as cross_walk reads it, and the grid of that tree.
-struct MsmGuard {
-  const uint4* qnodes;
-  const float4* tris;
-  int root;
-  float frame[6];
-  CrossMesh mesh;
-};
-
-struct MsmGuards {
-  int n, max_depth;
-  MsmGuard g[MSM_MAX_GUARDS];
-};
-
 template <int STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) void msm_guard(const float* __restrict__ P, CrossMesh m, int first, int round,
-                                                        int32_t* stamp, MsmGuards G) {
+                                                        int32_t* stamp, CrossGuards G) {
   __shared__ int s_node[STACK][TRACE_BLOCK];
   const int lane = threadIdx.x;
   const long long f = (long long)blockIdx.x * TRACE_BLOCK + lane;
@@ -155,14 +140,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void msm_guard(const float* __restrict
     moved = moved || !msm_same_bits(x[c], P[3 * v]) || !msm_same_bits(y[c], P[3 * v + 1]) ||
             !msm_same_bits(z[c], P[3 * v + 2]);
   }
-  const bool live = face && moved && touched;
   bool bad = false;
-  for (int g = 0; g < G.n; ++g) {
-    const MsmGuard& gd = G.g[g];
-    const CrossBox qb = cross_qbox(gd.frame, x, y, z);
-    cross_walk<STACK, false, false, false>(gd.qnodes, gd.tris, gd.mesh, T, qb, 0, live && !bad ? gd.root : TRACE_EMPTY,
-                                           s_node, lane, [&](int, const double*) { bad = true; });
-  }
+  cross_guards_hit<STACK>(G, T, x, y, z, face && moved && touched, bad, s_node, lane);
   if (bad) stamp[id[0]] = round, stamp[id[1]] = round, stamp[id[2]] = round;
 }
 
@@ -234,26 +213,9 @@ extern "C" int vsa_mesh_smooth_guard(const float* before, const float* after, co
                                      const int32_t* const* guard_faces, const long long* guard_nr_faces, int first_round,
                                      int round, void* workspace, long long workspace_bytes, void* stream) {
   if (!before || !after || !faces || first_round < 0 || round < first_round) return VSA_ERR_ARG;
-  if (nr_guards < 1 || nr_guards > MSM_MAX_GUARDS) return VSA_ERR_ARG;
-  if (!guard_qnodes || !guard_tris || !guard_roots || !guard_frames || !guard_max_depths || !guard_vertices ||
-      !guard_nr_verts || !guard_faces || !guard_nr_faces)
-    return VSA_ERR_ARG;
-  MsmGuards G = {};
-  G.n = nr_guards;
-  for (int g = 0; g < nr_guards; ++g) {
-    MT_TRY(check_qtree(guard_qnodes[g], guard_tris[g], guard_roots + g, guard_frames + 6 * g, 1, guard_max_depths[g],
-                       VSA_ERR_ARG));
-    if (guard_roots[g] < 0 || !guard_vertices[g] || !guard_faces[g]) return VSA_ERR_ARG;
-    if (guard_nr_verts[g] < 1 || guard_nr_faces[g] < 1) return VSA_ERR_ARG;
-    if (guard_nr_verts[g] > 0x7fffffffll || guard_nr_faces[g] > 0x7fffffffll / 3 - 1) return VSA_ERR_UNSUPPORTED;
-    MsmGuard& d = G.g[g];
-    d.qnodes = reinterpret_cast<const uint4*>(guard_qnodes[g]);
-    d.tris = reinterpret_cast<const float4*>(guard_tris[g]);
-    d.root = guard_roots[g];
-    for (int k = 0; k < 6; ++k) d.frame[k] = guard_frames[6 * g + k];
-    d.mesh = CrossMesh{guard_vertices[g], guard_faces[g], guard_nr_verts[g], guard_nr_faces[g]};
-    G.max_depth = guard_max_depths[g] > G.max_depth ? guard_max_depths[g] : G.max_depth;
-  }
+  CrossGuards G;
+  MT_TRY(cross_guards_bind(nr_guards, guard_qnodes, guard_tris, guard_roots, guard_frames, guard_max_depths,
+                           guard_vertices, guard_nr_verts, guard_faces, guard_nr_faces, &G));
   MsmLayout l;
   MT_TRY(msm_bind(nr_verts, nr_faces, workspace, workspace_bytes, &l));
   char* ws = static_cast<char*>(workspace);

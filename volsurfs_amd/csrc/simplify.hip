@@ -44,8 +44,6 @@
 #define CTR_G 6          // (round, edge) verdicts the guard turned down; read with CTR_V
 #define CTR_N 8
 
-#define SMP_MAX_GUARDS 4
-
 using mt::u64;
 
 // ------------------------------------------------------------------------------------------------ fp64 geometry
@@ -372,26 +370,13 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_cost(const float* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------ guard
 
-// One guard mesh: its q16 tree as cross_walk reads it, and the grid of that tree.
-struct SmpGuard {
-  const uint4* qnodes;
-  const float4* tris;
-  int root;
-  float frame[6];
-  CrossMesh mesh;
-};
-
-struct SmpGuards {
-  int n, max_depth;
-  SmpGuard g[SMP_MAX_GUARDS];
-};
-
 // One lane per edge id, one wave per block.  A lane whose edge is still a candidate places the new vertex as
 // smp_collapse will (recomputed: 2 x 80 bytes of Q, 2 x 12 of P and 2 x 4 of flags read per candidate, against a
 // 12-byte store per edge in smp_cost, a 12-byte load here and 36 bytes per face of workspace for a position buffer --
 // and smp_cost, which the unguarded entry shares, stays as it is), then takes the surviving faces of a's ring and of
 // b's ring one at a time.  cross_walk loops on wave ballots, so the wave stays together: the loop over the faces runs
-// to the wave's longest ring, and a lane with no face left, or with its verdict already in, walks from TRACE_EMPTY.
+// to the wave's longest ring, and a lane with no face left, or with its verdict already in, walks from TRACE_EMPTY
+// (cross_guards_hit of cross_walk.h, the loop over the guards that msm_guard shares).
 template <int STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) void smp_guard(const float* __restrict__ P, const double* __restrict__ Q,
                                                         const unsigned* __restrict__ vflag,
@@ -402,7 +387,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void smp_guard(const float* __restrict
                                                         const int32_t* __restrict__ vstart,
                                                         const int32_t* __restrict__ vend, int s,
                                                         long long* __restrict__ ctr, u64* __restrict__ ekey,
-                                                        SmpGuards G) {
+                                                        CrossGuards G) {
   __shared__ int s_node[STACK][TRACE_BLOCK];
   const int lane = threadIdx.x;
   const long long e = (long long)blockIdx.x * TRACE_BLOCK + lane;
@@ -452,13 +437,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void smp_guard(const float* __restrict
       z[c] = moved ? p[2] : P[3 * v + 2];
       T.x[c] = (double)x[c], T.y[c] = (double)y[c], T.z[c] = (double)z[c];
     }
-    for (int g = 0; g < G.n; ++g) {
-      const SmpGuard& gd = G.g[g];
-      const CrossBox qb = cross_qbox(gd.frame, x, y, z);
-      cross_walk<STACK, false, false, false>(gd.qnodes, gd.tris, gd.mesh, T, qb, 0,
-                                             have && !rejected ? gd.root : TRACE_EMPTY, s_node, lane,
-                                             [&](int, const double*) { rejected = true; });
-    }
+    cross_guards_hit<STACK>(G, T, x, y, z, have, rejected, s_node, lane);
   }
   if (rejected) ekey[e] = SMP_NONE;
   const unsigned long long turned_down = __builtin_amdgcn_ballot_w64(rejected);
@@ -708,7 +687,7 @@ int build_rings(Smp& m) {
 
 // The rounds.  `guards`: null (vsa_simplify) or the guard meshes of vsa_simplify_guarded, whose stage sits between cost
 // and select and moves the later stages' timer slots up by one; stats then has a sixth entry.
-int run(Smp& m, const float* verts, const int32_t* faces, long long target, const SmpGuards* guards, float* out_verts,
+int run(Smp& m, const float* verts, const int32_t* faces, long long target, const CrossGuards* guards, float* out_verts,
         int32_t* out_faces, long long* stats) {
   const long long V = m.V;
   const int later = guards ? 1 : 0;
@@ -851,8 +830,8 @@ namespace {
 
 // Binds the workspace and runs: the body both entry points share.
 int simplify(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, long long target_faces,
-             const SmpGuards* guards, void* workspace, long long workspace_bytes, float* out_verts, int32_t* out_faces,
-             long long* stats, float* stage_ms, void* stream) {
+             const CrossGuards* guards, void* workspace, long long workspace_bytes, float* out_verts,
+             int32_t* out_faces, long long* stats, float* stage_ms, void* stream) {
   if (!verts || !faces || !workspace || !out_verts || !out_faces || !stats || target_faces < 0) return VSA_ERR_ARG;
   MT_TRY(mt::check_vf(nr_verts, nr_faces));
   Smp m;
@@ -911,26 +890,9 @@ extern "C" int vsa_simplify_guarded(const float* verts, long long nr_verts, cons
                                     const int32_t* const* guard_faces, const long long* guard_nr_faces,
                                     void* workspace, long long workspace_bytes, float* out_verts, int32_t* out_faces,
                                     long long* stats, float* stage_ms, void* stream) {
-  if (nr_guards < 1 || nr_guards > SMP_MAX_GUARDS) return VSA_ERR_ARG;
-  if (!guard_qnodes || !guard_tris || !guard_roots || !guard_frames || !guard_max_depths || !guard_vertices ||
-      !guard_nr_verts || !guard_faces || !guard_nr_faces)
-    return VSA_ERR_ARG;
-  SmpGuards G = {};
-  G.n = nr_guards;
-  for (int g = 0; g < nr_guards; ++g) {
-    MT_TRY(check_qtree(guard_qnodes[g], guard_tris[g], guard_roots + g, guard_frames + 6 * g, 1, guard_max_depths[g],
-                       VSA_ERR_ARG));
-    if (guard_roots[g] < 0 || !guard_vertices[g] || !guard_faces[g]) return VSA_ERR_ARG;
-    if (guard_nr_verts[g] < 1 || guard_nr_faces[g] < 1) return VSA_ERR_ARG;
-    if (guard_nr_verts[g] > 0x7fffffffll || guard_nr_faces[g] > 0x7fffffffll / 3 - 1) return VSA_ERR_UNSUPPORTED;
-    SmpGuard& d = G.g[g];
-    d.qnodes = reinterpret_cast<const uint4*>(guard_qnodes[g]);
-    d.tris = reinterpret_cast<const float4*>(guard_tris[g]);
-    d.root = guard_roots[g];
-    for (int k = 0; k < 6; ++k) d.frame[k] = guard_frames[6 * g + k];
-    d.mesh = CrossMesh{guard_vertices[g], guard_faces[g], guard_nr_verts[g], guard_nr_faces[g]};
-    G.max_depth = guard_max_depths[g] > G.max_depth ? guard_max_depths[g] : G.max_depth;
-  }
+  CrossGuards G;
+  MT_TRY(cross_guards_bind(nr_guards, guard_qnodes, guard_tris, guard_roots, guard_frames, guard_max_depths,
+                           guard_vertices, guard_nr_verts, guard_faces, guard_nr_faces, &G));
   return simplify(verts, nr_verts, faces, nr_faces, target_faces, &G, workspace, workspace_bytes, out_verts, out_faces,
                   stats, stage_ms, stream);
 }

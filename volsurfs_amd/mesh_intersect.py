@@ -54,7 +54,7 @@ class SelfCrossings(collections.namedtuple("SelfCrossings", "pairs count segment
     length = _length
 
 
-def _arrays(mesh, device, what):
+def arrays_of(mesh, device, what):
     """(vertices [V, 3] f32, faces [F, 3] i32) of a TensorMesh, contiguous on `device`."""
     v = mesh.vertices.detach().to(device, torch.float32).contiguous()
     f = mesh.faces.detach().to(device, torch.int32).contiguous()
@@ -64,11 +64,11 @@ def _arrays(mesh, device, what):
     return v, f
 
 
-def _tree(mesh, what):
+def tree_of(mesh, what):
     """(tracer, mesh_id, vertices, faces) of the mesh whose tree is walked."""
     tracer, mesh_id = _resolve(mesh, what)
     tracer.require_q16(what)
-    return (tracer, mesh_id) + _arrays(tracer._meshes[mesh_id], tracer.device, what)
+    return (tracer, mesh_id) + arrays_of(tracer._meshes[mesh_id], tracer.device, what)
 
 
 def _query(mesh, device, what):
@@ -76,17 +76,18 @@ def _query(mesh, device, what):
     if isinstance(mesh, TensorMesh):
         if not mesh.vertices.is_cuda:
             raise ValueError(f"{what}: the mesh must be on cuda, got {mesh.vertices.device}")
-        return _arrays(mesh, device, what) + (None,)
+        return arrays_of(mesh, device, what) + (None,)
     tracer, mesh_id = _resolve(mesh, what)
-    return _arrays(tracer._meshes[mesh_id], device, what) + (_leaf_order(tracer, mesh_id),)
+    return arrays_of(tracer._meshes[mesh_id], device, what) + (leaf_order(tracer, mesh_id),)
 
 
-def _leaf_order(tracer, mesh_id):
+def leaf_order(tracer, mesh_id):
+    """The face ids of the tracer's mesh `mesh_id` in the order of its tree's leaf slots."""
     first, nr = tracer.mesh_tri_offset[mesh_id], tracer.mesh_nr_tris[mesh_id]
     return tracer.slot_face_id[first:first + nr].contiguous()
 
 
-def _cross(tree, query, self_mode, segments, emit, max_depth=None):
+def cross_passes(tree, query, self_mode, segments, emit, max_depth=None):
     """The two passes.  Returns (pairs or None, count_query, count_tree or None, segments or None, P)."""
     tracer, mesh_id, tv, tf = tree
     qv, qf, order = query
@@ -124,16 +125,16 @@ def _cross(tree, query, self_mode, segments, emit, max_depth=None):
 def mesh_crossings(a, b, segments=False):
     """`Crossings` of the faces of `a` against the faces of `b` (the tree walked is b's): a count pass, one blocking read
     of the number of pairs, an emit pass, a sort.  The same meshes give the same bytes whatever b's builder."""
-    tree = _tree(b, "mesh_crossings")
-    pairs, ca, cb, segs, _ = _cross(tree, _query(a, tree[0].device, "mesh_crossings"), False, segments, True)
+    tree = tree_of(b, "mesh_crossings")
+    pairs, ca, cb, segs, _ = cross_passes(tree, _query(a, tree[0].device, "mesh_crossings"), False, segments, True)
     return Crossings(pairs, ca, cb, segs)
 
 
 @torch.no_grad()
 def self_crossings(mesh, segments=False):
     """`SelfCrossings` of one mesh: the pairs i < j of its faces that cross, each evaluated with face i as A."""
-    tracer, mesh_id, v, f = tree = _tree(mesh, "self_crossings")
-    pairs, count, _, segs, _ = _cross(tree, (v, f, _leaf_order(tracer, mesh_id)), True, segments, True)
+    tracer, mesh_id, v, f = tree = tree_of(mesh, "self_crossings")
+    pairs, count, _, segs, _ = cross_passes(tree, (v, f, leaf_order(tracer, mesh_id)), True, segments, True)
     return SelfCrossings(pairs, count, segs)
 
 
@@ -146,8 +147,8 @@ def _stats(count_q, count_t, total):
 def crossing_stats(a, b):
     """(pairs, faces_a, faces_b): the number of crossing pairs, of faces of a that cross b and of faces of b that cross
     a, from the count pass alone: nothing is emitted or sorted."""
-    tree = _tree(b, "crossing_stats")
-    _, ca, cb, _, total = _cross(tree, _query(a, tree[0].device, "crossing_stats"), False, False, False)
+    tree = tree_of(b, "crossing_stats")
+    _, ca, cb, _, total = cross_passes(tree, _query(a, tree[0].device, "crossing_stats"), False, False, False)
     return _stats(ca, cb, total)
 
 
@@ -186,7 +187,7 @@ def shells_nested(meshes, sign="pseudonormal"):
         if pairs:
             out.append(False)
             continue
-        v, f = _arrays(tracer._meshes[k], tracer.device, "shells_nested")
+        v, f = arrays_of(tracer._meshes[k], tracer.device, "shells_nested")
         clusters, sizes, _ = cluster_connected_triangles(TensorMesh(v, f, device=tracer.device))
         first = torch.full((sizes.shape[0],), f.shape[0], dtype=torch.int64, device=tracer.device)
         first.scatter_reduce_(0, clusters.long(), torch.arange(f.shape[0], device=tracer.device), "amin")
@@ -202,16 +203,15 @@ def check_shells(meshes_dir, sign="pseudonormal"):
     them: {files, self_crossings = the crossing pairs i < j of each shell, crossings = `shell_crossings`, nested =
     `shells_nested`}."""
     from .mesh import load_meshes_indexed_from_path
+    from .shell_stack import self_crossing_count                  # (shell_stack is built on this module)
     meshes, paths = load_meshes_indexed_from_path(None, meshes_dir, return_paths=True)
     tracer = RayTracer(meshes, builder="device")
-    selfs = []
-    for k in range(tracer.nr_meshes):
-        tree = _tree((tracer, k), "check_shells")
-        _, _, _, _, total = _cross(tree, (tree[2], tree[3], _leaf_order(tracer, k)), True, False, False)
-        selfs.append(total)
+    selfs = [self_crossing_count(tracer, k) for k in range(tracer.nr_meshes)]
     return {"files": paths, "self_crossings": [int(t) for t in torch.cat(selfs).cpu().tolist()],
             "crossings": shell_crossings(tracer), "nested": shells_nested(tracer, sign=sign)}
 
 
+_arrays, _tree, _leaf_order, _cross = arrays_of, tree_of, leaf_order, cross_passes           # (tests call these names)
+
 __all__ = ["Crossings", "SelfCrossings", "mesh_crossings", "self_crossings", "crossing_stats", "shell_crossings",
-           "shells_nested", "check_shells"]
+           "shells_nested", "check_shells", "arrays_of", "tree_of", "leaf_order", "cross_passes"]

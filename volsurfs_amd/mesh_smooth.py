@@ -28,7 +28,7 @@ does not cross itself (self_crossings_after), anything about shells that are not
 
 * `smooth_mesh(mesh, guards=...)` — one mesh, unguarded (2 x iterations launches, no read until the statistics) or
   against 1..4 guard meshes.
-* `smooth_shells(meshes)` — a stack in `simplify_shells`' order: the anchor against its two input neighbours, then
+* `smooth_shells(meshes)` — a stack in `shell_stack.stack_order`'s order: the anchor against its two input neighbours, then
   outward and inward, each shell against its already smoothed neighbour and its other input neighbour, so the crossing
   pairs of two consecutive outputs are a subset of the input's.
 * `smooth_meshes(meshes_dir, out_dir)` — a `meshes*/` directory into the same names and formats.  The pipeline order is
@@ -36,7 +36,6 @@ does not cross itself (self_crossings_after), anything about shells that are not
   `compute_meshes_atlas`; it may also run after the atlas, since only vertices move.
 """
 import collections
-import ctypes
 import math
 import numbers
 
@@ -44,8 +43,10 @@ import torch
 
 from . import _lib
 from .mesh import TensorMesh
-
-MAX_GUARDS = 4
+from .mesh_intersect import check_shells
+from .raytrace import RayTracer
+from .shell_stack import (MAX_GUARDS, StackReports, check_stack, displacement, guard_block, load_shell_dir,
+                          resolve_guards, save_shell_dir, self_crossing_count, stack_order, with_vertices)
 
 SmoothReport = collections.namedtuple(
     "SmoothReport", "shell guards iterations moved_vertices max_displacement boundary_vertices stuck reverted "
@@ -61,11 +62,10 @@ self_crossings_after = the crossing pairs i < j of the output's own faces (None 
 not finite: no tree is built over such a mesh)."""
 
 
-class SmoothReports(list):
+class SmoothReports(StackReports):
     """The K `SmoothReport`s of `smooth_shells`, inner to outer, with the stack's own figures: crossings_in /
     crossings_out = the crossing face pairs of every consecutive pair (k, k + 1) of the inputs / of the outputs
     (`mesh_intersect.shell_crossings`), nested = `mesh_intersect.shells_nested` of the outputs."""
-    crossings_in = crossings_out = nested = None
 
 
 def workspace_bytes(nr_verts, nr_faces):
@@ -103,29 +103,10 @@ def _check_mesh(mesh, what):
     return v, f
 
 
-def _guard_args(guards):
-    """The guard block of vsa_mesh_smooth_guard (vsa_simplify_guarded's layout) for the resolved guards [(tracer,
-    mesh_id)], and the objects that keep its arrays alive."""
-    from .mesh_intersect import _tree
-    G = len(guards)
-    trees = [_tree(g, "smooth_mesh") for g in guards]             # (tracer, mesh_id, vertices, faces)
-    ptrs = lambda ts: (ctypes.c_void_p * G)(*[t.data_ptr() for t in ts])
-    frames = (ctypes.c_float * (6 * G))()
-    for i, (tracer, mesh_id, _, _) in enumerate(trees):
-        frame = ctypes.cast(tracer.q16_tree_args(mesh_id)[3], ctypes.POINTER(ctypes.c_float))
-        frames[6 * i:6 * i + 6] = frame[0:6]
-    args = (G, ptrs([t[0].qnodes for t in trees]), ptrs([t[0].tris for t in trees]),
-            (ctypes.c_int32 * G)(*[t[0].roots[t[1]] for t in trees]), frames,
-            (ctypes.c_int32 * G)(*[t[0].max_depth for t in trees]),
-            ptrs([t[2] for t in trees]), (ctypes.c_longlong * G)(*[t[2].shape[0] for t in trees]),
-            ptrs([t[3] for t in trees]), (ctypes.c_longlong * G)(*[t[3].shape[0] for t in trees]))
-    return args, trees
-
-
 @torch.no_grad()
-def _smooth(v0, f, iterations, lam, mu, fix_boundary, guards, log=None):
+def _smooth(v0, f, iterations, lam, mu, fix_boundary, block, log=None):
     """The launches: (vertices, {moved_vertices, max_displacement, boundary_vertices, stuck, reverted, guard_rounds,
-    finite}) of the checked arrays (v0, f) against the resolved guards [(tracer, mesh_id)] or None."""
+    finite}) of the checked arrays (v0, f) against the guards of `block` (`shell_stack.guard_block`) or None."""
     dev = v0.device
     V, F = v0.shape[0], f.shape[0]
     nbytes = workspace_bytes(V, F)
@@ -133,7 +114,7 @@ def _smooth(v0, f, iterations, lam, mu, fix_boundary, guards, log=None):
     state = torch.zeros(2, dtype=torch.int64, device=dev)         # stuck, reverted
     st = _lib.stream_ptr()
     _lib.call("vsa_mesh_smooth_prepare", f, V, F, ws, nbytes, st)
-    guard_args, trees = _guard_args(guards) if guards else (None, None)     # (trees: alive to the last launch)
+    guard_args, _ = block or (None, None)                         # (its second entry keeps the trees alive)
     cur, mid, new = v0, torch.empty_like(v0), torch.empty_like(v0)
     fixed = int(bool(fix_boundary))
     rnd = reverted = rounds = 0
@@ -153,10 +134,7 @@ def _smooth(v0, f, iterations, lam, mu, fix_boundary, guards, log=None):
         if log is not None:
             log.append((back, n))
         cur, new = new, (torch.empty_like(v0) if cur is v0 else cur)
-    changed = (cur.view(torch.int32) != v0.view(torch.int32)).any(1)
-    d = cur.double() - v0.double()
-    disp = torch.where(changed, ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).sqrt(),
-                       torch.zeros((), dtype=torch.float64, device=dev))
+    changed, disp = displacement(cur, v0)
     boundary = ws[:4 * V].view(torch.int32)
     s = torch.stack([changed.sum().double(), disp.max(), boundary.sum().double(), state[0].double(),
                      torch.isfinite(cur).all().double()]).cpu().tolist()
@@ -165,14 +143,8 @@ def _smooth(v0, f, iterations, lam, mu, fix_boundary, guards, log=None):
                  "stuck": int(s[3]), "reverted": reverted, "guard_rounds": rounds, "finite": bool(s[4])}
 
 
-def _with_vertices(mesh, vertices):
-    from .shell_untangle import _with_vertices as carry
-    return carry(mesh, vertices, vertices.device)
-
-
 def _self_count(tracer, mesh_id):
-    from .shell_untangle import _self_count as count
-    return int(count(tracer, mesh_id).item())
+    return int(self_crossing_count(tracer, mesh_id).item())
 
 
 def _report(shell, names, iterations, st, selfs):
@@ -188,15 +160,14 @@ def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, guard
     RayTracer(builder="device") of its own) or a pair (RayTracer, mesh_id) of a tracer with q16 nodes: after every
     iteration, no face that moved crosses a face of a guard.  `log` (a list) takes one (reverted, guard rounds) per
     iteration.  Argument errors raise before any HIP call."""
-    from .raytrace import RayTracer
-    from .simplify import _resolve_guards
     iterations, lam, mu = _check_rule(iterations, lam, mu)
     if guards is not None and len(guards) > MAX_GUARDS:
         raise ValueError(f"smooth_mesh: 1..{MAX_GUARDS} guards, got {len(guards)}")
     v0, f = _check_mesh(mesh, "smooth_mesh")
-    resolved = _resolve_guards(guards) if guards is not None and len(guards) else None
-    v, st = _smooth(v0, f, iterations, lam, mu, fix_boundary, resolved, log)
-    out = _with_vertices(mesh, v)
+    resolved = resolve_guards(guards, "smooth_mesh") if guards is not None and len(guards) else None
+    block = guard_block(resolved, "smooth_mesh") if resolved else None
+    v, st = _smooth(v0, f, iterations, lam, mu, fix_boundary, block, log)
+    out = with_vertices(mesh, v)
     selfs = _self_count(RayTracer([out], builder="device"), 0) if st["finite"] else None
     names = [("guard", i) for i in range(len(resolved or ()))]
     return out, _report(0, names, iterations, st, selfs)
@@ -205,7 +176,7 @@ def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, guard
 @torch.no_grad()
 def smooth_shells(meshes, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, anchor=None, builder="device"):
     """(meshes, reports): the K >= 2 shells `meshes` (inner to outer, cuda TensorMeshes) each smoothed under the guard
-    of its neighbours, in `simplify.stack_order`'s order: the anchor (default K // 2) against the input shells anchor - 1
+    of its neighbours, in `shell_stack.stack_order`'s order: the anchor (default K // 2) against the input shells anchor - 1
     and anchor + 1; then outward, shell k against the already smoothed shell k - 1 and the input shell k + 1 (if there is
     one); then inward, mirrored.  Two tracers are built with `builder`, one over the inputs and one that is refit, never
     rebuilt, as the shells are smoothed; the result does not depend on the builder.
@@ -213,39 +184,22 @@ def smooth_shells(meshes, iterations=10, lam=0.5, mu=-0.53, fix_boundary=True, a
     For every consecutive pair the crossing face pairs of the outputs are a subset of the inputs': a stack that comes in
     without crossings goes out without.  `reports` is a `SmoothReports`: one `SmoothReport` per shell, and crossings_in,
     crossings_out and nested of the stack.  Argument errors raise before any HIP call."""
-    from .mesh_intersect import shell_crossings, shells_nested
-    from .raytrace import RayTracer
-    from .simplify import stack_order
-    meshes = list(meshes)
-    K = len(meshes)
-    if K < 2:
-        raise ValueError(f"smooth_shells: at least 2 shells, got {K}")
-    anchor = K // 2 if anchor is None else int(anchor)
-    if not 0 <= anchor < K:
-        raise ValueError(f"smooth_shells: anchor {anchor} outside 0..{K - 1}")
-    if builder not in RayTracer.BUILDERS:
-        raise ValueError(f"builder must be one of {RayTracer.BUILDERS}, got {builder!r}")
     iterations, lam, mu = _check_rule(iterations, lam, mu)
-    for k, m in enumerate(meshes):
-        if not (m.vertices.is_cuda and m.faces.is_cuda):
-            raise ValueError(f"smooth_shells: shell {k} must be on cuda, got {m.vertices.device}")
+    meshes, K, anchor = check_stack(meshes, anchor, builder, "smooth_shells")
     arrays = [_check_mesh(m, f"smooth_shells: shell {k}") for k, m in enumerate(meshes)]
     inputs = RayTracer(meshes, builder=builder)
     done = RayTracer(meshes, builder=builder)                     # refit shell by shell: ("out", k) is its shell k
     out, stats = list(meshes), [None] * K
     for k, names in stack_order(K, anchor):
         guards = [(inputs if which == "in" else done, g) for which, g in names]
-        v, stats[k] = _smooth(*arrays[k], iterations, lam, mu, fix_boundary, guards)
+        v, stats[k] = _smooth(*arrays[k], iterations, lam, mu, fix_boundary, guard_block(guards, "smooth_shells"))
         stats[k]["guards"] = names
-        out[k] = _with_vertices(meshes[k], v)
+        out[k] = with_vertices(meshes[k], v)
         done.refit(out)
     reports = SmoothReports(
         _report(k, st["guards"], iterations, st, _self_count(done, k) if st["finite"] else None)
         for k, st in enumerate(stats))
-    reports.crossings_in = [c["pairs"] for c in shell_crossings(inputs)]
-    reports.crossings_out = [c["pairs"] for c in shell_crossings(done)]
-    reports.nested = shells_nested(done)
-    return out, reports
+    return out, reports.fill(inputs, done)
 
 
 def smooth_meshes(meshes_dir, out_dir, **kw):
@@ -254,11 +208,9 @@ def smooth_meshes(meshes_dir, out_dir, **kw):
     `untangle_meshes` keeps them: an OBJ its per-corner UVs, a PLY its wedge UVs, its vertex colours and its ascii /
     binary form.  Returns (reports, `check_shells(out_dir)`).  It sits between `clean_meshes` and `cull_meshes`; it may
     also run after `compute_meshes_atlas`: only vertices move, so the atlas stays valid."""
-    from .mesh_intersect import check_shells
-    from .shell_untangle import _load_shell_dir, _save_shell_dir
-    names, meshes, colors = _load_shell_dir(meshes_dir)
+    names, meshes, colors = load_shell_dir(meshes_dir)
     out, reports = smooth_shells(meshes, **kw)
-    _save_shell_dir(meshes_dir, out_dir, names, out, colors)
+    save_shell_dir(meshes_dir, out_dir, names, out, colors)
     return reports, check_shells(out_dir)
 
 

@@ -4,7 +4,8 @@ right for nested shells; `mesh_intersect.check_shells` says when they are not, t
 no such stage: the rule is this library's own (include/volsurfs_hip.h "Shell untangling"), restated in
 tests/shell_untangle_restated.py and unpinned.
 
-The anchor shell (the middle one by default) never moves.  The shells outside it are taken from the anchor outward, each
+The anchor shell (the middle one by default) never moves; the order is `shell_stack.stack_order`'s, each shell against
+its "out" neighbour.  The shells outside it are taken from the anchor outward, each
 moving OUTWARD (side +1) against its already final inner neighbour; then the shells inside it from the anchor inward,
 each moving INWARD (side -1) against its already final outer neighbour.  For one moving shell M against one fixed shell
 X every vertex of M carries a level, 0 at first, and the rounds repeat:
@@ -33,16 +34,16 @@ anything about shells that are not consecutive.
 """
 import collections
 import math
-import os
 import struct
 
 import torch
 
 from . import _lib
-from .mesh import TensorMesh, load_obj, load_ply, save_obj, save_ply
-from .mesh_intersect import _arrays, _cross, _leaf_order, _tree, check_shells
+from .mesh_intersect import arrays_of, check_shells, leaf_order, tree_of
 from .mesh_sdf import pseudonormals
 from .raytrace import RayTracer
+from .shell_stack import (check_stack, displacement, load_shell_dir, save_shell_dir, self_crossing_count, stack_order,
+                          with_vertices)
 
 UntangleReport = collections.namedtuple(
     "UntangleReport", "shell side against rounds moved_vertices max_displacement max_level stuck crossings_before "
@@ -69,21 +70,6 @@ def _check_rule(margin, max_rounds, max_level, sign):
     return margin, int(max_rounds), int(max_level)
 
 
-def _with_vertices(mesh, vertices, device):
-    """A new TensorMesh with these vertices and the mesh's faces, UVs and (where it carries them) vertex colours."""
-    new = TensorMesh(vertices, mesh.faces, mesh.faces_uvs, device=device)
-    for name in ("has_uvs", "vertex_colors"):
-        if hasattr(mesh, name):
-            setattr(new, name, getattr(mesh, name))
-    return new
-
-
-def _self_count(tracer, mesh_id):
-    """[1] i64 on the device: the crossing pairs i < j of shell `mesh_id` (the self count pass)."""
-    tree = _tree((tracer, mesh_id), "untangle")
-    return _cross(tree, (tree[2], tree[3], _leaf_order(tracer, mesh_id)), True, False, False)[4]
-
-
 @torch.no_grad()
 def untangle_pair(tracer, mesh_id, against, side, margin=1e-3, max_rounds=16, max_level=6, sign="pseudonormal",
                   beta=2.0, log=None):
@@ -107,12 +93,12 @@ def untangle_pair(tracer, mesh_id, against, side, margin=1e-3, max_rounds=16, ma
     if rule == "winding":
         moments, entries = tracer.winding_moments()
         moment_root = int(entries[against])
-    _, _, tv, tf = _tree((tracer, against), "untangle")
+    _, _, tv, tf = tree_of((tracer, against), "untangle")
     mesh = tracer._meshes[mesh_id]
-    v0, f = _arrays(mesh, dev, "untangle")
+    v0, f = arrays_of(mesh, dev, "untangle")
     v = v0.clone()
     V, F, Ft = v.shape[0], f.shape[0], tf.shape[0]
-    order = _leaf_order(tracer, mesh_id)
+    order = leaf_order(tracer, mesh_id)
     if order.shape[0] != F:
         raise _lib.VolsurfsHipError(f"the tracer holds {order.shape[0]} faces of a mesh of {F}")
     nbytes = _lib.workspace_bytes("vsa_shell_untangle_workspace_bytes", V)
@@ -141,14 +127,11 @@ def untangle_pair(tracer, mesh_id, against, side, margin=1e-3, max_rounds=16, ma
         if moved == 0 and pairs == 0:
             converged = True
             break
-    changed = (v.view(torch.int32) != v0.view(torch.int32)).any(1)
-    d = v.double() - v0.double()
-    disp = torch.where(changed, ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).sqrt(),
-                       torch.zeros((), dtype=torch.float64, device=dev))
+    changed, disp = displacement(v, v0)
     meshes = list(tracer._meshes)
-    meshes[mesh_id] = _with_vertices(mesh, v, dev)
+    meshes[mesh_id] = with_vertices(mesh, v)
     tracer.refit(meshes)
-    selfs = _self_count(tracer, mesh_id)
+    selfs = self_crossing_count(tracer, mesh_id)
     level = ws[:4 * V].view(torch.int32)
     summary = torch.stack([changed.sum().double(), disp.max(), level.max().double(), before[0].double(),
                            selfs[0].double()]).cpu().tolist()
@@ -164,73 +147,23 @@ def untangle_shells(meshes, anchor=None, margin=1e-3, max_rounds=16, max_level=6
     (default K // 2) never moves.  The returned meshes are new TensorMeshes with the input's faces, UVs and vertex
     colours; `report` is a list of K `UntangleReport`, the anchor's with side 0.  `log` (a dict) takes the round log
     of every moved shell: {shell: [(moved, stuck, max |t|, P), ...]}.  Argument errors raise before any HIP call."""
-    is_tracer = isinstance(meshes, RayTracer)
-    if not is_tracer:
-        meshes = list(meshes)
-    K = meshes.nr_meshes if is_tracer else len(meshes)
-    if K < 2:
-        raise ValueError(f"untangle_shells: at least 2 shells, got {K}")
-    anchor = K // 2 if anchor is None else int(anchor)
-    if not 0 <= anchor < K:
-        raise ValueError(f"untangle_shells: anchor {anchor} outside 0..{K - 1}")
     _check_rule(margin, max_rounds, max_level, sign)
     if not float(beta) > 1.0:
         raise ValueError(f"beta must be > 1 (math.inf: every leaf is summed exactly), got {beta}")
-    if not is_tracer:
-        for k, m in enumerate(meshes):
-            if not (m.vertices.is_cuda and m.faces.is_cuda):
-                raise ValueError(f"untangle_shells: shell {k} must be on cuda, got {m.vertices.device}")
+    meshes, K, anchor = check_stack(meshes, anchor, None, "untangle_shells")
     tracer = RayTracer.over(meshes)
     reports = [None] * K
     kw = dict(margin=margin, max_rounds=max_rounds, max_level=max_level, sign=sign, beta=beta)
-    for k, against, side in ([(k, k - 1, 1) for k in range(anchor + 1, K)] +
-                             [(k, k + 1, -1) for k in range(anchor - 1, -1, -1)]):
+    for k, guards in stack_order(K, anchor)[1:]:                  # (the anchor, first in the order, never moves)
+        against = dict(guards)["out"]                             # the already final neighbour
+        side = 1 if k > against else -1
         rounds = [] if log is not None else None
         reports[k] = tracer.untangle(k, against, side, log=rounds, **kw)
         if log is not None:
             log[k] = rounds
-    reports[anchor] = UntangleReport(anchor, 0, None, 0, 0, 0.0, 0, 0, 0, 0, int(_self_count(tracer, anchor).item()),
-                                     True)
-    return [_with_vertices(m, m.vertices, tracer.device) for m in tracer._meshes], reports
-
-
-def _ply_is_binary(path):
-    with open(path, "rb") as f:
-        f.readline()
-        return not f.readline().split()[1:2] == [b"ascii"]
-
-
-def _load_shell_dir(meshes_dir):
-    """(names, meshes, vertex colours or None) of a `meshes*/` directory (`<level>.ply` / `.obj`), sorted by level as
-    `VolSurfs.from_meshes_path` sorts them."""
-    names = [n for n in os.listdir(meshes_dir) if n.endswith(".obj") or n.endswith(".ply")]
-    names.sort(key=lambda x: float(x[:-4]))
-    if not names:
-        raise FileNotFoundError(f"no meshes found in {meshes_dir}")
-    meshes, colors = [], []
-    for n in names:
-        path = os.path.join(meshes_dir, n)
-        if n.endswith(".ply"):
-            m, c = load_ply(path, return_colors=True)
-        else:
-            m, c = load_obj(path), None
-        meshes.append(m)
-        colors.append(c)
-    return names, meshes, colors
-
-
-def _save_shell_dir(meshes_dir, out_dir, names, out, colors):
-    """The meshes `out` into `out_dir` under the names and in the formats of `meshes_dir`: an OBJ keeps its per-corner
-    UVs, a PLY its wedge UVs, its vertex colours and its ascii / binary form."""
-    os.makedirs(out_dir, exist_ok=True)
-    for n, m, c in zip(names, out, colors):
-        src, dst = os.path.join(meshes_dir, n), os.path.join(out_dir, n)
-        if n.endswith(".obj"):
-            save_obj(dst, m)
-        else:
-            uvs = m.faces_uvs if getattr(m, "has_uvs", True) else None
-            save_ply(dst, TensorMesh(m.vertices, m.faces, uvs, device=m.vertices.device), binary=_ply_is_binary(src),
-                     vertex_colors=c)
+    reports[anchor] = UntangleReport(anchor, 0, None, 0, 0, 0.0, 0, 0, 0, 0,
+                                     int(self_crossing_count(tracer, anchor).item()), True)
+    return [with_vertices(m, m.vertices) for m in tracer._meshes], reports
 
 
 def untangle_meshes(meshes_dir, out_dir, **kw):
@@ -239,9 +172,9 @@ def untangle_meshes(meshes_dir, out_dir, **kw):
     its per-corner UVs, a PLY its wedge UVs, its vertex colours and its ascii / binary form.  Returns (report,
     `check_shells(out_dir)`).  It can sit after `simplify_meshes`, or after `compute_meshes_atlas`: only vertices move,
     so the atlas stays valid."""
-    names, meshes, colors = _load_shell_dir(meshes_dir)
+    names, meshes, colors = load_shell_dir(meshes_dir)
     out, report = untangle_shells(meshes, **kw)
-    _save_shell_dir(meshes_dir, out_dir, names, out, colors)
+    save_shell_dir(meshes_dir, out_dir, names, out, colors)
     return report, check_shells(out_dir)
 
 

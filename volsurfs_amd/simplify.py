@@ -26,10 +26,13 @@ import torch
 from . import _lib
 from .isosurface import _uvless
 from .mesh import TensorMesh, check_mesh, level_files, load_ply, save_ply
+from .mesh_intersect import check_shells
+from .raytrace import RayTracer
+from .shell_stack import (StackReports, check_stack, guard_block, resolve_guards, self_crossing_count,
+                          stack_order)
 
 STAGES = ("init", "edges", "cost", "select", "collapse", "compact")
 GUARDED_STAGES = ("init", "edges", "cost", "guard", "select", "collapse", "compact")
-MAX_GUARDS = 4
 
 ShellSimplifyReport = collections.namedtuple(
     "ShellSimplifyReport", "shell guards faces_in faces_out target rounds collapses stalled guard_rejected "
@@ -40,11 +43,10 @@ target, rounds, collapses, stalled as `simplify_mesh`'s stats; guard_rejected = 
 turned down; self_crossings = the crossing pairs i < j of the output's own faces."""
 
 
-class ShellSimplifyReports(list):
+class ShellSimplifyReports(StackReports):
     """The K `ShellSimplifyReport`s of `simplify_shells`, inner to outer, with the stack's own figures: crossings_in /
     crossings_out = the crossing face pairs of every consecutive pair (k, k + 1) of the inputs / of the outputs
     (`mesh_intersect.shell_crossings`, count passes), nested = `mesh_intersect.shells_nested` of the outputs."""
-    crossings_in = crossings_out = nested = None
 
 
 def workspace_bytes(nr_verts, nr_faces):
@@ -84,50 +86,20 @@ def _simplify(V, F, target, stage_ms=None):
     return out_v[:vout].clone(), out_f[:fout].clone(), st
 
 
-def _resolve_guards(guards):
-    """[(tracer, mesh_id)] of `guards`: a cuda TensorMesh gets a RayTracer(builder="device") of its own.  Raises
-    before any HIP call for a wrong count, a wrong type, a mesh off the device or without faces."""
-    from .mesh_distance import _resolve
-    from .raytrace import RayTracer
-    guards = list(guards)
-    if not 1 <= len(guards) <= MAX_GUARDS:
-        raise ValueError(f"simplify_mesh: 1..{MAX_GUARDS} guards, got {len(guards)}")
-    for g in guards:
-        if isinstance(g, TensorMesh):
-            if not (g.vertices.is_cuda and g.faces.is_cuda):
-                raise ValueError(f"simplify_mesh: a guard must be on cuda, got {g.vertices.device}")
-            if g.vertices.shape[0] < 1 or g.faces.shape[0] < 1:
-                raise ValueError("simplify_mesh: a guard has no faces")
-        elif not (isinstance(g, (tuple, list)) and len(g) == 2 and isinstance(g[0], RayTracer)):
-            raise TypeError(f"simplify_mesh: a guard is a TensorMesh or (RayTracer, mesh_id), got {type(g).__name__}")
-    return [_resolve(g, "simplify_mesh") for g in guards]
-
-
 @torch.no_grad()
-def _simplify_guarded(V, F, target, guards, stage_ms=None):
-    """vsa_simplify_guarded against the resolved guards [(tracer, mesh_id)]: (vertices, faces, stats dict)."""
-    from .mesh_intersect import _tree
-    nv, nf, G = int(V.shape[0]), int(F.shape[0]), len(guards)
-    trees = [_tree(g, "simplify_mesh") for g in guards]           # (tracer, mesh_id, vertices, faces); keeps them alive
-    ptrs = lambda ts: (ctypes.c_void_p * G)(*[t.data_ptr() for t in ts])
-    frames = (ctypes.c_float * (6 * G))()
-    for i, (tracer, mesh_id, _, _) in enumerate(trees):
-        frame = ctypes.cast(tracer.q16_tree_args(mesh_id)[3], ctypes.POINTER(ctypes.c_float))
-        frames[6 * i:6 * i + 6] = frame[0:6]
+def _simplify_guarded(V, F, target, block, stage_ms=None):
+    """vsa_simplify_guarded against the guards of `block` (`shell_stack.guard_block`): (vertices, faces, stats dict)."""
+    nv, nf = int(V.shape[0]), int(F.shape[0])
+    guard_args, _ = block                                         # (its second entry keeps the trees alive)
     ws = torch.empty(_lib.workspace_bytes("vsa_simplify_guarded_workspace_bytes", nv, nf), dtype=torch.uint8,
                      device=V.device)
     out_v = torch.empty(nv, 3, device=V.device)
     out_f = torch.empty(nf, 3, dtype=torch.int32, device=V.device)
     stats = (ctypes.c_longlong * 6)()
     ms = _lib.stage_array(GUARDED_STAGES, stage_ms)
-    _lib.call("vsa_simplify_guarded", V, nv, F, nf, int(target), G,
-              ptrs([t[0].qnodes for t in trees]), ptrs([t[0].tris for t in trees]),
-              (ctypes.c_int32 * G)(*[t[0].roots[t[1]] for t in trees]), frames,
-              (ctypes.c_int32 * G)(*[t[0].max_depth for t in trees]),
-              ptrs([t[2] for t in trees]), (ctypes.c_longlong * G)(*[t[2].shape[0] for t in trees]),
-              ptrs([t[3] for t in trees]), (ctypes.c_longlong * G)(*[t[3].shape[0] for t in trees]),
-              ws, ws.numel(), out_v, out_f, ctypes.cast(stats, ctypes.c_void_p),
-              ctypes.cast(ms, ctypes.c_void_p) if ms is not None else None, _lib.stream_ptr())
+    _lib.call("vsa_simplify_guarded", V, nv, F, nf, int(target), *guard_args, ws, ws.numel(), out_v, out_f,
+              ctypes.cast(stats, ctypes.c_void_p), ctypes.cast(ms, ctypes.c_void_p) if ms is not None else None,
+              _lib.stream_ptr())
     _lib.stage_update(GUARDED_STAGES, stage_ms, ms)
     rounds, collapses, stalled, vout, fout, rejected = (int(x) for x in stats)
     st = {"rounds": rounds, "collapses": collapses, "stalled": bool(stalled), "faces_in": nf, "faces_out": fout,
@@ -148,7 +120,7 @@ def simplify_mesh(mesh, target_nr_faces_ratio=0.1, return_stats=False, guards=No
     Crossings the input already has with a guard stay until a collapse removes their faces; a guard that rejects
     nothing leaves the unguarded bits."""
     V, F, ratio = _check(mesh, target_nr_faces_ratio)
-    resolved = _resolve_guards(guards) if guards is not None and len(guards) else None
+    resolved = resolve_guards(guards, "simplify_mesh") if guards is not None and len(guards) else None
     target = target_faces(F.shape[0], ratio)
     if F.shape[0] == 0:
         out = _uvless(torch.zeros(0, 3, device=V.device), torch.zeros(0, 3, dtype=torch.int32, device=V.device))
@@ -156,7 +128,8 @@ def simplify_mesh(mesh, target_nr_faces_ratio=0.1, return_stats=False, guards=No
         if resolved:
             st["guard_rejected"] = 0
     else:
-        v, f, st = _simplify_guarded(V, F, target, resolved) if resolved else _simplify(V, F, target)
+        v, f, st = (_simplify_guarded(V, F, target, guard_block(resolved, "simplify_mesh")) if resolved else
+                    _simplify(V, F, target))
         out = _uvless(v, f)
     return (out, st) if return_stats else out
 
@@ -179,17 +152,6 @@ def simplify_meshes(meshes_dir, out_dir, target_nr_faces_ratio=0.025, device="cu
     return paths
 
 
-def stack_order(K, anchor):
-    """[(shell, guards)] in the order `simplify_shells` takes K shells: the anchor against its two input neighbours,
-    then outward, then inward; guards as in `ShellSimplifyReport`, lower shell first."""
-    order = [(anchor, [("in", k) for k in (anchor - 1, anchor + 1) if 0 <= k < K])]
-    for k in range(anchor + 1, K):
-        order.append((k, [("out", k - 1)] + ([("in", k + 1)] if k + 1 < K else [])))
-    for k in range(anchor - 1, -1, -1):
-        order.append((k, ([("in", k - 1)] if k - 1 >= 0 else []) + [("out", k + 1)]))
-    return order
-
-
 @torch.no_grad()
 def simplify_shells(meshes, target_nr_faces_ratio=0.025, anchor=None, builder="device", sign="pseudonormal"):
     """(meshes, reports): the K >= 2 shells `meshes` (inner to outer, cuda TensorMeshes) each simplified to
@@ -205,25 +167,13 @@ def simplify_shells(meshes, target_nr_faces_ratio=0.025, anchor=None, builder="d
 
     `reports` is a `ShellSimplifyReports`: one `ShellSimplifyReport` per shell, and crossings_in, crossings_out and
     nested (by `sign`) of the stack.  Argument errors raise before any HIP call."""
-    from .mesh_intersect import _cross, _leaf_order, _tree, shell_crossings, shells_nested
-    from .raytrace import RayTracer
-    meshes = list(meshes)
-    K = len(meshes)
-    if K < 2:
-        raise ValueError(f"simplify_shells: at least 2 shells, got {K}")
-    anchor = K // 2 if anchor is None else int(anchor)
-    if not 0 <= anchor < K:
-        raise ValueError(f"simplify_shells: anchor {anchor} outside 0..{K - 1}")
-    if builder not in RayTracer.BUILDERS:
-        raise ValueError(f"builder must be one of {RayTracer.BUILDERS}, got {builder!r}")
+    meshes, K, anchor = check_stack(meshes, anchor, builder, "simplify_shells")
     if sign not in RayTracer.SIGNS:
         raise ValueError(f"sign must be one of {RayTracer.SIGNS}, got {sign!r}")
     ratio = float(target_nr_faces_ratio)
     if not 0.0 < ratio <= 1.0:
         raise ValueError(f"target_nr_faces_ratio must lie in (0, 1], got {ratio}")
     for k, m in enumerate(meshes):
-        if not (m.vertices.is_cuda and m.faces.is_cuda):
-            raise ValueError(f"simplify_shells: shell {k} must be on cuda, got {m.vertices.device}")
         if m.vertices.shape[0] < 1 or m.faces.shape[0] < 1:
             raise ValueError(f"simplify_shells: shell {k} is empty")
     inputs = RayTracer(meshes, builder=builder)
@@ -239,19 +189,12 @@ def simplify_shells(meshes, target_nr_faces_ratio=0.025, anchor=None, builder="d
 
     for k, names in stack_order(K, anchor):
         run(k, names)
-    selfs = []
-    for k in range(K):
-        tree = _tree((done[k], 0), "simplify_shells")
-        selfs.append(_cross(tree, (tree[2], tree[3], _leaf_order(done[k], 0)), True, False, False)[4])
-    selfs = torch.cat(selfs).cpu().tolist()
+    selfs = torch.cat([self_crossing_count(done[k], 0) for k in range(K)]).cpu().tolist()
     reports = ShellSimplifyReports(
         ShellSimplifyReport(k, st["guards"], st["faces_in"], st["faces_out"], st["target"], st["rounds"],
                             st["collapses"], st["stalled"], st["guard_rejected"], int(selfs[k]))
         for k, st in enumerate(stats))
-    reports.crossings_in = [c["pairs"] for c in shell_crossings(inputs)]
-    reports.crossings_out = [c["pairs"] for c in shell_crossings(out)]
-    reports.nested = shells_nested(out, sign=sign)
-    return out, reports
+    return out, reports.fill(inputs, out, sign)
 
 
 def simplify_meshes_nested(meshes_dir, out_dir, target_nr_faces_ratio=0.025, device="cuda"):
@@ -259,7 +202,6 @@ def simplify_meshes_nested(meshes_dir, out_dir, target_nr_faces_ratio=0.025, dev
     to outer) through `simplify_shells`, written under the same names into `out_dir` without texcoords.  Returns
     (paths, reports, `mesh_intersect.check_shells(out_dir)`).  It sits between `cull_meshes` and
     `compute_meshes_atlas`; `untangle_meshes` is for the crossings the input already had."""
-    from .mesh_intersect import check_shells
     names = level_files(meshes_dir)
     meshes = [load_ply(os.path.join(meshes_dir, n), device=device) for n in names]
     out, reports = simplify_shells(meshes, target_nr_faces_ratio)
