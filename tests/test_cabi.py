@@ -25,6 +25,19 @@ def test_exported_symbols_are_c_linkage():
         assert n in exported
 
 
+def test_kernel_sources_have_one_build():
+    """No line of csrc/*.hip, *.h, *.cpp begins a preprocessor conditional: every kernel has exactly one build, the
+    tested one (headers use #pragma once)."""
+    import glob
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    files = [f for ext in ("hip", "h", "cpp") for f in glob.glob(os.path.join(csrc, "*." + ext))]
+    assert len(files) > 40
+    bad = [f"{os.path.basename(f)}:{i}: {l.strip()}" for f in sorted(files)
+           for i, l in enumerate(open(f, encoding="utf-8"), 1) if re.match(r"\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", l)]
+    assert not bad, "\n".join(bad)
+
+
 def test_argument_errors_are_reported_not_ignored():
     """Every entry point validates its arguments before touching the device and returns a
     negative VSA_ERR_* status (SURVEY §8b "Errors": never continue silently); checked here

@@ -4,7 +4,9 @@ tag=$1; regex=$2; ctrs=$3; shift 3
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --pmc $ctrs --kernel-include-regex "$regex" --output-format csv -d $root/gpurun_out/$tag -- python3 $root/bench.py --no-cpu-baseline "$@" > $root/gpurun_out/$tag.log 2>&1
-echo "rocprof rc=$?"
+rc=$?
+echo "rocprof rc=$rc"
+[ $rc -eq 0 ] || exit $rc     # a failed GPU program: no summary, and the caller's chain ends here
 python3 - <<PY
 import csv,glob,collections
 fs=glob.glob("$root/gpurun_out/$tag/*/*counter_collection.csv")

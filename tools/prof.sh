@@ -5,7 +5,9 @@ tag=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $root/gpurun_out/$tag -- python3 $root/bench.py --no-cpu-baseline "$@" > $root/gpurun_out/$tag.log 2>&1
-echo "rocprof rc=$?"
+rc=$?
+echo "rocprof rc=$rc"
+[ $rc -eq 0 ] || exit $rc     # a failed GPU program: no summary, and the caller's chain ends here
 python3 - <<PY
 import csv,glob
 f=glob.glob("$root/gpurun_out/$tag/*/*kernel_stats.csv")[0]

@@ -7,7 +7,9 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c --output-format csv -d $root/gpurun_out/traffic_${tag}_$c -- python3 $root/bench.py --no-cpu-baseline --no-noisy --steps 3 --warmup 1 "$@" > $root/gpurun_out/traffic_${tag}_$c.log 2>&1
-  echo "$c rc=$?"
+  rc=$?
+  echo "$c rc=$rc"
+  [ $rc -eq 0 ] || exit $rc     # a failed pass: the next pass is not started and nothing is summarised
 done
 python3 - <<PY
 import csv,glob,collections,json

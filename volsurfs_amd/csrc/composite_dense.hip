@@ -18,9 +18,7 @@
 
 namespace {
 
-#ifndef VSA_COMP_TILE
 #define VSA_COMP_TILE 256
-#endif
 constexpr int TILE = VSA_COMP_TILE;
 
 template <int K>

@@ -29,9 +29,7 @@ __device__ __forceinline__ float head_gelu_grad(float x, float dy) {
 // row / column division and on waves that mix GELU and copy lanes than on the GELU: 850 us for
 // 2.1 M rows against 340 us of traffic.)
 constexpr int FH_BLOCK = 256;
-#ifndef FH_ROWS_PER_TRIP
 #define FH_ROWS_PER_TRIP 8
-#endif
 constexpr int FH_ROWS = FH_ROWS_PER_TRIP;
 
 __global__ __launch_bounds__(FH_BLOCK) void field_head_fwd_kernel(const float* __restrict__ y1,

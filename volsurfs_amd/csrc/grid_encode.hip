@@ -401,17 +401,11 @@ __global__ __launch_bounds__(GS_THREADS) void grid_encode_bwd_sliced_kernel(
 //   4. grid_bin_accumulate: a workgroup per (level, slice) streams its bin (all lanes active) into
 //                        the 64-bit fixed-point LDS accumulators of the sliced kernel and flushes.
 // Traffic: 2 x 12 B x 8 L B (4.8 GB written + read at 2.1 M samples) instead of 32x the index VALU.
-#ifndef VSA_GB_SAMPLES
 #define VSA_GB_SAMPLES 512
-#endif
 constexpr int GB_SAMPLES = VSA_GB_SAMPLES;          // samples per scatter trip = threads per workgroup (512: three workgroups per CU overlap their phases; 1024 = one per CU: 1.82 -> 1.49 ms)
 constexpr int GB_MAX_SLICES = 32;                   // 2^18 entries / 2^13
-#ifndef VSA_GB_QUANTUM_LOG2
 #define VSA_GB_QUANTUM_LOG2 18
-#endif
-#ifndef GB_RPL
 #define GB_RPL 4                                    // records per lane and trip of the accumulation
-#endif
 constexpr unsigned long long GB_QUANTUM = 1ull << VSA_GB_QUANTUM_LOG2;   // records per accumulate workgroup
 
 template <int D>

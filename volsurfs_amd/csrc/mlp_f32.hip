@@ -709,9 +709,7 @@ size_t max_layer_bytes(const vsa_mlp_plan& p) {
 // with the most 32 x 32 block pairs.  Networks up to 96 wide (NerfHash) take the small instances:
 // 32 / 48 accumulator and loader registers instead of 64 / 64 leave room for a second tile in
 // flight and a fourth co-resident workgroup.
-#ifndef MLP_WG_SMALL_WGS
 #define MLP_WG_SMALL_WGS 4
-#endif
 struct WgradShape {
   int nb, q, wgs;
 };

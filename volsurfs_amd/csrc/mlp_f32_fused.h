@@ -27,11 +27,6 @@
 // MFMA work per round and SIMD: ~290 (data) + ~290 (weight) v_mfma_f32_32x32x2_f32 of 64 cycles each.
 #pragma once
 
-// FB_DIAG (timing-only builds, results WRONG; tools/diag_mlp.sh): 1 no weight-gradient MFMAs, 2 no data-gradient
-// MFMAs, 4 identity instead of the GELU evaluation, 8 no staging stores, 16 no barriers
-#ifndef FB_DIAG
-#define FB_DIAG 0
-#endif
 constexpr int FB_BLOCK = 512;               // 4 data waves + 4 weight waves
 constexpr int FB_POINTS = 4 * MLP_TILE;      // points of a round (4 waves x 32)
 constexpr int FB_SP = FB_POINTS + 4;         // staging row stride in floats: 16-byte aligned rows, 4-bank skew
@@ -120,13 +115,13 @@ __global__ __launch_bounds__(FB_BLOCK, 1) void mlp_bwd_fused_kernel(
     for (int q = 0; q < Q; ++q) accw[q] = f32x16{0}, bsum[q] = 0.f;
     for (int rd = 0; rd < rounds; ++rd) {
       for (int l = L - 1; l >= 0; --l) {
-        if (!(FB_DIAG & 16) || (rd == 0 && l == L - 1)) __syncthreads();     // B
-        if (!(FB_DIAG & 16)) __syncthreads();                                // A: layer l is staged
+        __syncthreads();     // B
+        __syncthreads();     // A: layer l is staged
         // A operand lane (i, kk): dZ[32 m + i][point], B operand lane (j, kk): A[32 b + j][point]; the k-slot -> point
         // map is free: half kk takes points 64 kk + 4 t .. + 3 of step group t (one 16-byte read = four MFMAs)
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-          if (pl[q] == l && !(FB_DIAG & 1)) {
+          if (pl[q] == l) {
             const float4* ar = reinterpret_cast<const float4*>(s_dz + (32 * pm[q] + p) * FB_SP + 64 * h);
             const float4* br = reinterpret_cast<const float4*>(s_a + (32 * pb[q] + p) * FB_SP + 64 * h);
             float bs = 0.f;
@@ -244,38 +239,35 @@ __global__ __launch_bounds__(FB_BLOCK, 1) void mlp_bwd_fused_kernel(
         for (int r = 0; r < 16; ++r) {
           const float zz = nq[b][r];
           float cdf, pdf;
-          if (FB_DIAG & 4) cdf = 0.5f, pdf = zz; else
           gelu_cdf_pdf(zz, cdf, pdf);
           gd[b][r] = __builtin_fmaf(zz, pdf, cdf);
           a[b][r] = zz * cdf;          // (rows of invalid points / absent blocks: z = 0 -> 0)
         }
     }
-    if (!(FB_DIAG & 16) || (rd == 0 && TOP)) __syncthreads();     // B: the weight waves are done with the rows
-    if (!(FB_DIAG & 8)) {
+    __syncthreads();     // B: the weight waves are done with the rows
 #pragma unroll
-      for (int b = 0; b < IB; ++b)
-        if (b < inb) {
+    for (int b = 0; b < IB; ++b)
+      if (b < inb) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float v;
-            if constexpr (BOT) v = nq[b][r]; else v = a[b][r];
-            s_a[(32 * b + rho(r, h)) * FB_SP + col] = v;
-          }
+        for (int r = 0; r < 16; ++r) {
+          float v;
+          if constexpr (BOT) v = nq[b][r]; else v = a[b][r];
+          s_a[(32 * b + rho(r, h)) * FB_SP + col] = v;
         }
+      }
 #pragma unroll
-      for (int m = 0; m < OB; ++m)
-        if (m < outb) {
+    for (int m = 0; m < OB; ++m)
+      if (m < outb) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) s_dz[(32 * m + rho(r, h)) * FB_SP + col] = dz[m][r];
-        }
-    }
-    if (!(FB_DIAG & 16)) __syncthreads();                                // A: staged
+        for (int r = 0; r < 16; ++r) s_dz[(32 * m + rho(r, h)) * FB_SP + col] = dz[m][r];
+      }
+    __syncthreads();     // A: staged
     // ---- data gradient of the own tile: dA[k][p] = sum_n W[n][k] dZ[n][p]
     f32x16 da[IB];
 #pragma unroll
     for (int b = 0; b < IB; ++b) {
       da[b] = f32x16{0};
-      if (b < inb && (!BOT || dx != nullptr) && !(FB_DIAG & 2)) {
+      if (b < inb && (!BOT || dx != nullptr)) {
 #pragma unroll
         for (int m = 0; m < OB; ++m) {
           if (m < outb) {

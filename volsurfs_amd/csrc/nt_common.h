@@ -112,7 +112,7 @@ struct Work {
 // Persistent work split (one workgroup per CU for the LDS-hungry kernels).  The launch's
 // work = n_planes x (every active texture's slots), laid out on one cost axis: plane-major,
 // and within a plane each non-empty texture contributes `ovh` units of spacing (the per-piece
-// setup: staging / zeroing / flushing LDS, fitted from per-workgroup timings, tools/fit_cost.py)
+// setup: staging / zeroing / flushing LDS, fitted from per-workgroup timings, profiles/NOTEBOOK.md A9.0)
 // followed by ceil(len / UNIT) units of UNIT slots, each weighted by wt(plane, degree, type) / 16
 // (a unit's relative cost where the kernel takes different code paths per level, or per output
 // width: type 0 = colour, 1 = alpha texture).  The axis is kept
@@ -128,7 +128,7 @@ struct NtUnitWeight16 {
 
 // ---- measured-time rebalancing of the work split (plan.balance; vsa_nt_rebalance).  The cost axis is
 // a fitted model; what it cannot know (which CU a workgroup shares with whom, table locality, the
-// scene) shows up as 4-11 % of span lost to the slowest workgroup (tools/wg_span.py).  Every
+// scene) shows up as 4-11 % of span lost to the slowest workgroup (profiles/NOTEBOOK.md A9.0).  Every
 // persistent kernel stamps its workgroups' busy times; once per frame nt_rebalance_kernel turns the
 // previous frame's times into shares of the axis.  Pieces and arithmetic are unchanged - only the
 // [lo, hi) a workgroup takes - so results are bit-identical to the equal split.
@@ -248,8 +248,8 @@ __device__ __forceinline__ int nt_wave_incl_scan(int v) {
 // The split with ONE TEXTURE PER LANE (up to 64 textures = 8 shells; more fall back to the scalar
 // walk below).  The scalar version looks the segment table and the plan up ~100 times per
 // workgroup with dependent scalar loads: 24 us per workgroup at the head of every persistent
-// launch (stamps: 19 k cycles for the class counts, 9 k for the plane costs, 23 k for the scan —
-// `-DNT_SPAN`, g_split), whatever the size of the frame.  Here every lane loads its texture's
+// launch (stamps: 19 k cycles for the class counts, 9 k for the plane costs, 23 k for the scan),
+// whatever the size of the frame.  Here every lane loads its texture's
 // segment once (two vector loads per pass), the plane costs are wave sums, a texture's position in
 // a plane is a wave prefix sum, and the few textures that overlap the workgroup's stretch are
 // picked off a ballot.  Same axis, same integer arithmetic, same pieces.
@@ -350,24 +350,4 @@ __device__ __forceinline__ void nt_for_each_piece(const vsa_nt_plan& plan,
     c0 += pc;
   }
 }
-
-// Diagnostic build only (make EXTRA=-DNT_SPAN; tools/wg_span.py): wall-clock begin / end of
-// every workgroup of the persistent kernels, to see how evenly the cost axis splits the work.
-#ifdef NT_SPAN
-static __device__ unsigned long long g_span[4][2048][3];
-#define NT_SPAN_MARK(id, which)                                                          \
-  if (threadIdx.x == 0 && blockIdx.x < 2048) {                                           \
-    unsigned long long t__;                                                              \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");     \
-    g_span[id][blockIdx.x][which] = t__;                                                 \
-    if (which == 0) {                                                                    \
-      unsigned hw__, xcc__;                                                              \
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw__));                 \
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc__));               \
-      g_span[id][blockIdx.x][2] = ((unsigned long long)xcc__ << 32) | hw__;             \
-    }                                                                                    \
-  }
-#else
-#define NT_SPAN_MARK(id, which)
-#endif
 

@@ -22,34 +22,18 @@ namespace {
 
 // per-piece overheads of the cost axis (units of 256 slots): forward hashed / dense, backward hashed / dense
 // (re-swept after the per-lane work split: 60/20/120/45 and 110/35/180/80 are within 2 % of these either way)
-#ifndef NT_ENC_OVH_FH
 #define NT_ENC_OVH_FH 87
-#endif
-#ifndef NT_ENC_OVH_FD
 #define NT_ENC_OVH_FD 27
-#endif
-#ifndef NT_ENC_OVH_BH
 #define NT_ENC_OVH_BH 145
-#endif
-#ifndef NT_ENC_OVH_BD
 #define NT_ENC_OVH_BD 64
-#endif
-#ifndef NT_ENC_PAIR_W
 #define NT_ENC_PAIR_W 22       /* cost of a (colour, alpha) pair unit in 1/16 of a single texture's (forward, dense) */
-#endif
 constexpr int ENC_BLOCK = 1024;     // 16 waves: a 128 KiB level pins one workgroup per CU
 constexpr int ENC_UNROLL = 8;       // slots in flight per lane (backward)
-#ifndef ENC_UNROLL_FWD_N
 #define ENC_UNROLL_FWD_N 4
-#endif
 constexpr int ENC_UNROLL_FWD = ENC_UNROLL_FWD_N;   // forward
 constexpr int ENC_UNIT = 256;       // slot granularity of the persistent work split (nt_common.h)
 constexpr int LDS_ENTRIES = 32768;    // 4-byte entries of LDS a workgroup may use (128 KiB)
 
-
-#ifndef NT_ENC_DIAG_FWD
-#define NT_ENC_DIAG_FWD 0
-#endif
 constexpr int ENC_PAIR_OFF = 15360;   // entries: the second table of a pair sits at a FIXED LDS offset (61 440 B: an
                                       // immediate of the gathers); the largest dense level has 15 136 entries
 template <bool HASHED>
@@ -60,11 +44,10 @@ __device__ __forceinline__ void nt_encode_fwd_body(
   half2_t* s_tab = reinterpret_cast<half2_t*>(s_raw);
   const long long n_entries = plan.level_offset[plan.n_levels];
   const int nl = plan.n_levels;
-  NT_SPAN_MARK(HASHED ? 1 : 0, 0);
   NT_BAL_BEGIN();
   // dense levels: pieces are (shell, degree) pairs (nt_for_each_piece, paired) — both tables in LDS
   const bool pair_mode = !HASHED && plan.nr_shells * 2 * VSA_NT_MAX_DEG <= 64;
-  // per-piece overheads and unit weights: fitted from per-workgroup timings (tools/fit_cost.py):
+  // per-piece overheads and unit weights: fitted from per-workgroup timings (profiles/NOTEBOOK.md A9.0):
   // a piece costs 87 (hashed: a 128 KiB table to stage) / 27 (dense) units of 256 slots, and a
   // unit of a level finer than the texture (no reuse of the previous slot's cell) 0.92 of one
   // that goes through the reuse bookkeeping; a pair costs NT_ENC_PAIR_W / 16 of one texture
@@ -123,11 +106,7 @@ __device__ __forceinline__ void nt_encode_fwd_body(
       constexpr bool PAIR = decltype(pair_tag)::value;
       for (int s0 = a_first + threadIdx.x * ENC_UNROLL_FWD; s0 < last; s0 += ENC_BLOCK * ENC_UNROLL_FWD) {
         float4 xyv[ENC_UNROLL_FWD / 2];
-#if NT_ENC_DIAG_FWD & 1   /* timing-only: texel centres from a 64 KiB window (L2-resident) */
-        const float4* xp = reinterpret_cast<const float4*>(slot_xy + (s0 & 0x1fff));
-#else
         const float4* xp = reinterpret_cast<const float4*>(slot_xy + s0);
-#endif
 #pragma unroll
         for (int i = 0; i < ENC_UNROLL_FWD / 2; ++i) xyv[i] = xp[i];
         CellRefS cr[ENC_UNROLL_FWD];
@@ -179,16 +158,7 @@ __device__ __forceinline__ void nt_encode_fwd_body(
             outw[u] = enc_blend(ew, cr[u].w);
           }
         }
-#if NT_ENC_DIAG_FWD & 2   /* timing-only: no feature stores */
-#pragma unroll
-        for (int u = 0; u < ENC_UNROLL_FWD; ++u) asm volatile("" ::"v"(outw[u]));
-        continue;
-#endif
-#if NT_ENC_DIAG_FWD & 4   /* timing-only: feature stores into a 64 KiB window */
-        const long long o_in = nt_feat_in_plane(nl, s0 & 0x3fff);
-#else
         const long long o_in = nt_feat_in_plane(nl, s0);
-#endif
         unsigned* op = reinterpret_cast<unsigned*>(out) + o_in;
         unsigned* op2 = reinterpret_cast<unsigned*>(out2) + o_in;
         if (s0 >= first && s0 + ENC_UNROLL_FWD <= last) {
@@ -223,7 +193,6 @@ __device__ __forceinline__ void nt_encode_fwd_body(
     }   // pass
   }, 0, 1 << 30, unit_weight, HASHED ? NT_BAL_ENC_FWD_H : NT_BAL_ENC_FWD_D, pair_mode);
   __syncthreads();
-  NT_SPAN_MARK(HASHED ? 1 : 0, 1);
   NT_BAL_END(HASHED ? NT_BAL_ENC_FWD_H : NT_BAL_ENC_FWD_D);
 }
 
@@ -268,17 +237,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_both_kernel(
 // of `level`.  NF = 1: feature `feat` only (the plane fills the LDS); NF = 2: both
 // features in one pass over the slots (two planes; levels of <= 16384 entries), which
 // shares the loads, the cell arithmetic and the indices between the features.
-#ifndef NT_ENC_DIAG
-#define NT_ENC_DIAG 0
-#endif
-#ifndef NT_ENC_FLUSH_BATCH
 #define NT_ENC_FLUSH_BATCH 8     /* table entries per thread whose flush is in flight together */
-#endif
-#if NT_ENC_DIAG & 64   /* timing-only: the scatter's LDS atomics compiled out (values kept alive) */
-#define ENC_LDS_ADD(ptr, val) asm volatile("" ::"v"(ptr), "v"(val))
-#else
-#define ENC_LDS_ADD(ptr, val) atomicAdd(ptr, val)
-#endif
 template <bool HASHED, int NF, bool MERGE>
 __device__ __forceinline__ void enc_bwd_piece(
     const vsa_nt_plan& plan, int* s_g, int level, int feat, int tex, int first, int last,
@@ -305,18 +264,13 @@ __device__ __forceinline__ void enc_bwd_piece(
     }
   }
   if (!any) return;   // nothing to add (uniform across the workgroup)
-#if NT_ENC_DIAG & 8
-  return;
-#endif
   int copies = 1;
   if (!HASHED) {
     while (copies < 32 && (long long)g.size * copies * 2 * NF <= LDS_ENTRIES) copies *= 2;
   }
   const int plane = (int)g.size * copies;   // LDS entries per feature
   __syncthreads();   // the previous piece's flush has read the planes
-#if !(NT_ENC_DIAG & 2)
   for (int i = threadIdx.x; i < plane * NF; i += ENC_BLOCK) s_g[i] = 0;
-#endif
   int* my_g = s_g + (threadIdx.x & (copies - 1)) * g.size;   // consecutive lanes -> different copies
   const int type = (tex / VSA_NT_MAX_DEG) & 1;
   const unsigned* dFw = reinterpret_cast<const unsigned*>(dfeatures + nt_feat_plane_base(plan, type, level));
@@ -337,16 +291,8 @@ __device__ __forceinline__ void enc_bwd_piece(
   float4 xyn[PD][ENC_UNROLL / 2];
   uint4 dn[PD][ENC_UNROLL / 4];
   auto request = [&](int s, float4 (&xd)[ENC_UNROLL / 2], uint4 (&dd)[ENC_UNROLL / 4]) {
-#if NT_ENC_DIAG & 16   /* timing-only: texel centres and gradients from a small window (L2-resident) */
-    const int sc = (s < s_max ? s : s_max) & 0x1fff;
-#else
     const int sc = s < s_max ? s : s_max;
-#endif
-#if NT_ENC_DIAG & 32   /* timing-only: only the texel centres from a window */
-    const float4* xp = reinterpret_cast<const float4*>(slot_xy + (sc & 0x1fff));
-#else
     const float4* xp = reinterpret_cast<const float4*>(slot_xy + sc);
-#endif
     const uint4* dp = reinterpret_cast<const uint4*>(dFw + nt_feat_in_plane(nl, sc));
 #pragma unroll
     for (int i = 0; i < ENC_UNROLL / 2; ++i) xd[i] = xp[i];
@@ -412,7 +358,7 @@ __device__ __forceinline__ void enc_bwd_piece(
 #pragma unroll
           for (int f = 0; f < NF; ++f)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) ENC_LDS_ADD(&my_g[f * plane + idx[k]], v[f][k]);
+            for (int k = 0; k < 4; ++k) atomicAdd(&my_g[f * plane + idx[k]], v[f][k]);
         } else if (cr.cx == cur_cx && cr.cy == cur_cy) {
 #pragma unroll
           for (int f = 0; f < NF; ++f)
@@ -423,7 +369,7 @@ __device__ __forceinline__ void enc_bwd_piece(
 #pragma unroll
             for (int f = 0; f < NF; ++f)
 #pragma unroll
-              for (int k = 0; k < 4; ++k) ENC_LDS_ADD(&my_g[f * plane + cur_idx[k]], acc[f][k]);
+              for (int k = 0; k < 4; ++k) atomicAdd(&my_g[f * plane + cur_idx[k]], acc[f][k]);
           }
           cur_cx = cr.cx, cur_cy = cr.cy;
           cell_indices<HASHED>(g, cr.cx, cr.cy, cur_idx);
@@ -438,7 +384,7 @@ __device__ __forceinline__ void enc_bwd_piece(
 #pragma unroll
       for (int f = 0; f < NF; ++f)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ENC_LDS_ADD(&my_g[f * plane + cur_idx[k]], acc[f][k]);
+        for (int k = 0; k < 4; ++k) atomicAdd(&my_g[f * plane + cur_idx[k]], acc[f][k]);
     }
   }
   // retire the last (unused) request here: left pending, its landing registers made the
@@ -454,9 +400,6 @@ __device__ __forceinline__ void enc_bwd_piece(
       asm volatile("" ::"v"(dn[d][i].x), "v"(dn[d][i].y), "v"(dn[d][i].z), "v"(dn[d][i].w));
   }
   __syncthreads();
-#if NT_ENC_DIAG & 1
-  return;
-#endif
   float* gt = grad_tables + ((long long)nt_param_tex(plan, tex) * n_entries + plan.level_offset[level]) * 2 + feat;
   // FB entries per thread and trip: their table values are all requested before the first one is
   // waited for.  (One entry at a time — LDS read, test, global load, add, store, with a branch in
@@ -526,10 +469,9 @@ __device__ __forceinline__ void nt_encode_bwd_body(
     float dscale_inv, const float2* __restrict__ slot_xy, const int* __restrict__ seg_start,
     float* __restrict__ grad_tables, int tex_begin, int tex_end, unsigned char* s_raw) {
   int* s_g = reinterpret_cast<int*>(s_raw);
-  NT_SPAN_MARK(HASHED ? 3 : 2, 0);
   NT_BAL_BEGIN();
   const bool full_range = tex_begin <= 0 && tex_end >= plan.nr_shells * 2 * VSA_NT_MAX_DEG;
-  // fitted (tools/fit_cost.py): 145 (hashed) / 64 (dense) units per piece (zeroing + flushing the
+  // fitted (profiles/NOTEBOOK.md A9.0): 145 (hashed) / 64 (dense) units per piece (zeroing + flushing the
   // LDS plane), and a unit on the no-merge path (level finer than the texture) costs 0.875
   auto unit_weight = [&](int pl, int deg, int) {
     return !HASHED || plan.level_scale[level0 + (pl >> 1)] < (float)plan.tex_res[deg] ? 16 : 14;
@@ -564,7 +506,6 @@ __device__ __forceinline__ void nt_encode_bwd_body(
      // a launch over a sub-range of the textures (the sliced backward of parallel.py) keeps equal shares
      full_range ? (HASHED ? NT_BAL_ENC_BWD_H : NT_BAL_ENC_BWD_D) : -1);
   __syncthreads();
-  NT_SPAN_MARK(HASHED ? 3 : 2, 1);
   if (full_range) { NT_BAL_END(HASHED ? NT_BAL_ENC_BWD_H : NT_BAL_ENC_BWD_D); }
 }
 
@@ -700,14 +641,6 @@ static int set_lds_attr(K kernel) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
   return VSA_OK;
 }
-
-#ifdef NT_SPAN
-extern "C" int vsa_span_read_encode(void* dst) {
-  VSA_HIP_TRY(hipDeviceSynchronize());
-  VSA_HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_span), sizeof(g_span)));
-  return 0;
-}
-#endif
 
 extern "C" int vsa_nt_encode_fwd(const vsa_nt_plan* plan, const void* tables_h,
                                  const float* slot_xy, const int32_t* seg_start, void* features,

@@ -38,20 +38,11 @@ namespace {
 
 constexpr int FU_BLOCK = 256;
 constexpr int FU_WAVES = FU_BLOCK / 64;
-#ifndef NT_FU_WGS_PER_CU
 #define NT_FU_WGS_PER_CU 2
-#endif
 constexpr int FU_WGS_PER_CU = NT_FU_WGS_PER_CU;
-#ifndef NT_FU_BATCH
 #define NT_FU_BATCH 4            /* levels whose 4 x NT_FU_BATCH gathers are in flight together */
-#endif
 constexpr int FU_BATCH = NT_FU_BATCH;
-#ifndef NT_FU_W_PER_GROUP
 #define NT_FU_W_PER_GROUP 1      /* 1/16 unit per further 8-channel output group */
-#endif
-#ifndef NT_FU_DIAG
-#define NT_FU_DIAG 0             /* diagnostic builds (WRONG results): 1 no table gathers, 2 no MLP, 4 no XCD grouping */
-#endif
 
 // levels [L0, L0 + FU_BATCH) of the lane's slot: all fetches first, then the blends.  The table entries are gathered
 // per lane: staging a wave's texel-row run of each level through LDS-DMA was bit-exact but slower, 0.65 -> 0.85 ms
@@ -75,7 +66,7 @@ __device__ __forceinline__ void fu_encode_batch(const vsa_nt_plan& plan, int lh,
     else
       cell_indices<false>(g, c[b].cx, c[b].cy, idx);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) e[b][k] = (NT_FU_DIAG & 1) ? (idx[k] & 0x03ff03ffu) | ((unsigned)(size_t)tl & 1u) : tl[idx[k]];
+    for (int k = 0; k < 4; ++k) e[b][k] = tl[idx[k]];
   }
 #pragma unroll
   for (int b = 0; b < FU_BATCH; ++b) F[L0 + b] = enc_blend(e[b], c[b].w);
@@ -113,7 +104,7 @@ __device__ __forceinline__ void fu_for_each_piece(const vsa_nt_plan& plan,
                                                   const int* __restrict__ seg_start, Body&& body) {
   const int n_all = plan.nr_shells * 2 * VSA_NT_MAX_DEG;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n_x = (gridDim.x % 8 == 0 && !(NT_FU_DIAG & 4)) ? 8 : 1;   // groups of workgroups that share an L2
+  const int n_x = gridDim.x % 8 == 0 ? 8 : 1;   // groups of workgroups that share an L2
   const int x = blockIdx.x % n_x, j = blockIdx.x / n_x, J = gridDim.x / n_x;
   const int gw = j * FU_WAVES + wave, GW = J * FU_WAVES;  // this wave among its group's waves
   const int rgb_deg = plan.rgb_degrees, alpha_deg = plan.alpha_degrees;
@@ -228,10 +219,6 @@ __global__ __launch_bounds__(FU_BLOCK, FU_WGS_PER_CU) void nt_encmlp_fwd_kernel(
           bxa[s] = __builtin_bit_cast(half8_t, make_uint4(F[8 * s], F[8 * s + 1], F[8 * s + 2], F[8 * s + 3]));
           bxb[s] = __builtin_bit_cast(half8_t, make_uint4(F[8 * s + 4], F[8 * s + 5], F[8 * s + 6], F[8 * s + 7]));
         }
-#if NT_FU_DIAG & 2
-        asm volatile("" ::"v"(bxa[0]), "v"(bxa[1]), "v"(bxb[0]), "v"(bxb[1]));
-        continue;
-#endif
         half8_t b2[4], b3[4];
         float16_t acc3;
         mlp_tile_fwd(wf, bxa, b2, b3, acc3);

@@ -47,13 +47,9 @@ __device__ __forceinline__ void load_features(const unsigned* __restrict__ F,
 
 // Persistent: gridDim.x workgroups split the frame's 32-slot tiles evenly
 // (nt_for_each_piece: cost axis with the weight staging of a run priced at 8 tiles).
-#ifndef NT_FWD_W_PER_GROUP
 #define NT_FWD_W_PER_GROUP 2     /* 1/16 tile units per further 8-channel output group */
-#endif
-#ifndef NT_FWD_RUN_COST
 #define NT_FWD_RUN_COST 16
-#endif
-constexpr int MLP_FWD_RUN_COST = NT_FWD_RUN_COST;   // tiles: fitted 7.6 us per run / 0.48 us per tile (tools/fit_cost.py)
+constexpr int MLP_FWD_RUN_COST = NT_FWD_RUN_COST;   // tiles: fitted 7.6 us per run / 0.48 us per tile (profiles/NOTEBOOK.md A9.0)
 constexpr int MLP_FWD_WGS_PER_CU = 3;   // 148 VGPRs -> 3 waves per SIMD, one per workgroup
 
 // PRE: also write the pre-sigmoid outputs (tests only; the production launch has no such stores).
@@ -67,10 +63,9 @@ __global__ __launch_bounds__(MLP_BLOCK, MLP_FWD_WGS_PER_CU) void nt_mlp_fwd_kern
   const int wave = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < 257; i += MLP_BLOCK) s_qt[i] = NT_QUANT_THR[i];
   __syncthreads();
-  NT_SPAN_MARK(0, 0);
   NT_BAL_BEGIN();
   // a tile's cost grows with the number of 8-channel groups the quantiser has to form and store
-  // (tools/wg_span.py: 0.85-0.88 span efficiency with equal weights)
+  // (profiles/NOTEBOOK.md A9: 0.85-0.88 span efficiency with equal weights)
   auto unit_weight = [&](int, int deg, int type) {
     const int channels = type == 0 ? 3 * (2 * deg + 1) : 2 * deg + 1;
     return 16 + NT_FWD_W_PER_GROUP * ((channels + 7) / 8 - 1);
@@ -115,7 +110,6 @@ __global__ __launch_bounds__(MLP_BLOCK, MLP_FWD_WGS_PER_CU) void nt_mlp_fwd_kern
     else if (ti.channels <= 24) run(std::integral_constant<int, 3>{});
     else run(std::integral_constant<int, 4>{});
   }, 0, 1 << 30, unit_weight, NT_BAL_MLP_FWD);
-  NT_SPAN_MARK(0, 1);
   NT_BAL_END(NT_BAL_MLP_FWD);
 }
 
@@ -179,16 +173,12 @@ __device__ __forceinline__ void prefetch_features(const vsa_nt_plan& plan,
 // plain VGPRs), hand-off is ONE workgroup barrier per tile over a double-buffered image set.
 // The tile loops are compiled once per output width (producer: 1..4 groups of 8 channels,
 // consumer: 1 or 2 k-steps of dH2); each instance owns its accumulators and its epilogue.
-// Round-2 stamps (NT_STAMP, tools/wg_timeline.py; cycles per tile, producer | consumer work):
+// Round-2 per-role cycle stamps (cycles per tile, producer | consumer work):
 // 5050 | 3880 before, 2740 | 3460 now — see profiles/NOTEBOOK.md A9.1 for what moved and what it cost.
 constexpr int PC_BLOCK = 512;
 constexpr int PC_PAIRS = 4;
-#ifndef NT_PC_S64
 #define NT_PC_S64 68
-#endif
-#ifndef NT_PC_S32
 #define NT_PC_S32 40
-#endif
 constexpr int S64 = NT_PC_S64, S32 = NT_PC_S32;   // row strides (halfs): 136 B (8-B aligned, bank-spread), 80 B (16-B aligned)
 constexpr int SET_DOUT = 0, SET_X = 32 * S32, SET_H2 = 2 * 32 * S32, SET_H1 = SET_H2 + 32 * S64;
 constexpr int SET_HALFS = SET_H1 + 32 * S64;          // one {dOut, X, H2, H1} set
@@ -233,22 +223,6 @@ __device__ __forceinline__ half8_t read_tr_s(const _Float16* img, int col_base, 
   return __builtin_bit_cast(half8_t, both);
 }
 
-#ifdef NT_STAMP
-__device__ unsigned long long g_dbg[16384 * 8];   // per-workgroup timeline of the last pc launch
-__device__ unsigned long long g_dbg_stage[16384 * 8];   // consumer wave 4 / producer wave 0: cycles per stage
-__device__ unsigned long long g_dbg_role[16384 * 4];   // {producer work, wait, consumer work, wait} cycles of wave 0 / 4
-#endif
-#ifdef NT_STAMP   // diagnostic build only (tools: make EXTRA=-DNT_STAMP): per-role cycles per tile
-#define STAMP(var)                                                               \
-  {                                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                           \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");   \
-    __builtin_amdgcn_sched_barrier(0);                                           \
-  }
-#else
-#define STAMP(var)
-#endif
-
 // LDS operations of this wave are done, then the workgroup barrier; does NOT drain the
 // vector-memory queue (prefetches and stores stay in flight across it)
 __device__ __forceinline__ void pc_barrier() {
@@ -269,11 +243,6 @@ __device__ __forceinline__ void pc_run(
     float* __restrict__ grad_weights, float* __restrict__ dfeat_abs_sum, float gw_scale) {
   half8_t* s_frag = reinterpret_cast<half8_t*>(s_raw) - PC_FRAG_ID0 * 64;   // indexed by fragment id (16|20)..35
   _Float16* s_img_all = reinterpret_cast<_Float16*>(s_raw + PC_FRAGS * 64 * 16);
-#ifdef NT_STAMP
-  unsigned long long ph0, ph1, ph2, ph3, rt0, rt1;
-  STAMP(ph0);
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt0)::"memory");
-#endif
   const int tex = wk.tex;
   const int ptex = nt_param_tex(plan, tex);     // parameters: shell 0's when the models are shared
   const TexInfo ti = tex_info(plan, seg_start, tex);
@@ -325,14 +294,8 @@ __device__ __forceinline__ void pc_run(
   float* s_part = reinterpret_cast<float*>(s_img_all) + pr * PC_PART_FLOATS;   // after the tile loop
   const int ntiles = (wk.last - wk.first + 31) >> 5;
   const int iters = (ntiles + PC_PAIRS - 1) / PC_PAIRS;     // same for every wave: barriers match
-#ifdef NT_STAMP
-  STAMP(ph1);
-#endif
 
   if (producer) {
-#ifdef NT_STAMP
-    unsigned long long tw_ = 0, tb_ = 0, q0, q1, q2;
-#endif
     // The tile loop, compiled once per number NG of 8-channel groups the texture's output has
     // (alpha textures and degree 0: 1, degrees 1-2: 2, degree 3: 3): nothing inside tests
     // ti.channels, and channels 16..31 of dOut are neither formed nor stored when NG <= 2 (the
@@ -383,7 +346,6 @@ __device__ __forceinline__ void pc_run(
         }
       };
       auto trip = [&](const int it) {
-        STAMP(q0);
         {
           // dW3 of the PREVIOUS tile, from the set written before the last barrier (the consumer
           // reads the same set meanwhile): no wait on this trip's own LDS stores
@@ -417,7 +379,6 @@ __device__ __forceinline__ void pc_run(
           // rows' loads have returned (the copy above waited for them).  Program order per trip is
           // {copy, clear stores, next loads}: the only wait on the vector-memory counter is the
           // copy's, for loads that are a whole trip old, and it is exact (nothing newer in flight).
-#if !defined(NT_DIAG_NOCLEAR)
           if (ti.channels > 0) {
             const int s0 = slot - p, nq = min(32, wk.last - s0) * ti.own_quads;
             half4_t* rows = reinterpret_cast<half4_t*>(grad_rows) + ti.row_first +
@@ -427,7 +388,6 @@ __device__ __forceinline__ void pc_run(
               rows[sl * ti.row_quads + (i - sl * ti.own_quads)] = half4_t{0, 0, 0, 0};
             }
           }
-#endif
           // the next tile's operands: unconditional (past the end the loads clamp to the last slot)
           prefetch_features(plan, features, ti.type, slot + PC_PAIRS * 32, wk.last, h, bx_next);
           load_grows(slot + PC_PAIRS * 32, gr_next);
@@ -490,15 +450,11 @@ __device__ __forceinline__ void pc_run(
             const bool keep = row_ok[g] && slot < wk.last;
 #pragma unroll
             for (int i2 = 0; i2 < 2; ++i2) {
-#ifdef NT_DIAG_NOSIG      /* diagnostic only: prices the sigmoid' of dOut in the producer's stream */
-              const unsigned db = mul_mix_pk(gb[i2], 0.25f, 0.25f);
-#else
               const half2_t o_h = {(_Float16)acc3[4 * g + 2 * i2], (_Float16)acc3[4 * g + 2 * i2 + 1]};
               const unsigned ob = __builtin_bit_cast(unsigned, o_h);
               const float sg0 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(mul_mix<0>(ob, -1.4426950408889634f)));
               const float sg1 = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(mul_mix<1>(ob, -1.4426950408889634f)));
               const unsigned db = mul_mix_pk(gb[i2], __builtin_fmaf(-sg0, sg0, sg0), __builtin_fmaf(-sg1, sg1, sg1));
-#endif
               dq[2 * g + i2] = keep ? db : 0u;
             }
           }
@@ -510,20 +466,11 @@ __device__ __forceinline__ void pc_run(
               *reinterpret_cast<uint2v_*>(row + 8 * g) = g < NG ? uint2v_{dq[2 * (g < NG ? g : 0)], dq[2 * (g < NG ? g : 0) + 1]} : uint2v_{0u, 0u};
           }
         }
-        STAMP(q1);
         pc_barrier();
-        STAMP(q2);
-#ifdef NT_STAMP
-        tw_ += q1 - q0; tb_ += q2 - q1;
-#endif
       };
       for (int it = 0; it < iters; ++it) trip(it);
       if (iters > 0) dw3_from(pair + ((iters - 1) & 1) * SET_HALFS + SET_DOUT, pair + ((iters - 1) & 1) * SET_HALFS + SET_H2);
       pc_barrier();     // the consumer's last tile
-#ifdef NT_STAMP
-      STAMP(ph2);
-      if (wave == 0 && lane == 0 && blockIdx.x < 16384) { g_dbg_role[4 * blockIdx.x + 0] = tw_; g_dbg_role[4 * blockIdx.x + 1] = tb_; }
-#endif
       // weight-gradient partials of this pair into its own 32 KiB of the (now free) image area
       __syncthreads();
       {
@@ -542,10 +489,6 @@ __device__ __forceinline__ void pc_run(
     else if (ti.channels <= 24) run_producer(std::integral_constant<int, 3>{});
     else run_producer(std::integral_constant<int, 4>{});
   } else {
-#ifdef NT_STAMP
-    unsigned long long tw_ = 0, tb_ = 0, q0, q1, q2;
-    unsigned long long st_[5] = {0, 0, 0, 0, 0};
-#endif
     auto run_consumer = [&](auto ks_tag) {
     constexpr int KS3 = decltype(ks_tag)::value;   // k-steps of dH2 = W3^T dOut
     float16_t gW2[2][2], gW1[2];
@@ -557,7 +500,6 @@ __device__ __forceinline__ void pc_run(
     }
     float16_t dabs = {0};   // per-lane sum |dF| per feature row (hash-grad fixed-point bound)
     for (int it = 0; it <= iters; ++it) {
-      STAMP(q0);
       if (it > 0) {
         const int t = it - 1;
         const int slot = wk.first + (pr + t * PC_PAIRS) * 32 + p;
@@ -568,13 +510,6 @@ __device__ __forceinline__ void pc_run(
         // round trips are in flight (issued in the order written: each MFMA of the plain version
         // waited for an LDS read issued right in front of it, ~28 exposed LDS latencies per tile).
 #define NT_FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifdef NT_STAMP
-        unsigned long long c0_, c1_, c2_, c3_, c4_, c5_;
-        STAMP(c0_);
-#define CSTAMP(v) STAMP(v)
-#else
-#define CSTAMP(v)
-#endif
         half8_t dh2[4], dh1[4];
         float16_t dx;
         {
@@ -603,7 +538,6 @@ __device__ __forceinline__ void pc_run(
         store_frags_s<S64>(priv, 0, dh2[0], dh2[1], p, h);
         store_frags_s<S64>(priv, 32, dh2[2], dh2[3], p, h);
         NT_FENCE();
-        CSTAMP(c1_);
         {
           // ---- stage 2: dH1 = W2^T dH2 (from registers) while the dH2 image lands
           half8_t f2[8], hr[4];
@@ -619,7 +553,6 @@ __device__ __forceinline__ void pc_run(
             a1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f2[4 + q], dh2[q], a1, 0, 0, 0);
           }
           NT_FENCE();
-          CSTAMP(c2_);
           // ---- stage 3: operands of dW2 += dH2 . H1^T (transposed reads), then the masks of dH1
           half8_t a2[2][2], b1[2][2];
 #pragma unroll
@@ -641,7 +574,6 @@ __device__ __forceinline__ void pc_run(
                 gW2[m][mj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2[sx][m], b1[sx][mj], gW2[m][mj], 0, 0, 0);
         }
         NT_FENCE();
-        CSTAMP(c3_);
         // ---- stage 4: dH1 image (dW2's reads of the private image are done), dX = W1^T dH1 meanwhile
         store_frags_s<S64>(priv, 0, dh1[0], dh1[1], p, h);
         store_frags_s<S64>(priv, 32, dh1[2], dh1[3], p, h);
@@ -656,7 +588,6 @@ __device__ __forceinline__ void pc_run(
 #pragma unroll
           for (int q = 0; q < 4; ++q) dx = __builtin_amdgcn_mfma_f32_32x32x16_f16(f1[q], dh1[q], dx, 0, 0, 0);
           NT_FENCE();
-          CSTAMP(c4_);
           // ---- stage 5: dW1 += dH1 . X^T
           half8_t a1t[2][2];
 #pragma unroll
@@ -670,11 +601,6 @@ __device__ __forceinline__ void pc_run(
             for (int m = 0; m < 2; ++m)
               gW1[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1t[sx][m], bxx[sx], gW1[m], 0, 0, 0);
         }
-        CSTAMP(c5_);
-#ifdef NT_STAMP
-        st_[0] += c1_ - c0_; st_[1] += c2_ - c1_; st_[2] += c3_ - c2_; st_[3] += c4_ - c3_; st_[4] += c5_ - c4_;
-#endif
-#undef CSTAMP
 #undef NT_FENCE
         if (valid) {
 #pragma unroll
@@ -692,20 +618,8 @@ __device__ __forceinline__ void pc_run(
             }
         }
       }
-      STAMP(q1);
       pc_barrier();
-      STAMP(q2);
-#ifdef NT_STAMP
-      tw_ += q1 - q0; tb_ += q2 - q1;
-#endif
     }
-#ifdef NT_STAMP
-    STAMP(ph2);
-    if (wave == PC_PAIRS && lane == 0 && blockIdx.x < 16384) {
-      g_dbg_role[4 * blockIdx.x + 2] = tw_; g_dbg_role[4 * blockIdx.x + 3] = tb_;
-      for (int i = 0; i < 5; ++i) g_dbg_stage[8 * blockIdx.x + i] = st_[i];
-    }
-#endif
     __syncthreads();
     {
       // sum |dF| per feature row: the lanes' partial sums go to the (now free) fragment area and
@@ -755,18 +669,6 @@ __device__ __forceinline__ void pc_run(
       if (v != 0.0f) atomicAdd(&dfeat_abs_sum[tex * 32 + f], v);
     }
   }
-#ifdef NT_STAMP
-  STAMP(ph3);
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1)::"memory");
-  if (threadIdx.x == 0 && blockIdx.x < 16384) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    unsigned long long* d = g_dbg + 8 * blockIdx.x;
-    d[0] = rt0; d[1] = rt1; d[2] = ((unsigned long long)xcc << 32) | hwid; d[3] = iters;
-    d[4] = ph1 - ph0; d[5] = ph2 - ph1; d[6] = ph3 - ph2; d[7] = 1 + tex;
-  }
-#endif
 }
 
 // (The one-role backward "t" of round 4 — every weight-gradient operand formed transposed by the matrix
@@ -781,10 +683,8 @@ __device__ __forceinline__ void pc_run(
 // worst-case capacity (70 % of them empty at the bench frame, each still needing the whole
 // CU's LDS to launch and exit; in-kernel timeline: 196 of 256 CUs busy on average, 26 %
 // of a workgroup's cycles in staging + reduction): 1.35 -> 0.88 ms.
-#ifndef NT_PC_RUN_COST
 #define NT_PC_RUN_COST 74
-#endif
-constexpr int PC_RUN_COST = NT_PC_RUN_COST;   // fitted: 38.6 us per run / 0.52 us per tile (tools/fit_cost.py)
+constexpr int PC_RUN_COST = NT_PC_RUN_COST;   // fitted: 38.6 us per run / 0.52 us per tile (profiles/NOTEBOOK.md A9.0)
 
 __global__ __launch_bounds__(PC_BLOCK, 2) void nt_mlp_bwd_pc_kernel(
     vsa_nt_plan plan, const _Float16* __restrict__ weights,
@@ -792,7 +692,6 @@ __global__ __launch_bounds__(PC_BLOCK, 2) void nt_mlp_bwd_pc_kernel(
     _Float16* __restrict__ grad_rows, float* __restrict__ grad_weights,
     float* __restrict__ dfeat_abs_sum, float gw_scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  NT_SPAN_MARK(1, 0);
   NT_BAL_BEGIN();
   nt_for_each_piece<32>(plan, seg_start, 1, PC_RUN_COST,
                         [&](int, int tex, int first, int last, int seg_begin, int seg_end) {
@@ -804,31 +703,10 @@ __global__ __launch_bounds__(PC_BLOCK, 2) void nt_mlp_bwd_pc_kernel(
     pc_run(plan, wk, s_raw, weights, features, seg_start, grad_rows, grad_weights, dfeat_abs_sum, gw_scale);
     __syncthreads();   // the next run re-stages the fragments
   }, 0, 1 << 30, NtUnitWeight16(), NT_BAL_MLP_BWD);
-  NT_SPAN_MARK(1, 1);
   NT_BAL_END(NT_BAL_MLP_BWD);
 }
 
 }  // namespace
-
-#ifdef NT_SPAN
-extern "C" int vsa_span_read_mlp(void* dst) {
-  VSA_HIP_TRY(hipDeviceSynchronize());
-  VSA_HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_span), sizeof(g_span)));
-  return 0;
-}
-#endif
-
-#ifdef NT_STAMP
-extern "C" int vsa_debug_read(void* dst) {
-  VSA_HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_dbg), sizeof(unsigned long long) * 16384 * 8));
-  VSA_HIP_TRY(hipMemcpyFromSymbol(static_cast<unsigned long long*>(dst) + 16384 * 8, HIP_SYMBOL(g_dbg_role),
-                                  sizeof(unsigned long long) * 16384 * 4));
-  VSA_HIP_TRY(hipMemcpyFromSymbol(static_cast<unsigned long long*>(dst) + 16384 * 12, HIP_SYMBOL(g_dbg_stage),
-                                  sizeof(unsigned long long) * 16384 * 8));
-  VSA_HIP_TRY(hipMemset(nullptr, 0, 0));
-  return 0;
-}
-#endif
 
 extern "C" int vsa_nt_mlp_fwd(const vsa_nt_plan* plan, const void* weights_h, const void* features,
                               const int32_t* seg_start, uint8_t* texels, void* pre_out,

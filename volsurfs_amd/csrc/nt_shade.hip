@@ -306,9 +306,7 @@ __device__ __forceinline__ void shade_hit(const vsa_nt_plan& plan, const HitCtx&
   }
 }
 
-#ifndef NT_SHADE_FWD_OCC
 #define NT_SHADE_FWD_OCC 3     /* round 3: 4 waves per SIMD (128 VGPRs) gave 0.163 -> 0.152 ms with run-time band counts; with FULL4 the hoisted slot-id loads spill there (0.19) and 3 waves run 0.139 */
-#endif
 template <bool FULL4, bool F16ROWS = false>
 __global__ __launch_bounds__(SH_BLOCK, NT_SHADE_FWD_OCC) void nt_shade_fwd_kernel(
     vsa_nt_plan plan, const int* __restrict__ hit_slot, const float* __restrict__ tex_uv,
@@ -378,16 +376,6 @@ __global__ __launch_bounds__(SH_BLOCK, NT_SHADE_FWD_OCC) void nt_shade_fwd_kerne
 // that phase 2 reads is 39 dwords (4 g_raw, 16 basis, 2 row ids + 2 lerp fractions per band)
 // so that a 128-thread workgroup needs 20 KiB of LDS and 16 waves fit a CU: halving the
 // occupancy of this atomic-bound kernel cost 27 % (measured), i.e. it is latency-sensitive.
-// Diagnostic build only (-DSHADE_SPAN; tools/shade_span.py): begin / end of every workgroup of the
-// shading backward, to see whether the launch has idle stretches or a tail.
-#ifdef SHADE_SPAN
-static __device__ unsigned long long g_sspan[1 << 16][2];
-__device__ __forceinline__ unsigned long long shade_now() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#endif
 constexpr int SHB_BLOCK = 128;
 
 // no-return packed f16 add at the memory side (global_atomic_pk_add_f16: one dword per lane)
@@ -397,10 +385,8 @@ __device__ __forceinline__ void atomic_pk_add_f16(const _Float16* base, unsigned
   asm volatile("global_atomic_pk_add_f16 %0, %1, %2" ::"v"(byte_off), "v"(__builtin_bit_cast(unsigned, v)), "s"(base) : "memory");
 }
 
-template <bool RECOMPUTE, bool FULL4, bool F16ROWS = false>
-#ifndef NT_SHADE_BWD_OCC
 #define NT_SHADE_BWD_OCC 4
-#endif
+template <bool RECOMPUTE, bool FULL4, bool F16ROWS = false>
 __global__ __launch_bounds__(SHB_BLOCK, RECOMPUTE ? 2 : NT_SHADE_BWD_OCC) void nt_shade_bwd_kernel(
     vsa_nt_plan plan, const int* __restrict__ hit_slot, const float* __restrict__ tex_uv,
     const float* __restrict__ rays_d, const float4* __restrict__ tris,
@@ -413,9 +399,6 @@ __global__ __launch_bounds__(SHB_BLOCK, RECOMPUTE ? 2 : NT_SHADE_BWD_OCC) void n
   __shared__ float s_basis[SHB_BLOCK][17];
   __shared__ int s_row[SHB_BLOCK][9];    // corners (x0,y0) and (x0,y1) per band; x1 = the next slot's row
   __shared__ float s_f[SHB_BLOCK][9];
-#ifdef SHADE_SPAN
-  const unsigned long long span_t0 = shade_now();
-#endif
   if (RECOMPUTE) {
     build_lut(plan, s_lut);
     __syncthreads();
@@ -594,12 +577,6 @@ __global__ __launch_bounds__(SHB_BLOCK, RECOMPUTE ? 2 : NT_SHADE_BWD_OCC) void n
     for (int k = 0; k < 4; ++k)
       if (cur[k] >= 0) atomic_pk_add_f16(grad_rows, (unsigned)cur[k] * 64u + lofs_b, acc[k].x, acc[k].y);
   }
-#ifdef SHADE_SPAN
-  {
-    const int w = blockIdx.y * gridDim.x + blockIdx.x;
-    if (threadIdx.x == 0 && w < (1 << 16)) g_sspan[w][0] = span_t0, g_sspan[w][1] = shade_now();
-  }
-#endif
 }
 
 }  // namespace
@@ -674,11 +651,3 @@ extern "C" int vsa_nt_shade_bwd(const vsa_nt_plan* plan, const int32_t* hit_slot
                        g_surfs_alpha, grad_scale, reinterpret_cast<_Float16*>(grad_rows), nullptr);
   VSA_RETURN_LAUNCH_STATUS();
 }
-
-#ifdef SHADE_SPAN
-extern "C" int vsa_span_read_shade(void* dst) {
-  VSA_HIP_TRY(hipDeviceSynchronize());
-  VSA_HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_sspan), sizeof(g_sspan)));
-  return 0;
-}
-#endif

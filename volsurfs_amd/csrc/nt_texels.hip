@@ -68,20 +68,14 @@ __device__ __forceinline__ void nt_rebalance_body(NtBalance* __restrict__ b, int
   const bool have = b->frac_wgs[k] == G && b->frac[k][G] == (unsigned)NT_BAL_ONE;
   const float equal = (float)NT_BAL_ONE / (float)G;
   const float share = t < G ? (have ? (float)(b->frac[k][t + 1] - b->frac[k][t]) : equal) : 0.f;
-#ifndef NT_BAL_GAIN
 #define NT_BAL_GAIN 0.5f
-#endif
-#ifndef NT_BAL_EMA
 #define NT_BAL_EMA 1.0f       /* weight of the newest time in the running mean kept in ema[] */
-#endif
-#ifndef NT_BAL_MASK
-#define NT_BAL_MASK 0x30      /* kernels whose shares are corrected (bit = NT_BAL_* id): the two MLP kernels.
+#define NT_BAL_MASK 0x30     /* kernels whose shares are corrected (bit = NT_BAL_* id): the two MLP kernels.
                                  Measured (profiles/r03/rebalance.txt): nt_mlp_bwd 0.68-0.70 -> 0.64-0.65 ms as a
                                  stage, nt_mlp_fwd unchanged; the encode kernels get SLOWER with their shares
                                  corrected (backward 0.61-0.63 -> 0.63-0.65 at any gain 0.15-0.5, with or without a
                                  running mean of the times): a piece's cost there is mostly its fixed part (table
                                  staging / plane flush), which a moved boundary duplicates instead of moving */
-#endif
   if (!((NT_BAL_MASK >> k) & 1)) return;
   float time = t < G ? (float)b->ticks[k][t] : 0.f;
   if (NT_BAL_EMA < 1.0f && t < G) {

@@ -20,12 +20,8 @@
 #include "common.h"
 #include <cstdint>
 
-#ifndef PERMUTO_LDS_LEVELS
 #define PERMUTO_LDS_LEVELS 10
-#endif
-#ifndef PERMUTO_LDS_MIN_POINTS
 #define PERMUTO_LDS_MIN_POINTS 512
-#endif
 
 namespace {
 
@@ -226,9 +222,7 @@ __global__ __launch_bounds__(256) void permuto_bwd_kernel(vsa_permuto_plan plan_
 constexpr int PL_THREADS = 512;
 constexpr int PL_SLOTS = 4096;            // keys 16 KiB + 2 x 32 KiB of accumulators
 constexpr int PL_PROBES = 16;
-#ifndef PL_CHUNK_POINTS
 #define PL_CHUNK_POINTS 1024
-#endif
 constexpr int PL_CHUNK = PL_CHUNK_POINTS;  // points per workgroup
 constexpr unsigned PL_EMPTY = 0xffffffffu;
 

@@ -42,28 +42,6 @@ __device__ __forceinline__ bool box_test(float lx, float ly, float lz, float hx,
   return tn <= tf * 1.0000004f + 1e-30f && tf >= t_min && tn <= t_max;
 }
 
-// Diagnostic build only (tools/build_variant.sh span "-DTRACE_SPAN"; tools/trace_span.py): wall-clock
-// begin / end of every wave of trace_q_kernel and WAVE-level counts (an elected lane adds to LDS; a
-// per-lane variable would only count that lane's own trips): trips of the walk loop, lane visits, leaf
-// phases.  g_torder, when set, replaces the dispatch order (the launch-order experiments of profiles/NOTEBOOK.md A9.4).
-#ifdef TRACE_SPAN
-constexpr int TRACE_SPAN_WAVES = 1 << 17;
-static __device__ unsigned long long g_tspan[TRACE_SPAN_WAVES][3];
-static __device__ int g_torder[TRACE_SPAN_WAVES];
-static __device__ int g_torder_on;
-__device__ __forceinline__ unsigned long long trace_now() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-enum { SP_ROUNDS, SP_VISITS, SP_OUTER };
-#define SPAN_ADD(k, v)                                                                        \
-  do {                                                                                        \
-    const unsigned v__ = (unsigned)(v);                                                       \
-    if ((int)threadIdx.x == __builtin_ctzll(__builtin_amdgcn_read_exec())) s_span[k] += v__;  \
-  } while (0)
-#endif
-
 template <int STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) void trace_ww_kernel(
     const float4* __restrict__ nodes, const float4* __restrict__ tris, Roots roots,
@@ -123,7 +101,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) void trace_q_kernel(
     float* __restrict__ hit_t, int* __restrict__ hit_slot, float* __restrict__ hit_uv, int rpw) {
   __shared__ int s_stack[STACK][TRACE_BLOCK];
   const int lane = threadIdx.x;
-#ifndef TRACE_SPAN
   // rpw (rays per wave) < 64: NARROW waves for small batches (vsa_trace_q_narrow) — lanes >= rpw sit out.  A wave walks
   // until its slowest ray is done, and a batch of a few ten thousand incoherent rays (a training batch) is a few
   // waves per SIMD each carrying the maximum of 64 unrelated walks: with 16 rays per wave the chains are shorter and
@@ -131,15 +108,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) void trace_q_kernel(
   if (lane >= rpw) return;
   const long long n = (long long)blockIdx.x * rpw + lane;
   const int mesh = blockIdx.y;
-#else
-  int item = blockIdx.y * gridDim.x + blockIdx.x;
-  if (g_torder_on) item = g_torder[item];
-  const int mesh = item / (int)gridDim.x;
-  const long long n = (long long)(item - mesh * (int)gridDim.x) * TRACE_BLOCK + lane;
-  const unsigned long long span_t0 = trace_now();
-  __shared__ unsigned s_span[8];
-  if (threadIdx.x < 8) s_span[threadIdx.x] = 0;
-#endif
   if (n >= N) return;
   const float ox = rays_o[3 * n], oy = rays_o[3 * n + 1], oz = rays_o[3 * n + 2];
   const float dx = rays_d[3 * n], dy = rays_d[3 * n + 1], dz = rays_d[3 * n + 2];
@@ -150,14 +118,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void trace_q_kernel(
   // q_walk's walk as per-lane loops, from the same pieces: the ballot form measured 1.5 % slower on a frame's stateless
   // launch (0.2782 against 0.2740 ms)
   while (cur != TRACE_EMPTY) {
-#ifdef TRACE_SPAN
-    SPAN_ADD(SP_OUTER, 1);
-#endif
     while ((unsigned)cur < (unsigned)TRACE_EMPTY) {
-#ifdef TRACE_SPAN
-      SPAN_ADD(SP_ROUNDS, 1);
-      SPAN_ADD(SP_VISITS, __builtin_popcountll(__builtin_amdgcn_read_exec()));
-#endif
       const uint4 a = qnodes[2 * (long long)cur], b = qnodes[2 * (long long)cur + 1];
       float tn0, tn1;
       const bool h0 = qbox_test(a.x, a.y, a.z, qr, t_min, best.t, tn0);
@@ -180,13 +141,6 @@ __global__ __launch_bounds__(TRACE_BLOCK) void trace_q_kernel(
       cur = sp ? s_stack[--sp][lane] : TRACE_EMPTY;
     }
   }
-#ifdef TRACE_SPAN
-  if (lane == __builtin_ctzll(__builtin_amdgcn_read_exec()) && item < TRACE_SPAN_WAVES) {
-    g_tspan[item][0] = span_t0;
-    g_tspan[item][1] = trace_now();
-    g_tspan[item][2] = ((unsigned long long)s_span[SP_ROUNDS] << 48) | ((unsigned long long)(s_span[SP_OUTER] & 0xffff) << 32) | s_span[SP_VISITS];
-  }
-#endif
   write_hit(best, (long long)mesh * N + n, hit_t, hit_slot, hit_uv);
 }
 
@@ -202,16 +156,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) void trace_q_kernel(
 // less — the hits are the ones of the one-ray-per-lane walk bit for bit (keys: ds_min_u64 on {ordered t, id}).
 // The queue lives in the stack's own LDS: the rows above the deepest straggler's stack are free, the entries are
 // gathered there and moved down to row 0 (+ 1.8 KB for the entries' ray lanes and the rays' keys).
-#ifndef TRACE_COOP_CHUNK
 #define TRACE_COOP_CHUNK 16      /* trips between two looks at how many lanes are left */
-#endif
-#ifndef TRACE_COOP_LANES
 #define TRACE_COOP_LANES 24      /* at most this many lanes still walking: the wave finishes them together */
-#endif
-#ifndef TRACE_COOP_WAVES
 #define TRACE_COOP_WAVES 4096    /* launches of at most this many waves: four per SIMD on 256 CUs (the finish's kernel holds no
                                     more; 65 536 rays x 5 shells = 5 120 waves already ran 0.103 -> 0.114 ms with it) */
-#endif
 constexpr int TRACE_COOP_Q = 1536;      // (the 24-row stack's own 1 536 words hold the queue)
 struct TraceCoop {
   unsigned long long key[TRACE_BLOCK];
@@ -349,7 +297,7 @@ __device__ __forceinline__ int q_finish_coop(const uint4* __restrict__ qnodes, c
 }
 
 // ---- cost-feedback launch order (vsa_trace_q_fb).  The one-pass kernel's launch is full for its first
-// 155 us and then drains for 100 us (tools/trace_span.py, profiles/NOTEBOOK.md A9.4): the waves that hold grazing rays
+// 155 us and then drains for 100 us (profiles/r03/trace_span.txt, profiles/NOTEBOOK.md A9.4): the waves that hold grazing rays
 // walk 100-200 trips against a median of 9, and those that happen to be dispatched late are still walking
 // when everything else has finished.  With the heaviest waves dispatched FIRST (sorted by their measured
 // trips: the upper bound of any predictor) the same kernel takes 203 us instead of 300 with stamps.  A
@@ -398,9 +346,7 @@ __global__ void trace_fb_flip_kernel(int* phase_word, char* half0, char* half1) 
   if (threadIdx.x == 0) *phase_word = ph;
   if (threadIdx.x < 4) reinterpret_cast<int*>(ph ? half0 : half1)[threadIdx.x] = 0;
 }
-#ifndef TRACE_FB_T
 #define TRACE_FB_T 160, 128, 64     /* same-box sweep in profiles/r03/trace_feedback.txt */
-#endif
 constexpr int TRACE_FB_TS[3] = {TRACE_FB_T};
 constexpr int TRACE_FB_T0 = TRACE_FB_TS[0], TRACE_FB_T1 = TRACE_FB_TS[1], TRACE_FB_T2 = TRACE_FB_TS[2];   // trips: list 0 / 1 / 2
 
@@ -710,18 +656,3 @@ extern "C" int vsa_hit_attributes(const float* tris, const float* rays_o, const 
                      barycentric);
   VSA_RETURN_LAUNCH_STATUS();
 }
-
-#ifdef TRACE_SPAN
-extern "C" int vsa_span_set_order(const void* order, int n) {
-  VSA_HIP_TRY(hipDeviceSynchronize());
-  const int on = order != nullptr;
-  if (on) VSA_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_torder), order, sizeof(int) * n));
-  VSA_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_torder_on), &on, sizeof(int)));
-  return 0;
-}
-extern "C" int vsa_span_read_trace(void* dst) {
-  VSA_HIP_TRY(hipDeviceSynchronize());
-  VSA_HIP_TRY(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tspan), sizeof(g_tspan)));
-  return 0;
-}
-#endif
