@@ -471,6 +471,21 @@ int vsa_nt_encode_bwd(const vsa_nt_plan* plan, const void* dfeatures, const floa
                       float grad_scale, const float* slot_xy, const int32_t* seg_start,
                       float* grad_tables, void* stream);
 
+/* Process-wide setting of the hash-grid encode launches (vsa_nt_encode_fwd, vsa_nt_encode_bwd, _bwd_range).
+ *   sibling_groups  0: the plain walk.  1: the hashed levels are walked in SIBLING GROUPS — two (forward: colour,
+ *                   alpha) or four (backward: colour, alpha x feature 0, 1) workgroups of one XCD take the same
+ *                   stretch of slots at the same time, each on its own plane, so that the texel centres and dF words
+ *                   they all read cross the fabric once (csrc/nt_common.h).  2: in the backward only, 3: in the
+ *                   forward only.  The pieces' arithmetic is the plain walk's: features bit for bit, table gradients
+ *                   equal wherever a plane is flushed by stores.  Taken when the grid is a multiple of 16 (forward) /
+ *                   32 (backward), for at most 64 textures and the whole shell range; any other launch keeps the
+ *                   plain walk.  Default 2: the backward fetches 1.3 GB less per 800 x 800 frame and is 6 % shorter,
+ *                   the forward fetches 0.2 GB less and is 6 % LONGER.
+ *   grid_override   > 0: that many workgroups instead of one per compute unit (tests: cuts and groups on small
+ *                   frames); 0: the compute-unit count.
+ * Returns VSA_ERR_ARG for sibling_groups outside 0..3 or grid_override outside 0..4096. */
+int vsa_nt_encode_config(int sibling_groups, int grid_override);
+
 /* The same, restricted to the textures of shells [shell_begin, shell_end): lets a
  * data-parallel caller start the all-reduce of one shell's table gradients (a contiguous
  * slice of grad_tables) while the next shell's are still being accumulated. */

@@ -351,3 +351,115 @@ __device__ __forceinline__ void nt_for_each_piece(const vsa_nt_plan& plan,
   }
 }
 
+// ---- SIBLING GROUPS (hashed levels of the encode kernels).  The colour and the alpha texture of one (shell,
+// degree) have the same slots and texel centres, and so have the two features of a texture in the backward; as
+// separate pieces of the walk above they stream those centres (and the dF words) two / four times, at unrelated
+// moments and on unrelated XCDs.  Here the axis is laid out over CARRIERS — a (shell, degree), carried by the lane
+// of its colour texture (by the alpha texture's where the colour texture is inactive) — level-major, and it is cut
+// into gridDim.x / G stretches.  A GROUP of G workgroups walks one stretch, member m on its own sibling plane:
+//   G = 2 (forward):   siblings {colour, alpha}
+//   G = 4 (backward):  siblings {colour, alpha} x {f0, f1}:  type = m & 1, feature = m >> 1
+// Workgroups are dealt to the 8 XCDs round-robin by linear id, so the members of a group are the blocks
+// b, b + 8, ..., b + 8 (G - 1) of one run of 8 G consecutive ids: same XCD, dispatched together.  They start the same
+// stretch at the same time and cost the same, so the first to ask for a line of centres fetches it and the others can
+// find it in that XCD's L2.  Nobody waits for anybody.
+// A carrier with fewer siblings (no alpha model on the shell, an inactive degree: n_sib = 1 or 2 of G) keeps all
+// members busy: sibling = m % n_sib, and the G / n_sib members of one sibling share the stretch's units of the
+// carrier, member share j = m / n_sib taking units [ua + n j / r, ua + n (j + 1) / r), n = ub - ua, r = G / n_sib.
+// Its unit weight on the axis is w n_sib / G accordingly.  Only for grids that are a multiple of 8 G.
+__host__ __device__ inline bool nt_sibling_grid_ok(int grid, int G) { return grid > 0 && grid % (8 * G) == 0; }
+
+// block -> (group, member), and the group's stretch [lo, hi) of an axis of length `total`
+__host__ __device__ inline void nt_sibling_stretch(int block, int grid, int G, long long total, int& group,
+                                                   int& member, long long& lo, long long& hi) {
+  const int r = block % (8 * G), n_groups = grid / G;
+  group = block / (8 * G) * 8 + r % 8;
+  member = r / 8;
+  lo = total * group / n_groups;           // total < 2^38, group < 2^10: no overflow
+  hi = total * (group + 1) / n_groups;
+}
+
+// member -> its sibling (type = sib % n_types, feature = sib / n_types) and its share of the units [ua, ub)
+__host__ __device__ inline void nt_sibling_share(int member, int G, int n_sib, int& sib, int& ua, int& ub) {
+  const int r = G / n_sib, j = member / n_sib, n = ub - ua;
+  sib = member % n_sib;
+  ub = ua + n * (j + 1) / r;               // n < 2^15 units, r <= 4
+  ua = ua + n * j / r;
+}
+
+// body(plane, tex, first_slot, last_slot, seg_begin, seg_end) with plane = level * (G / 2) + feature, as the walks
+// above number the planes of the forward (one per level) and of the backward's hashed levels (two per level);
+// wt(plane, degree, type) as there.  <= 64 textures, the whole texture range, equal shares.
+template <int UNIT, int G, typename Body, typename Weight>
+__device__ __forceinline__ void nt_for_each_sibling_piece(const vsa_nt_plan& plan, const int* __restrict__ seg_start,
+                                                          int n_levels, int ovh, Body&& body, Weight wt) {
+  constexpr int NF = G / 2;
+  const int n_all = plan.nr_shells * 2 * VSA_NT_MAX_DEG;
+  const int lane = threadIdx.x & 63;
+  const int tex = lane;
+  const int deg = tex % VSA_NT_MAX_DEG, type = (tex / VSA_NT_MAX_DEG) & 1, shell = tex / (2 * VSA_NT_MAX_DEG);
+  const bool rgb_act = deg < plan.rgb_degrees, alpha_act = nt_shell_has_alpha(plan, shell) && deg < plan.alpha_degrees;
+  bool act = tex < n_all && (type == 0 ? rgb_act : (alpha_act && !rgb_act));     // the carrier's lane
+  const int n_types = (rgb_act ? 1 : 0) + (alpha_act ? 1 : 0);
+  const int sd = shell * VSA_NT_MAX_DEG + deg;
+  int begin = 0, end = 0;
+  if (act) {
+    begin = seg_start[sd];
+    end = seg_start[sd + 1];
+  }
+  act = act && end > begin;
+  const int units = act ? (end - begin + UNIT - 1) / UNIT : 0;
+  if (__ballot(act) == 0ull) return;
+  auto unit_w = [&](int lvl) {
+    const int w = wt(lvl * NF, deg, type) * n_types * NF / G;
+    return w > 0 ? w : 1;
+  };
+  auto lane_cost = [&](int lvl) { return act ? ovh * 16 + units * unit_w(lvl) : 0; };
+  long long total = 0;
+  for (int lvl = 0; lvl < n_levels; ++lvl)
+    total += (long long)(unsigned)__builtin_amdgcn_readlane(nt_wave_incl_scan(lane_cost(lvl)), 63);
+  int group, member;
+  long long lo, hi;
+  nt_sibling_stretch((int)blockIdx.x, (int)gridDim.x, G, total, group, member, lo, hi);
+  if (hi <= lo) return;
+  long long c0 = 0;
+  for (int lvl = 0; lvl < n_levels && c0 < hi; ++lvl) {
+    const int cl = lane_cost(lvl);
+    const int incl = nt_wave_incl_scan(cl);
+    const long long pc = (long long)(unsigned)__builtin_amdgcn_readlane(incl, 63);
+    if (c0 + pc <= lo) {
+      c0 += pc;
+      continue;
+    }
+    // as nt_for_each_piece: the carrier's units start at t0; those whose start lies in [lo, hi) are the stretch's
+    const long long t0l = c0 + (long long)(incl - cl) + (long long)ovh * 16;
+    const int w = unit_w(lvl);
+    const long long span = (long long)units * w;
+    bool hit = act && t0l < hi;
+    int ua = 0, ub = 0;
+    if (hit) {
+      const long long a = lo > t0l ? lo - t0l : 0, b = hi - t0l < span ? hi - t0l : span;
+      hit = b > a;
+      if (hit) {
+        ua = (int)(((unsigned)a + (unsigned)w - 1u) / (unsigned)w);
+        ub = (int)(((unsigned)b + (unsigned)w - 1u) / (unsigned)w);
+        hit = ub > ua;
+      }
+    }
+    unsigned long long todo = __ballot(hit);
+    while (todo) {
+      const int j = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int jb = __builtin_amdgcn_readlane(begin, j), je = __builtin_amdgcn_readlane(end, j);
+      const int jn = __builtin_amdgcn_readlane(n_types, j);
+      int sib, ma = __builtin_amdgcn_readlane(ua, j), mb = __builtin_amdgcn_readlane(ub, j);
+      nt_sibling_share(member, G, jn * NF, sib, ma, mb);
+      if (mb <= ma) continue;
+      const int jtex = sib % jn ? j ^ VSA_NT_MAX_DEG : j;      // (two types: the carrier is the colour texture)
+      const int first = jb + ma * UNIT;
+      const long long lastl = (long long)jb + (long long)mb * UNIT;
+      body(lvl * NF + sib / jn, jtex, first, lastl < je ? (int)lastl : je, jb, je);
+    }
+    c0 += pc;
+  }
+}

@@ -26,6 +26,10 @@ namespace {
 #define NT_ENC_OVH_FD 27
 #define NT_ENC_OVH_BH 145
 #define NT_ENC_OVH_BD 64
+// default of vsa_nt_encode_config: 2 = the backward's hashed levels walk in sibling groups, the forward's do not.
+// Measured (800x800, K = 5; profiles/NOTEBOOK.md "Encode kernels"): backward 2.79 -> 1.50 GB fetched, 0.538 -> 0.507 ms;
+// forward 1.11 -> 0.92 GB fetched but 0.299 -> 0.316 ms, so the forward keeps the plain walk.
+#define NT_ENC_SIBLING_GROUPS 2
 #define NT_ENC_PAIR_W 22       /* cost of a (colour, alpha) pair unit in 1/16 of a single texture's (forward, dense) */
 constexpr int ENC_BLOCK = 1024;     // 16 waves: a 128 KiB level pins one workgroup per CU
 constexpr int ENC_UNROLL = 8;       // slots in flight per lane (backward)
@@ -36,7 +40,7 @@ constexpr int LDS_ENTRIES = 32768;    // 4-byte entries of LDS a workgroup may u
 
 constexpr int ENC_PAIR_OFF = 15360;   // entries: the second table of a pair sits at a FIXED LDS offset (61 440 B: an
                                       // immediate of the gathers); the largest dense level has 15 136 entries
-template <bool HASHED>
+template <bool HASHED, bool SIB = false>
 __device__ __forceinline__ void nt_encode_fwd_body(
     const vsa_nt_plan& plan, int level0, int n_levels, const half2_t* __restrict__ tables,
     const float2* __restrict__ slot_xy, const int* __restrict__ seg_start,
@@ -55,8 +59,7 @@ __device__ __forceinline__ void nt_encode_fwd_body(
     const int w = !HASHED || plan.level_scale[level0 + pl] < (float)plan.tex_res[deg] ? 16 : 15;
     return wtype == 2 ? (w * NT_ENC_PAIR_W) >> 4 : w;
   };
-  nt_for_each_piece<ENC_UNIT>(plan, seg_start, n_levels, HASHED ? NT_ENC_OVH_FH : NT_ENC_OVH_FD,
-                              [&](int pl, int tex, int first, int last, int, int) {
+  auto piece = [&](int pl, int tex, int first, int last, int, int) {
     const int level = level0 + pl;
     const LevelGeom g = level_geom(plan, level);
     // (a pair stages its second table at the fixed offset ENC_PAIR_OFF: a dense level of another grid
@@ -191,7 +194,14 @@ __device__ __forceinline__ void nt_encode_fwd_body(
       else run(std::false_type{}, std::false_type{});
     }
     }   // pass
-  }, 0, 1 << 30, unit_weight, HASHED ? NT_BAL_ENC_FWD_H : NT_BAL_ENC_FWD_D, pair_mode);
+  };
+  // SIB (hashed levels, the host's choice: vsa_nt_encode_config): groups of two workgroups of one XCD walk a
+  // stretch together, one on the colour and one on the alpha texture (nt_common.h, sibling groups)
+  if constexpr (SIB)
+    nt_for_each_sibling_piece<ENC_UNIT, 2>(plan, seg_start, n_levels, NT_ENC_OVH_FH, piece, unit_weight);
+  else
+    nt_for_each_piece<ENC_UNIT>(plan, seg_start, n_levels, HASHED ? NT_ENC_OVH_FH : NT_ENC_OVH_FD, piece,
+                                0, 1 << 30, unit_weight, HASHED ? NT_BAL_ENC_FWD_H : NT_BAL_ENC_FWD_D, pair_mode);
   __syncthreads();
   NT_BAL_END(HASHED ? NT_BAL_ENC_FWD_H : NT_BAL_ENC_FWD_D);
 }
@@ -209,6 +219,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_kernel(
 // dense cost axis, then its share of the hashed one (the two classes touch different planes: no
 // ordering between workgroups).  As two launches the dense one (0.1 ms) ended behind its slowest
 // workgroups (span efficiency 0.76-0.80: stragglers, not a slope of the axis) with the chip idle.
+template <bool SIB>
 __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_both_kernel(
     vsa_nt_plan plan, int lh, const half2_t* __restrict__ tables,
     const float2* __restrict__ slot_xy, const int* __restrict__ seg_start,
@@ -216,7 +227,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_both_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   nt_encode_fwd_body<false>(plan, 0, lh, tables, slot_xy, seg_start, features, s_raw);
   __syncthreads();
-  nt_encode_fwd_body<true>(plan, lh, plan.n_levels - lh, tables, slot_xy, seg_start, features, s_raw);
+  nt_encode_fwd_body<true, SIB>(plan, lh, plan.n_levels - lh, tables, slot_xy, seg_start, features, s_raw);
 }
 
 // Backward: grad_table[tex][level entries][feature] += w * dF[slot]; one
@@ -462,7 +473,7 @@ __device__ __host__ inline bool enc_both_features(const vsa_nt_plan& p, int leve
   return !hashed && (long long)p.level_size[level] * 2 <= LDS_ENTRIES;
 }
 
-template <bool HASHED>
+template <bool HASHED, bool SIB = false>
 __device__ __forceinline__ void nt_encode_bwd_body(
     const vsa_nt_plan& plan, int level0, int n_levels, int n_planes,
     const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
@@ -476,8 +487,7 @@ __device__ __forceinline__ void nt_encode_bwd_body(
   auto unit_weight = [&](int pl, int deg, int) {
     return !HASHED || plan.level_scale[level0 + (pl >> 1)] < (float)plan.tex_res[deg] ? 16 : 14;
   };
-  nt_for_each_piece<ENC_UNIT>(plan, seg_start, n_planes, HASHED ? NT_ENC_OVH_BH : NT_ENC_OVH_BD,
-                              [&](int pl, int tex, int first, int last, int seg_begin, int seg_end) {
+  auto piece = [&](int pl, int tex, int first, int last, int seg_begin, int seg_end) {
     int level = level0, r = pl;
     bool both = enc_both_features(plan, level, HASHED);
     while (r >= (both ? 1 : 2)) {
@@ -502,9 +512,16 @@ __device__ __forceinline__ void nt_encode_bwd_body(
     else
       enc_bwd_piece<HASHED, 1, false>(plan, s_g, level, r, tex, first, last, store, dfeatures,
                                       dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
-  }, tex_begin, tex_end, unit_weight,
-     // a launch over a sub-range of the textures (the sliced backward of parallel.py) keeps equal shares
-     full_range ? (HASHED ? NT_BAL_ENC_BWD_H : NT_BAL_ENC_BWD_D) : -1);
+  };
+  // SIB (hashed levels, the whole texture range; the host's choice): groups of four workgroups of one XCD walk a
+  // stretch together, each on one of {colour, alpha} x {f0, f1} (nt_common.h, sibling groups)
+  if constexpr (SIB)
+    nt_for_each_sibling_piece<ENC_UNIT, 4>(plan, seg_start, n_levels, NT_ENC_OVH_BH, piece, unit_weight);
+  else
+    nt_for_each_piece<ENC_UNIT>(plan, seg_start, n_planes, HASHED ? NT_ENC_OVH_BH : NT_ENC_OVH_BD, piece,
+                                tex_begin, tex_end, unit_weight,
+                                // a launch over a sub-range of the textures (the sliced backward of parallel.py) keeps equal shares
+                                full_range ? (HASHED ? NT_BAL_ENC_BWD_H : NT_BAL_ENC_BWD_D) : -1);
   __syncthreads();
   if (full_range) { NT_BAL_END(HASHED ? NT_BAL_ENC_BWD_H : NT_BAL_ENC_BWD_D); }
 }
@@ -521,6 +538,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_kernel(
 }
 
 // dense planes, then hashed planes, in one launch (as nt_encode_fwd_both_kernel)
+template <bool SIB>
 __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_both_kernel(
     vsa_nt_plan plan, int lh, int n_planes_dense,
     const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
@@ -530,8 +548,8 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_both_kernel(
   nt_encode_bwd_body<false>(plan, 0, lh, n_planes_dense, dfeatures, dfeat_abs_sum, dscale_inv, slot_xy,
                             seg_start, grad_tables, tex_begin, tex_end, s_raw);
   __syncthreads();
-  nt_encode_bwd_body<true>(plan, lh, plan.n_levels - lh, 2 * (plan.n_levels - lh), dfeatures, dfeat_abs_sum,
-                           dscale_inv, slot_xy, seg_start, grad_tables, tex_begin, tex_end, s_raw);
+  nt_encode_bwd_body<true, SIB>(plan, lh, plan.n_levels - lh, 2 * (plan.n_levels - lh), dfeatures, dfeat_abs_sum,
+                                dscale_inv, slot_xy, seg_start, grad_tables, tex_begin, tex_end, s_raw);
 }
 
 // The data-parallel form (vsa_nt_encode_bwd_phased): every workgroup first walks its share of the dense
@@ -635,6 +653,33 @@ static int max_level_size(const vsa_nt_plan* p, int l0, int l1) {
   return m;
 }
 
+// process-wide setting of the encode launches (vsa_nt_encode_config)
+struct EncConfig {
+  int sibling_groups, grid_override;
+};
+static EncConfig& enc_config() {
+  static EncConfig cfg{NT_ENC_SIBLING_GROUPS, 0};
+  return cfg;
+}
+extern "C" int vsa_nt_encode_config(int sibling_groups, int grid_override) {
+  if (sibling_groups < 0 || sibling_groups > 3 || grid_override < 0 || grid_override > 4096) return VSA_ERR_ARG;
+  enc_config() = EncConfig{sibling_groups, grid_override};
+  return VSA_OK;
+}
+// workgroups of an encode launch, and whether its hashed levels walk in sibling groups of G
+static int enc_grid(int* grid) {
+  if (enc_config().grid_override > 0) {
+    *grid = enc_config().grid_override;
+    return VSA_OK;
+  }
+  return vsa_cu_count(grid);
+}
+static bool enc_siblings(const vsa_nt_plan* p, int grid, int G) {
+  const int mode = enc_config().sibling_groups;      // 1: both launches, 2: the backward only, 3: the forward only
+  const bool on = mode == 1 || mode == (G == 4 ? 2 : 3);
+  return on && nt_sibling_grid_ok(grid, G) && p->nr_shells * 2 * VSA_NT_MAX_DEG <= 64;
+}
+
 template <typename K>
 static int set_lds_attr(K kernel) {
   VSA_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
@@ -652,7 +697,8 @@ extern "C" int vsa_nt_encode_fwd(const vsa_nt_plan* plan, const void* tables_h,
   if (!attr_set) {
     if ((rc = set_lds_attr(nt_encode_fwd_kernel<false>))) return rc;
     if ((rc = set_lds_attr(nt_encode_fwd_kernel<true>))) return rc;
-    if ((rc = set_lds_attr(nt_encode_fwd_both_kernel))) return rc;
+    if ((rc = set_lds_attr(nt_encode_fwd_both_kernel<false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_fwd_both_kernel<true>))) return rc;
     attr_set = true;
   }
   const int lh = first_hashed_level(plan);
@@ -660,10 +706,14 @@ extern "C" int vsa_nt_encode_fwd(const vsa_nt_plan* plan, const void* tables_h,
   const float2* xy = reinterpret_cast<const float2*>(slot_xy);
   half2_t* out = reinterpret_cast<half2_t*>(features);
   int nr_cus = 0;
-  if ((rc = vsa_cu_count(&nr_cus))) return rc;
+  if ((rc = enc_grid(&nr_cus))) return rc;
   if (lh > 0 && lh < plan->n_levels) {
-    hipLaunchKernelGGL(nt_encode_fwd_both_kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
-                       (hipStream_t)stream, *plan, lh, tab, xy, seg_start, out);
+    if (enc_siblings(plan, nr_cus, 2))
+      hipLaunchKernelGGL(nt_encode_fwd_both_kernel<true>, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
+                         (hipStream_t)stream, *plan, lh, tab, xy, seg_start, out);
+    else
+      hipLaunchKernelGGL(nt_encode_fwd_both_kernel<false>, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
+                         (hipStream_t)stream, *plan, lh, tab, xy, seg_start, out);
     VSA_RETURN_LAUNCH_STATUS();
   }
   if (lh > 0)
@@ -705,20 +755,27 @@ extern "C" int vsa_nt_encode_bwd_range(const vsa_nt_plan* plan, const void* dfea
   if (!attr_set) {
     if ((rc = set_lds_attr(nt_encode_bwd_kernel<false>))) return rc;
     if ((rc = set_lds_attr(nt_encode_bwd_kernel<true>))) return rc;
-    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<true>))) return rc;
     attr_set = true;
   }
   const int lh = first_hashed_level(plan);
   const half2_t* dF = reinterpret_cast<const half2_t*>(dfeatures);
   const float2* xy = reinterpret_cast<const float2*>(slot_xy);
   int nr_cus = 0;
-  if ((rc = vsa_cu_count(&nr_cus))) return rc;
+  if ((rc = enc_grid(&nr_cus))) return rc;
   if (lh > 0 && lh < plan->n_levels) {
     int n_planes = 0;
     for (int l = 0; l < lh; ++l) n_planes += enc_both_features(*plan, l, false) ? 1 : 2;
-    hipLaunchKernelGGL(nt_encode_bwd_both_kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
-                       (hipStream_t)stream, *plan, lh, n_planes, dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
-                       seg_start, grad_tables, tex_begin, tex_end);
+    // (a launch over some of the shells keeps the plain walk)
+    if (shell_begin == 0 && shell_end == plan->nr_shells && enc_siblings(plan, nr_cus, 4))
+      hipLaunchKernelGGL(nt_encode_bwd_both_kernel<true>, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
+                         (hipStream_t)stream, *plan, lh, n_planes, dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
+                         seg_start, grad_tables, tex_begin, tex_end);
+    else
+      hipLaunchKernelGGL(nt_encode_bwd_both_kernel<false>, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
+                         (hipStream_t)stream, *plan, lh, n_planes, dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
+                         seg_start, grad_tables, tex_begin, tex_end);
     VSA_RETURN_LAUNCH_STATUS();
   }
   if (lh > 0) {

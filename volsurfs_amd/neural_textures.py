@@ -328,6 +328,13 @@ class NeuralTextureBank(torch.nn.Module):
             torch.cuda.current_stream().wait_event(ev)
             self._params_event = None
 
+    @staticmethod
+    def encode_config(sibling_groups, grid_override=0):
+        """Process-wide setting of the hash-grid encode launches (vsa_nt_encode_config): the hashed levels walked by the
+        plain walk (0) or in sibling groups (1: forward and backward, 2: backward only — the default, 3: forward only),
+        and a forced number of workgroups (0: one per compute unit)."""
+        _lib.call("vsa_nt_encode_config", int(sibling_groups), int(grid_override))
+
     def encode(self):
         self.wait_params()
         _lib.call("vsa_nt_encode_fwd", ctypes.byref(self.plan), self.tables_h, self.slot_xy,
