@@ -2235,6 +2235,92 @@ int vsa_mesh_smooth_guard(const float* before, const float* after, const int32_t
 int vsa_mesh_smooth_revert(const float* before, float* after, long long nr_verts, long long nr_faces, int round,
                            const void* workspace, long long workspace_bytes, long long* state, void* stream);
 
+/* ---- Texture transfer (no counterpart in the reference; csrc/texture_transfer.hip) ----
+ * The baked 8-bit SH textures of a stack of K source shells carried onto K destination shells with other faces and
+ * other per-corner UVs: the planes of "Texture export / import" in, planes of the same layout at the destination's
+ * per-degree resolutions out.  The rule is this library's own, restated in tests/texture_transfer_restated.py and
+ * unpinned.  Everything is per shell s and SH degree d; R = the source's tex_res[d], R' = the destination's.  fp32,
+ * one rounding per operation, in the order written (the build compiles without contraction).
+ *   texel centre  pixel (row r, column c) of a plane is read by the baked shade with both lerp fractions zero at
+ *                 uv = ((c + 0.5) / R, (r + 0.5) / R): nt_footprint's lerp branch gives i0 = floor(R - v R - 0.5),
+ *                 j0 = floor(u R - 0.5), its corner 0 is texel (iy, ix) = (j0, i0), and the orientation rule above
+ *                 stores texel (iy, ix) at pixel (R-1-ix, iy); so R - v R - 0.5 = R-1-r and u R - 0.5 = c.  (Exact
+ *                 where R is a power of two; elsewhere the fractions are a rounding of zero.)  In TEXEL UNITS (uv
+ *                 times R') the centre is (c + 0.5, r + 0.5): row r runs along v, column c along u, the orientation
+ *                 of vsa_atlas_rasterize.
+ *   uv record     of a destination face: its corners in texel units, x_k = u_k * (float)R', y_k = v_k * (float)R',
+ *                 as a record of "Mesh distance" with z = 0: v0 = (x_0, y_0, 0), e1 = (x_1 - x_0, y_1 - y_0, 0), e2
+ *                 alike.
+ *   projection    of a texel-unit point (qx, qy) onto a uv record: closest_on_triangle of (qx, qy, 0) gives (d2, u, v);
+ *                 where its region is the interior, d2 = 0 (the point is its own nearest point; the residual the
+ *                 chain forms there is the rounding of u and v).  A zero-area uv triangle falls through as there.
+ *   inside        a texel centre lies INSIDE face f iff f covers texel (i, j) = (c, r) by the rule of "UV atlas", raster
+ *                 (corners snapped in fp64 to 1/256 texel, int64 edge functions, top-left rule, snapped area > 0):
+ *                 vsa_atlas_rasterize's rule, restated, so that the two stages agree texel for texel.  The projection
+ *                 onto the exact triangle alone differs from it within the snapping step.
+ *   ownership     face f is a candidate of texel (r, c) iff the centre lies inside it (its d2 is 0 then) or the
+ *                 projection of the centre onto it has d2 <= reach * reach (a NaN d2 fails).  A face with a uv or a
+ *                 vertex that is not finite is a candidate of nothing.  The owner is the minimum over (centre not
+ *                 inside, bits of d2, face id): a texel whose centre lies inside a face belongs to the lowest such
+ *                 face, vsa_atlas_rasterize's face_id.  The owned barycentrics are the projection's (u, v) in every
+ *                 case.  A texel with d2 = 0 is COVERED.  No candidate: UNOWNED.
+ *   samples       samples = S in 1..4; sample n = b S + a (a, b in 0..S-1) of texel (r, c) is the texel-unit point
+ *                 qx = ((float)c + 0.5) + (((float)a + 0.5) / (float)S - 0.5), qy alike with r and b, projected onto
+ *                 the owner's uv record (S = 1: the centre itself).  Its 3-D point is p = (v0 + u e1) + v e2 per
+ *                 component on the destination face's record (v0, e1 = v1 - v0, e2 = v2 - v0), vsa_surface_sample's
+ *                 expression.
+ *   source lookup the closest point of source shell s to p by the walk of "Mesh distance" (slot, weights and d2 are
+ *                 vsa_closest_point_q's bits); uv = nt_interp_uv of that slot's per-corner uvs; nt_footprint(uv, R,
+ *                 anchor as the source plan says) gives (i0, j0, fx, fy).  Corner k = 2 ky + kx reads texel (iy, ix) =
+ *                 (clamp(j0 + ky, 0, R-1), clamp(i0 + kx, 0, R-1)), i.e. pixel (R-1-ix, iy), with weight
+ *                 (kx ? fx : 1 - fx) * (ky ? fy : 1 - fy) -- vsa_nt_import_planes' clamp-to-edge apron; under anchor
+ *                 all four corners are texel (j0, i0).  Per channel: acc = 0; acc = acc + lut[byte_k] * w_k for k =
+ *                 0..3; the sample's coefficient = fp16(acc).  lut[q] = fp16(sh_lo + fp16(sh_span * fp16(q / 255))).
+ *                 A p without a closest record (not finite) contributes nothing and counts as far.
+ *   resolve       x = (the sample coefficients added in sample order to 0) * (1 / ((float)S * (float)S)); the stored
+ *                 byte is the q in 0..255 with the smallest |lut[q] - x| (one fp32 subtract), the lowest such q.  A
+ *                 stored byte therefore survives a fetch with zero fractions.  R, G, B = colour channel 0..2 of
+ *                 coefficient i, A = alpha coefficient i; A = 255 on a shell without an alpha model.  Unowned texels:
+ *                 R = G = B = 0, A = 0 (255 without an alpha model).
+ *   report        per shell, TT words u64 [8]: 0 owned texels, 1 covered texels, 2 samples (owned * S^2), 3 the bits
+ *                 of the largest d = sqrt(d2) of a sample's closest point (fp32, zero-extended), 4 the samples with
+ *                 d > max_distance or without a closest record, 5 the bits of the fp64 sum of (double)d2: per lane in
+ *                 sample order, per 8 x 8 tile (lane = 8 (r % 8) + c % 8) by the butterfly s += s[lane ^ m], m = 32,
+ *                 16, .. 1, then the tiles in row-major order in vsa_surface_distance's shape (lane t of 1024 adds
+ *                 tiles [t c, (t + 1) c), c = ceil(tiles / 1024); lane 0 adds the 1024 sums in order).
+ * reach: every texel the shade can read for a hit inside a uv triangle has its centre closer than 1 texel to the hit on
+ *   each axis, hence closer than sqrt(2) to the triangle: with reach >= 1.5 it has an owner.
+ * vsa_textransfer_owners: the owner words of every shell at one resolution into the workspace, one wave per face over
+ *   the face's uv box grown by reach, one 64-bit atomicMin per candidate pair of the word (bit 63: centre not inside;
+ *   bits 32..62: d2; bits 0..31: face).
+ *   dst_uvs [F, 3, 2], dst_recs [F, 12] (v0.xyz, - | e1.xyz, - | e2.xyz, -; 16-byte aligned) hold the K shells' faces
+ *   one after the other, shell s the rows face_base[s] .. face_base[s + 1] - 1 (face_base: host, [K + 1], from 0).
+ * vsa_textransfer_owner_fields: shell `shell`'s words as face [R', R'] i32 (-1: unowned), bary [R', R', 2], d2 [R', R']
+ *   (unowned: 0 and +inf).
+ * vsa_textransfer_planes: degree `degree` of every shell after vsa_textransfer_owners at dst_tex_res[degree] with the
+ *   same workspace: a wave per 8 x 8 tile, the walk's stack in LDS.  src_planes / dst_planes are whole plane buffers
+ *   (vsa_nt_planes_bytes of the source plan; the same with dst_tex_res), 16-byte aligned; the tree arguments are
+ *   vsa_closest_point_q's, nr_meshes = the plan's nr_shells; src_face_uvs [slots, 6] in the order of tris; stats
+ *   [K, 8] u64 is cleared and written.  No float atomics: the same inputs give the same bytes.
+ * workspace = vsa_textransfer_workspace_bytes(K, R') bytes, 16-byte aligned: 8 R'^2 per shell and 8 per tile.
+ * VSA_ERR_ARG (before any HIP call): a NULL pointer, misalignment, K outside 1..16, a resolution outside 1..16384, a
+ *   shell without faces, a short workspace, reach negative, NaN or above 64, samples outside 1..4, a NaN max_distance,
+ *   a degree outside the plan's, nr_meshes != nr_shells, wrong planes_bytes, a tree deeper than the stack.
+ *   VSA_ERR_UNSUPPORTED: 2^31 faces or more, alpha_degrees != rgb_degrees, row_format != 0. */
+long long vsa_textransfer_workspace_bytes(int nr_shells, int dst_res);
+int vsa_textransfer_owners(const float* dst_uvs, const float* dst_recs, const long long* face_base, int nr_shells,
+                           int dst_res, float reach, void* workspace, long long workspace_bytes, void* stream);
+int vsa_textransfer_owner_fields(const void* workspace, long long workspace_bytes, const float* dst_uvs,
+                                 const long long* face_base, int nr_shells, int shell, int dst_res, int32_t* face,
+                                 float* bary, float* d2, void* stream);
+int vsa_textransfer_planes(const vsa_nt_plan* src_plan, int degree, const uint8_t* src_planes,
+                           long long src_planes_bytes, const uint32_t* qnodes, const float* tris,
+                           const int32_t* mesh_roots, const float* mesh_frames, int nr_meshes, int max_depth,
+                           const float* src_face_uvs, const float* dst_uvs, const float* dst_recs,
+                           const long long* face_base, const int32_t* dst_tex_res, int samples, float max_distance,
+                           void* workspace, long long workspace_bytes, uint8_t* dst_planes,
+                           long long dst_planes_bytes, unsigned long long* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

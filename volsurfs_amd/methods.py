@@ -705,6 +705,11 @@ class VolSurfs(torch.nn.Module):
             out = {k: v.reshape(-1, s * s, *v.shape[1:]).float().mean(1) for k, v in out.items()}
         return out
 
+    def transfer_to(self, dst_meshes, **kw):
+        """`texture_transfer.transfer_scene(self, dst_meshes, ...)`: the baked textures on other faces and UVs."""
+        from .texture_transfer import transfer_scene
+        return transfer_scene(self, dst_meshes, **kw)
+
     # -- fused training path: the same forward + mean-L1 + backward as `forward(...)` followed by
     # `loss.backward()`, as ONE sequence of C-ABI launches on the current stream (no autograd
     # graph, no temporaries for the gradients, no host synchronisation): trace -> mark/compact ->

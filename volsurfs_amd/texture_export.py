@@ -349,6 +349,71 @@ class BakedScene:
         return self.render_baked(rays_o, rays_d, chunk=chunk)
 
 
+def _empty_baked_bank(K, D, res, rng, inner_solid, shared_alpha, decay, lerp, device):
+    """A bank of K shells and D degrees that holds 8-bit texel rows only, every texel of every domain with the slot
+    `bake_all` would give it, the rows not yet written.  res / rng: the D per-degree resolutions and sh ranges."""
+    textures_res = list(res) + [res[-1]] * (MAX_DEG - D)
+    sh_range = list(rng) + [rng[-1]] * (MAX_DEG - D)
+    bank = NeuralTextureBank(K, NeuralTextureBank.full_capacity_rays(res), sh_degree=D - 1, alpha_sh_degree=D - 1,
+                             sh_range=sh_range, textures_res=textures_res, inner_solid=inner_solid,
+                             with_alpha_decay=decay, device=device, training=False, anchor=not lerp, lerp=lerp,
+                             shared_alpha=shared_alpha, parameters=False)
+    bank.compact_all(want_texel_of_slot=False)
+    # only slot_of / seg_start / texels are read from here on
+    bank.marks = bank.slot_xy = bank.texel_of_slot = bank.block_scratch = None
+    return bank
+
+
+def _import_planes(bank, planes):
+    """The flat device buffer of every image (export_planes' order) into the bank's texel rows, the apron clamped to
+    the edge (vsa_nt_import_planes); the bank is baked afterwards."""
+    total = _planes_bytes(bank)
+    if planes.dtype != torch.uint8 or planes.numel() != total:
+        raise _lib.VolsurfsHipError(f"expected {total} plane bytes (uint8), got {planes.numel()} of {planes.dtype}")
+    _lib.call("vsa_nt_import_planes", ctypes.byref(bank.plan), planes, total, bank.slot_of, bank.seg_start,
+              bank.texels, _lib.stream_ptr())
+    bank.baked = True
+
+
+@torch.no_grad()
+def write_scene(scene, out_dir, cameras=None, resolution=None, compress_level=6, write_meshes=True):
+    """Write a `BakedScene` (or a baked VolSurfs) the way `extract_textures` writes a method: the same
+    textures/mesh_{m}_texture_{d}_feature_{i}.png, meshes/{m}.obj and scene.json, so that `load_scene` and
+    `VolsurfsRenderer.from_scene` read it.  cameras / resolution default to the scene's own; returns the scene dict."""
+    from .mesh import save_obj
+    bank = getattr(scene, "baked", None)
+    if bank is None:
+        raise _lib.VolsurfsHipError("write_scene needs a baked scene: a BakedScene, or a VolSurfs after bake()")
+    planes, layout = _export_flat(bank)
+    flat = planes.cpu().numpy()
+    tex_dir = os.path.join(out_dir, "textures")
+    os.makedirs(tex_dir, exist_ok=True)
+    jobs = []
+    for s, d, off, n, R in layout:
+        img = flat[off:off + n * R * R * 4].reshape(n, R, R, 4)
+        jobs.extend((os.path.join(tex_dir, texture_name(s, d, i)), img[i]) for i in range(n))
+    with ThreadPoolExecutor(max_workers=min(_PNG_THREADS, len(jobs))) as ex:
+        list(ex.map(lambda j: _save_png(j[0], j[1], compress_level), jobs))
+    if write_meshes:
+        os.makedirs(os.path.join(out_dir, "meshes"), exist_ok=True)
+        for m, mesh in enumerate(scene.tensor_meshes):
+            save_obj(os.path.join(out_dir, "meshes", f"{m}.obj"), mesh)
+    ignore = [bank.tex_channels(bank.tex_index(s, 1, 0)) == 0 for s in range(bank.K)]
+    sh_range = [-float(bank.plan.sh_lo[d]) for d in range(MAX_DEG)]
+    info = meshes_info_of(bank.K, bank.tex_res, sh_range, bank.D, ignore)
+    cams = cameras if cameras is not None else (getattr(scene, "cameras", None) or {})
+    if resolution is None:
+        resolution = getattr(scene, "resolution", None)
+    if resolution is None:
+        first = next((c for split in ("train", "test") for c in cams.get(split, [])), None)
+        resolution = (first.width, first.height) if first is not None else (800, 800)
+    out = scene_info(info, resolution, scene.bg_color, cams, lerp=not bank.anchor,
+                     with_alpha_decay=bool(bank.plan.with_alpha_decay))
+    with open(os.path.join(out_dir, "scene.json"), "w") as f:
+        json.dump(out, f, indent=2)
+    return out
+
+
 @torch.no_grad()
 def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None):
     """Read a directory written by `extract_textures` (scene.json, meshes/*.obj, textures/*.png) into a BakedScene.
@@ -370,15 +435,7 @@ def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None):
     meshes = [load_obj(os.path.join(scene_path, m["mesh_path"]), device=device) for m in meta["meshes"]]
     t1 = time.perf_counter()
     K = len(meshes)
-    textures_res = list(res) + [res[-1]] * (MAX_DEG - D)
-    sh_range = list(rng) + [rng[-1]] * (MAX_DEG - D)
-    bank = NeuralTextureBank(K, NeuralTextureBank.full_capacity_rays(res), sh_degree=D - 1, alpha_sh_degree=D - 1,
-                             sh_range=sh_range, textures_res=textures_res, inner_solid=inner_solid,
-                             with_alpha_decay=decay, device=device, training=False, anchor=not lerp, lerp=lerp,
-                             shared_alpha=shared_alpha, parameters=False)
-    bank.compact_all(want_texel_of_slot=False)
-    # only slot_of / seg_start / texels are read from here on
-    bank.marks = bank.slot_xy = bank.texel_of_slot = bank.block_scratch = None
+    bank = _empty_baked_bank(K, D, res, rng, inner_solid, shared_alpha, decay, lerp, device)
     layout, total = _plane_layout(bank.plan, K, D)
     host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
     flat = host.numpy()
@@ -397,11 +454,9 @@ def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None):
     planes = host.to(device)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
-    _lib.call("vsa_nt_import_planes", ctypes.byref(bank.plan), planes, total, bank.slot_of, bank.seg_start,
-              bank.texels, _lib.stream_ptr())
+    _import_planes(bank, planes)
     torch.cuda.synchronize()
     t4 = time.perf_counter()
-    bank.baked = True
     W, H = (int(v) for v in meta.get("resolution", [[800, 800]])[0])
     cameras = {}
     for split, cams in (meta.get("cameras") or {}).items():
