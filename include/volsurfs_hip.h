@@ -2321,6 +2321,61 @@ int vsa_textransfer_planes(const vsa_nt_plan* src_plan, int degree, const uint8_
                            void* workspace, long long workspace_bytes, uint8_t* dst_planes,
                            long long dst_planes_bytes, unsigned long long* stats, void* stream);
 
+/* ---- Texture fit (no counterpart in the reference; csrc/texel_fit.hip) ----
+ * Adam whose parameters are the 8-bit texel rows of a baked bank: what lets a baked scene (a LOD above all) be fitted
+ * to target views through vsa_nt_shade_fwd(act_out) -> vsa_composite_dense_fwd_bwd_l1 -> vsa_nt_shade_bwd.  The rule
+ * is this library's own, restated in tests/texture_fit_restated.py, which the step equals BIT FOR BIT in p, m, v,
+ * texels, grad_rows and stats; unpinned against the reference, which has no such stage.
+ *   state     p, m, v: fp32 arrays indexed like texels / grad_rows (row_base[last] * 4 elements; vsa_texel_fit_state_bytes
+ *             is the bytes of ONE of them).  p in [0, 1] is the master of one texel-row element in units of q / 255, the
+ *             quantity vsa_nt_shade_bwd differentiates (round = straight-through estimator); m, v are Adam's moments.
+ *             Only INTERIOR texels own state: the one-texel apron does not exist on disk (vsa_nt_import_planes clamps
+ *             it to the edge), so apron texel (ay, ax) of the (R+2)^2 domain FOLDS INTO interior texel
+ *             (clamp(ay, 1, R), clamp(ax, 1, R)): 1 apron texel per plain edge texel, 3 per corner, 8 for R = 1.
+ *             Elements the launches never reach (apron rows, segment padding) keep what the caller put there.
+ *   rows      found through slot_of / seg_start / row_base as vsa_nt_export_planes finds them; a texel whose slot lies
+ *             outside its segment is skipped (nothing read, nothing written), as an interior texel and as an apron texel.
+ *   init      per interior texel: p = (float)byte / 255.0f (one division), m = v = 0; then every apron row of `texels`
+ *             becomes the row of the interior texel it folds into.  A bank out of bake() holds the network's values in
+ *             the apron: this makes it what a write_scene -> load_scene round trip gives.
+ *   step      per interior texel and per quad (4 elements):
+ *     fold    g = 0; the quad's own f16 gradients converted to fp32 are added, then those of the apron texels that fold
+ *             into the texel, in row-major (ay, ax) order: fp32, one rounding per add.  A gradient quad whose 64 bits
+ *             are all zero is neither added nor stored to.  Then g = g * inv_grad_scale; an element that is not finite
+ *             counts in stats[1] and is taken as 0.
+ *     consume every other gradient quad read is reset to zero bits, idle or not: grad_rows is all zero wherever the
+ *             step reads it, vsa_nt_mlp_bwd's contract with that buffer.
+ *     lazy    a quad whose four g are all zero (either sign) is IDLE: p, m, v and the bytes are neither read nor
+ *             written, the moments do not decay (SparseAdam's rule at the granularity of vsa_adam_step's idle skip);
+ *             bias correction uses the global `step`.
+ *     update  vsa_adam_step's formulas, operation order and host-side coefficients (step_size = (float)(lr / (1 -
+ *             beta1^step)), inv_bc2_sqrt = (float)(1 / sqrt(1 - beta2^step)), both formed in double) with grad_scale 1:
+ *               m = m + (1 - beta1) * (g - m);  v = v * beta2 + ((1 - beta2) * g) * g;
+ *               p = p - step_size * (m / (sqrtf(v) * inv_bc2_sqrt + eps));
+ *             an element with !(0 <= p <= 1) counts in stats[3]; p = fminf(fmaxf(p, 0), 1); byte = (int)rintf(255.0f * p).
+ *             IEEE division and square root, no contraction.
+ *     tie     the four bytes are stored to the texel's own quad and to that quad of every apron row that folds into it:
+ *             after any number of steps the apron equals its clamped interior.
+ *     stats   u64 [4], cleared by the call: 0 quads updated, 1 gradient elements that were not finite, 2 bytes of
+ *             interior texels that changed, 3 elements clamped.  Integer atomics, at most one per workgroup and counter.
+ * Given its inputs the step is deterministic.  What feeds it is not: vsa_nt_shade_bwd adds f16 atomically, so two fits
+ * of the same scene to the same views need not give the same bytes.
+ * Elements of shells without an alpha model and the rows' padding receive no gradient from vsa_nt_shade_bwd and are
+ * therefore idle for ever; nothing treats them specially.
+ * One lane per (interior texel, quad) in domain (= slot) order: 8-byte gradient, 16-byte p / m / v and 4-byte texel
+ * accesses; no scratch, and no LDS but 64 bytes for the counters.  An idle quad costs its 8 gradient bytes; a live one
+ * 116 (8 + 8 gradient, 3 x 32 state, 4 + 4 bytes).
+ * All pointers 16-byte aligned (stats: 8).  VSA_ERR_ARG (before any HIP call): a NULL pointer, misalignment, step < 1,
+ * lr, eps or inv_grad_scale negative or not finite, a beta outside [0, 1), nr_shells, rgb_degrees or a resolution out
+ * of range.  VSA_ERR_UNSUPPORTED: row_format != 0, alpha_degrees != rgb_degrees, a row buffer beyond
+ * vsa_nt_shade_bwd's 32-bit offset limit (row_base[last] * 8 >= 2^32). */
+long long vsa_texel_fit_state_bytes(const vsa_nt_plan* plan);
+int vsa_texel_fit_init(const vsa_nt_plan* plan, const int32_t* slot_of, const int32_t* seg_start, uint8_t* texels,
+                       float* p, float* m, float* v, void* stream);
+int vsa_texel_fit_step(const vsa_nt_plan* plan, const int32_t* slot_of, const int32_t* seg_start, uint16_t* grad_rows,
+                       float inv_grad_scale, float* p, float* m, float* v, uint8_t* texels, float lr, float beta1,
+                       float beta2, float eps, int step, unsigned long long* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

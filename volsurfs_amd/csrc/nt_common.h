@@ -87,6 +87,31 @@ __host__ __device__ inline bool nt_shell_has_alpha(const vsa_nt_plan& p, int she
   return !(p.inner_solid && (shell == 0 || p.shared_alpha));
 }
 
+// The texel rows of one (shell, degree) segment as a baked bank lays them out (texture_io.hip, texel_fit.hip).
+struct NtRowSeg {
+  const int32_t* slot_of;  // slot_of + dom_off of the segment
+  long long row0;          // first byte of the segment's rows (= first element of a per-element array)
+  int seg0, nrows;         // first slot, rows the segment reserves
+};
+
+__device__ __forceinline__ NtRowSeg nt_row_seg(const vsa_nt_plan& p, int shell, int deg, const int32_t* slot_of,
+                                               const int32_t* seg_start) {
+  const int sd = shell * VSA_NT_MAX_DEG + deg;
+  NtRowSeg s;
+  s.slot_of = slot_of + p.dom_off[sd];
+  s.row0 = p.row_base[sd] * 4;
+  s.seg0 = seg_start[sd];
+  s.nrows = (int)((p.row_base[sd + 1] - p.row_base[sd]) / VSA_NT_ROW_QUADS(deg));
+  return s;
+}
+
+// Row index of domain texel t within its segment, or -1 when the slot lies outside it (a bank whose slots were not
+// set up by marking every texel: nothing is read or written then).
+__device__ __forceinline__ int nt_seg_row(const NtRowSeg& s, long long t) {
+  const int rel = s.slot_of[t] - s.seg0;
+  return (rel >= 0 && rel < s.nrows) ? rel : -1;
+}
+
 // Parameter texture of logical texture `tex`: itself, or shell 0's texture of the same type and degree when the
 // models of that type are shared by all shells (plan.shared_rgb / shared_alpha; volsurfs.py:524-527, 553-556).
 // Slots, feature planes, texel rows and dfeat_abs_sum stay indexed by the LOGICAL texture.

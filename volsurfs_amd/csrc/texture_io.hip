@@ -104,32 +104,8 @@ __device__ __forceinline__ void tio_row_of(const uint32_t* px, int stride, bool 
   }
 }
 
-struct TioSeg {
-  const int32_t* slot_of;  // slot_of + dom_off of the segment
-  long long row0;          // first byte of the segment's rows
-  int seg0, nrows;         // first slot, rows the segment reserves
-};
-
-__device__ __forceinline__ TioSeg tio_seg(const vsa_nt_plan& p, int shell, int deg, const int32_t* slot_of,
-                                          const int32_t* seg_start) {
-  const int sd = shell * VSA_NT_MAX_DEG + deg;
-  TioSeg s;
-  s.slot_of = slot_of + p.dom_off[sd];
-  s.row0 = p.row_base[sd] * 4;
-  s.seg0 = seg_start[sd];
-  s.nrows = (int)((p.row_base[sd + 1] - p.row_base[sd]) / VSA_NT_ROW_QUADS(deg));
-  return s;
-}
-
-// Row index of domain texel t within its segment, or -1 when the slot lies outside it (a bank whose slots were not
-// set up by marking every texel: nothing is read or written then).
-__device__ __forceinline__ int tio_row(const TioSeg& s, long long t) {
-  const int rel = s.slot_of[t] - s.seg0;
-  return (rel >= 0 && rel < s.nrows) ? rel : -1;
-}
-
 template <int D>
-__device__ void tio_export_tile(const vsa_nt_plan& p, int shell, int tile, const TioSeg& s, const uint8_t* texels,
+__device__ void tio_export_tile(const vsa_nt_plan& p, int shell, int tile, const NtRowSeg& s, const uint8_t* texels,
                                 uint8_t* planes, TioLds* lds) {
   constexpr int N = 2 * D + 1, Q = VSA_NT_ROW_QUADS(D);
   const int R = p.tex_res[D], W = R + 2, tx = (R + TIO_TILE - 1) / TIO_TILE;
@@ -140,7 +116,7 @@ __device__ void tio_export_tile(const vsa_nt_plan& p, int shell, int tile, const
     const int pr = k % TIO_TILE, pc = k / TIO_TILE;
     const int r = r0 + pr, c = c0 + pc;
     if (r >= R || c >= R) continue;
-    const int row = tio_row(s, (long long)(c + 1) * W + (R - r));       // (iy, ix) = (c, R-1-r), apron offset 1
+    const int row = nt_seg_row(s, (long long)(c + 1) * W + (R - r));       // (iy, ix) = (c, R-1-r), apron offset 1
     uint32_t w[Q];
     if (row >= 0)
       tio_load_row<Q>(texels + s.row0 + (long long)row * Q * 4, w);
@@ -169,7 +145,7 @@ __device__ void tio_export_tile(const vsa_nt_plan& p, int shell, int tile, const
 }
 
 template <int D>
-__device__ void tio_import_tile(const vsa_nt_plan& p, int shell, int tile, const TioSeg& s, const uint8_t* planes,
+__device__ void tio_import_tile(const vsa_nt_plan& p, int shell, int tile, const NtRowSeg& s, const uint8_t* planes,
                                 uint8_t* texels, TioLds* lds) {
   constexpr int Q = VSA_NT_ROW_QUADS(D), N = 2 * D + 1;
   const int R = p.tex_res[D], W = R + 2, tx = (R + TIO_TILE - 1) / TIO_TILE;
@@ -199,7 +175,7 @@ __device__ void tio_import_tile(const vsa_nt_plan& p, int shell, int tile, const
     const int pr = k % TIO_TILE, pc = k / TIO_TILE;
     const int r = r0 + pr, c = c0 + pc;
     if (r >= R || c >= R) continue;
-    const int row = tio_row(s, (long long)(c + 1) * W + (R - r));
+    const int row = nt_seg_row(s, (long long)(c + 1) * W + (R - r));
     if (row < 0) continue;
     uint32_t w[Q];
     tio_row_of<D>(&lds[0][pr][pc], TIO_TILE * TIO_PITCH, has_alpha, w);
@@ -210,7 +186,7 @@ __device__ void tio_import_tile(const vsa_nt_plan& p, int shell, int tile, const
 // Apron texels (domain row or column 0 or R+1): clamp to the edge, i.e. the row of the nearest interior texel, read
 // straight from the planes (4 R + 4 texels per domain; not worth a tile).
 template <int D>
-__device__ void tio_import_apron(const vsa_nt_plan& p, int shell, int block, const TioSeg& s, const uint8_t* planes,
+__device__ void tio_import_apron(const vsa_nt_plan& p, int shell, int block, const NtRowSeg& s, const uint8_t* planes,
                                  uint8_t* texels) {
   constexpr int Q = VSA_NT_ROW_QUADS(D);
   const int R = p.tex_res[D], W = R + 2;
@@ -225,7 +201,7 @@ __device__ void tio_import_apron(const vsa_nt_plan& p, int shell, int block, con
     const int k = a - 2 * W;
     Y = 1 + k / 2; X = (k & 1) ? W - 1 : 0;
   }
-  const int row = tio_row(s, (long long)Y * W + X);
+  const int row = nt_seg_row(s, (long long)Y * W + X);
   if (row < 0) return;
   const int iy = min(max(Y - 1, 0), R - 1), ix = min(max(X - 1, 0), R - 1);
   const uint32_t* px = reinterpret_cast<const uint32_t*>(planes + tio_plane_off(p, shell, D)) +
@@ -268,7 +244,7 @@ tio_export_kernel(const vsa_nt_plan p, const int32_t* __restrict__ slot_of, cons
   bool is_apron;
   tio_decode(p, false, shell, deg, idx, is_apron);
   if (deg < 0) return;
-  const TioSeg s = tio_seg(p, shell, deg, slot_of, seg_start);
+  const NtRowSeg s = nt_row_seg(p, shell, deg, slot_of, seg_start);
   switch (deg) {
     case 0: tio_export_tile<0>(p, shell, idx, s, texels, planes, lds); break;
     case 1: tio_export_tile<1>(p, shell, idx, s, texels, planes, lds); break;
@@ -285,7 +261,7 @@ tio_import_kernel(const vsa_nt_plan p, const uint8_t* __restrict__ planes, const
   bool is_apron;
   tio_decode(p, true, shell, deg, idx, is_apron);
   if (deg < 0) return;
-  const TioSeg s = tio_seg(p, shell, deg, slot_of, seg_start);
+  const NtRowSeg s = nt_row_seg(p, shell, deg, slot_of, seg_start);
   if (is_apron) {
     switch (deg) {
       case 0: tio_import_apron<0>(p, shell, idx, s, planes, texels); break;

@@ -710,6 +710,11 @@ class VolSurfs(torch.nn.Module):
         from .texture_transfer import transfer_scene
         return transfer_scene(self, dst_meshes, **kw)
 
+    def refit_to(self, cameras, **kw):
+        """`texture_fit.fit_textures(self, cameras, ...)`: (a copy with the baked textures fitted to targets, report)."""
+        from .texture_fit import fit_textures
+        return fit_textures(self, cameras, **kw)
+
     # -- fused training path: the same forward + mean-L1 + backward as `forward(...)` followed by
     # `loss.backward()`, as ONE sequence of C-ABI launches on the current stream (no autograd
     # graph, no temporaries for the gradients, no host synchronisation): trace -> mark/compact ->

@@ -344,6 +344,7 @@ class BakedScene:
     render_baked = VolSurfs.render_baked
     _shade_baked = VolSurfs._shade_baked
     render_baked_camera = VolSurfs.render_baked_camera
+    refit_to = VolSurfs.refit_to
 
     def render_rays(self, rays_o, rays_d, chunk=1 << 20):
         return self.render_baked(rays_o, rays_d, chunk=chunk)
