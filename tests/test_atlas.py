@@ -15,11 +15,12 @@ from volsurfs_amd import atlas
 from volsurfs_amd._lib import VolsurfsHipError
 from volsurfs_amd.mesh import icosphere
 
+from uv_raster_restated import raster
+
 AX_U = np.array([1, 2, 2, 0, 0, 1])
 AX_V = np.array([2, 1, 0, 2, 1, 0])
 DEPTH_CAP = 24
 MAX_ROUNDS = 100
-SNAP = 256
 
 
 # ------------------------------------------------------------------------------------------------- restatement
@@ -170,40 +171,6 @@ def _emit(P, F, lab, cidx, box, off, s, R, p):
         uv[:, k, 0] = (lx * s + ox) / r
         uv[:, k, 1] = (ly * s + oy) / r
     return uv
-
-
-def raster(uv, R):
-    """(face_id [R, R], count [R, R], pair faces, pair texel index) of the header's rasterization rule."""
-    q = float(SNAP) * R
-    c = np.clip(np.asarray(uv, np.float32), np.float32(0), np.float32(1)).astype(np.float64)
-    X = np.rint(c[:, :, 0] * q).astype(np.int64)
-    Y = np.rint(c[:, :, 1] * q).astype(np.int64)
-    a2 = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])
-    h = SNAP // 2
-    i0 = np.maximum(-((-(X.min(1) - h)) // SNAP), 0)
-    i1 = np.minimum((X.max(1) - h) // SNAP, R - 1)
-    j0 = np.maximum(-((-(Y.min(1) - h)) // SNAP), 0)
-    j1 = np.minimum((Y.max(1) - h) // SNAP, R - 1)
-    ni = np.where(a2 > 0, np.maximum(i1 - i0 + 1, 0), 0)
-    nj = np.maximum(j1 - j0 + 1, 0)
-    n = ni * nj
-    f = np.repeat(np.arange(len(uv)), n)
-    k = np.arange(n.sum()) - np.repeat(np.cumsum(n) - n, n)
-    i = i0[f] + k % np.maximum(ni[f], 1)
-    j = j0[f] + k // np.maximum(ni[f], 1)
-    px, py = i * SNAP + h, j * SNAP + h
-    inside = np.ones(len(f), bool)
-    for a, b in ((0, 1), (1, 2), (2, 0)):
-        ax, ay, bx, by = X[f, a], Y[f, a], X[f, b], Y[f, b]
-        dx, dy = bx - ax, by - ay
-        e = dx * (py - ay) - dy * (px - ax)
-        inside &= (e > 0) | ((e == 0) & ((dy < 0) | ((dy == 0) & (dx < 0))))
-    f, t = f[inside], (j * R + i)[inside]
-    count = np.bincount(t, minlength=R * R).astype(np.int32)
-    fid = np.full(R * R, np.iinfo(np.int64).max)
-    np.minimum.at(fid, t, f)
-    fid[count == 0] = -1
-    return fid.reshape(R, R).astype(np.int32), count.reshape(R, R), f, t
 
 
 def restate(P, F, R=1024, p=4, return_labels=False):

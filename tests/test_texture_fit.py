@@ -8,11 +8,14 @@ import pytest
 import torch
 
 import texture_fit_restated as TF
+from texture_scene_cases import RENDER_KEYS, SH_RANGE
+from texture_scene_cases import camera as _camera
+from texture_scene_cases import random_planes as _random_planes
+from texture_scene_cases import scene as _scene
+from texture_scene_cases import smooth_planes as _smooth_planes
+from texture_scene_cases import stack as _stack
 
-RADII = (0.5, 0.6, 0.7)
-SH_RANGE = (15.0, 12.0, 9.0, 6.0)
 RES = (32, 32, 16)
-RENDER_KEYS = ("rgb", "surfs_rgb", "surfs_alpha", "bg_transmittance")
 ALPHA_QUAD = (1, 3, 4, 6)           # VSA_NT_ALPHA_QUAD(d)
 
 # test_recovery: loss_after / loss_before measured on the MI355X and the asserted bound, twice that
@@ -29,53 +32,6 @@ UNSEEN_CAP = 0.10
 
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers
-
-@functools.lru_cache(maxsize=None)
-def _stack(subdiv, K=3, resolution=64, padding=2):
-    from volsurfs_amd.atlas import compute_atlas
-    from volsurfs_amd.mesh import TensorMesh, icosphere
-    out = []
-    for r in RADII[:K]:
-        v, f = icosphere(subdiv, r)
-        out.append(compute_atlas(TensorMesh(v, f, None), resolution, padding))
-    return tuple(out)
-
-
-def _random_planes(K, res, seed, solid=False, no_alpha=False):
-    g = torch.Generator().manual_seed(seed)
-    planes = {}
-    for s in range(K):
-        for d, R in enumerate(res):
-            p = torch.randint(0, 256, (2 * d + 1, R, R, 4), generator=g, dtype=torch.uint8)
-            if no_alpha or (solid and s == 0):
-                p[..., 3] = 255
-            planes[(s, d)] = p.cuda()
-    return planes
-
-
-def _smooth_planes(K, res, seed):
-    """Smooth random planes with bytes in 64..191: a coarse random grid, bilinearly enlarged."""
-    g = torch.Generator().manual_seed(seed)
-    planes = {}
-    for s in range(K):
-        for d, R in enumerate(res):
-            coarse = torch.rand(2 * d + 1, 4, 5, 5, generator=g)
-            fine = torch.nn.functional.interpolate(coarse, size=(R, R), mode="bilinear", align_corners=True)
-            planes[(s, d)] = (64 + 127 * fine).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous().cuda()
-    return planes
-
-
-def _scene(meshes, planes, lerp=True, solid=False, shared_alpha=False):
-    from volsurfs_amd.texture_transfer import scene_from_planes
-    D = len({d for _, d in planes})
-    return scene_from_planes(meshes, planes, SH_RANGE[:D], inner_solid=solid, shared_alpha=shared_alpha, lerp=lerp,
-                             bg_color=(0.25, 0.5, 1.0))
-
-
-def _camera(eye, size=64, focal=60.0):
-    from volsurfs_amd.camera import Camera
-    return Camera.look_at(eye, focal=focal, height=size, width=size)
-
 
 def _tetra_cameras(distance=3.0, focal=125.0):
     c = distance / 3 ** 0.5

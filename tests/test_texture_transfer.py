@@ -2,7 +2,6 @@
 shells onto another with other faces and other UVs (include/volsurfs_hip.h "Texture transfer"), against the
 numpy restatement tests/texture_transfer_restated.py."""
 import ctypes
-import functools
 import os
 
 import numpy as np
@@ -11,64 +10,21 @@ import torch
 
 import mesh_distance_restated as MD
 import texture_transfer_restated as TT
+from texture_scene_cases import RENDER_KEYS, SH_RANGE
+from texture_scene_cases import camera as _camera
+from texture_scene_cases import constant_byte as _constant_byte
+from texture_scene_cases import constant_planes as _constant_planes
+from texture_scene_cases import random_planes as _random_planes
+from texture_scene_cases import scene as _scene
+from texture_scene_cases import stack as _stack
 
-RADII = (0.5, 0.6, 0.7)
-SH_RANGE = (15.0, 12.0, 9.0, 6.0)
 SRC_RES = (32, 32, 16)              # one degree coarser than the others: the per-degree grids differ
 DST_RES_UP = (40, 24, 24)           # above / equal-ish / above the source's, not multiples of the 8 x 8 tile
 DST_RES_DOWN = (16, 16, 8)
-RENDER_KEYS = ("rgb", "surfs_rgb", "surfs_alpha", "bg_transmittance")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # helpers
-
-@functools.lru_cache(maxsize=None)
-def _stack(subdiv, resolution=64, padding=2):
-    """Nested icospheres (80 faces at subdiv 1, 320 at 2) of radii 0.5 / 0.6 / 0.7 with UVs from compute_atlas."""
-    from volsurfs_amd.atlas import compute_atlas
-    from volsurfs_amd.mesh import TensorMesh, icosphere
-    out = []
-    for r in RADII:
-        v, f = icosphere(subdiv, r)
-        out.append(compute_atlas(TensorMesh(v, f, None), resolution, padding))
-    return tuple(out)
-
-
-def _random_planes(K, res, seed, solid):
-    g = torch.Generator().manual_seed(seed)
-    planes = {}
-    for s in range(K):
-        for d, R in enumerate(res):
-            p = torch.randint(0, 256, (2 * d + 1, R, R, 4), generator=g, dtype=torch.uint8)
-            if solid and s == 0:
-                p[..., 3] = 255
-            planes[(s, d)] = p.cuda()
-    return planes
-
-
-def _constant_planes(K, res, solid):
-    planes = {}
-    for s in range(K):
-        for d, R in enumerate(res):
-            p = torch.empty(2 * d + 1, R, R, 4, dtype=torch.uint8)
-            for i in range(2 * d + 1):
-                p[i] = _constant_byte(s, d, i)
-            if solid and s == 0:
-                p[..., 3] = 255
-            planes[(s, d)] = p.cuda()
-    return planes
-
-
-def _constant_byte(s, d, i):
-    return (53 * s + 29 * d + 7 * i + 11) % 256
-
-
-def _scene(meshes, planes, lerp=True, solid=False, builder="device"):
-    from volsurfs_amd.texture_transfer import scene_from_planes
-    return scene_from_planes(meshes, planes, SH_RANGE, inner_solid=solid, lerp=lerp, bg_color=(0.25, 0.5, 1.0),
-                             builder=builder)
-
 
 def _restated(scene, dst_meshes, res, samples, reach, max_distance):
     """The restatement's planes and reports for every (shell, degree) of a transfer."""
@@ -87,11 +43,6 @@ def _restated(scene, dst_meshes, res, samples, reach, max_distance):
                 tris[off:off + n], fuv[off:off + n], src_planes[(s, d)].cpu().numpy(), float(bank.plan.sh_lo[d]),
                 float(bank.plan.sh_span[d]), bank.anchor, has_alpha, V, F, UV, res[d], samples, reach, max_distance)
     return planes, reports
-
-
-def _camera(eye, size=64, focal=60.0):
-    from volsurfs_amd.camera import Camera
-    return Camera.look_at(eye, focal=focal, height=size, width=size)
 
 
 def _assert_same_render(a, b, keys=RENDER_KEYS):

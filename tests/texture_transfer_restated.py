@@ -5,6 +5,7 @@ float64 in the rule's shape.  The yardstick of tests/test_texture_transfer.py.""
 import numpy as np
 
 import mesh_distance_restated as MD
+from uv_raster_restated import covers as raster_covers   # the rasterizer's rule ("UV atlas", raster)
 
 F32, F16 = np.float32, np.float16
 TILE = 8
@@ -97,25 +98,6 @@ def project(qx, qy, rec):
         dd = (rx * rx + ry * ry) + zero
         dd = np.where(interior, zero, dd).astype(F32)
     return dd, u, v
-
-
-def raster_covers(faces_uvs, R, i, j):
-    """[N, F] bool: does face f cover texel (i[n], j[n]) by the rasterizer's rule ("UV atlas", raster)?  Corners snapped
-    in float64 to 1/256 texel (rint of clamp(uv, 0, 1) * 256 R), int64 edge functions, top-left rule; a face whose snapped
-    area is <= 0 covers nothing."""
-    uv = np.asarray(faces_uvs, F32).reshape(-1, 3, 2)
-    with np.errstate(all="ignore"):
-        snapped = np.rint(np.clip(uv, F32(0), F32(1)).astype(np.float64) * (256.0 * R))
-    snapped = np.where(np.isfinite(snapped), snapped, 0).astype(np.int64)
-    X, Y = snapped[None, :, :, 0], snapped[None, :, :, 1]
-    px = (np.asarray(i, np.int64) * 256 + 128)[:, None]
-    py = (np.asarray(j, np.int64) * 256 + 128)[:, None]
-    inside = ((X[..., 1] - X[..., 0]) * (Y[..., 2] - Y[..., 0]) - (Y[..., 1] - Y[..., 0]) * (X[..., 2] - X[..., 0])) > 0
-    for a, b in ((0, 1), (1, 2), (2, 0)):
-        dx, dy = X[..., b] - X[..., a], Y[..., b] - Y[..., a]
-        e = dx * (py - Y[..., a]) - dy * (px - X[..., a])
-        inside = inside & ((e > 0) | ((e == 0) & ((dy < 0) | ((dy == 0) & (dx < 0)))))
-    return inside
 
 
 OUTSIDE = np.uint64(1) << np.uint64(63)

@@ -15,8 +15,9 @@
 //            width prefix per shelf: about sqrt(charts) shelves); the host reads the fit flag.  The last walk writes
 //            the shelves, and one lane per sorted rectangle finds its shelf and offset.
 //   emit:    one lane per face writes its three corners' UVs.
-//   raster:  faces snapped to 1/256 texel; a scan of every face's 8x8-tile count gives (face, tile) work items, one lane
-//            per item tests its 64 texel centres with int64 edge functions (top-left rule) and counts them; a second
+//   raster:  the coverage rule is uv_raster.h's (faces snapped to 1/256 texel, int64 edge functions, top-left rule); a
+//            scan of every face's 8x8-tile count gives (face, tile) work items, one lane per item tests its 64 texel
+//            centres and counts them; a second
 //            pass over the same items flags the charts with a texel counted twice.  Flagged charts are split by a bit
 //            of their faces' split codes and the round repeats.
 // No float is summed by atomics: the normal sums have a fixed order, and integer atomics form minima, maxima, unions,
@@ -27,10 +28,10 @@
 #include <cstring>
 
 #include "mesh_topology.h"
+#include "uv_raster.h"
 
 #define ATL_BLOCK MT_BLOCK
 #define ATL_TILE 8
-#define ATL_SNAP 256
 #define ATL_DEPTH_CAP 24
 #define ATL_MIN_RES 8
 #define ATL_MAX_RES 16384
@@ -329,58 +330,15 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_emit(const float* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------ raster
 
-struct AtlTri {
-  long long x[3], y[3];
-  int i0, i1, j0, j1;   // texel box (inclusive); empty when i0 > i1 or j0 > j1
-};
-
-__device__ __forceinline__ long long atl_floordiv(long long a, long long b) {
-  return a >= 0 ? a / b : -((-a + b - 1) / b);
-}
-
-// Snapped corners (rint(clamp(uv, 0, 1) * 256 R), fp64) and the texel box; a face whose snapped signed area is <= 0
-// gets an empty box.
-__device__ void atl_tri(const float* __restrict__ uv, long long f, int R, AtlTri* t) {
-  const double q = (double)ATL_SNAP * (double)R;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float u = fminf(fmaxf(uv[6 * f + 2 * k], 0.f), 1.f), v = fminf(fmaxf(uv[6 * f + 2 * k + 1], 0.f), 1.f);
-    t->x[k] = (long long)rint((double)u * q);
-    t->y[k] = (long long)rint((double)v * q);
-  }
-  const long long a2 = (t->x[1] - t->x[0]) * (t->y[2] - t->y[0]) - (t->y[1] - t->y[0]) * (t->x[2] - t->x[0]);
-  const long long xl = min(t->x[0], min(t->x[1], t->x[2])), xh = max(t->x[0], max(t->x[1], t->x[2]));
-  const long long yl = min(t->y[0], min(t->y[1], t->y[2])), yh = max(t->y[0], max(t->y[1], t->y[2]));
-  const long long h = ATL_SNAP / 2;
-  long long i0 = -atl_floordiv(-(xl - h), ATL_SNAP), i1 = atl_floordiv(xh - h, ATL_SNAP);
-  long long j0 = -atl_floordiv(-(yl - h), ATL_SNAP), j1 = atl_floordiv(yh - h, ATL_SNAP);
-  i0 = i0 < 0 ? 0 : i0;
-  j0 = j0 < 0 ? 0 : j0;
-  i1 = i1 > R - 1 ? R - 1 : i1;
-  j1 = j1 > R - 1 ? R - 1 : j1;
-  if (a2 <= 0) i1 = i0 - 1;
-  t->i0 = (int)i0;
-  t->i1 = (int)i1;
-  t->j0 = (int)j0;
-  t->j1 = (int)j1;
-}
-
-__device__ __forceinline__ bool atl_edge_in(long long ax, long long ay, long long bx, long long by, long long px,
-                                            long long py) {
-  const long long dx = bx - ax, dy = by - ay;
-  const long long e = dx * (py - ay) - dy * (px - ax);
-  return e > 0 || (e == 0 && (dy < 0 || (dy == 0 && dx < 0)));
-}
-
+// Coverage is uv_raster.h's rule: the snapped corners, the texel box and the edge tests are its own.
 __global__ __launch_bounds__(ATL_BLOCK) void atl_tile_counts(const float* __restrict__ uv, long long F, int R,
                                                             long long* __restrict__ ntile) {
   const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (f >= F) return;
-  AtlTri t;
-  atl_tri(uv, f, R, &t);
-  ntile[f] = (t.i0 > t.i1 || t.j0 > t.j1)
+  const UvBox b = uv_box(uv_snap(uv + 6 * f, R), R);
+  ntile[f] = (b.i0 > b.i1 || b.j0 > b.j1)
                  ? 0
-                 : (long long)(t.i1 / ATL_TILE - t.i0 / ATL_TILE + 1) * (t.j1 / ATL_TILE - t.j0 / ATL_TILE + 1);
+                 : (long long)(b.i1 / ATL_TILE - b.i0 / ATL_TILE + 1) * (b.j1 / ATL_TILE - b.j0 / ATL_TILE + 1);
 }
 
 // mode 0: count[j R + i] += 1 and face_id[j R + i] = min(face) (unsigned: empty stays -1) for every covered texel;
@@ -398,22 +356,18 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_raster(const float* __restrict_
       else hi = mid - 1;
     }
     const long long f = lo;
-    AtlTri t;
-    atl_tri(uv, f, R, &t);
+    const UvTri t = uv_snap(uv + 6 * f, R);
+    const UvBox b = uv_box(t, R);
     const long long k = it - toff[f];
-    const int ntx = t.i1 / ATL_TILE - t.i0 / ATL_TILE + 1;
-    const int tx = t.i0 / ATL_TILE + (int)(k % ntx), ty = t.j0 / ATL_TILE + (int)(k / ntx);
-    const int ia = max(tx * ATL_TILE, t.i0), ib = min(tx * ATL_TILE + ATL_TILE - 1, t.i1);
-    const int ja = max(ty * ATL_TILE, t.j0), jb = min(ty * ATL_TILE + ATL_TILE - 1, t.j1);
+    const int ntx = b.i1 / ATL_TILE - b.i0 / ATL_TILE + 1;
+    const int tx = b.i0 / ATL_TILE + (int)(k % ntx), ty = b.j0 / ATL_TILE + (int)(k / ntx);
+    const int ia = max(tx * ATL_TILE, b.i0), ib = min(tx * ATL_TILE + ATL_TILE - 1, b.i1);
+    const int ja = max(ty * ATL_TILE, b.j0), jb = min(ty * ATL_TILE + ATL_TILE - 1, b.j1);
     bool hit2 = false;
     for (int j = ja; j <= jb; ++j) {
-      const long long py = (long long)j * ATL_SNAP + ATL_SNAP / 2;
+      const long long py = uv_centre(j);
       for (int i = ia; i <= ib; ++i) {
-        const long long px = (long long)i * ATL_SNAP + ATL_SNAP / 2;
-        if (!atl_edge_in(t.x[0], t.y[0], t.x[1], t.y[1], px, py) ||
-            !atl_edge_in(t.x[1], t.y[1], t.x[2], t.y[2], px, py) ||
-            !atl_edge_in(t.x[2], t.y[2], t.x[0], t.y[0], px, py))
-          continue;
+        if (!uv_edges_in(t, uv_centre(i), py)) continue;      // (the box is empty unless the face is front)
         const long long o = (long long)j * R + i;
         if (mode == 0) {
           atomicAdd(count + o, 1);

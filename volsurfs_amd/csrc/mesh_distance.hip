@@ -11,6 +11,7 @@
 // atomics, the sums as one fp64 pair per wave added in a fixed order: exact or fixed-order, the same for every schedule.
 #include "closest_walk.h"
 #include "mesh_topology.h"
+#include "ordered_sum.h"
 
 namespace {
 
@@ -158,37 +159,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) void surface_distance_kernel(
   }
 }
 
-// The waves' fp64 pairs added in wave order, in a shape fixed by the number of waves alone: lane t of 1024 adds the
-// consecutive waves [t c, (t + 1) c), c = ceil(waves / 1024), one after the other; lane 0 then adds the 1024 segment
-// sums in lane order.  (One lane adding every pair in turn is a chain of 15 625 dependent loads and adds for 10^6
-// samples: it took as long as the walk.)
-constexpr int SUM_BLOCK = 1024;
-
-__global__ __launch_bounds__(SUM_BLOCK) void distance_sum_kernel(const double2* __restrict__ partials,
-                                                                 long long nr_waves,
-                                                                 unsigned long long* __restrict__ stats) {
-  __shared__ double s_a[SUM_BLOCK], s_b[SUM_BLOCK];
-  const int t = threadIdx.x;
-  const long long c = (nr_waves + SUM_BLOCK - 1) / SUM_BLOCK;
-  const long long begin = t * c, end = begin + c < nr_waves ? begin + c : nr_waves;
-  double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-  for (long long w = begin; w < end; ++w) {
-    const double2 p = partials[w];
-    s1 += p.x;
-    s2 += p.y;
-  }
-  s_a[t] = s1;
-  s_b[t] = s2;
-  __syncthreads();
-  if (t != 0) return;
-  double t1 = 0.0, t2 = 0.0;
-  for (int l = 0; l < SUM_BLOCK; ++l) {
-    t1 += s_a[l];
-    t2 += s_b[l];
-  }
-  stats[ST_SUM] = (unsigned long long)__double_as_longlong(t1);
-  stats[ST_SUM2] = (unsigned long long)__double_as_longlong(t2);
+// The waves' fp64 pairs (sum of d, sum of d^2) added in ordered_sum.h's fixed order.
+__global__ __launch_bounds__(ORDERED_SUM_BLOCK) void distance_sum_kernel(const double2* __restrict__ partials,
+                                                                         long long nr_waves,
+                                                                         unsigned long long* __restrict__ stats) {
+  double total[2];
+  if (!ordered_sum<2, 4>(reinterpret_cast<const double*>(partials), nr_waves, total)) return;
+  stats[ST_SUM] = (unsigned long long)__double_as_longlong(total[0]);
+  stats[ST_SUM2] = (unsigned long long)__double_as_longlong(total[1]);
 }
 
 // rocPRIM's temporary storage for the scan of n weights, after the weights [n] and the maximum (one aligned word)
@@ -333,7 +311,7 @@ extern "C" int vsa_surface_distance(const float* src_tris, long long src_first_s
                          t.roots, t.frames, nr_samples, seed, th, nr_thresholds, stats, partials);
     });
   });
-  hipLaunchKernelGGL(distance_sum_kernel, dim3(1), dim3(SUM_BLOCK), 0, st, reinterpret_cast<const double2*>(partials), waves,
+  hipLaunchKernelGGL(distance_sum_kernel, dim3(1), dim3(ORDERED_SUM_BLOCK), 0, st, reinterpret_cast<const double2*>(partials), waves,
                      stats);
   VSA_RETURN_LAUNCH_STATUS();
 }

@@ -87,6 +87,62 @@ __host__ __device__ inline bool nt_shell_has_alpha(const vsa_nt_plan& p, int she
   return !(p.inner_solid && (shell == 0 || p.shared_alpha));
 }
 
+// ---- a baked 8-bit bank and its RGBA8 planes ("Texture export"), for every stage that consumes one: texture_io.hip,
+// texel_fit.hip, texture_transfer.hip.
+constexpr int NT_MAX_TEX_RES = 16384;   // the largest texture resolution of a baked bank and of a plane
+
+__host__ __device__ static inline long long nt_plane_bytes(int R) { return (long long)R * R * 4; }
+
+// The planes' byte layout over per-degree resolutions res[0..degrees): planes are ordered (shell, degree, coefficient),
+// 2d + 1 planes of res[d]^2 RGBA pixels per (shell, degree).  stride: bytes per shell; before: bytes of a shell before
+// `degree`.
+__host__ __device__ static inline void nt_plane_layout(const int32_t* res, int degrees, int degree, long long* stride,
+                                                long long* before) {
+  *stride = *before = 0;
+  for (int d = 0; d < degrees; ++d) {
+    const long long b = (2 * d + 1) * nt_plane_bytes(res[d]);
+    if (d < degree) *before += b;
+    *stride += b;
+  }
+}
+
+// First byte of plane (shell, degree, coefficient 0) of a plan's own planes; (nr_shells, 0): their total.
+__host__ __device__ static inline long long nt_plane_offset(const vsa_nt_plan& p, int shell, int degree) {
+  long long stride, before;
+  nt_plane_layout(p.tex_res, p.rgb_degrees, degree, &stride, &before);
+  return shell * stride + before;
+}
+
+// Is this the plan of a baked 8-bit bank?  nt_baked_plan_args is the VSA_ERR_ARG half: a plan with shells and degrees in
+// range (nt_baked_plan_counts), then every tex_res in 1..NT_MAX_TEX_RES (nt_baked_plan_resolutions, which reads
+// rgb_degrees and so comes after the counts).  nt_baked_plan_supported is the VSA_ERR_UNSUPPORTED half: 8-bit rows, one
+// alpha coefficient per rgb coefficient.  Each entry keeps its own precedence by the order in which it calls them:
+// texel_fit reports every argument fault first; texture_io and the transfer report an unsupported plan before a bad
+// resolution and so call counts, supported, resolutions.
+inline int nt_baked_plan_counts(const vsa_nt_plan* p) {
+  if (!p) return VSA_ERR_ARG;
+  if (p->nr_shells < 1 || p->nr_shells > VSA_MAX_SHELLS) return VSA_ERR_ARG;
+  if (p->rgb_degrees < 1 || p->rgb_degrees > VSA_NT_MAX_DEG) return VSA_ERR_ARG;
+  return VSA_OK;
+}
+
+inline int nt_baked_plan_resolutions(const vsa_nt_plan* p) {
+  for (int d = 0; d < p->rgb_degrees; ++d)
+    if (p->tex_res[d] < 1 || p->tex_res[d] > NT_MAX_TEX_RES) return VSA_ERR_ARG;
+  return VSA_OK;
+}
+
+inline int nt_baked_plan_args(const vsa_nt_plan* p) {
+  if (const int rc = nt_baked_plan_counts(p)) return rc;
+  return nt_baked_plan_resolutions(p);
+}
+
+inline int nt_baked_plan_supported(const vsa_nt_plan* p) {
+  if (p->row_format != 0) return VSA_ERR_UNSUPPORTED;                    // 8-bit rows only
+  if (p->alpha_degrees != p->rgb_degrees) return VSA_ERR_UNSUPPORTED;    // one alpha coefficient per rgb coefficient
+  return VSA_OK;
+}
+
 // The texel rows of one (shell, degree) segment as a baked bank lays them out (texture_io.hip, texel_fit.hip).
 struct NtRowSeg {
   const int32_t* slot_of;  // slot_of + dom_off of the segment

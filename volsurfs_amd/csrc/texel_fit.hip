@@ -208,18 +208,9 @@ __global__ __launch_bounds__(TF_BLOCK) void texel_fit_step_kernel(const vsa_nt_p
   tf_count(counts, stats);
 }
 
-int tf_check_plan(const vsa_nt_plan* p) {
-  if (!p) return VSA_ERR_ARG;
-  if (p->nr_shells < 1 || p->nr_shells > VSA_MAX_SHELLS) return VSA_ERR_ARG;
-  if (p->rgb_degrees < 1 || p->rgb_degrees > VSA_NT_MAX_DEG) return VSA_ERR_ARG;
-  for (int d = 0; d < p->rgb_degrees; ++d)
-    if (p->tex_res[d] < 1 || p->tex_res[d] > 16384) return VSA_ERR_ARG;
-  return VSA_OK;
-}
-
+// This stage's own limits, after nt_common.h's nt_baked_plan_supported.
 int tf_check_supported(const vsa_nt_plan* p) {
-  if (p->row_format != 0) return VSA_ERR_UNSUPPORTED;                    // 8-bit rows only
-  if (p->alpha_degrees != p->rgb_degrees) return VSA_ERR_UNSUPPORTED;    // as the planes of texture_io.hip
+  if (const int rc = nt_baked_plan_supported(p)) return rc;
   if (p->row_base[VSA_MAX_SHELLS * VSA_NT_MAX_DEG] * 8 >= (1ll << 32)) return VSA_ERR_UNSUPPORTED;   // vsa_nt_shade_bwd's limit
   if (p->nr_shells * tf_blocks_per_shell(*p) >= (1ll << 31)) return VSA_ERR_UNSUPPORTED;
   return VSA_OK;
@@ -231,7 +222,7 @@ bool tf_finite_nonneg(float x) { return x >= 0.f && x <= 3.4028234663852886e38f;
 }  // namespace
 
 extern "C" long long vsa_texel_fit_state_bytes(const vsa_nt_plan* plan) {
-  int rc = tf_check_plan(plan);
+  int rc = nt_baked_plan_args(plan);
   if (!rc) rc = tf_check_supported(plan);
   if (rc) return rc;
   return plan->row_base[VSA_MAX_SHELLS * VSA_NT_MAX_DEG] * 4 * (long long)sizeof(float);
@@ -239,7 +230,7 @@ extern "C" long long vsa_texel_fit_state_bytes(const vsa_nt_plan* plan) {
 
 extern "C" int vsa_texel_fit_init(const vsa_nt_plan* plan, const int32_t* slot_of, const int32_t* seg_start,
                                   uint8_t* texels, float* p, float* m, float* v, void* stream) {
-  int rc = tf_check_plan(plan);
+  int rc = nt_baked_plan_args(plan);
   if (rc) return rc;
   if (!slot_of || !seg_start || !texels || !p || !m || !v) return VSA_ERR_ARG;
   if (!tf_aligned16(texels) || !tf_aligned16(p) || !tf_aligned16(m) || !tf_aligned16(v)) return VSA_ERR_ARG;
@@ -255,7 +246,7 @@ extern "C" int vsa_texel_fit_step(const vsa_nt_plan* plan, const int32_t* slot_o
                                   uint16_t* grad_rows, float inv_grad_scale, float* p, float* m, float* v,
                                   uint8_t* texels, float lr, float beta1, float beta2, float eps, int step,
                                   unsigned long long* stats, void* stream) {
-  int rc = tf_check_plan(plan);
+  int rc = nt_baked_plan_args(plan);
   if (rc) return rc;
   if (!slot_of || !seg_start || !grad_rows || !p || !m || !v || !texels || !stats) return VSA_ERR_ARG;
   if (!tf_aligned16(grad_rows) || !tf_aligned16(p) || !tf_aligned16(m) || !tf_aligned16(v) || !tf_aligned16(texels) ||

@@ -16,19 +16,6 @@
 
 typedef uint32_t TioLds[TIO_TILE][TIO_PITCH];
 
-__host__ __device__ static inline long long tio_plane_bytes(int R) { return (long long)R * R * 4; }
-
-// First byte of plane (shell, d, coefficient 0): planes are ordered (shell, degree, coefficient).
-__host__ __device__ static inline long long tio_plane_off(const vsa_nt_plan& p, int shell, int deg) {
-  long long shell_bytes = 0, before = 0;
-  for (int d = 0; d < p.rgb_degrees; ++d) {
-    const long long b = (2 * d + 1) * tio_plane_bytes(p.tex_res[d]);
-    if (d < deg) before += b;
-    shell_bytes += b;
-  }
-  return shell * shell_bytes + before;
-}
-
 __host__ __device__ static inline int tio_tiles(int R) {
   const int t = (R + TIO_TILE - 1) / TIO_TILE;
   return t * t;
@@ -131,11 +118,11 @@ __device__ void tio_export_tile(const vsa_nt_plan& p, int shell, int tile, const
   const int pr = threadIdx.x / 8, g = threadIdx.x % 8;
   const int r = r0 + pr, c = c0 + 4 * g;
   if (r >= R || c >= R) return;
-  uint8_t* dst = planes + tio_plane_off(p, shell, D) + ((long long)r * R + c) * 4;
+  uint8_t* dst = planes + nt_plane_offset(p, shell, D) + ((long long)r * R + c) * 4;
 #pragma unroll
   for (int i = 0; i < N; ++i) {
     const uint32_t* src = &lds[i][pr][4 * g];
-    uint8_t* d = dst + i * tio_plane_bytes(R);
+    uint8_t* d = dst + i * nt_plane_bytes(R);
     if ((R & 3) == 0) {
       *reinterpret_cast<uint4*>(d) = make_uint4(src[0], src[1], src[2], src[3]);
     } else {
@@ -155,11 +142,11 @@ __device__ void tio_import_tile(const vsa_nt_plan& p, int shell, int tile, const
     const int pr = threadIdx.x / 8, g = threadIdx.x % 8;
     const int r = r0 + pr, c = c0 + 4 * g;
     if (r < R && c < R) {
-      const uint8_t* src = planes + tio_plane_off(p, shell, D) + ((long long)r * R + c) * 4;
+      const uint8_t* src = planes + nt_plane_offset(p, shell, D) + ((long long)r * R + c) * 4;
 #pragma unroll
       for (int i = 0; i < N; ++i) {
         uint32_t* dst = &lds[i][pr][4 * g];
-        const uint8_t* sp = src + i * tio_plane_bytes(R);
+        const uint8_t* sp = src + i * nt_plane_bytes(R);
         if ((R & 3) == 0) {
           const uint4 v = *reinterpret_cast<const uint4*>(sp);
           dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
@@ -204,10 +191,10 @@ __device__ void tio_import_apron(const vsa_nt_plan& p, int shell, int block, con
   const int row = nt_seg_row(s, (long long)Y * W + X);
   if (row < 0) return;
   const int iy = min(max(Y - 1, 0), R - 1), ix = min(max(X - 1, 0), R - 1);
-  const uint32_t* px = reinterpret_cast<const uint32_t*>(planes + tio_plane_off(p, shell, D)) +
+  const uint32_t* px = reinterpret_cast<const uint32_t*>(planes + nt_plane_offset(p, shell, D)) +
                        ((long long)(R - 1 - ix) * R + iy);
   uint32_t w[Q];
-  tio_row_of<D>(px, (int)(tio_plane_bytes(R) / 4), nt_shell_has_alpha(p, shell), w);
+  tio_row_of<D>(px, (int)(nt_plane_bytes(R) / 4), nt_shell_has_alpha(p, shell), w);
   tio_store_row<Q>(texels + s.row0 + (long long)row * Q * 4, w);
 }
 
@@ -279,14 +266,12 @@ tio_import_kernel(const vsa_nt_plan p, const uint8_t* __restrict__ planes, const
   }
 }
 
+// nt_common.h's checks in this stage's order (an unsupported plan is reported before a bad resolution), then its own
+// limit on the grid.
 static int tio_check(const vsa_nt_plan* p) {
-  if (!p) return VSA_ERR_ARG;
-  if (p->nr_shells < 1 || p->nr_shells > VSA_MAX_SHELLS) return VSA_ERR_ARG;
-  if (p->rgb_degrees < 1 || p->rgb_degrees > VSA_NT_MAX_DEG) return VSA_ERR_ARG;
-  if (p->alpha_degrees != p->rgb_degrees) return VSA_ERR_UNSUPPORTED;   // one alpha coefficient per rgb coefficient
-  if (p->row_format != 0) return VSA_ERR_UNSUPPORTED;                   // 8-bit rows only
-  for (int d = 0; d < p->rgb_degrees; ++d)
-    if (p->tex_res[d] < 1 || p->tex_res[d] > 16384) return VSA_ERR_ARG;
+  if (const int rc = nt_baked_plan_counts(p)) return rc;
+  if (const int rc = nt_baked_plan_supported(p)) return rc;
+  if (const int rc = nt_baked_plan_resolutions(p)) return rc;
   long long blocks = (long long)p->nr_shells * tio_blocks_per_shell(*p, true);
   if (blocks >= (1ll << 31)) return VSA_ERR_UNSUPPORTED;
   return VSA_OK;
@@ -295,7 +280,7 @@ static int tio_check(const vsa_nt_plan* p) {
 extern "C" long long vsa_nt_planes_bytes(const vsa_nt_plan* plan) {
   const int rc = tio_check(plan);
   if (rc) return rc;
-  return tio_plane_off(*plan, plan->nr_shells, 0);
+  return nt_plane_offset(*plan, plan->nr_shells, 0);
 }
 
 extern "C" int vsa_nt_export_planes(const vsa_nt_plan* plan, const int32_t* slot_of, const int32_t* seg_start,
@@ -304,7 +289,7 @@ extern "C" int vsa_nt_export_planes(const vsa_nt_plan* plan, const int32_t* slot
   if (rc) return rc;
   if (!slot_of || !seg_start || !texels || !planes) return VSA_ERR_ARG;
   if (((uintptr_t)planes & 15) || ((uintptr_t)texels & 15)) return VSA_ERR_ARG;
-  if (planes_bytes != tio_plane_off(*plan, plan->nr_shells, 0)) return VSA_ERR_ARG;
+  if (planes_bytes != nt_plane_offset(*plan, plan->nr_shells, 0)) return VSA_ERR_ARG;
   const int blocks = plan->nr_shells * tio_blocks_per_shell(*plan, false);
   hipLaunchKernelGGL(tio_export_kernel, dim3(blocks), dim3(TIO_THREADS), 0, (hipStream_t)stream, *plan, slot_of,
                      seg_start, texels, planes);
@@ -317,7 +302,7 @@ extern "C" int vsa_nt_import_planes(const vsa_nt_plan* plan, const uint8_t* plan
   if (rc) return rc;
   if (!slot_of || !seg_start || !texels || !planes) return VSA_ERR_ARG;
   if (((uintptr_t)planes & 15) || ((uintptr_t)texels & 15)) return VSA_ERR_ARG;
-  if (planes_bytes != tio_plane_off(*plan, plan->nr_shells, 0)) return VSA_ERR_ARG;
+  if (planes_bytes != nt_plane_offset(*plan, plan->nr_shells, 0)) return VSA_ERR_ARG;
   const int blocks = plan->nr_shells * tio_blocks_per_shell(*plan, true);
   hipLaunchKernelGGL(tio_import_kernel, dim3(blocks), dim3(TIO_THREADS), 0, (hipStream_t)stream, *plan, planes,
                      slot_of, seg_start, texels);

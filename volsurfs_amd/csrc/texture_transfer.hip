@@ -13,11 +13,12 @@
 // order: the same inputs give the same bytes.
 #include "closest_walk.h"
 #include "nt_common.h"
+#include "ordered_sum.h"
+#include "uv_raster.h"
 
 namespace {
 
 constexpr int TT_TILE = 8;                  // 8 x 8 texels = one wave
-constexpr int TT_SUM_BLOCK = 1024;
 constexpr unsigned long long TT_UNOWNED = ~0ull;
 enum { TT_OWNED = 0, TT_COVERED = 1, TT_SAMPLES = 2, TT_MAX = 3, TT_FAR = 4, TT_SUM2 = 5, TT_WORDS = 8 };
 
@@ -51,41 +52,6 @@ __device__ __forceinline__ void tt_project(const float4 a0, const float4 e1, con
 }
 
 __device__ __forceinline__ bool tt_finite(float x) { return fabsf(x) < INFINITY; }
-
-// The coverage rule of "UV atlas", raster (vsa_atlas_rasterize), restated: corners snapped in fp64 to 1/256 texel, int64
-// edge functions, top-left rule; a face whose snapped area is <= 0 covers nothing.
-constexpr long long TT_SNAP = 256;
-
-struct TtSnapped {
-  long long x[3], y[3];
-  bool front;
-};
-
-__device__ __forceinline__ TtSnapped tt_snap(const float* __restrict__ uv6, int R) {
-  TtSnapped t;
-  const double q = (double)TT_SNAP * (double)R;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float u = fminf(fmaxf(uv6[2 * k], 0.f), 1.f), v = fminf(fmaxf(uv6[2 * k + 1], 0.f), 1.f);
-    t.x[k] = (long long)rint((double)u * q);
-    t.y[k] = (long long)rint((double)v * q);
-  }
-  t.front = (t.x[1] - t.x[0]) * (t.y[2] - t.y[0]) - (t.y[1] - t.y[0]) * (t.x[2] - t.x[0]) > 0;
-  return t;
-}
-
-__device__ __forceinline__ bool tt_edge_in(long long ax, long long ay, long long bx, long long by, long long px,
-                                           long long py) {
-  const long long dx = bx - ax, dy = by - ay;
-  const long long e = dx * (py - ay) - dy * (px - ax);
-  return e > 0 || (e == 0 && (dy < 0 || (dy == 0 && dx < 0)));
-}
-
-__device__ __forceinline__ bool tt_covers(const TtSnapped& t, int i, int j) {
-  const long long px = i * TT_SNAP + TT_SNAP / 2, py = j * TT_SNAP + TT_SNAP / 2;
-  return t.front && tt_edge_in(t.x[0], t.y[0], t.x[1], t.y[1], px, py) &&
-         tt_edge_in(t.x[1], t.y[1], t.x[2], t.y[2], px, py) && tt_edge_in(t.x[2], t.y[2], t.x[0], t.y[0], px, py);
-}
 
 // An owner word: the faces whose raster covers the texel come first (bit 63 clear, d2 = 0), then the others by the
 // projection's d2; ties go to the lowest face.  d2 >= 0: the order of its bits is the order of its values.
@@ -129,14 +95,14 @@ __global__ __launch_bounds__(64) void tt_owner_kernel(const float* __restrict__ 
   const int j1 = (int)fminf(fmaxf(ceilf(maxy + reach + 0.5f), 0.0f), top);
   const int w = i1 - i0 + 1, h = j1 - j0 + 1;
   const float reach2 = reach * reach;
-  const TtSnapped snapped = tt_snap(uv6, R);
+  const UvTri snapped = uv_snap(uv6, R);                // coverage: uv_raster.h, vsa_atlas_rasterize's rule
   const unsigned face = (unsigned)(gf - sh.face_base[shell]);
   unsigned long long* map = keys + (long long)shell * R * R;
   for (long long t = lane; t < (long long)w * h; t += 64) {
     const int i = i0 + (int)(t % w), j = j0 + (int)(t / w);
     float d2, u, v;
     tt_project(a0, e1, e2, (float)i + 0.5f, (float)j + 0.5f, d2, u, v);
-    const bool covers = tt_covers(snapped, i, j);
+    const bool covers = uv_covers(snapped, i, j);
     if (!(covers || d2 <= reach2)) continue;
     const unsigned long long key = tt_key(covers, d2, face);
     unsigned long long* word = map + (long long)j * R + i;
@@ -325,25 +291,15 @@ __global__ __launch_bounds__(TRACE_BLOCK) void tt_transfer_kernel(const TtArgs a
   }
 }
 
-// A shell's per-wave sums added in wave order, in a shape fixed by the number of waves alone (distance_sum_kernel's
-// shape): lane t of 1024 adds the consecutive waves [t c, (t + 1) c), c = ceil(waves / 1024), lane 0 then adds the
-// 1024 lane sums in lane order.
-__global__ __launch_bounds__(TT_SUM_BLOCK) void tt_sum_kernel(const double* __restrict__ partials, int nr_waves,
-                                                              int samples, unsigned long long* __restrict__ stats) {
-  __shared__ double s_a[TT_SUM_BLOCK];
-  const int t = threadIdx.x, shell = blockIdx.x;
-  const double* p = partials + (long long)shell * nr_waves;
-  const int cw = (nr_waves + TT_SUM_BLOCK - 1) / TT_SUM_BLOCK;
-  const long long begin = (long long)t * cw, end = begin + cw < nr_waves ? begin + cw : nr_waves;
-  double s = 0.0;
-  for (long long w = begin; w < end; ++w) s += p[w];
-  s_a[t] = s;
-  __syncthreads();
-  if (t != 0) return;
-  double total = 0.0;
-  for (int l = 0; l < TT_SUM_BLOCK; ++l) total += s_a[l];
+// One block per shell: the shell's per-wave sums of d2 added in ordered_sum.h's fixed order.
+__global__ __launch_bounds__(ORDERED_SUM_BLOCK) void tt_sum_kernel(const double* __restrict__ partials, int nr_waves,
+                                                                   int samples,
+                                                                   unsigned long long* __restrict__ stats) {
+  const int shell = blockIdx.x;
+  double total[1];
+  if (!ordered_sum<1, 1>(partials + (long long)shell * nr_waves, nr_waves, total)) return;
   unsigned long long* st = stats + (long long)shell * TT_WORDS;
-  st[TT_SUM2] = (unsigned long long)__double_as_longlong(total);
+  st[TT_SUM2] = (unsigned long long)__double_as_longlong(total[0]);
   st[TT_SAMPLES] = st[TT_OWNED] * (unsigned long long)(samples * samples);
 }
 
@@ -361,7 +317,7 @@ TtLayout tt_layout(int nr_shells, int R) {
 
 int tt_check_dst(const float* dst_uvs, const float* dst_recs, const long long* face_base, int nr_shells, int dst_res,
                  const void* workspace, long long workspace_bytes) {
-  if (nr_shells < 1 || nr_shells > VSA_MAX_SHELLS || dst_res < 1 || dst_res > 16384) return VSA_ERR_ARG;
+  if (nr_shells < 1 || nr_shells > VSA_MAX_SHELLS || dst_res < 1 || dst_res > NT_MAX_TEX_RES) return VSA_ERR_ARG;
   if (!dst_uvs || !dst_recs || !face_base || !workspace) return VSA_ERR_ARG;
   if (((uintptr_t)workspace & 15) || ((uintptr_t)dst_recs & 15)) return VSA_ERR_ARG;
   if (face_base[0] != 0) return VSA_ERR_ARG;
@@ -378,20 +334,10 @@ TtShells tt_shells(const long long* face_base, int nr_shells) {
   return sh;
 }
 
-// First byte of image (shell 0, degree, 0) and bytes per shell of planes with these per-degree resolutions.
-void tt_plane_offsets(const int32_t* res, int degrees, int degree, long long* stride, long long* before) {
-  *stride = *before = 0;
-  for (int d = 0; d < degrees; ++d) {
-    const long long b = (long long)(2 * d + 1) * res[d] * res[d] * 4;
-    if (d < degree) *before += b;
-    *stride += b;
-  }
-}
-
 }  // namespace
 
 extern "C" long long vsa_textransfer_workspace_bytes(int nr_shells, int dst_res) {
-  if (nr_shells < 1 || nr_shells > VSA_MAX_SHELLS || dst_res < 1 || dst_res > 16384) return VSA_ERR_ARG;
+  if (nr_shells < 1 || nr_shells > VSA_MAX_SHELLS || dst_res < 1 || dst_res > NT_MAX_TEX_RES) return VSA_ERR_ARG;
   return (long long)tt_layout(nr_shells, dst_res).total;
 }
 
@@ -413,7 +359,7 @@ extern "C" int vsa_textransfer_owners(const float* dst_uvs, const float* dst_rec
 extern "C" int vsa_textransfer_owner_fields(const void* workspace, long long workspace_bytes, const float* dst_uvs,
                                             const long long* face_base, int nr_shells, int shell, int dst_res,
                                             int32_t* face, float* bary, float* d2, void* stream) {
-  if (nr_shells < 1 || nr_shells > VSA_MAX_SHELLS || dst_res < 1 || dst_res > 16384) return VSA_ERR_ARG;
+  if (nr_shells < 1 || nr_shells > VSA_MAX_SHELLS || dst_res < 1 || dst_res > NT_MAX_TEX_RES) return VSA_ERR_ARG;
   if (!workspace || !dst_uvs || !face_base || !face || !bary || !d2 || shell < 0 || shell >= nr_shells)
     return VSA_ERR_ARG;
   if ((uintptr_t)workspace & 15) return VSA_ERR_ARG;
@@ -434,24 +380,25 @@ extern "C" int vsa_textransfer_planes(const vsa_nt_plan* src_plan, int degree, c
                                       float max_distance, void* workspace, long long workspace_bytes,
                                       uint8_t* dst_planes, long long dst_planes_bytes, unsigned long long* stats,
                                       void* stream) {
-  if (!src_plan || !dst_tex_res) return VSA_ERR_ARG;
+  // (nt_common.h's checks in this entry's order: an unsupported plan is reported before a bad resolution)
+  if (!dst_tex_res) return VSA_ERR_ARG;
+  if (const int rc = nt_baked_plan_counts(src_plan)) return rc;
+  if (const int rc = nt_baked_plan_supported(src_plan)) return rc;
   const vsa_nt_plan& p = *src_plan;
-  if (p.nr_shells < 1 || p.nr_shells > VSA_MAX_SHELLS || p.rgb_degrees < 1 || p.rgb_degrees > VSA_NT_MAX_DEG)
-    return VSA_ERR_ARG;
-  if (p.alpha_degrees != p.rgb_degrees || p.row_format != 0) return VSA_ERR_UNSUPPORTED;
   if (degree < 0 || degree >= p.rgb_degrees || samples < 1 || samples > 4 || nr_meshes != p.nr_shells)
     return VSA_ERR_ARG;
   if (max_distance != max_distance) return VSA_ERR_ARG;
+  if (const int rc = nt_baked_plan_resolutions(src_plan)) return rc;
   for (int d = 0; d < p.rgb_degrees; ++d)
-    if (p.tex_res[d] < 1 || p.tex_res[d] > 16384 || dst_tex_res[d] < 1 || dst_tex_res[d] > 16384) return VSA_ERR_ARG;
+    if (dst_tex_res[d] < 1 || dst_tex_res[d] > NT_MAX_TEX_RES) return VSA_ERR_ARG;
   if (const int rc = check_qtree(qnodes, tris, mesh_roots, mesh_frames, nr_meshes, max_depth, VSA_ERR_ARG)) return rc;
   const int R2 = dst_tex_res[degree];
   if (const int rc = tt_check_dst(dst_uvs, dst_recs, face_base, nr_meshes, R2, workspace, workspace_bytes)) return rc;
   if (!src_planes || !src_face_uvs || !dst_planes || !stats) return VSA_ERR_ARG;
   if (((uintptr_t)src_planes & 15) || ((uintptr_t)dst_planes & 15) || ((uintptr_t)stats & 7)) return VSA_ERR_ARG;
   TtArgs a;
-  tt_plane_offsets(p.tex_res, p.rgb_degrees, degree, &a.src_shell_stride, &a.src_deg_off);
-  tt_plane_offsets(dst_tex_res, p.rgb_degrees, degree, &a.dst_shell_stride, &a.dst_deg_off);
+  nt_plane_layout(p.tex_res, p.rgb_degrees, degree, &a.src_shell_stride, &a.src_deg_off);
+  nt_plane_layout(dst_tex_res, p.rgb_degrees, degree, &a.dst_shell_stride, &a.dst_deg_off);
   if (src_planes_bytes != a.src_shell_stride * p.nr_shells || dst_planes_bytes != a.dst_shell_stride * p.nr_shells)
     return VSA_ERR_ARG;
   const QTree t = make_qtree(qnodes, tris, mesh_roots, mesh_frames, nr_meshes);
@@ -484,7 +431,7 @@ extern "C" int vsa_textransfer_planes(const vsa_nt_plan* src_plan, int degree, c
     });
   });
   VSA_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(tt_sum_kernel, dim3((unsigned)nr_meshes), dim3(TT_SUM_BLOCK), 0, st, a.partials, tiles, samples,
+  hipLaunchKernelGGL(tt_sum_kernel, dim3((unsigned)nr_meshes), dim3(ORDERED_SUM_BLOCK), 0, st, a.partials, tiles, samples,
                      stats);
   VSA_RETURN_LAUNCH_STATUS();
 }

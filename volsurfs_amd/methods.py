@@ -141,11 +141,7 @@ class VolSurfs(torch.nn.Module):
         self.nr_meshes = len(tensor_meshes)
         dev = tensor_meshes[0].vertices.device
         self.raytracer = RayTracer(tensor_meshes, builder=bvh_builder)  # volsurfs.py:128
-        fu = []
-        for m, off, n in zip(tensor_meshes, self.raytracer.mesh_tri_offset, self.raytracer.mesh_nr_tris):
-            ids = self.raytracer.slot_face_id[off:off + n].long()
-            fu.append(m.get_faces_uvs().reshape(-1, 6)[ids])
-        self.face_uvs = torch.cat(fu, 0).contiguous()
+        self.face_uvs = self.raytracer.slot_face_uvs(tensor_meshes)
         self.bank, self.models = None, torch.nn.ModuleDict()
         if using_neural_textures:
             self.bank = NeuralTextureBank(self.nr_meshes, max_rays, sh_degree=sh_degree,

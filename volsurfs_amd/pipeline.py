@@ -104,12 +104,7 @@ class KShellPipeline:
         self.bg = torch.tensor([bg_color], device=dev, dtype=torch.float32)
         self.timer = StageTimer()
         N, K = self.nr_rays, self.K
-        # per-corner uvs in the tracer's leaf (slot) order
-        fu = []
-        for m, off, n in zip(meshes, self.tracer.mesh_tri_offset, self.tracer.mesh_nr_tris):
-            ids = self.tracer.slot_face_id[off:off + n].long()
-            fu.append(m.faces_uvs.reshape(-1, 6)[ids])
-        self.face_uvs = torch.cat(fu, 0).contiguous()
+        self.face_uvs = self.tracer.slot_face_uvs(meshes)
         self.bank = NeuralTextureBank(K, N, device=dev, seed=seed)
         if init == "spread":
             # larger parameters: textures with visible structure (parity tests)

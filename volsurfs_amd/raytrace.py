@@ -217,6 +217,14 @@ class RayTracer:
         # original face id of every leaf-ordered triangle slot (for uv tables etc.)
         self.slot_face_id = self.tris[:, 3].contiguous().view(torch.int32)
 
+    def slot_face_uvs(self, meshes):
+        """[slots, 6]: the per-corner UVs of `meshes` (this tracer's shells, in its order) gathered into the tracer's
+        leaf (slot) order, the table `tex_uv_only` and the texture stages index by hit slot."""
+        fu = []
+        for m, off, n in zip(meshes, self.mesh_tri_offset, self.mesh_nr_tris):
+            fu.append(m.get_faces_uvs().reshape(-1, 6)[self.slot_face_id[off:off + n].long()])
+        return torch.cat(fu, 0).contiguous()
+
     def _record_shells(self, sizes):
         """The shells' (nr_nodes, nr_tris, depth), in mesh order, into the layout of the concatenated arrays: `_layout`
         ((node_base, nr_nodes, tri_base, nr_tris) per shell), `mesh_tri_offset`, `mesh_nr_tris`, `max_depth` and the

@@ -34,15 +34,21 @@ def texture_name(mesh_idx, degree, feature):
     return f"mesh_{mesh_idx}_texture_{degree}_feature_{feature}.png"
 
 
-def _plane_layout(plan, K, D):
-    """[(shell, degree, byte offset, coefficients, R)] in the planes' order (include/volsurfs_hip.h)."""
+def plane_layout(resolutions, K, D):
+    """([(shell, degree, byte offset, coefficients, R)], total bytes) of the planes of K shells and D degrees with these
+    per-degree resolutions, in the planes' order (include/volsurfs_hip.h; csrc/nt_common.h nt_plane_layout)."""
     out, off = [], 0
     for s in range(K):
         for d in range(D):
-            R, n = int(plan.tex_res[d]), 2 * d + 1
+            R, n = int(resolutions[d]), 2 * d + 1
             out.append((s, d, off, n, R))
             off += n * R * R * 4
     return out, off
+
+
+def plane_views(flat, layout):
+    """{(shell, degree): [2d+1, R, R, 4] view} of a flat buffer (torch or numpy) with `plane_layout`'s layout."""
+    return {(s, d): flat[off:off + n * R * R * 4].reshape(n, R, R, 4) for s, d, off, n, R in layout}
 
 
 def _planes_bytes(bank):
@@ -61,6 +67,15 @@ def _check_exportable(bank):
             "with zip(rgb, alpha) and would drop the rgb degrees above the alpha ones")
 
 
+def baked_bank_of(scene, what):
+    """The baked, exportable bank of `scene` (a BakedScene, or a VolSurfs after bake()); `what` names the caller."""
+    bank = getattr(scene, "baked", None)
+    if bank is None or not getattr(bank, "baked", False):
+        raise _lib.VolsurfsHipError(f"{what} needs a baked scene: a BakedScene, or a VolSurfs after bake()")
+    _check_exportable(bank)
+    return bank
+
+
 def _export_flat(bank):
     """(uint8 device buffer of every image, layout) from one vsa_nt_export_planes launch."""
     if not getattr(bank, "baked", False):
@@ -70,7 +85,7 @@ def _export_flat(bank):
     planes = torch.empty(total, dtype=torch.uint8, device=bank.texels.device)
     _lib.call("vsa_nt_export_planes", ctypes.byref(bank.plan), bank.slot_of, bank.seg_start, bank.texels, planes,
               total, _lib.stream_ptr())
-    return planes, _plane_layout(bank.plan, bank.K, bank.D)[0]
+    return planes, plane_layout(bank.tex_res, bank.K, bank.D)[0]
 
 
 @torch.no_grad()
@@ -79,7 +94,7 @@ def export_planes(bank):
     RGBA image of `textures/mesh_{shell}_texture_{degree}_feature_{i}.png` (pixel (r, c) = texel (c, R-1-r) of
     `bank.baked_textures()`; A = 255 on a shell without an alpha model).  `bank` must be baked."""
     planes, layout = _export_flat(bank)
-    return {(s, d): planes[off:off + n * R * R * 4].view(n, R, R, 4) for s, d, off, n, R in layout}
+    return plane_views(planes, layout)
 
 
 def opengl_camera(camera, near=NEAR, far=FAR):
@@ -185,57 +200,59 @@ def extract_textures(method, out_dir, cameras=None, resolution=None, bg_color=No
     timings: a dict that receives {bake_ms, export_ms, d2h_ms, png_s, meshes_s} (wall clock).
     Raises VolsurfsHipError for the legacy appearance branch, a bank that is not 8-bit and transp_view_dep=0 with
     sh_degree > 0."""
-    from .mesh import save_obj
     if not getattr(method, "using_neural_textures", False) or method.bank is None:
         raise _lib.VolsurfsHipError("legacy texture extraction method deprecated: texture export needs "
                                     "using_neural_textures=1 (the reference exits here, baker.py:896-900)")
     _check_exportable(method.bank)
     t = {} if timings is None else timings
-
-    def now():
-        torch.cuda.synchronize()
-        return time.perf_counter()
-
-    t0 = now()
+    t0 = _now()
     if method.baked is None:
         method.bake()
-    t1 = now()
-    bank = method.baked
+    t["bake_ms"] = (_now() - t0) * 1e3
+    return _write_baked(method, method.baked, out_dir, cameras or {}, resolution,
+                        method.bg_color if bg_color is None else bg_color, compress_level, write_meshes, t)
+
+
+def _now():
+    torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+def _write_baked(scene, bank, out_dir, cams, resolution, bg_color, compress_level, write_meshes, t):
+    """The writer of `extract_textures` and `write_scene`: the PNGs of `bank`, the OBJs of `scene.tensor_meshes` and
+    scene.json; returns the scene dict.  resolution None: the first camera's, else (800, 800).  t: a dict that
+    receives {export_ms, d2h_ms, png_s, meshes_s} (wall clock)."""
+    from .mesh import save_obj
+    t1 = _now()
     planes, layout = _export_flat(bank)
-    t2 = now()
+    t2 = _now()
     flat = planes.cpu().numpy()
-    t3 = now()
+    t3 = _now()
     tex_dir = os.path.join(out_dir, "textures")
     os.makedirs(tex_dir, exist_ok=True)
     jobs = []
-    for s, d, off, n, R in layout:
-        img = flat[off:off + n * R * R * 4].reshape(n, R, R, 4)
-        for i in range(n):
-            jobs.append((os.path.join(tex_dir, texture_name(s, d, i)), img[i]))
+    for (s, d), img in plane_views(flat, layout).items():
+        jobs.extend((os.path.join(tex_dir, texture_name(s, d, i)), img[i]) for i in range(len(img)))
     with ThreadPoolExecutor(max_workers=min(_PNG_THREADS, len(jobs))) as ex:
         list(ex.map(lambda j: _save_png(j[0], j[1], compress_level), jobs))
     t4 = time.perf_counter()
     if write_meshes:
         os.makedirs(os.path.join(out_dir, "meshes"), exist_ok=True)
-        for m, mesh in enumerate(method.tensor_meshes):
+        for m, mesh in enumerate(scene.tensor_meshes):
             save_obj(os.path.join(out_dir, "meshes", f"{m}.obj"), mesh)
     t5 = time.perf_counter()
     ignore = [bank.tex_channels(bank.tex_index(s, 1, 0)) == 0 for s in range(bank.K)]   # no alpha model
     sh_range = [-float(bank.plan.sh_lo[d]) for d in range(MAX_DEG)]
     info = meshes_info_of(bank.K, bank.tex_res, sh_range, bank.D, ignore)
-    cams = cameras or {}
     if resolution is None:
         first = next((c for split in ("train", "test") for c in cams.get(split, [])), None)
         resolution = (first.width, first.height) if first is not None else (800, 800)
-    if bg_color is None:
-        bg_color = method.bg_color
-    scene = scene_info(info, resolution, bg_color, cams, lerp=not bank.anchor,
-                       with_alpha_decay=bool(bank.plan.with_alpha_decay))
+    out = scene_info(info, resolution, bg_color, cams, lerp=not bank.anchor,
+                     with_alpha_decay=bool(bank.plan.with_alpha_decay))
     with open(os.path.join(out_dir, "scene.json"), "w") as f:
-        json.dump(scene, f, indent=2)
-    t.update({"bake_ms": (t1 - t0) * 1e3, "export_ms": (t2 - t1) * 1e3, "d2h_ms": (t3 - t2) * 1e3,
-              "png_s": t4 - t3, "meshes_s": t5 - t4})
-    return scene
+        json.dump(out, f, indent=2)
+    t.update({"export_ms": (t2 - t1) * 1e3, "d2h_ms": (t3 - t2) * 1e3, "png_s": t4 - t3, "meshes_s": t5 - t4})
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -329,11 +346,7 @@ class BakedScene:
         from .raytrace import RayTracer
         self.tensor_meshes, self.nr_meshes = meshes, len(meshes)
         self.raytracer = RayTracer(meshes, builder=bvh_builder)
-        fu = []
-        for m, off, n in zip(meshes, self.raytracer.mesh_tri_offset, self.raytracer.mesh_nr_tris):
-            ids = self.raytracer.slot_face_id[off:off + n].long()
-            fu.append(m.get_faces_uvs().reshape(-1, 6)[ids])
-        self.face_uvs = torch.cat(fu, 0).contiguous()
+        self.face_uvs = self.raytracer.slot_face_uvs(meshes)
         self.baked = bank
         self.bg_color = torch.tensor([bg_color], dtype=torch.float32, device=bank.texels.device)
         self.cameras = cameras
@@ -381,38 +394,11 @@ def write_scene(scene, out_dir, cameras=None, resolution=None, compress_level=6,
     """Write a `BakedScene` (or a baked VolSurfs) the way `extract_textures` writes a method: the same
     textures/mesh_{m}_texture_{d}_feature_{i}.png, meshes/{m}.obj and scene.json, so that `load_scene` and
     `VolsurfsRenderer.from_scene` read it.  cameras / resolution default to the scene's own; returns the scene dict."""
-    from .mesh import save_obj
-    bank = getattr(scene, "baked", None)
-    if bank is None:
-        raise _lib.VolsurfsHipError("write_scene needs a baked scene: a BakedScene, or a VolSurfs after bake()")
-    planes, layout = _export_flat(bank)
-    flat = planes.cpu().numpy()
-    tex_dir = os.path.join(out_dir, "textures")
-    os.makedirs(tex_dir, exist_ok=True)
-    jobs = []
-    for s, d, off, n, R in layout:
-        img = flat[off:off + n * R * R * 4].reshape(n, R, R, 4)
-        jobs.extend((os.path.join(tex_dir, texture_name(s, d, i)), img[i]) for i in range(n))
-    with ThreadPoolExecutor(max_workers=min(_PNG_THREADS, len(jobs))) as ex:
-        list(ex.map(lambda j: _save_png(j[0], j[1], compress_level), jobs))
-    if write_meshes:
-        os.makedirs(os.path.join(out_dir, "meshes"), exist_ok=True)
-        for m, mesh in enumerate(scene.tensor_meshes):
-            save_obj(os.path.join(out_dir, "meshes", f"{m}.obj"), mesh)
-    ignore = [bank.tex_channels(bank.tex_index(s, 1, 0)) == 0 for s in range(bank.K)]
-    sh_range = [-float(bank.plan.sh_lo[d]) for d in range(MAX_DEG)]
-    info = meshes_info_of(bank.K, bank.tex_res, sh_range, bank.D, ignore)
+    bank = baked_bank_of(scene, "write_scene")
     cams = cameras if cameras is not None else (getattr(scene, "cameras", None) or {})
     if resolution is None:
         resolution = getattr(scene, "resolution", None)
-    if resolution is None:
-        first = next((c for split in ("train", "test") for c in cams.get(split, [])), None)
-        resolution = (first.width, first.height) if first is not None else (800, 800)
-    out = scene_info(info, resolution, scene.bg_color, cams, lerp=not bank.anchor,
-                     with_alpha_decay=bool(bank.plan.with_alpha_decay))
-    with open(os.path.join(out_dir, "scene.json"), "w") as f:
-        json.dump(out, f, indent=2)
-    return out
+    return _write_baked(scene, bank, out_dir, cams, resolution, scene.bg_color, compress_level, write_meshes, {})
 
 
 @torch.no_grad()
@@ -437,7 +423,7 @@ def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None):
     t1 = time.perf_counter()
     K = len(meshes)
     bank = _empty_baked_bank(K, D, res, rng, inner_solid, shared_alpha, decay, lerp, device)
-    layout, total = _plane_layout(bank.plan, K, D)
+    layout, total = plane_layout(res, K, D)
     host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
     flat = host.numpy()
     jobs = []

@@ -34,38 +34,20 @@ clamped: sums of the steps' counters; nonfinite: gradient elements that were not
 healthy fit)."""
 
 
-def _baked_bank(scene, what):
-    from .texture_export import _check_exportable
-    bank = getattr(scene, "baked", None)
-    if bank is None or not getattr(bank, "baked", False):
-        raise _lib.VolsurfsHipError(f"{what} needs a baked scene: a BakedScene, or a VolSurfs after bake()")
-    _check_exportable(bank)
-    return bank
-
-
-def _copy_scene(scene, builder):
-    """A new BakedScene with the bytes of `scene`: export_planes -> scene_from_planes (the apron clamped)."""
-    from .texture_export import export_planes
-    from .texture_transfer import scene_from_planes
-    bank, bg = scene.baked, scene.bg_color
-    return scene_from_planes(
-        scene.tensor_meshes, export_planes(bank), [-float(bank.plan.sh_lo[d]) for d in range(bank.D)],
-        bool(bank.plan.inner_solid), bool(bank.shared_alpha), not bank.anchor, bool(bank.plan.with_alpha_decay),
-        (1.0, 1.0, 1.0) if bg is None else bg.flatten().tolist(), getattr(scene, "cameras", None),
-        getattr(scene, "resolution", None) or (800, 800), builder)
-
-
 class TextureFit:
     """Adam on the texel rows of a copy of `scene` (a `BakedScene`, or a `VolSurfs` after `bake()`; never mutated).
     `.scene` is the scene being fitted: it renders at any time through `render_baked*`.  `.loss`: the mean L1 of the
     last `accumulate`, a device scalar.  lr / betas / eps: Adam's, on parameters in units of q / 255."""
 
     def __init__(self, scene, lr=DEFAULT_LR, betas=(0.9, 0.99), eps=1e-15, builder="device"):
-        _baked_bank(scene, "TextureFit")
+        from .texture_export import baked_bank_of, export_planes
+        from .texture_transfer import scene_like
+        src_bank = baked_bank_of(scene, "TextureFit")
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         if not (self.lr >= 0.0 and self.eps >= 0.0 and all(0.0 <= b < 1.0 for b in self.betas)):
             raise _lib.VolsurfsHipError(f"TextureFit: lr {lr}, betas {betas}, eps {eps} out of range")
-        self.scene = _copy_scene(scene, builder)
+        # a new BakedScene with the bytes of `scene` (the apron clamped)
+        self.scene = scene_like(scene, scene.tensor_meshes, export_planes(src_bank), builder)
         bank = self.scene.baked
         n = _lib.workspace_bytes("vsa_texel_fit_state_bytes", ctypes.byref(bank.plan)) // 4
         dev = bank.texels.device

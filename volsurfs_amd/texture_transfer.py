@@ -106,22 +106,14 @@ def texel_owners(mesh, resolution, reach=1.5):
 
 
 def _source(src, builder):
-    """(baked bank, tracer with q16 nodes, per-slot uv table, the source object) of anything that renders baked."""
+    """(tracer with q16 nodes, per-slot uv table) of anything that renders baked."""
     from .raytrace import RayTracer
-    from .texture_export import _check_exportable
-    bank = getattr(src, "baked", None)
-    if bank is None or not getattr(bank, "baked", False):
-        raise _lib.VolsurfsHipError("texture transfer needs a baked source: a BakedScene, or a VolSurfs after bake()")
-    _check_exportable(bank)
     tracer, face_uvs = src.raytracer, src.face_uvs
     if tracer.node_format != "q16":
         tracer = RayTracer(src.tensor_meshes, builder=builder)
-        fu = []
-        for m, off, n in zip(src.tensor_meshes, tracer.mesh_tri_offset, tracer.mesh_nr_tris):
-            fu.append(m.get_faces_uvs().reshape(-1, 6)[tracer.slot_face_id[off:off + n].long()])
-        face_uvs = torch.cat(fu, 0).contiguous()
+        face_uvs = tracer.slot_face_uvs(src.tensor_meshes)
     tracer.require_q16("texture transfer")
-    return bank, tracer, face_uvs
+    return tracer, face_uvs
 
 
 def _report(words, samples, texels):
@@ -146,11 +138,9 @@ def transfer_planes(src, dst_meshes, textures_res=None, samples=1, reach=1.5, ma
     The same inputs give the same bytes.  Raises VolsurfsHipError for a shell-count mismatch, meshes without UVs,
     resolutions out of range and a source that is not exportable, before any launch."""
     from .neural_textures import MAX_DEG
-    from .texture_export import _export_flat
+    from .texture_export import _export_flat, baked_bank_of, plane_layout, plane_views
     samples, reach, max_distance = _check_options(samples, reach, max_distance)
-    bank = getattr(src, "baked", None)
-    if bank is None or not getattr(bank, "baked", False):
-        raise _lib.VolsurfsHipError("texture transfer needs a baked source: a BakedScene, or a VolSurfs after bake()")
+    bank = baked_bank_of(src, "texture transfer")
     dst_meshes = list(dst_meshes)
     K, D = bank.K, bank.D
     if len(dst_meshes) != K:
@@ -162,17 +152,12 @@ def transfer_planes(src, dst_meshes, textures_res=None, samples=1, reach=1.5, ma
     for k, m in enumerate(dst_meshes):
         if not isinstance(m, TensorMesh) or m.get_faces_uvs() is None:
             raise _lib.VolsurfsHipError(f"texture transfer: destination shell {k} has no per-corner UVs")
-    bank, tracer, face_uvs = _source(src, builder)
+    tracer, face_uvs = _source(src, builder)
     uvs, recs, base = _dst_tables(dst_meshes, "texture transfer")
     dev = uvs.device
     src_planes, _ = _export_flat(bank)
     dst_res = (ctypes.c_int32 * MAX_DEG)(*(res + [res[-1]] * (MAX_DEG - D)))
-
-    layout, total = [], 0                           # (texture_export._plane_layout with the destination's resolutions)
-    for s in range(K):
-        for d in range(D):
-            layout.append((s, d, total, 2 * d + 1, res[d]))
-            total += (2 * d + 1) * res[d] * res[d] * 4
+    layout, total = plane_layout(res, K, D)
     dst_planes = torch.empty(total, dtype=torch.uint8, device=dev)
     stats = torch.empty(D, K, STAT_WORDS, dtype=torch.int64, device=dev)
     for d in range(D):
@@ -182,9 +167,8 @@ def transfer_planes(src, dst_meshes, textures_res=None, samples=1, reach=1.5, ma
                   *tracer.q16_tree_args(), face_uvs, uvs, recs, base, dst_res, samples, max_distance, ws, n,
                   dst_planes, total, stats[d], _lib.stream_ptr())
     words = stats.cpu().numpy()                     # the one blocking read
-    planes = {(s, d): dst_planes[off:off + n * R * R * 4].view(n, R, R, 4) for s, d, off, n, R in layout}
     reports = {(s, d): _report(words[d, s], samples, res[d] * res[d]) for s in range(K) for d in range(D)}
-    return planes, reports
+    return plane_views(dst_planes, layout), reports
 
 
 @torch.no_grad()
@@ -214,19 +198,25 @@ def scene_from_planes(meshes, planes, sh_range, inner_solid=False, shared_alpha=
 
 
 @torch.no_grad()
+def scene_like(src, meshes, planes, builder="device"):
+    """`scene_from_planes(meshes, planes)` with everything else taken from the baked scene `src`: sh ranges,
+    inner_solid, shared_alpha, lerp, alpha decay, background colour (white when it has none), cameras and resolution."""
+    bank, bg = src.baked, src.bg_color
+    return scene_from_planes(
+        meshes, planes, [-float(bank.plan.sh_lo[d]) for d in range(bank.D)], bool(bank.plan.inner_solid),
+        bool(bank.shared_alpha), not bank.anchor, bool(bank.plan.with_alpha_decay),
+        (1.0, 1.0, 1.0) if bg is None else bg.flatten().tolist(), getattr(src, "cameras", None),
+        getattr(src, "resolution", None) or (800, 800), builder)
+
+
+@torch.no_grad()
 def transfer_scene(src, dst_meshes, textures_res=None, samples=1, reach=1.5, max_distance=math.inf,
                    builder="device", return_reports=False):
     """`transfer_planes` as a `BakedScene` of `dst_meshes` (its tracer built with `builder`): renders through
     `render_baked*` like a loaded scene.  Background colour, cameras, resolution, lerp and with_alpha_decay are the
     source's.  With `return_reports` also the reports."""
     planes, reports = transfer_planes(src, dst_meshes, textures_res, samples, reach, max_distance, builder)
-    bank = src.baked
-    bg = src.bg_color
-    scene = scene_from_planes(
-        dst_meshes, planes, [-float(bank.plan.sh_lo[d]) for d in range(bank.D)], bool(bank.plan.inner_solid),
-        bool(bank.shared_alpha), not bank.anchor, bool(bank.plan.with_alpha_decay),
-        (1.0, 1.0, 1.0) if bg is None else bg.flatten().tolist(), getattr(src, "cameras", None),
-        getattr(src, "resolution", None) or (800, 800), builder)
+    scene = scene_like(src, dst_meshes, planes, builder)
     return (scene, reports) if return_reports else scene
 
 
@@ -242,9 +232,8 @@ def make_lod(src, ratio, textures_res=None, padding=4, samples=1, anchor_shell=N
     of the source (the returned scene is the fitted one) and the report gains "refit", the `FitReport`."""
     from .atlas import compute_atlas
     from .simplify import simplify_mesh, simplify_shells
-    bank = getattr(src, "baked", None)
-    if bank is None:
-        raise _lib.VolsurfsHipError("make_lod needs a baked source: a BakedScene, or a VolSurfs after bake()")
+    from .texture_export import baked_bank_of
+    bank = baked_bank_of(src, "make_lod")
     _check_options(samples, reach, max_distance)
     res = list(bank.tex_res if textures_res is None else textures_res)[:bank.D]
     bare = [TensorMesh(m.vertices, m.faces, None, device=m.vertices.device) for m in src.tensor_meshes]
@@ -283,4 +272,5 @@ def lod_chain(src, ratios, out_dir, textures_res=None, padding=4, samples=1, anc
     return reports
 
 
-__all__ = ["texel_owners", "transfer_planes", "transfer_scene", "scene_from_planes", "make_lod", "lod_chain"]
+__all__ = ["texel_owners", "transfer_planes", "transfer_scene", "scene_from_planes", "scene_like", "make_lod",
+           "lod_chain"]
