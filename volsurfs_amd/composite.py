@@ -152,15 +152,13 @@ def reduce_scratch(device):
     last-ticket protocol that is only valid for calls SERIALISED on one stream — so there is one per (device, stream):
     two reductions on different streams (look-ahead traversal, the alpha chain, the optimiser's side stream) never
     share a ticket."""
-    import ctypes
     dev = torch.device(device)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     sc = _reduce_scratch.get(key)
     if sc is None:
-        fn = _lib.lib().vsa_reduce_scratch_bytes
-        fn.restype = ctypes.c_longlong
-        sc = _reduce_scratch[key] = torch.zeros(int(fn()), dtype=torch.uint8, device=dev)
+        sc = _reduce_scratch[key] = torch.zeros(_lib.workspace_bytes("vsa_reduce_scratch_bytes"), dtype=torch.uint8,
+                                                device=dev)
     return sc
 
 

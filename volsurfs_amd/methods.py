@@ -10,7 +10,8 @@ import torch
 
 from . import _lib
 from .composite import composite_dense
-from .neural_textures import NeuralTextureBank
+from .neural_textures import NeuralTextureBank, chain_scale
+from .optim import take_clean_grads
 from .raytrace import RayTracer
 
 
@@ -20,40 +21,23 @@ class _ShadeStage(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tables, weights, method, hit_slot, hit_uv, rays_d):
-        bank = method.bank
-        tex_uv = bank.mark_and_compact(hit_slot, hit_uv, method.face_uvs)
+        frame = method.bank.frame(hit_slot, hit_uv, method.face_uvs)
         # (torch.is_grad_enabled() is always False inside Function.forward and parameters keep
         # requires_grad under no_grad: render_rays records whether the call is differentiated)
         need = getattr(method, "_grad_on", True) and (tables.requires_grad or weights.requires_grad)
-        bank.evaluate(need_features=need)
-        act = torch.empty(hit_slot.shape[0], hit_slot.shape[1], 4, device=hit_slot.device) if need else None
-        rgb, alpha, normals, _ = bank.shade(hit_slot, tex_uv, rays_d, method.raytracer.tris,
-                                            want_normals=True, act_out=act)
-        # backward reads the bank's per-frame state (slot_of, seg_start, texels, features): stamp it
-        bank.frame_generation = getattr(bank, "frame_generation", 0) + 1
-        ctx.generation = bank.frame_generation
-        ctx.method, ctx.saved = method, (hit_slot, tex_uv, rays_d, act)
-        ctx.mark_non_differentiable(normals, tex_uv)
-        return rgb, alpha, normals, tex_uv
+        rgb, alpha, normals = frame.forward(rays_d, method.raytracer.tris, differentiable=need, want_normals=True)
+        ctx.method, ctx.frame = method, frame
+        ctx.mark_non_differentiable(normals, frame.tex_uv)
+        return rgb, alpha, normals, frame.tex_uv
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, *unused):
         method = ctx.method
-        bank = method.bank
-        hit_slot, tex_uv, rays_d, act = ctx.saved
-        if bank.frame_generation != ctx.generation:
-            raise _lib.VolsurfsHipError(
-                "backward of a render_rays call whose per-frame texel state was overwritten by a "
-                "later render_rays: call backward before rendering again")
         # The kernels ACCUMULATE into bank.tables.grad / bank.weights.grad (autograd semantics), so
         # the gradients are written straight into the persistent .grad buffers and None is returned
         # for the two parameters: no 113 MB temporary, no second pass adding it to .grad.
-        bank._ensure_grads()
-        opt = getattr(method, "optimizer", None)
-        # the fused Adam step (or zero_grad) has just cleared them — and nothing has touched the buffers since
-        zeroed = bool(opt.grads_are_clean()) if hasattr(opt, "grads_are_clean") else bool(getattr(opt, "_grads_clean", False))
-        if hasattr(opt, "mark_grads_dirty"):
-            opt.mark_grads_dirty()
+        method.bank._ensure_grads()
+        zeroed = take_clean_grads(method.optimizer)
         # scale of the fp16 gradient chain (tcnn's loss scale).  By default a power of two that
         # brings the largest incoming per-ray gradient to 4: whatever the loss (mean- or
         # sum-reduced, any batch size) the chain neither underflows nor overflows in f16.  One
@@ -63,8 +47,7 @@ class _ShadeStage(torch.autograd.Function):
         if scale is None:
             gmax = max(g_rgb.abs().max().item(), g_alpha.abs().max().item())
             scale = 2.0 ** min(max(math.floor(math.log2(4.0 / gmax)), -24), 40) if gmax > 0 else 1.0
-        bank.backward(hit_slot, tex_uv, rays_d, method.raytracer.tris, g_rgb.contiguous(),
-                      g_alpha.contiguous(), scale, act, grads_zeroed=zeroed)
+        ctx.frame.backward(g_rgb.contiguous(), g_alpha.contiguous(), scale, grads_zeroed=zeroed)
         return None, None, None, None, None, None
 
 
@@ -668,9 +651,8 @@ class VolSurfs(torch.nn.Module):
 
     def _shade_baked(self, hit_slot, hit_uv, rays_d):
         """What follows the hits in a baked render: per-hit uv -> shade -> composite."""
-        tex_uv = self.baked.tex_uv_only(hit_slot, hit_uv, self.face_uvs)
-        rgb_k, alpha_k, normals, _ = self.baked.shade(hit_slot, tex_uv, rays_d, self.raytracer.tris,
-                                                      want_normals=True)
+        frame = self.baked.frame(hit_slot, hit_uv, self.face_uvs)
+        rgb_k, alpha_k, normals = frame.forward(rays_d, self.raytracer.tris, differentiable=False, want_normals=True)
         bg = self.bg_color if self.bg_color is not None else torch.ones(1, 3, device=rays_d.device)
         out = composite_dense(rgb_k, alpha_k, bg)
         out["surfs_normals"] = normals
@@ -712,10 +694,9 @@ class VolSurfs(torch.nn.Module):
         return fit_textures(self, cameras, **kw)
 
     # -- fused training path: the same forward + mean-L1 + backward as `forward(...)` followed by
-    # `loss.backward()`, as ONE sequence of C-ABI launches on the current stream (no autograd
-    # graph, no temporaries for the gradients, no host synchronisation): trace -> mark/compact ->
-    # encode -> MLP -> shade -> composite+L1+its backward (one launch) -> shade_bwd -> MLP bwd ->
-    # encode bwd, accumulating into the persistent bank.tables.grad / bank.weights.grad.
+    # `loss.backward()`, as ONE sequence of C-ABI launches on the current stream (no autograd graph, no temporaries for
+    # the gradients, no host synchronisation): trace -> a ShadedFrame's forward -> composite+L1+its backward (one launch)
+    # -> the frame's backward, accumulating into the persistent bank.tables.grad / bank.weights.grad.
     def supports_fused_step(self, gt_mask=None, is_training_masked=False):
         return (self.bank is not None and self.bg_color is not None and self.baked is None
                 and not (is_training_masked and gt_mask is not None))
@@ -739,28 +720,17 @@ class VolSurfs(torch.nn.Module):
         N = rays_o.shape[0]
         if N > self.max_rays:
             raise _lib.VolsurfsHipError(f"{N} rays > max_rays={self.max_rays}")
-        bank = self.bank
-        bank._ensure_grads()
-        opt = getattr(self, "optimizer", None)
-        # the fused Adam step (or zero_grad) has just cleared them — and nothing has touched the buffers since
-        zeroed = bool(opt.grads_are_clean()) if hasattr(opt, "grads_are_clean") else bool(getattr(opt, "_grads_clean", False))
-        if hasattr(opt, "mark_grads_dirty"):
-            opt.mark_grads_dirty()
-        bank.frame_generation = getattr(bank, "frame_generation", 0) + 1
+        self.bank._ensure_grads()
+        zeroed = take_clean_grads(self.optimizer)
         rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
         hit_t, hit_slot, hit_uv = self._trace_now(rays_o, rays_d)
         nr_hits = count_hits(hit_slot)               # one launch (the torch expression: compare, cast, fill, reduce)
-        tex_uv = bank.mark_and_compact(hit_slot, hit_uv, self.face_uvs)
-        bank.evaluate()
-        act = torch.empty(self.nr_meshes, N, 4, device=rays_o.device)
-        tris = self.raytracer.tris
-        rgb_k, alpha_k, _, _ = bank.shade(hit_slot, tex_uv, rays_d, tris, act_out=act)
+        frame = self.bank.frame(hit_slot, hit_uv, self.face_uvs)
+        rgb_k, alpha_k, _ = frame.forward(rays_d, self.raytracer.tris, differentiable=True)
         loss_scale = float(loss_weight) / (3.0 * N)
-        rgb, g_c, g_a = composite_fwd_bwd_l1_raw(rgb_k, alpha_k, self.bg_color, gt_rgb.contiguous(),
-                                                 loss_scale)
-        from .pipeline import GRAD_CHAIN_GAIN
-        scale = self.grad_scale if self.grad_scale is not None else GRAD_CHAIN_GAIN / (3.0 * loss_scale)
-        bank.backward(hit_slot, tex_uv, rays_d, tris, g_c, g_a, scale, act, grads_zeroed=zeroed)
+        rgb, g_c, g_a = composite_fwd_bwd_l1_raw(rgb_k, alpha_k, self.bg_color, gt_rgb.contiguous(), loss_scale)
+        scale = self.grad_scale if self.grad_scale is not None else chain_scale(loss_scale=loss_scale)
+        frame.backward(g_c, g_a, scale, grads_zeroed=zeroed)
         loss = l1_mean(rgb, gt_rgb)                  # the logged value, one launch
         return loss, nr_hits, rgb
 

@@ -34,6 +34,26 @@ WEIGHTS_PER_TEX = 8192
 REBALANCE = os.environ.get("VSA_NT_REBALANCE", "1") != "0"
 FUSED_FORWARD = {"0": False, "1": True}.get(os.environ.get("VSA_NT_FUSED", "auto"), "auto")
 
+# Scale of the f16 gradient chain relative to the ray count of a mean-L1 loss (the analogue of tiny-cuda-nn's
+# loss scale; divided out before anything is accumulated in fp32).  With 1 x N the chain carried 1/3 per
+# ray and channel: fine up to K = 7, but at K = 9 the shells behind eight others underflowed f16 — every
+# MLP-weight gradient within 3.6e-3 of its tensor's largest entry instead of 3.1e-4 at 16 x N, table entries over
+# 1e-3: 2.7e-5 -> 1.3e-6 of them (profiles/r05/parity_report.json; 16 and 256 measure the same, so 16 it is:
+# the headroom to f16's 65 504 stays > 10x even with hundreds of hits on one texel).  A power of two: exact.
+GRAD_CHAIN_GAIN = 16.0
+
+
+def chain_scale(nr_rays=None, loss_scale=None):
+    """The default scale of the f16 gradient chain of a mean-L1 step, from whichever the caller has: the number of rays
+    the mean runs over (GAIN x nr_rays), or the factor its composite + L1 launch applies per ray and channel
+    (GAIN / (3 x loss_scale)).  The same number when loss_scale = 1 / (3 nr_rays); a loss weight in it is divided out."""
+    return GRAD_CHAIN_GAIN * float(nr_rays) if loss_scale is None else GRAD_CHAIN_GAIN / (3.0 * loss_scale)
+
+
+def _stage(run, name, fn, *args, **kw):
+    """fn(*args, **kw), through the stage hook `run(stage_name, thunk)` when the caller has one; no closure otherwise."""
+    return fn(*args, **kw) if run is None else run(name, lambda: fn(*args, **kw))
+
 class Plan(ctypes.Structure):
     """Mirror of `vsa_nt_plan` (include/volsurfs_hip.h)."""
     _fields_ = [
@@ -196,10 +216,13 @@ class NeuralTextureBank(torch.nn.Module):
     def _alloc(self, dev, training):
         i32, u8 = torch.int32, torch.uint8
         cap, K = self.slot_capacity, self.K
+        self.frame_generation = 0        # (all per-frame and gradient state is declared here) bumped by frame()
+        self.baked, self._marks_dirty = False, False     # the rows hold EVERY texel (bake_all); a mark not yet compacted
+        self._grad_flat = None           # zero_grads(): tables.grad | weights.grad | _dfsum as one allocation, built lazily
+        self._dfsum, self._dfsum_clean = None, False     # per-texture sum |dF| of the MLP backward; "is all zero"
+        self._tables_grad_sig = None     # zero_grads() -> _take_grads_zeroed(): (id, version) of the all-zero tables.grad
         if REBALANCE:
-            fn = _lib.lib().vsa_nt_balance_bytes
-            fn.restype = ctypes.c_longlong
-            self.balance = torch.zeros(int(fn()), dtype=u8, device=dev)
+            self.balance = torch.zeros(_lib.workspace_bytes("vsa_nt_balance_bytes"), dtype=u8, device=dev)
             self.plan.balance = self.balance.data_ptr()
         self.marks = torch.zeros(self.dom_total, dtype=u8, device=dev)
         self.slot_of = torch.full((self.dom_total,), -1, dtype=i32, device=dev)
@@ -220,6 +243,7 @@ class NeuralTextureBank(torch.nn.Module):
         # texel rows: 4 elements per quad — bytes (8-bit quantised) or halves (row_format 1)
         self.texels = torch.zeros(self.row_quads_total * 4, dtype=texel_dtype, device=dev)
         self.grad_rows = torch.zeros(self.row_quads_total * 4, dtype=torch.float16, device=dev) if training else None
+        self._dfsum, self._dfsum_clean = torch.zeros(self.n_tex, 32, device=dev), True
         self.refresh_half_params()
 
     @torch.no_grad()
@@ -230,28 +254,32 @@ class NeuralTextureBank(torch.nn.Module):
         self.weights_h.copy_(self.weights)
 
     # -- stages --------------------------------------------------------------
+    def frame(self, hit_slot, hit_uv, face_uvs):
+        """The step for these hits as a ShadedFrame: the texels they touch get their slots (a baked bank has them and
+        only resolves the hits' uv).  An earlier frame's per-frame state is gone from here on: its backward refuses."""
+        tex_uv = (self.tex_uv_only if self.baked else self.mark_and_compact)(hit_slot, hit_uv, face_uvs)
+        self.frame_generation += 1
+        return ShadedFrame(self, hit_slot, tex_uv)
+
     def mark_and_compact(self, hit_slot, hit_uv, face_uvs, want_texel_of_slot=False):
         """hit_slot [K,N] i32, hit_uv [K,N,2], face_uvs [nr_tris,6] (leaf order).
         Returns tex_uv [K,N,2].  slot_of is valid for the touched texels only (vsa_nt_compact_frame);
         texel_of_slot (the inverse map: nothing on the path reads it) is written on request."""
         K, N = hit_slot.shape
         assert K == self.K and N <= self.max_rays
-        if getattr(self, "baked", False):
+        if self.baked:
             raise _lib.VolsurfsHipError("this bank holds baked textures: use tex_uv_only + shade")
-        st = _lib.stream_ptr()
-        tex_uv = torch.empty(K, N, 2, device=hit_slot.device)
         # Invariant: the marks are zero between frames — allocated so, and vsa_nt_compact_frame clears
         # what it reads.  `_marks_dirty` is set while a mark has not been followed by a compaction that
         # returned OK (an exception between the two, a failed launch): stale marks would silently
         # inflate every later frame's slot counts.
-        if getattr(self, "_marks_dirty", False):
+        if self._marks_dirty:
             self.marks.zero_()
         self._marks_dirty = True
-        _lib.call("vsa_nt_mark", ctypes.byref(self.plan), hit_slot, hit_uv, face_uvs, N, tex_uv,
-                  self.marks, st)
+        tex_uv = self.tex_uv_only(hit_slot, hit_uv, face_uvs, self.marks)
         _lib.call("vsa_nt_compact_frame", ctypes.byref(self.plan), self.marks, self.slot_of,
                   self.texel_of_slot if want_texel_of_slot else None, self.slot_xy, self.seg_start,
-                  self.block_scratch, st)
+                  self.block_scratch, _lib.stream_ptr())
         self._marks_dirty = False
         return tex_uv
 
@@ -312,12 +340,11 @@ class NeuralTextureBank(torch.nn.Module):
                     out[(s, 1, d)] = rows[..., 24:24 + n].contiguous()
         return out
 
-    def tex_uv_only(self, hit_slot, hit_uv, face_uvs):
-        """Per-hit texture uv without touching the compaction (inference from a baked bank)."""
+    def tex_uv_only(self, hit_slot, hit_uv, face_uvs, marks=None):
+        """Per-hit texture uv without touching the compaction (inference from a baked bank); marks: mark_and_compact's."""
         K, N = hit_slot.shape
         tex_uv = torch.empty(K, N, 2, device=hit_slot.device)
-        _lib.call("vsa_nt_mark", ctypes.byref(self.plan), hit_slot, hit_uv, face_uvs, N, tex_uv,
-                  None, _lib.stream_ptr())
+        _lib.call("vsa_nt_mark", ctypes.byref(self.plan), hit_slot, hit_uv, face_uvs, N, tex_uv, marks, _lib.stream_ptr())
         return tex_uv
 
     def wait_params(self):
@@ -348,9 +375,7 @@ class NeuralTextureBank(torch.nn.Module):
 
     def mlp(self, want_pre=False):
         self.wait_params()
-        pre = None
-        if want_pre:
-            pre = torch.zeros(self.slot_capacity, 32, dtype=torch.float16, device=self.texels.device)
+        pre = torch.zeros(self.slot_capacity, 32, dtype=torch.float16, device=self.texels.device) if want_pre else None
         _lib.call("vsa_nt_mlp_fwd", ctypes.byref(self.plan), self.weights_h, self.features,
                   self.seg_start, self.texels, pre, _lib.stream_ptr())
         return (self.rows_dense(self.texels), pre) if want_pre else self.texels
@@ -359,21 +384,20 @@ class NeuralTextureBank(torch.nn.Module):
         """encode() + mlp() as ONE launch (csrc/nt_fused.hip; bit-identical results).
         write_features=False: inference — the feature planes are neither written nor read."""
         self.wait_params()
-        pre = None
-        if want_pre:
-            pre = torch.zeros(self.slot_capacity, 32, dtype=torch.float16, device=self.texels.device)
+        pre = torch.zeros(self.slot_capacity, 32, dtype=torch.float16, device=self.texels.device) if want_pre else None
         _lib.call("vsa_nt_encode_mlp_fwd", ctypes.byref(self.plan), self.tables_h, self.weights_h,
                   self.slot_xy, self.seg_start, self.features if write_features else None,
                   self.texels, pre, _lib.stream_ptr())
         return (self.rows_dense(self.texels), pre) if want_pre else self.texels
 
-    def evaluate(self, need_features=True):
+    def evaluate(self, need_features=True, run=None):
         """Texel rows of the compacted slots.  need_features=False (inference, baking): the fused
-        launch; True (a backward pass follows): the level-major encode kernel, then the MLP kernel."""
+        launch; True (a backward pass follows): the level-major encode kernel, then the MLP kernel.
+        run: the stage hook of ShadedFrame."""
         if self.row_format == 0 and (FUSED_FORWARD is True or (FUSED_FORWARD == "auto" and not need_features)):
-            return self.encode_mlp(write_features=need_features)
-        self.encode()
-        return self.mlp()
+            return _stage(run, "nt_encode_mlp_fwd", self.encode_mlp, write_features=need_features)
+        _stage(run, "nt_encode_fwd", self.encode)
+        return _stage(run, "nt_mlp_fwd", self.mlp)
 
     def rows_dense(self, buf):
         """Tests / export: the per-degree rows of `texels` or `grad_rows` re-laid as
@@ -412,8 +436,7 @@ class NeuralTextureBank(torch.nn.Module):
         grad_scale keeps the fp16 intermediate gradients in range (the analogue of
         tiny-cuda-nn's loss scale); it is divided out before accumulation.
         grads_zeroed: see backward_encode."""
-        self.backward_shade(hit_slot, tex_uv, rays_d, tris, g_surfs_rgb, g_surfs_alpha, grad_scale,
-                            act)
+        self.backward_shade(hit_slot, tex_uv, rays_d, tris, g_surfs_rgb, g_surfs_alpha, grad_scale, act)
         self.backward_mlp(grad_scale)
         self.backward_encode(grad_scale, grads_zeroed=grads_zeroed)
 
@@ -428,7 +451,7 @@ class NeuralTextureBank(torch.nn.Module):
         allocation so that a training step clears them with one fill (three small launches
         otherwise).  Returns False if the gradient tensors are not (any more) those views —
         e.g. an optimiser's zero_grad(set_to_none=True) dropped them — and clears what exists."""
-        flat = getattr(self, "_grad_flat", None)
+        flat = self._grad_flat
         nt, nw = self.tables.numel(), self.weights.numel()
         if flat is None:
             flat = torch.zeros(nt + nw + self.n_tex * 32, device=self.tables.device)
@@ -437,44 +460,42 @@ class NeuralTextureBank(torch.nn.Module):
             self._dfsum = flat[nt + nw:].view(self.n_tex, 32)
         if self.tables.grad is None and self.weights.grad is None:
             self.tables.grad, self.weights.grad = self._flat_t, self._flat_w
-        self._tables_grad_zero = True        # (backward_encode: a sole writer's table plane is stored, not added)
-        if self.tables.grad is self._flat_t and self.weights.grad is self._flat_w:
+        whole = self.tables.grad is self._flat_t and self.weights.grad is self._flat_w
+        if whole:
             flat.zero_()
             self._dfsum_clean = True
-            self._tables_grad_sig = (id(self.tables.grad), self.tables.grad._version)
-            return True
-        self.tables.grad.zero_()
-        self.weights.grad.zero_()
+        else:
+            self.tables.grad.zero_()
+            self.weights.grad.zero_()
+        # (backward_encode: a sole writer's table plane is stored, not added, while tables.grad is this all-zero buffer)
         self._tables_grad_sig = (id(self.tables.grad), self.tables.grad._version)
-        return False
+        return whole
 
     def _take_grads_zeroed(self, grads_zeroed):
         """plan.grads_zeroed of the next hash-grid backward launch: the caller's word (it knows its optimiser
         has just cleared the gradients), else what zero_grads() left; either way the buffer holds something
         after the launch."""
-        z = bool(getattr(self, "_tables_grad_zero", False) if grads_zeroed is None else grads_zeroed)
-        if grads_zeroed is None and z:       # zero_grads() said so: still the same buffer, untouched by torch since? (ADVICE r5)
+        if grads_zeroed is None:       # zero_grads() said so: still the same buffer, untouched by torch since? (ADVICE r5)
             g = self.tables.grad
-            z = g is not None and getattr(self, "_tables_grad_sig", None) == (id(g), g._version)
+            grads_zeroed = g is not None and self._tables_grad_sig == (id(g), g._version)
         # (shared models: the kernel itself keeps a shared plane's flushes atomic — K shells write it)
-        self._tables_grad_zero = False
-        self.plan.grads_zeroed = int(z)
+        self._tables_grad_sig = None
+        self.plan.grads_zeroed = int(bool(grads_zeroed))
 
     def backward_shade(self, hit_slot, tex_uv, rays_d, tris, g_surfs_rgb, g_surfs_alpha, grad_scale,
-                       act=None):
-        self._ensure_grads()
+                       act=None, grad_rows=None):
+        """grad_rows: the caller's f16 rows instead of the bank's own (the texel fit, on a bank without parameters)."""
+        if grad_rows is None:
+            self._ensure_grads()
+            grad_rows = self.grad_rows
         if act is not None:
             _lib.check_f32(act, hit_slot.shape[0], hit_slot.shape[1], 4)
-        _lib.call("vsa_nt_shade_bwd", ctypes.byref(self.plan), hit_slot, tex_uv, rays_d, tris,
-                  self.slot_of, self.seg_start, self.texels, hit_slot.shape[1],
-                  g_surfs_rgb.contiguous(),
-                  g_surfs_alpha.contiguous(), float(grad_scale), self.grad_rows, act,
-                  _lib.stream_ptr())
+        _lib.call("vsa_nt_shade_bwd", ctypes.byref(self.plan), hit_slot, tex_uv, rays_d, tris, self.slot_of,
+                  self.seg_start, self.texels, hit_slot.shape[1], g_surfs_rgb.contiguous(), g_surfs_alpha.contiguous(),
+                  float(grad_scale), grad_rows, act, _lib.stream_ptr())
 
     def backward_mlp(self, grad_scale):
-        if getattr(self, "_dfsum", None) is None:
-            self._dfsum = torch.zeros(self.n_tex, 32, device=self.weights.device)
-        elif not getattr(self, "_dfsum_clean", False):
+        if not self._dfsum_clean:
             self._dfsum.zero_()
         self._dfsum_clean = False            # (zero_grads() has just cleared it together with the gradients)
         _lib.call("vsa_nt_mlp_bwd", ctypes.byref(self.plan), self.weights_h, self.features,
@@ -503,6 +524,59 @@ class NeuralTextureBank(torch.nn.Module):
                   float(grad_scale), self.slot_xy, self.seg_start, self.tables.grad, signals.n,
                   signals.phase_end_c, signals._flags, signals.counters, signals.epoch, int(signals.reserve_cus),
                   _lib.stream_ptr())
+
+
+class ShadedFrame:
+    """The neural-texture step of one batch of hits, written once: `bank.frame(hits)` (mark / compact) ->
+    `forward` (encode + MLP -> shade) -> the caller's own composite and loss -> `backward` (shade backward -> MLP
+    backward -> hash-grid backward).  Plain launches on the current stream, no autograd inside.  Holds what its backward
+    reads beside the bank's per-frame buffers, and the bank's generation it was made at.
+    run: an optional stage hook, run(stage_name, thunk) -> thunk(), once per launch (KShellPipeline's stage timer)."""
+    __slots__ = ("bank", "generation", "hit_slot", "tex_uv", "rays_d", "tris", "act")
+
+    def __init__(self, bank, hit_slot, tex_uv):
+        self.bank, self.generation, self.hit_slot, self.tex_uv = bank, bank.frame_generation, hit_slot, tex_uv
+        self.rays_d = self.tris = self.act = None
+
+    def forward(self, rays_d, tris, differentiable, want_normals=False, run=None):
+        """(surfs_rgb [N,K,3], surfs_alpha [N,K], normals | None).  differentiable: the feature planes and the hits'
+        output sigmoids are kept for a backward."""
+        bank, (K, N) = self.bank, self.hit_slot.shape
+        if not bank.baked:
+            bank.evaluate(need_features=differentiable, run=run)
+        self.rays_d, self.tris = rays_d, tris
+        self.act = torch.empty(K, N, 4, device=rays_d.device) if differentiable else None
+        return _stage(run, "nt_shade_fwd", bank.shade, self.hit_slot, self.tex_uv, rays_d, tris,
+                      want_normals=want_normals, act_out=self.act)[:3]
+
+    def _check(self):
+        if self.bank.frame_generation != self.generation:
+            raise _lib.VolsurfsHipError("backward of a frame whose per-frame texel state was overwritten by a later frame "
+                                        "(a render, a training step): call backward before rendering again")
+
+    def backward_rows(self, g_rgb, g_alpha, scale, grad_rows=None, run=None):
+        """Shade backward into the gradient rows, MLP backward into weights.grad and the feature gradients.
+        grad_rows: the caller's rows instead, and the shade backward alone (the texel fit, on a baked bank)."""
+        self._check()
+        bank = self.bank
+        _stage(run, "nt_shade_bwd", bank.backward_shade, self.hit_slot, self.tex_uv, self.rays_d, self.tris, g_rgb,
+               g_alpha, scale, self.act, grad_rows=grad_rows)
+        if grad_rows is None:
+            _stage(run, "nt_mlp_bwd", bank.backward_mlp, scale)
+
+    def backward_tables(self, scale, shells=None, signals=None, grads_zeroed=None, run=None):
+        """The hash-grid backward: whole, for shells=(begin, end), or phased with signals (parallel.StepSignals)."""
+        self._check()
+        if signals is not None:
+            _stage(run, "nt_encode_bwd", self.bank.backward_encode_phased, scale, signals, grads_zeroed=grads_zeroed)
+        else:
+            _stage(run, "nt_encode_bwd", self.bank.backward_encode, scale, shells=shells, grads_zeroed=grads_zeroed)
+
+    def backward(self, g_rgb, g_alpha, scale, grads_zeroed=None, grad_rows=None, run=None):
+        """backward_rows, then (unless grad_rows takes the gradient) backward_tables.  scale: chain_scale's."""
+        self.backward_rows(g_rgb, g_alpha, scale, grad_rows=grad_rows, run=run)
+        if grad_rows is None:
+            self.backward_tables(scale, grads_zeroed=grads_zeroed, run=run)
 
 
 def stage_accounting(bank, nr_rays, nr_hits, tracer_bytes=0):

@@ -403,6 +403,17 @@ class ShardedFusedAdam(FusedAdam):
                 self._all_gather(p.detach().view(-1), p_slice.clone())
 
 
+def take_clean_grads(opt):
+    """The handshake of a kernel about to write into the .grad buffers `opt` steps: True iff they are still the all-zero
+    buffers its last step() / zero_grad() left (`grads_are_clean`: the kernel may STORE, vsa_nt_plan.grads_zeroed); from
+    this call on they count as written.  None or another optimiser: False — accumulating is always right."""
+    if not isinstance(opt, FusedAdam):
+        return False
+    clean = opt.grads_are_clean()
+    opt.mark_grads_dirty()
+    return clean
+
+
 def accumulate_into_grad(param):
     """For autograd Functions whose backward kernel ACCUMULATES (+=) into a table-sized gradient:
     if `param` already owns a contiguous fp32 `.grad` (the persistent buffers FusedAdam keeps),

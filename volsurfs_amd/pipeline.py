@@ -10,16 +10,8 @@ import torch
 from . import _lib
 from .camera import pinhole_rays
 from .mesh import nested_shells, stress_shells
+from .neural_textures import GRAD_CHAIN_GAIN, chain_scale      # noqa: F401 (GRAD_CHAIN_GAIN: the benchmarks import it from here)
 from .raytrace import RayTracer
-
-
-# Scale of the f16 gradient chain relative to the ray count of a mean-L1 loss (the analogue of tiny-cuda-nn's
-# loss scale; divided out before anything is accumulated in fp32).  With 1 x N the chain carried 1/3 per
-# ray and channel: fine up to K = 7, but at K = 9 the shells behind eight others underflowed f16 — every
-# MLP-weight gradient within 3.6e-3 of its tensor's largest entry instead of 3.1e-4 at 16 x N, table entries over
-# 1e-3: 2.7e-5 -> 1.3e-6 of them (profiles/r05/parity_report.json; 16 and 256 measure the same, so 16 it is:
-# the headroom to f16's 65 504 stays > 10x even with hundreds of hits on one texel).  A power of two: exact.
-GRAD_CHAIN_GAIN = 16.0
 
 # Graph capture in "thread_local" error mode: under the default ("global") ANY thread's HIP call that is illegal during
 # a capture fails — and torch.distributed's ProcessGroupNCCL watchdog thread polls its Work events with hipEventQuery
@@ -113,13 +105,12 @@ class KShellPipeline:
                 self.bank.tables.copy_((torch.rand(self.bank.tables.shape, generator=g) * 2 - 1).to(dev))
             self.bank.refresh_half_params()
         self.shading = "neural_textures"
-        self.grad_scale = GRAD_CHAIN_GAIN * float(N)
+        self.grad_scale = chain_scale(nr_rays=N)
         # rays the mean of the L1 loss runs over: this pipeline's own, or — when it renders one
         # rank's share of a frame (bench.py --scaling strong) — the whole frame's
         self.loss_rays = N
         self.surfs_rgb = self.surfs_alpha = None
-        # per-hit output sigmoids kept from shade_fwd for shade_bwd of the same frame
-        self._act = torch.empty(K, N, 4, device=dev)
+        self.acct, self.mlp_flops_fwd, self.last_hits, self.last_slots = {}, 0, None, None     # the stage timer's: stats()
 
     def to_ray_order(self, x, dim=0):
         """Tests / inspection: a per-ray internal buffer (surfs_rgb, surfs_alpha, _hit_slot: in
@@ -152,7 +143,7 @@ class KShellPipeline:
             h_local = int(rows.numel())
         p = cls(meshes, o, d, gt, seed=seed, image_hw=(h_local, W), **kw)
         p.loss_rays = n_frame
-        p.grad_scale = GRAD_CHAIN_GAIN * float(n_frame)      # the f16 gradient chain sees 16 / 3 per ray and channel
+        p.grad_scale = chain_scale(nr_rays=n_frame)      # the f16 gradient chain sees 16 / 3 per ray and channel
         p.res = res
         p.subdiv = subdiv
         p.scene_desc = ("stress shells: 4 lobes of depth 0.3 r across the view axis (non-convex, up to 6 crossings per "
@@ -192,8 +183,8 @@ class KShellPipeline:
             "rays_per_gpu": self.nr_rays,
             "global_rays": self.loss_rays if self.loss_rays != self.nr_rays else self.nr_rays * world,
             "parallelism": f"tile-parallel x{world}",
-            "hits_per_frame": getattr(self, "last_hits", None),
-            "unique_texels_per_frame": getattr(self, "last_slots", None),
+            "hits_per_frame": self.last_hits,
+            "unique_texels_per_frame": self.last_slots,
             # the traversal's launch order comes from the previous frame's measured wave cost (same hits;
             # VSA_TRACE_FEEDBACK=0 = the stateless launch: profiles/NOTEBOOK.md A9.4)
             "trace_launch_order": "cost feedback from the previous frame (static camera: the previous frame has "
@@ -213,6 +204,20 @@ class KShellPipeline:
         self.acct, self.mlp_flops_fwd, self.last_slots = stage_accounting(bank, N, M, nodes_b)
         return self.last_hits, self.last_slots
 
+    def _warm_up(self, step_kw):
+        """Before a capture: two eager steps on a side stream (they advance dp's epoch and leave no event behind)."""
+        self._static_rgb = None
+        self._graph_dp = dp = step_kw.get("dp")
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        hook, _ = (dp.on_weights_final, setattr(dp, "on_weights_final", None)) if dp is not None else (None, None)
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self.step(**step_kw)
+        if dp is not None:
+            dp.on_weights_final = hook
+        torch.cuda.current_stream().wait_stream(s)
+
     def capture_graph_split(self, **step_kw):
         """The step as THREE graphs: `replay_prefix()` = what does not read a parameter or touch a
         gradient (ray tile order, traversal, mark / compact); `replay_mid()` = zero_grad .. MLP backward;
@@ -221,17 +226,7 @@ class KShellPipeline:
         waits, launches mid, records "weights.grad final", launches tail and queues its flag waits behind
         that record — so that they are pending beside ONE kernel, not beside twenty
         (parallel.OverlappedStep.run_split)."""
-        self._static_rgb = None
-        self._graph_dp = dp = step_kw.get("dp")
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        hook, _ = (dp.on_weights_final, setattr(dp, "on_weights_final", None)) if dp is not None else (None, None)
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self.step(**step_kw)      # (eager warm-ups: see capture_graph)
-        if dp is not None:
-            dp.on_weights_final = hook
-        torch.cuda.current_stream().wait_stream(s)
+        self._warm_up(step_kw)
         self._graph_prefix, self._graph_mid, self._graph_tail = (torch.cuda.CUDAGraph() for _ in range(3))
         with _no_gc():
             with torch.cuda.graph(self._graph_prefix, capture_error_mode=_CAPTURE_MODE):
@@ -258,26 +253,14 @@ class KShellPipeline:
         return self._static_rgb
 
     def replay_rest(self):
-        self._graph_mid.replay()
-        self._count_replay()
-        self._graph_tail.replay()
-        return self._static_rgb
+        self.replay_mid()
+        return self.replay_tail()
 
     def capture_graph(self, **step_kw):
         """Capture one whole step (zero_grad .. backward: ~25 launches on one stream, no
         host sync) into a HIP graph; `replay()` then costs one graph launch instead of
         the per-kernel host overhead of the eager path."""
-        self._static_rgb = None
-        self._graph_dp = dp = step_kw.get("dp")
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        hook, _ = (dp.on_weights_final, setattr(dp, "on_weights_final", None)) if dp is not None else (None, None)
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self.step(**step_kw)      # (eager warm-ups: they advance dp's epoch like any eager step, and leave no event behind)
-        if dp is not None:
-            dp.on_weights_final = hook
-        torch.cuda.current_stream().wait_stream(s)
+        self._warm_up(step_kw)
         self._graph = torch.cuda.CUDAGraph()
         with _no_gc(), torch.cuda.graph(self._graph, capture_error_mode=_CAPTURE_MODE):
             self._static_rgb = self.step(**step_kw)
@@ -304,65 +287,51 @@ class KShellPipeline:
         part: None = the whole step; "prefix" = only its parameter- and gradient-free head (ray tile
         order, traversal, mark / compact); "mid" = zero_grad .. MLP backward of a step whose prefix has run;
         "tail" = the hash-grid backward of a step whose mid has run; "rest" = mid + tail."""
-        from .composite import composite_fwd_raw, composite_bwd_raw
-        N, K = self.nr_rays, self.K
         T, bank = self.timer, self.bank
-        acct = getattr(self, "acct", None) or {}     # algorithmic bytes per stage (stats())
-
+        run = self._stage_hook() if record else None
         if part == "tail":
-            return self._step_tail(record, acct, grad_ready, dp, self._mid_out)
-        if part in ("rest", "mid"):
-            rays_d, gt, hit_slot, tex_uv = self._prefix_out
-        else:
-            rays_d, gt, hit_slot, tex_uv = self._step_prefix(record, acct)
+            return self._step_tail(record, run, grad_ready, dp, *self._mid_out)
+        if part not in ("rest", "mid"):
+            self._prefix_out = self._step_prefix(record)
             if part == "prefix":
-                self._prefix_out = (rays_d, gt, hit_slot, tex_uv)
                 return None
+        rays_d, gt, frame = self._prefix_out
         T.run("zero_grad", bank.zero_grads, record, bytes=(bank.tables.numel() + bank.weights.numel()) * 4)
-        rgb = self._step_rest(record, acct, dp, rays_d, gt, hit_slot, tex_uv)
+        rgb = self._step_rest(record, run, dp, rays_d, gt, frame)
         if part == "mid":
-            self._mid_out = rgb
+            self._mid_out = (frame, rgb)
             return None
         if dp is not None and dp.on_weights_final is not None and not torch.cuda.is_current_stream_capturing():
             dp.on_weights_final()          # (eager step: weights.grad is final on the current stream here)
-        return self._step_tail(record, acct, grad_ready, dp, rgb)
+        return self._step_tail(record, run, grad_ready, dp, frame, rgb)
 
-    def _step_prefix(self, record, acct):
-        N, T, bank = self.nr_rays, self.timer, self.bank
+    def _stage_hook(self):
+        """The frame's stages under the stage timer, each with its algorithmic bytes / FLOPs (stats())."""
+        T, acct, fl = self.timer, self.acct, self.mlp_flops_fwd
+        mfma = dict(flops=fl, bound="mfma")
+        meta = {"nt_encode_mlp_fwd": mfma, "nt_mlp_fwd": mfma, "nt_shade_bwd": dict(bound="atomic"),
+                "nt_mlp_bwd": dict(flops=2 * fl, bound="mfma")}
+        return lambda name, fn: T.run(name, fn, True, bytes=acct.get(name, 0), **meta.get(name, {}))
+
+    def _step_prefix(self, record):
+        N, T, acct = self.nr_rays, self.timer, self.acct
         rays_o, rays_d, gt = self.rays_o, self.rays_d, self.gt
         if self.image_hw is not None:
             H, W = self.image_hw
-
-            T.run("ray_tile_order",
-                  lambda: _lib.call("vsa_tile_order_rays", self.rays_o, self.rays_d, self.gt, self._o_t,
-                                    self._d_t, self._gt_t, H, W, _lib.stream_ptr()),
+            T.run("ray_tile_order", lambda: _lib.call("vsa_tile_order_rays", self.rays_o, self.rays_d, self.gt, self._o_t,
+                                                      self._d_t, self._gt_t, H, W, _lib.stream_ptr()),
                   record, bytes=N * 72)
             rays_o, rays_d, gt = self._o_t, self._d_t, self._gt_t
-        hit_t, hit_slot, hit_uv = T.run(
-            "trace", lambda: self.tracer.trace_all(rays_o, rays_d), record,
-            bytes=acct.get("trace", 0))
+        hit_t, hit_slot, hit_uv = T.run("trace", lambda: self.tracer.trace_all(rays_o, rays_d), record,
+                                        bytes=acct.get("trace", 0))
         self._hit_slot = hit_slot
-        tex_uv = T.run("nt_mark_compact",
-                       lambda: bank.mark_and_compact(hit_slot, hit_uv, self.face_uvs), record,
-                       bytes=acct.get("nt_mark_compact", 0))
-        return rays_d, gt, hit_slot, tex_uv
+        frame = T.run("nt_mark_compact", lambda: self.bank.frame(hit_slot, hit_uv, self.face_uvs), record,
+                      bytes=acct.get("nt_mark_compact", 0))
+        return rays_d, gt, frame
 
-    def _step_rest(self, record, acct, dp, rays_d, gt, hit_slot, tex_uv):
-        N, K = self.nr_rays, self.K
-        T, bank = self.timer, self.bank
-        mlp_flops = getattr(self, "mlp_flops_fwd", 0)
-        from . import neural_textures as _nt
-        if _nt.FUSED_FORWARD is True:      # encode + MLP as one launch (csrc/nt_fused.hip): VSA_NT_FUSED=1
-            T.run("nt_encode_mlp_fwd", bank.encode_mlp, record, bytes=acct.get("nt_encode_mlp_fwd", 0),
-                  flops=mlp_flops, bound="mfma")
-        else:
-            T.run("nt_encode_fwd", bank.encode, record, bytes=acct.get("nt_encode_fwd", 0))
-            T.run("nt_mlp_fwd", bank.mlp, record, bytes=acct.get("nt_mlp_fwd", 0), flops=mlp_flops,
-                  bound="mfma")
-        rgb_k, alpha_k, _, _ = T.run(
-            "nt_shade_fwd", lambda: bank.shade(hit_slot, tex_uv, rays_d, self.tracer.tris,
-                                               act_out=self._act),
-            record, bytes=acct.get("nt_shade_fwd", 0))
+    def _step_rest(self, record, run, dp, rays_d, gt, frame):
+        N, K, T = self.nr_rays, self.K, self.timer
+        rgb_k, alpha_k, _ = frame.forward(rays_d, self.tracer.tris, differentiable=True, run=run)
         self.surfs_rgb, self.surfs_alpha = rgb_k, alpha_k
         # forward composite, d mean|gt - pred| / d pred (utils/losses.py:14-19) and the composite
         # backward in one pass over the shells' colours (vsa_composite_dense_fwd_bwd_l1)
@@ -376,32 +345,22 @@ class KShellPipeline:
                                                      self.image_hw[1], 3, 1, _lib.stream_ptr()),
                   record, bytes=N * 24)
             rgb = self._rgb_out
-        tris = self.tracer.tris
-        T.run("nt_shade_bwd", lambda: bank.backward_shade(hit_slot, tex_uv, rays_d, tris, g_c, g_a,
-                                                           self.grad_scale, self._act), record,
-              bytes=acct.get("nt_shade_bwd", 0), bound="atomic")
-        T.run("nt_mlp_bwd", lambda: bank.backward_mlp(self.grad_scale), record,
-              bytes=acct.get("nt_mlp_bwd", 0), flops=2 * mlp_flops, bound="mfma")
+        frame.backward_rows(g_c, g_a, self.grad_scale, run=run)
         if dp is not None:
             dp.signal_weights()            # epoch += 1 (the hash-grid backward publishes it), weights word = epoch
         return rgb
 
-    def _step_tail(self, record, acct, grad_ready, dp, rgb):
+    def _step_tail(self, record, run, grad_ready, dp, frame, rgb):
         """The hash-grid backward: the last launch of the step."""
-        K, T, bank = self.K, self.timer, self.bank
-        enc_bytes = acct.get("nt_encode_bwd", 0)
-        if dp is not None:
-            T.run("nt_encode_bwd", lambda: bank.backward_encode_phased(self.grad_scale, dp), record,
-                  bytes=enc_bytes)
-        elif grad_ready is None:
-            T.run("nt_encode_bwd", lambda: bank.backward_encode(self.grad_scale), record,
-                  bytes=enc_bytes)
+        bank = self.bank
+        if grad_ready is None or dp is not None:
+            frame.backward_tables(self.grad_scale, signals=dp, run=run)
         else:
             grad_ready(bank.weights.grad)
 
             def by_shell():
-                for s in range(K):
-                    bank.backward_encode(self.grad_scale, shells=(s, s + 1))
+                for s in range(self.K):
+                    frame.backward_tables(self.grad_scale, shells=(s, s + 1))
                     grad_ready(bank.tables.grad[s * 8:(s + 1) * 8])
-            T.run("nt_encode_bwd", by_shell, record, bytes=enc_bytes)
+            self.timer.run("nt_encode_bwd", by_shell, record, bytes=self.acct.get("nt_encode_bwd", 0))
         return rgb

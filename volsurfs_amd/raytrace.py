@@ -301,11 +301,7 @@ class RayTracer:
                       hit_uv, int(rpw), _lib.stream_ptr())
         elif self.node_format == "q16" and self.cost_feedback and self.max_depth < 48:
             if self._fb is None or self._fb[1] < N or self._fb[0].device != rays_o.device:   # grows only
-                fn = _lib.lib().vsa_trace_feedback_bytes
-                fn.restype = ctypes.c_longlong
-                nbytes = int(fn(ctypes.c_int(N), ctypes.c_int(K)))
-                if nbytes < 0:
-                    raise _lib.VolsurfsHipError("vsa_trace_feedback_bytes failed")
+                nbytes = _lib.workspace_bytes("vsa_trace_feedback_bytes", N, K)
                 self._fb = [torch.zeros(nbytes, dtype=torch.uint8, device=rays_o.device), N, nbytes]
             # phase 2: the read / written halves alternate through a word in the buffer, flipped on the
             # device in front of every launch, so a captured graph alternates them on every replay too

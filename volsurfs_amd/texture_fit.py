@@ -4,8 +4,8 @@ library's own, restated in tests/texture_fit_restated.py and unpinned.
 
 `texture_transfer.make_lod` resamples appearance; it cannot make up for moved geometry, another atlas's seams or halved
 texel density.  Here the lighter scene's textures are optimised against renders of the source, through the kernels of
-the training path: trace -> `tex_uv_only` -> `shade(act_out)` -> fused composite + L1 -> `vsa_nt_shade_bwd` into
-gradient rows -> `vsa_texel_fit_step`.
+the training path: trace -> a `ShadedFrame` of the baked bank (per-hit uv, shade) -> fused composite + L1 -> the frame's
+shade backward into this fit's gradient rows -> `vsa_texel_fit_step`.
 
 * `TextureFit` — a copy of a baked scene with gradient rows and Adam state; `accumulate` views, then `step`.
 * `fit_textures` — the loop over cameras, with a report.
@@ -62,28 +62,24 @@ class TextureFit:
         """Adds the gradient of loss_weight * mean |target_rgb - rgb| over these rays to the gradient rows.  May be
         called for several views before one `step()`."""
         from .composite import composite_fwd_bwd_l1_raw, l1_mean
-        from .pipeline import GRAD_CHAIN_GAIN
+        from .neural_textures import chain_scale
         scene, bank = self.scene, self.scene.baked
         N = int(rays_o.shape[0])
         if N < 1 or tuple(target_rgb.shape) != (N, 3):
             raise _lib.VolsurfsHipError(f"accumulate: {N} rays with targets of shape {tuple(target_rgb.shape)}")
         loss_scale = float(loss_weight) / (3.0 * N)
         if self._scale is None:                  # one scale for everything that meets in the rows before a step
-            self._scale = GRAD_CHAIN_GAIN / (3.0 * loss_scale)
+            self._scale = chain_scale(loss_scale=loss_scale)
         tris, losses = scene.raytracer.tris, []
         for a in range(0, N, chunk):
             o, d = rays_o[a:a + chunk].contiguous(), rays_d[a:a + chunk].contiguous()
             gt = target_rgb[a:a + chunk].contiguous().float()
-            n = int(o.shape[0])
             _, hit_slot, hit_uv = scene._trace_now(o, d)
-            tex_uv = bank.tex_uv_only(hit_slot, hit_uv, scene.face_uvs)
-            act = torch.empty(bank.K, n, 4, device=o.device)
-            rgb_k, alpha_k, _, _ = bank.shade(hit_slot, tex_uv, d, tris, act_out=act)
+            frame = bank.frame(hit_slot, hit_uv, scene.face_uvs)
+            rgb_k, alpha_k, _ = frame.forward(d, tris, differentiable=True)
             rgb, g_c, g_a = composite_fwd_bwd_l1_raw(rgb_k, alpha_k, scene.bg_color, gt, loss_scale)
-            _lib.call("vsa_nt_shade_bwd", ctypes.byref(bank.plan), hit_slot, tex_uv, d, tris, bank.slot_of,
-                      bank.seg_start, bank.texels, n, g_c, g_a, float(self._scale), self.grad_rows, act,
-                      _lib.stream_ptr())
-            losses.append((l1_mean(rgb, gt), n))
+            frame.backward(g_c, g_a, self._scale, grad_rows=self.grad_rows)
+            losses.append((l1_mean(rgb, gt), int(o.shape[0])))
         self.loss = losses[0][0] if len(losses) == 1 else sum(l * (n / N) for l, n in losses)
         return self.loss
 

@@ -117,9 +117,8 @@ def train_step(method, rays_o, rays_d, gt_rgb, gt_mask=None, iter_nr=0, is_first
                 if nr_rays is not None and target_nr_of_training_samples and nr_samples:
                     nxt = dynamic_nr_rays(nr_rays, nr_samples, target_nr_of_training_samples)
                 prefetch(nxt)
-            opt = getattr(method, "optimizer", None)
-            if hasattr(opt, "mark_grads_dirty"):
-                opt.mark_grads_dirty()
+            from .optim import take_clean_grads
+            take_clean_grads(method.optimizer)       # (the legacy kernels always add: only "written from here on")
             method.fused_legacy_backward(state)
             l = {"loss": loss, "rgb": loss}
         else:
@@ -464,10 +463,8 @@ class GraphTrainLoop:
         self.ctl = torch.frombuffer(bytearray(bytes(c)), dtype=torch.uint8).to(dev)
         off = TrainCtl.nr_hits.offset
         self._hits_out = self.ctl[off:off + 8].view(torch.int64)
-        fn = _lib.lib().vsa_reduce_scratch_bytes
-        fn.restype = _ct.c_longlong
-        self._scr_hits = torch.zeros(int(fn()), dtype=torch.uint8, device=dev)
-        self._scr_loss = torch.zeros(int(fn()), dtype=torch.uint8, device=dev)
+        self._scr_hits, self._scr_loss = (torch.zeros(_lib.workspace_bytes("vsa_reduce_scratch_bytes"), dtype=torch.uint8,
+                                                      device=dev) for _ in range(2))
         # a ray that misses every shell: from the first camera's centre, straight away from the scene's centre
         o = reel.c2w[0, :, 3].detach().cpu().double()
         d = o / o.norm() if float(o.norm()) > 0 else torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64)
@@ -504,20 +501,18 @@ class GraphTrainLoop:
         hit_t, hit_slot, hit_uv = m._trace_now(o, d)
         _lib.call("vsa_count_hits", hit_slot, _ct.c_longlong(hit_slot.numel()), self._scr_hits, self._hits_out,
                   _lib.stream_ptr())
-        tex_uv = bank.mark_and_compact(hit_slot, hit_uv, m.face_uvs)
+        frame = bank.frame(hit_slot, hit_uv, m.face_uvs)
         main.wait_stream(self._side)            # the parameters (and their f16 copies) are final; the gradients are zero
-        bank.evaluate()
-        act = torch.empty(m.nr_meshes, cap, 4, device=dev)
-        tris = m.raytracer.tris
-        rgb_k, alpha_k, _, _ = bank.shade(hit_slot, tex_uv, d, tris, act_out=act)
+        rgb_k, alpha_k, _ = frame.forward(d, m.raytracer.tris, differentiable=True)
         rgb = torch.empty(cap, 3, device=dev)
         g_c, g_a = torch.empty_like(rgb_k), torch.empty_like(alpha_k)
         _lib.call("vsa_composite_dense_fwd_bwd_l1_ctl", rgb_k, alpha_k, m.bg_color, True, gt, ctl, rgb, g_c, g_a, cap,
                   m.nr_meshes, 0, _lib.stream_ptr())
         # (the f16 gradient chain's scale is any constant the kernels divide out again: the capacity's)
-        from .pipeline import GRAD_CHAIN_GAIN
-        scale = m.grad_scale if m.grad_scale is not None else GRAD_CHAIN_GAIN * float(cap)
-        bank.backward(hit_slot, tex_uv, d, tris, g_c, g_a, scale, act, grads_zeroed=True)
+        from .neural_textures import chain_scale
+        scale = m.grad_scale if m.grad_scale is not None else chain_scale(nr_rays=cap)
+        # grads_zeroed: this iteration's own Adam launch (above) cleared the gradient buffers on the device
+        frame.backward(g_c, g_a, scale, grads_zeroed=True)
         _lib.call("vsa_l1_mean_ctl", rgb, gt, cap, self._scr_loss, ctl, _lib.stream_ptr())
         _lib.call("vsa_train_ctl_tick", ctl, _lib.stream_ptr())
 
