@@ -2376,6 +2376,77 @@ int vsa_texel_fit_step(const vsa_nt_plan* plan, const int32_t* slot_of, const in
                        float inv_grad_scale, float* p, float* m, float* v, uint8_t* texels, float lr, float beta1,
                        float beta2, float eps, int step, unsigned long long* stats, void* stream);
 
+/* ---- Texture mips (no counterpart in the reference; csrc/texture_mip.hip) ----
+ * Minification filtering for baked scenes: a mip chain of the planes of "Texture export / import", built on the device,
+ * and a baked shade that takes each SH degree's coefficients from the level its pixel's footprint on the surface asks
+ * for.  The rule is this library's own, restated in tests/texture_mip_restated.py, which the three entry points equal
+ * BIT FOR BIT; unpinned against the reference, which has no such stage.  fp32 with one rounding per operation in the
+ * order written (the build compiles without contraction); sqrtf and / are IEEE, nothing of the log / exp / pow family
+ * is called.
+ *   chain       level 0 = the scene's planes at tex_res[d]; level l = 1..L the same layout at tex_res[d] >> l.  L is in
+ *               1..VSA_TEXMIP_MAX_LEVELS and every tex_res[d] is divisible by 2^L.  Coefficients are filtered as BYTES,
+ *               before the SH sum and the sigmoid ("Texture transfer" accepts the same): lut[q] is affine in q up to
+ *               its fp16 roundings, so a mean of bytes is a mean of coefficients.
+ *   reduce      pixel (r, c) of a level-l image has the four children (2r + a, 2c + b), a, b in 0..1, of the level
+ *               below.  Per channel byte: q = (2 sum + n) / (2 n), an integer division (the mean, halves rounded up),
+ *               over the n COVERED children; where no child is covered, over all four (n = 4).  Integers only: the
+ *               same bytes on every call.  An alpha of 255 on every child (a shell without an alpha model) stays 255.
+ *   coverage    an optional u8 mask per (shell, degree) at level 0, [R_d, R_d] in the planes' pixel orientation, ordered
+ *               (shell, degree): mask (s, d) starts at byte s * C + sum_{d' < d} R_d'^2, C = sum_d R_d^2; nonzero =
+ *               covered.  A level's mask is the OR of its children (stored as 0 / 1), with the same layout at that
+ *               level's resolutions.  NULL = every texel covered.  Without it the zero bytes outside the charts (sh_lo,
+ *               the most negative coefficient) bleed into the charts' edges at every level.
+ *   density     per face slot of the tracer's triangle array: du1 = u1 - u0, dv1 = v1 - v0, du2 = u2 - u0, dv2 = v2 - v0
+ *               of the slot's per-corner uvs; a2 = |du1 * dv2 - dv1 * du2|; c = e1 x e2 as vsa_nt_shade_fwd forms it
+ *               (cx = e1.y e2.z - e1.z e2.y, ...); a3 = sqrtf((cx cx + cy cy) + cz cz); density = a2 / a3, and 0 where
+ *               a3 is not > 0 or the quotient is not finite: uv area per world area.
+ *   footprint   of a hit at distance t along its ray (hit_t; the rays of vsa_camera_rays and of the rasterizer are UNIT
+ *               vectors, d / |d| in fp32, so t is a distance; the cosine below does not assume it):
+ *               nn = (cx cx + cy cy) + cz cz, dd = (dx dx + dy dy) + dz dz, nd = |(cx dx + cy dy) + cz dz| with c the
+ *               face's e1 x e2 and d the ray direction; cos = fmaxf(nd / sqrtf(nn * dd), 1/8) (a NaN quotient takes
+ *               1/8); A_uv = (((t * t) * spread2) * density[slot]) / cos.  spread2 is the host's: the solid angle of a
+ *               sample, 1 / (fx fy s^2) for a pinhole camera at supersample s, times 4^lod_bias.
+ *   level       per degree d: A = A_uv * ((float)R_d * (float)R_d), the footprint in texels of level 0.  !(A >= 1)
+ *               (magnification, NaN): l = 0, f = 0.  Else l0 = ((A's exponent field) - 127) >> 1 = floor(log4 A); where
+ *               l0 >= L: l = L, f = 0 (the top level alone; +inf too); else l = l0 and f = (A * 4^-l0 - 1) * 0.333333343f
+ *               (4^-l0 an exact power of two: f is linear in area between two levels, in [0, 1)).
+ *   fetch       level 0 is the scene's own bank through slot_of / seg_start / row_base, exactly as vsa_nt_shade_fwd
+ *               reads it (a bank out of bake() holds the network's values in the apron).  A level l >= 1 reads its
+ *               planes by the corner rule of "Texture transfer, source lookup": nt_footprint(uv, R_d >> l, anchor)
+ *               gives (i0, j0, fx, fy); corner k = 2 ky + kx reads texel (clamp(j0 + ky, 0, R-1), clamp(i0 + kx, 0, R-1))
+ *               with weight (kx ? fx : 1 - fx) * (ky ? fy : 1 - fy) (anchor: all four are texel (j0, i0)); per channel
+ *               acc = 0; acc = acc + lut[byte_k] * w_k for k = 0..3; the level's coefficient is fp16(acc).
+ *   blend       f = 0: the coefficient is level l's.  f > 0 (then l < L; level l + 1 is fetched only here):
+ *               c = fp16(c_l + f * (c_{l+1} - c_l)), a subtract, a multiply and an add in fp32 on the two fp16 values.
+ *               Everything after the coefficients (SH evaluation, sigmoid, alpha decay, the dense scatter) is
+ *               vsa_nt_shade_fwd's code (csrc/nt_shade_common.h).  Where every hit of a call has l = 0 and f = 0 in
+ *               every degree, every output byte equals vsa_nt_shade_fwd's.
+ * vsa_texmip_planes_bytes: the bytes of level `level`'s plane buffer, 0..L: vsa_nt_planes_bytes >> (2 level).
+ * vsa_texmip_reduce: level `level` (1..8) from level `level - 1`, every image in one launch.  src_cover / dst_cover:
+ *   the masks of the two levels; src_cover NULL = all covered (dst_cover, if given, is then all 1); dst_cover NULL =
+ *   not wanted.  A lane makes two adjacent texels from two 16-byte loads and stores 8 bytes (one texel from four
+ *   4-byte loads where the destination's rows are odd).  No LDS, no atomics.
+ * vsa_texmip_density: density [nr_slots] f32 from tris [nr_slots, 12] (the tracer's records) and face_uvs [nr_slots, 6].
+ * vsa_nt_shade_mip_fwd: vsa_nt_shade_fwd's arguments (forward only: no act_out; coeffs_out as there, the blended fp16
+ *   coefficients) plus hit_t [K, N], slot_density, spread2, levels = L, level_planes [host]: L device pointers,
+ *   level_planes[l - 1] = the planes of level l, and the optional lod_out [K, N, rgb_degrees] f32 = l + f per degree
+ *   (NaN on a miss).
+ * All device pointers 16-byte aligned.  VSA_ERR_ARG (before any HIP call): a NULL pointer, misalignment, level / levels
+ *   outside 1..8, a tex_res[d] not divisible by 2^level (2^levels), wrong planes_bytes, src_planes == dst_planes,
+ *   nr_slots < 1, nr_rays < 0, a spread2 that is negative or not finite, nr_shells, rgb_degrees or a resolution out of
+ *   range.  VSA_ERR_UNSUPPORTED: alpha_degrees != rgb_degrees, row_format != 0. */
+#define VSA_TEXMIP_MAX_LEVELS 8
+long long vsa_texmip_planes_bytes(const vsa_nt_plan* plan, int level);
+int vsa_texmip_reduce(const vsa_nt_plan* plan, int level, const uint8_t* src_planes, long long src_planes_bytes,
+                      const uint8_t* src_cover, uint8_t* dst_planes, long long dst_planes_bytes, uint8_t* dst_cover,
+                      void* stream);
+int vsa_texmip_density(const float* tris, const float* face_uvs, long long nr_slots, float* density, void* stream);
+int vsa_nt_shade_mip_fwd(const vsa_nt_plan* plan, const int32_t* hit_slot, const float* tex_uv, const float* rays_d,
+                         const float* tris, const int32_t* slot_of, const int32_t* seg_start, const uint8_t* texels,
+                         int nr_rays, const float* hit_t, const float* slot_density, float spread2, int levels,
+                         const uint8_t* const* level_planes, float* surfs_rgb, float* surfs_alpha,
+                         float* surfs_normals, float* coeffs_out, float* lod_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,7 @@ class VolSurfs(torch.nn.Module):
         self.save_checkpoints_path = self.load_checkpoints_path = None
         self.profiler = None        # a trainer.Profiler (or any object with start(name) / end(name))
         self.baked = None
+        self.mips = None            # a texture_mip.MipChain of `baked` (build_mips)
         self.is_training = True
         self.lr = lr
         self.optimizer = None
@@ -653,32 +654,65 @@ class VolSurfs(torch.nn.Module):
         """What follows the hits in a baked render: per-hit uv -> shade -> composite."""
         frame = self.baked.frame(hit_slot, hit_uv, self.face_uvs)
         rgb_k, alpha_k, normals = frame.forward(rays_d, self.raytracer.tris, differentiable=False, want_normals=True)
-        bg = self.bg_color if self.bg_color is not None else torch.ones(1, 3, device=rays_d.device)
+        return self._composite_baked(rgb_k, alpha_k, normals)
+
+    def _composite_baked(self, rgb_k, alpha_k, normals):
+        """The end of every baked shade: the dense composite over the background colour (white when there is none)."""
+        bg = self.bg_color if self.bg_color is not None else torch.ones(1, 3, device=rgb_k.device)
         out = composite_dense(rgb_k, alpha_k, bg)
         out["surfs_normals"] = normals
         return out
 
+    def _camera_hit_chunks(self, camera, s, hits, chunk=1 << 20):
+        """(hit_t, hit_slot, hit_uv, rays_d) of a camera's samples at supersample s, as `render_baked_camera` takes
+        them: hits="raster" the rasterizer's whole frame; "trace" `get_camera_rays` (jittered when s > 1) + `trace_all`
+        in `render_baked`'s chunks."""
+        if hits == "raster":
+            from .rasterize import camera_hits
+            _, rays_d, (hit_t, hit_slot, hit_uv) = camera_hits(self.raytracer, camera, s)
+            yield hit_t, hit_slot, hit_uv, rays_d
+            return
+        from .camera import get_camera_rays
+        rays_o, rays_d, _ = get_camera_rays(camera, s * s, s > 1)
+        for a in range(0, rays_o.shape[0], chunk):
+            o, d = rays_o[a:a + chunk].contiguous(), rays_d[a:a + chunk].contiguous()
+            yield (*self._trace_now(o, d), d)
+
     @torch.no_grad()
-    def render_baked_camera(self, camera, supersample=1, hits="trace"):
+    def build_mips(self, levels=None, coverage="owners"):
+        """`texture_mip.build_mips(self, ...)`, kept at `.mips`: what `render_baked_camera(filter="mip")` reads."""
+        from .texture_mip import build_mips
+        self.mips = build_mips(self, levels=levels, coverage=coverage)
+        return self.mips
+
+    @torch.no_grad()
+    def render_baked_camera(self, camera, supersample=1, hits="trace", filter="bilinear", lod_bias=0.0):
         """`render_baked` from the camera down: the `ray_traced` dict per pixel, [H * W, C], the mean over the pixel's
         s^2 samples when supersample = s > 1.
+        filter="bilinear" (default): one bilinear fetch from the full-resolution textures per hit and degree.
+        filter="mip": every degree of a hit reads the level of the scene's mip chain that its pixel's footprint on the
+        surface asks for, blended with the next (`texture_mip`); lod_bias shifts the level (+1: one level
+        coarser).  Needs `build_mips()`: ValueError without a chain or with a stale one.  Both `hits` modes.
         hits="trace" (default): `get_camera_rays` (jittered when s > 1, as BaseRenderer.render draws them) +
         `trace_all`.  hits="raster": `RayTracer.rasterize` -- no ray-generation launch, no ray in memory, no BVH walk;
         the s^2 samples lie on the s x s grid of `face_view_counts`.  At s = 1 the two give the same bytes in every
         buffer.  Measured: the raster path is faster for simplified shells seen from outside (a few faces
         per 8 x 8 tile; 1.3x, 2x at s = 2); the trace is faster, by far, for dense meshes (tens of faces per tile) and
         for a camera inside a shell."""
-        from .rasterize import camera_hits, check_hits_mode
+        from .rasterize import check_hits_mode
         s = int(supersample)
         if not 1 <= s <= 8:
             raise ValueError(f"supersample must be in 1..8, got {supersample}")
-        if check_hits_mode(hits) == "raster":
-            _, rays_d, (_, hit_slot, hit_uv) = camera_hits(self.raytracer, camera, s)
-            out = self._shade_baked(hit_slot, hit_uv, rays_d)
+        if filter not in ("bilinear", "mip"):
+            raise ValueError(f'filter must be "bilinear" or "mip", got {filter!r}')
+        if filter == "mip":
+            from .texture_mip import mip_shader
+            shade = mip_shader(self, camera, s, lod_bias)
         else:
-            from .camera import get_camera_rays
-            rays_o, rays_d, _ = get_camera_rays(camera, s * s, s > 1)
-            out = self.render_baked(rays_o, rays_d)
+            def shade(hit_t, hit_slot, hit_uv, rays_d):
+                return self._shade_baked(hit_slot, hit_uv, rays_d)
+        outs = [shade(*h) for h in self._camera_hit_chunks(camera, s, check_hits_mode(hits))]
+        out = outs[0] if len(outs) == 1 else {k: torch.cat([o_[k] for o_ in outs], 0) for k in outs[0]}
         if s > 1:
             out = {k: v.reshape(-1, s * s, *v.shape[1:]).float().mean(1) for k, v in out.items()}
         return out
@@ -839,7 +873,7 @@ class VolSurfs(torch.nn.Module):
                     w.copy_(st["weights"])
         if self.bank is not None:
             self.bank.refresh_half_params()
-            self.baked = None                                   # baked textures are stale now
+            self.baked = self.mips = None                       # baked textures (and their mip chain) are stale now
         for key, model in self.models.items():
             f = os.path.join(path, f"{key}.pt")
             if os.path.exists(f):

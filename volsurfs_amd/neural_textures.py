@@ -217,6 +217,8 @@ class NeuralTextureBank(torch.nn.Module):
         i32, u8 = torch.int32, torch.uint8
         cap, K = self.slot_capacity, self.K
         self.frame_generation = 0        # (all per-frame and gradient state is declared here) bumped by frame()
+        self.texels_version = 0          # bumped by whatever rewrites a BAKED bank's bytes (bake_all, the plane import,
+                                         # a texel-fit step): a texture_mip.MipChain built before is stale afterwards
         self.baked, self._marks_dirty = False, False     # the rows hold EVERY texel (bake_all); a mark not yet compacted
         self._grad_flat = None           # zero_grads(): tables.grad | weights.grad | _dfsum as one allocation, built lazily
         self._dfsum, self._dfsum_clean = None, False     # per-texture sum |dF| of the MLP backward; "is all zero"
@@ -300,6 +302,7 @@ class NeuralTextureBank(torch.nn.Module):
         self.compact_all()
         self.evaluate(need_features=False)
         self.baked = True
+        self.texels_version += 1
         return self
 
     @torch.no_grad()

@@ -192,18 +192,25 @@ class VolsurfsRenderer(BaseRenderer):
         self.active_render_mode, self.active_shader = "ray_traced", "rgb"
 
     @classmethod
-    def from_scene(cls, scene_path, device="cuda", bvh_builder="host", profiler=None):
+    def from_scene(cls, scene_path, device="cuda", bvh_builder="host", profiler=None, mips=None):
         """The renderer of a scene written by texture_export.extract_textures (scene.json, meshes/*.obj,
-        textures/*.png), loaded with texture_export.load_scene."""
+        textures/*.png), loaded with texture_export.load_scene.  mips: the levels of the mip chain to build after
+        loading (for `render_baked_camera(filter="mip")`), or None."""
         from .texture_export import load_scene
-        return cls(load_scene(scene_path, device=device, bvh_builder=bvh_builder), profiler=profiler)
+        return cls(load_scene(scene_path, device=device, bvh_builder=bvh_builder, mips=mips), profiler=profiler)
 
     @torch.no_grad()
     def render_rays(self, rays_o, rays_d, verbose=False) -> dict:
         return {"renders": {"ray_traced": self.method.render_baked(rays_o, rays_d)}}
 
     @torch.no_grad()
-    def render_baked_camera(self, camera, supersample=1, hits="trace"):
+    def render_baked_camera(self, camera, supersample=1, hits="trace", filter="bilinear", lod_bias=0.0):
         """The method's `render_baked_camera`: the `ray_traced` dict per pixel, on the device; hits="raster" takes
-        the frame's hits from `RayTracer.rasterize` instead of `get_camera_rays` + `trace_all`."""
-        return self.method.render_baked_camera(camera, supersample=supersample, hits=hits)
+        the frame's hits from `RayTracer.rasterize` instead of `get_camera_rays` + `trace_all`; filter="mip" shades
+        through the method's mip chain (`build_mips`)."""
+        return self.method.render_baked_camera(camera, supersample=supersample, hits=hits, filter=filter,
+                                               lod_bias=lod_bias)
+
+    def build_mips(self, levels=None, coverage="owners"):
+        """The method's `build_mips`."""
+        return self.method.build_mips(levels=levels, coverage=coverage)

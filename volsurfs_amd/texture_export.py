@@ -348,6 +348,7 @@ class BakedScene:
         self.raytracer = RayTracer(meshes, builder=bvh_builder)
         self.face_uvs = self.raytracer.slot_face_uvs(meshes)
         self.baked = bank
+        self.mips = None            # a texture_mip.MipChain of `baked` (build_mips)
         self.bg_color = torch.tensor([bg_color], dtype=torch.float32, device=bank.texels.device)
         self.cameras = cameras
         self.resolution = resolution
@@ -356,7 +357,10 @@ class BakedScene:
     _trace_now = VolSurfs._trace_now
     render_baked = VolSurfs.render_baked
     _shade_baked = VolSurfs._shade_baked
+    _composite_baked = VolSurfs._composite_baked
+    _camera_hit_chunks = VolSurfs._camera_hit_chunks
     render_baked_camera = VolSurfs.render_baked_camera
+    build_mips = VolSurfs.build_mips
     refit_to = VolSurfs.refit_to
 
     def render_rays(self, rays_o, rays_d, chunk=1 << 20):
@@ -387,6 +391,7 @@ def _import_planes(bank, planes):
     _lib.call("vsa_nt_import_planes", ctypes.byref(bank.plan), planes, total, bank.slot_of, bank.seg_start,
               bank.texels, _lib.stream_ptr())
     bank.baked = True
+    bank.texels_version += 1
 
 
 @torch.no_grad()
@@ -402,8 +407,10 @@ def write_scene(scene, out_dir, cameras=None, resolution=None, compress_level=6,
 
 
 @torch.no_grad()
-def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None):
+def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None, mips=None):
     """Read a directory written by `extract_textures` (scene.json, meshes/*.obj, textures/*.png) into a BakedScene.
+    mips: None, or the levels of the mip chain to build after loading (`BakedScene.build_mips(levels=mips)`; the chain
+    is derived, nothing of it is on disk).
     sh_range comes from texture_scale, the degrees and resolutions from the texture list, the alpha models from
     ignore_alpha and lerp / with_alpha_decay from the "volsurfs_amd" key (absent: lerp, with alpha decay — the shipped
     configs).  The textures are uploaded with vsa_nt_import_planes into the slots `bake_all` would give them; the
@@ -451,4 +458,6 @@ def load_scene(scene_path, device="cuda", bvh_builder="host", timings=None):
                           for _, c in sorted(cams.items(), key=lambda kv: int(kv[0]))]
     scene = BakedScene(meshes, bank, _bg_color_of(meta.get("bg_color", "black")), cameras, (W, H), bvh_builder)
     t.update({"meshes_s": t1 - t0, "png_s": t2 - t1, "h2d_ms": (t3 - t2) * 1e3, "import_ms": (t4 - t3) * 1e3})
+    if mips is not None:
+        scene.build_mips(levels=mips)
     return scene

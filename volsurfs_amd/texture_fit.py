@@ -12,7 +12,10 @@ shade backward into this fit's gradient rows -> `vsa_texel_fit_step`.
 * `refit_lod` — `fit_textures` of a LOD against renders of its source from hemisphere cameras.
 
 NOT promised: two fits of the same scene to the same views need not give the same bytes (the shade backward adds f16
-atomically; the step itself is deterministic).  hits="trace" only, L1 only, no regulariser, no mip chain.
+atomically; the step itself is deterministic).  hits="trace" only, L1 only, no regulariser, no mip chain: the fit
+renders and differentiates the bilinear fetch of level 0 only, and its results (`TextureFit.scene`, `fit_textures`,
+`refit_to`) carry no `texture_mip.MipChain`.  A fitted scene needs `build_mips` again before `filter="mip"`; a chain
+built before a `step()` is stale and refused.
 """
 import collections
 import ctypes
@@ -95,6 +98,7 @@ class TextureFit:
         _lib.call("vsa_texel_fit_step", ctypes.byref(bank.plan), bank.slot_of, bank.seg_start, self.grad_rows,
                   1.0 / self._scale, self.p, self.m, self.v, bank.texels, self.lr, self.betas[0], self.betas[1],
                   self.eps, self.steps, stats, _lib.stream_ptr())
+        bank.texels_version += 1                     # a mip chain of these bytes is stale now
         self._scale = None
         self.totals += stats
         return stats
