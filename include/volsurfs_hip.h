@@ -1443,12 +1443,59 @@ int vsa_simplify_guarded(const float* verts, long long nr_verts, const int32_t* 
  * vsa_atlas_rasterize: the raster rule above on any faces_uvs [F, 3, 2] f32 (device): out_face_id [R, R] i32 (the lowest
  * covering face, -1 when none) and out_count [R, R] i32 (covering faces), row j = v.  Workspace
  * vsa_atlas_rasterize_workspace_bytes(F) (16 bytes per face plus a scan's storage).  Synchronises `stream`.
+ *
+ * vsa_atlas_merged: vsa_atlas with its box charts merged into plane-projected groups first.  A connected
+ * patch of box charts whose faces all fit one cone of directions is projected along its own summed normal, with the
+ * box rule's kind of guarantee: every face keeps at least min_cos of its area and none flips.  Arguments: vsa_atlas's,
+ * plus min_cos in (0, 1] and merge_rounds >= 0 (0: vsa_atlas's output, bit for bit).  Everything not named here is
+ * vsa_atlas's rule unchanged, in the same operations and the same order; tests/atlas_merge_restated.py restates it.
+ *   start         labels and charts as in vsa_atlas, all codes 1.  Every chart is a group, named by its minimum face,
+ *                 unmerged, with the area vector A_g = 0 + the n_f of its faces (the label stage's fp32 normals, as
+ *                 fp64) in ascending face index, per component, in fp64.
+ *   adjacency     two groups are adjacent when faces of theirs share an undirected edge that has exactly two face
+ *                 corners and is traversed in opposite directions (the join rule's edge test without the label test);
+ *                 the weight of the pair is the number of such edges.
+ *   validity      an adjacent pair a < b is valid when, with D = A_a + A_b (fp64, per component) and t2 = min_cos *
+ *                 min_cos, every face f of both groups has n_f = 0, or c = (nx Dx + ny Dy) + nz Dz > 0 and c c >=
+ *                 (t2 ((nx nx + ny ny) + nz nz)) ((Dx Dx + Dy Dy) + Dz Dz), all in fp64.  No square root is taken.
+ *                 (A valid pair has D != 0, so no frame divides by zero: faces with n_f = 0 all carry label 0, adjacent
+ *                 ones are one box chart already, and so no two adjacent groups consist of such faces only; a pair
+ *                 with D = 0 and a face of n_f != 0 has c = 0 and fails.)
+ *   round         every group picks, among its valid pairs, the neighbour of largest weight, ties to the smaller group
+ *                 id.  Two groups that pick each other merge: the id is the smaller one (a), A_a becomes A_a + A_b (the
+ *                 D that was tested, bit for bit), and the group is marked merged.  Picks are taken from the state at
+ *                 the start of the round; the merging pairs are disjoint.  While a valid pair exists a round merges at
+ *                 least one (the valid pair of largest weight, least smaller id, least other id is mutual).  Rounds
+ *                 repeat until one finds no valid pair (it counts as a round run) or merge_rounds rounds have run;
+ *                 every intermediate state is a valid set of groups.
+ *   frames        an unmerged group keeps its label's coordinate pick.  A merged group with D = A_g: k = the index of
+ *                 the smallest |D_k| (ties to the earlier); t = e_k x D, written out: k = 0: (0, -Dz, Dy), k = 1: (Dz, 0,
+ *                 -Dx), k = 2: (-Dy, Dx, 0); b = D x t = (Dy tz - Dz ty, Dz tx - Dx tz, Dx ty - Dy tx); each divided by
+ *                 the square root of its own squared length ((x x + y y) + z z), in fp64.  A corner's plane coordinates
+ *                 are ((Px tx + Py ty) + Pz tz, (Px bx + Py by) + Pz bz) in fp64, each rounded once to fp32.  (t, b, D)
+ *                 is right-handed, so a valid face's projected signed area is >= 0; both kinds of frame are isometries
+ *                 of the plane, so one density s serves all charts.
+ *   after         the join rule's "same label" reads "same group"; chart boxes, the 90 degree turn, the pack, the UV
+ *                 formula, the raster and the overlap test are vsa_atlas's on the plane coordinates, and the split reads
+ *                 the corners' coordinates along the box's longer side from them, so splits act inside groups.
+ *   output        vsa_atlas's; [host] stats 8 long long: the four of vsa_atlas, then box charts before merging, groups
+ *                 after it, merge rounds run, and valid pairs left when the rounds stopped.
+ *   stage_ms      [host] 6 floats or NULL: vsa_atlas's five, then merge.
+ * The host reads, on top of vsa_atlas's reads, the edge and box-chart counts once, the valid-pair count once per merge
+ * round, and the merge count once.
+ *   workspace     vsa_atlas_merged_workspace_bytes(V, F, R): vsa_atlas's plus 190 bytes per face -- O(V + F + R^2).
+ * VSA_ERR_ARG: as vsa_atlas, and min_cos outside (0, 1] or NaN, merge_rounds < 0.  Other codes as vsa_atlas.
  */
 #define VSA_ERR_ATLAS_FULL (-3)
 long long vsa_atlas_workspace_bytes(long long nr_verts, long long nr_faces, int resolution);
 int vsa_atlas(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, int resolution,
               int padding, void* workspace, long long workspace_bytes, float* out_faces_uvs, int32_t* out_chart,
               long long* stats, float* scale, float* stage_ms, void* stream);
+long long vsa_atlas_merged_workspace_bytes(long long nr_verts, long long nr_faces, int resolution);
+int vsa_atlas_merged(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces, int resolution,
+                     int padding, double min_cos, int merge_rounds, void* workspace, long long workspace_bytes,
+                     float* out_faces_uvs, int32_t* out_chart, long long* stats, float* scale, float* stage_ms,
+                     void* stream);
 long long vsa_atlas_rasterize_workspace_bytes(long long nr_faces);
 int vsa_atlas_rasterize(const float* faces_uvs, long long nr_faces, int resolution, void* workspace,
                         long long workspace_bytes, int32_t* out_face_id, int32_t* out_count, void* stream);

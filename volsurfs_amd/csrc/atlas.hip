@@ -1,11 +1,22 @@
 // UV atlas of one consistently wound triangle mesh by box projection (vsa_atlas*; rules in include/volsurfs_hip.h,
-// DESIGN §16).
+// DESIGN §16), and with the box charts merged into plane-projected groups first (vsa_atlas_merged).
 //
 // One stream.  Once per call:
 //   label:   fp32 face normals; the (vertex, face) list radix-sorted by vertex (ascending face within a vertex) gives
 //            the per-vertex normal sums in a fixed order; one lane per face picks the face's direction label.  The 3F
 //            (min, max) edge keys are radix-sorted with their slots: an edge with exactly two slots, traversed in
 //            opposite directions by two faces of one label, is a join pair; pairs are compacted by a scan.
+// vsa_atlas_merged only, once per call:
+//   merge:   the join pairs are the eligible edges without the label test.  The box charts (a union-find over the pairs
+//            of one label) are the first groups; the faces radix-sorted by group give every group's run, and one wave
+//            per group sums its area vector in ascending face order.  Then merge rounds: the pairs' (lo group, hi group)
+//            keys radix-sorted and run-lengthed into adjacent pairs with weights; a scan of the pairs' face counts lays
+//            out (face, pair) items, one lane per item tests its face against the pair's summed area vector and clears
+//            the pair's flag when it fails; every valid pair offers itself to both groups by a 64-bit atomic max of
+//            (weight, ~neighbour); pairs that picked each other merge (parent, area vector, merged mark), every face
+//            is relabelled through the parent, and the faces are sorted by group again.  The host reads the valid-pair
+//            count once per round.  Last, one lane per merged group builds its frame and one lane per face writes its
+//            corners' plane coordinates, which the boxes, the UVs and the split read instead of the label's pick.
 // Then rounds, until no chart overlaps itself:
 //   charts:  union-find over the join pairs whose faces carry the same split code (CAS hooks of the larger root under
 //            the smaller, so a root is its component's minimum face index whatever the order); roots flagged and
@@ -45,7 +56,11 @@
 #define ACT_OVL 4
 #define ACT_COV 5
 #define ACT_PROG 6
-#define ACT_N 8
+#define ACT_BOX 8      // vsa_atlas_merged: box charts, adjacent group pairs, valid pairs, merges
+#define ACT_NP 9
+#define ACT_NV 10
+#define ACT_MERGES 11
+#define ACT_N 16
 
 using mt::at;
 using mt::u64;
@@ -130,7 +145,8 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_labels(const int32_t* __restric
   label[f] = (dn >= 0.0 && 4.0 * (dn * dn) >= nn) ? cand : atl_argmax6(nx, ny, nz);
 }
 
-// Join flag at the first sorted slot of an edge with exactly two slots, opposite directions and one label.
+// Join flag at the first sorted slot of an edge with exactly two slots, opposite directions and one label (label
+// null: the edge test alone, vsa_atlas_merged's).
 __global__ __launch_bounds__(ATL_BLOCK) void atl_join_flags(const u64* __restrict__ sorted,
                                                            const uint32_t* __restrict__ slot,
                                                            const int32_t* __restrict__ faces,
@@ -144,7 +160,7 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_join_flags(const u64* __restric
     const long long s0 = slot[i], s1 = slot[i + 1];
     const long long f0 = s0 / 3, f1 = s1 / 3;
     const int c0 = (int)(s0 - 3 * f0), c1 = (int)(s1 - 3 * f1);
-    ok = faces[3 * f0 + c0] == faces[3 * f1 + (c1 == 2 ? 0 : c1 + 1)] && label[f0] == label[f1];
+    ok = faces[3 * f0 + c0] == faces[3 * f1 + (c1 == 2 ? 0 : c1 + 1)] && (!label || label[f0] == label[f1]);
   }
   flags[i] = ok;
 }
@@ -162,13 +178,16 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_join_compact(const uint32_t* __
 // ------------------------------------------------------------------------------------------------ charts
 
 // Every parent is <= its child, so the root of a component is its minimum face index (mesh_topology.h).
+// key (vsa_atlas_merged: the label, then the group): the pair's faces must also agree on it.
 __global__ __launch_bounds__(ATL_BLOCK) void atl_hook(const int2* __restrict__ pairs, const long long* __restrict__ ctr,
-                                                     const uint32_t* __restrict__ code, int32_t* par) {
+                                                     const uint32_t* __restrict__ code,
+                                                     const int32_t* __restrict__ key, int32_t* par) {
   const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (i >= ctr[ACT_J]) return;
   const int2 pr = pairs[i];
   const uint32_t k = code[pr.x];
   if (k == 0u || k != code[pr.y]) return;
+  if (key && key[pr.x] != key[pr.y]) return;
   fu_union(par, pr.x, pr.y);
 }
 
@@ -188,17 +207,30 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_box_init(unsigned* __restrict__
   if (i < n) box[i] = (i & 1) ? 0u : 0xFFFFFFFFu;
 }
 
+// Corner c of face f in its chart's plane.  PC (vsa_atlas_merged): the plane coordinates atl_plane_coords wrote; else
+// the two coordinates the face's label picks.
+template <bool PC>
+__device__ __forceinline__ float2 atl_corner(const float* __restrict__ P, const int32_t* __restrict__ faces,
+                                             const int32_t* __restrict__ label, const float* __restrict__ pc,
+                                             long long f, int c) {
+  if (PC) return make_float2(pc[6 * f + 2 * c], pc[6 * f + 2 * c + 1]);
+  const int l = label[f];
+  const long long v = faces[3 * f + c];
+  return make_float2(P[3 * v + atl_ax_u[l]], P[3 * v + atl_ax_v[l]]);
+}
+
+template <bool PC>
 __global__ __launch_bounds__(ATL_BLOCK) void atl_boxes(const float* __restrict__ P, const int32_t* __restrict__ faces,
                                                       long long F, const int32_t* __restrict__ label,
+                                                      const float* __restrict__ pc,
                                                       const int32_t* __restrict__ cidx, unsigned* __restrict__ box) {
   const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (f >= F) return;
-  const int l = label[f], au = atl_ax_u[l], av = atl_ax_v[l];
   unsigned umin = 0xFFFFFFFFu, umax = 0u, vmin = 0xFFFFFFFFu, vmax = 0u;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const long long v = faces[3 * f + c];
-    const unsigned ku = atl_ord(P[3 * v + au]), kv = atl_ord(P[3 * v + av]);
+    const float2 q = atl_corner<PC>(P, faces, label, pc, f, c);
+    const unsigned ku = atl_ord(q.x), kv = atl_ord(q.y);
     umin = ku < umin ? ku : umin;
     umax = ku > umax ? ku : umax;
     vmin = kv < vmin ? kv : vmin;
@@ -303,14 +335,14 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_offsets(const u64* __restrict__
 // ------------------------------------------------------------------------------------------------ emit
 
 // uv = (local * s + (offset + p)) / R in fp32; local = (u - umin, v - vmin), or (vmax - v, u - umin) when rotated.
+template <bool PC>
 __global__ __launch_bounds__(ATL_BLOCK) void atl_emit(const float* __restrict__ P, const int32_t* __restrict__ faces,
                                                      long long F, const int32_t* __restrict__ label,
-                                                     const int32_t* __restrict__ cidx,
+                                                     const float* __restrict__ pc, const int32_t* __restrict__ cidx,
                                                      const unsigned* __restrict__ box, const int2* __restrict__ off,
                                                      float s, int R, int p, float* __restrict__ uv) {
   const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
   if (f >= F) return;
-  const int l = label[f], au = atl_ax_u[l], av = atl_ax_v[l];
   const long long c = cidx[f];
   const float umin = atl_unord(box[4 * c]), umax = atl_unord(box[4 * c + 1]);
   const float vmin = atl_unord(box[4 * c + 2]), vmax = atl_unord(box[4 * c + 3]);
@@ -319,8 +351,8 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_emit(const float* __restrict__ 
   const float ox = (float)(o.x + p), oy = (float)(o.y + p), r = (float)R;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    const long long v = faces[3 * f + k];
-    const float u = P[3 * v + au], w = P[3 * v + av];
+    const float2 q = atl_corner<PC>(P, faces, label, pc, f, k);
+    const float u = q.x, w = q.y;
     const float lx = rot ? vmax - w : u - umin;
     const float ly = rot ? u - umin : w - vmin;
     uv[6 * f + 2 * k] = (lx * s + ox) / r;
@@ -405,9 +437,10 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_count_flags(const int32_t* __re
 
 // A face of a flagged chart: code 0 (one chart per face) at the depth cap, else code = 2 code + side, side = 1 when
 // the sum of its corners' coordinates along the box's longer side (u on a tie) exceeds 3 x the side's midpoint (fp64).
+template <bool PC>
 __global__ __launch_bounds__(ATL_BLOCK) void atl_split(const float* __restrict__ P, const int32_t* __restrict__ faces,
                                                       long long F, const int32_t* __restrict__ label,
-                                                      const int32_t* __restrict__ cidx,
+                                                      const float* __restrict__ pc, const int32_t* __restrict__ cidx,
                                                       const unsigned* __restrict__ box,
                                                       const int32_t* __restrict__ flag, uint32_t* __restrict__ code,
                                                       long long* __restrict__ ctr) {
@@ -424,11 +457,16 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_split(const float* __restrict__
         const float umin = atl_unord(box[4 * c]), umax = atl_unord(box[4 * c + 1]);
         const float vmin = atl_unord(box[4 * c + 2]), vmax = atl_unord(box[4 * c + 3]);
         const bool along_u = (umax - umin) >= (vmax - vmin);
-        const int ax = along_u ? atl_ax_u[label[f]] : atl_ax_v[label[f]];
         const double lo = along_u ? umin : vmin, hi = along_u ? umax : vmax;
-        const double sum = ((double)P[3 * (long long)faces[3 * f] + ax] +
-                            (double)P[3 * (long long)faces[3 * f + 1] + ax]) +
-                           (double)P[3 * (long long)faces[3 * f + 2] + ax];
+        double sum;
+        if (PC) {
+          const float* q = pc + 6 * f + (along_u ? 0 : 1);
+          sum = ((double)q[0] + (double)q[2]) + (double)q[4];
+        } else {
+          const int ax = along_u ? atl_ax_u[label[f]] : atl_ax_v[label[f]];
+          sum = ((double)P[3 * (long long)faces[3 * f] + ax] + (double)P[3 * (long long)faces[3 * f + 1] + ax]) +
+                (double)P[3 * (long long)faces[3 * f + 2] + ax];
+        }
         code[f] = 2u * k + (sum > 1.5 * (lo + hi) ? 1u : 0u);
       }
     }
@@ -439,11 +477,269 @@ __global__ __launch_bounds__(ATL_BLOCK) void atl_split(const float* __restrict__
     atomicAdd((unsigned long long*)(ctr + ACT_PROG), (unsigned long long)__popcll(m));
 }
 
+// ------------------------------------------------------------------------------------------------ merge
+
+// vsa_atlas_merged (rules in include/volsurfs_hip.h).  A group is named by its minimum face; grp[f] is the
+// group of face f, and gA, merged, best, gstart, gend and fr are indexed by group id.  Integer atomics only: the area
+// vectors are summed in a fixed order.
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_group_list(const int32_t* __restrict__ flags,
+                                                           const int32_t* __restrict__ rank, long long F,
+                                                           int32_t* __restrict__ glist, long long* __restrict__ ctr) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  if (flags[f]) glist[rank[f]] = (int32_t)f;
+  if (f == F - 1) ctr[ACT_BOX] = rank[f] + flags[f];
+}
+
+// The run of group g in the faces sorted by group: gf[gstart[g] .. gend[g]).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_group_runs(const uint32_t* __restrict__ sg, long long F,
+                                                           int32_t* __restrict__ gstart, int32_t* __restrict__ gend) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= F) return;
+  if (i == 0 || sg[i] != sg[i - 1]) gstart[sg[i]] = (int32_t)i;
+  if (i == F - 1 || sg[i] != sg[i + 1]) gend[sg[i]] = (int32_t)(i + 1);
+}
+
+// A_g = 0 + the fp64 n_f of the group's faces in ascending face index.  One wave per group: the lanes load 64 faces'
+// normals at once, and every lane adds them one after the other in lane order, so the order is the rule's while the
+// loads run side by side (one lane walking a sphere's 25 000-face chart alone is a chain of as many dependent loads).
+__global__ __launch_bounds__(VSA_WAVE) void atl_group_area(const float* __restrict__ fn, const uint32_t* __restrict__ gf,
+                                                          const int32_t* __restrict__ gstart,
+                                                          const int32_t* __restrict__ gend,
+                                                          const int32_t* __restrict__ glist, double* __restrict__ gA) {
+  const long long g = glist[blockIdx.x];
+  const int lane = threadIdx.x, end = gend[g];
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int i = gstart[g]; i < end; i += VSA_WAVE) {
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (i + lane < end) {
+      const long long f = gf[i + lane];
+      x = (double)fn[3 * f];
+      y = (double)fn[3 * f + 1];
+      z = (double)fn[3 * f + 2];
+    }
+    const int m = end - i < VSA_WAVE ? end - i : VSA_WAVE;
+    for (int k = 0; k < m; ++k) {
+      sx += __shfl(x, k, VSA_WAVE);
+      sy += __shfl(y, k, VSA_WAVE);
+      sz += __shfl(z, k, VSA_WAVE);
+    }
+  }
+  if (lane == 0) {
+    gA[3 * g] = sx;
+    gA[3 * g + 1] = sy;
+    gA[3 * g + 2] = sz;
+  }
+}
+
+// Key of an eligible edge between two groups: lo << s | hi at s = the bits of F - 1; all ones inside one group (no
+// key of two groups is: lo < hi < 2^s).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_pair_keys(const int2* __restrict__ pairs, long long E,
+                                                          const int32_t* __restrict__ grp, int s,
+                                                          u64* __restrict__ keys) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= E) return;
+  const int2 pr = pairs[i];
+  const unsigned a = (unsigned)grp[pr.x], b = (unsigned)grp[pr.y];
+  keys[i] = a == b ? (1ull << (2 * s)) - 1ull : (u64)(a < b ? a : b) << s | (u64)(a < b ? b : a);
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_pair_heads(const u64* __restrict__ sk, long long E, int s,
+                                                           int32_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= E) return;
+  flags[i] = sk[i] != (1ull << (2 * s)) - 1ull && (i == 0 || sk[i - 1] != sk[i]);
+}
+
+// Pair j = the j-th run of equal keys: its groups, and its run [pstart, pend) (the weight is the run's length).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_pair_runs(const u64* __restrict__ sk, const int32_t* __restrict__ flags,
+                                                          const int32_t* __restrict__ rank, long long E, int s,
+                                                          int2* __restrict__ gp, int32_t* __restrict__ pstart,
+                                                          int32_t* __restrict__ pend, long long* __restrict__ ctr) {
+  const long long i = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (i >= E) return;
+  const u64 k = sk[i];
+  if (k != (1ull << (2 * s)) - 1ull) {
+    const long long j = rank[i] + flags[i] - 1;
+    if (flags[i]) {
+      gp[j] = make_int2((int)(k >> s), (int)(k & ((1ull << s) - 1ull)));
+      pstart[j] = (int32_t)i;
+    }
+    if (i == E - 1 || sk[i + 1] != k) pend[j] = (int32_t)(i + 1);
+  }
+  if (i == E - 1) ctr[ACT_NP] = rank[i] + flags[i];
+}
+
+// cnt[j] = the (face, pair) items of pair j: the faces of both groups (0 past the last pair).  Pairs start valid, and
+// the picks of their groups empty.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_pair_items(const int2* __restrict__ gp, long long E,
+                                                           const long long* __restrict__ ctr,
+                                                           const int32_t* __restrict__ gstart,
+                                                           const int32_t* __restrict__ gend,
+                                                           long long* __restrict__ cnt, int32_t* __restrict__ valid,
+                                                           u64* __restrict__ best) {
+  const long long j = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (j >= E) return;
+  if (j >= ctr[ACT_NP]) {
+    cnt[j] = 0;
+    return;
+  }
+  const int2 ab = gp[j];
+  cnt[j] = (long long)(gend[ab.x] - gstart[ab.x]) + (long long)(gend[ab.y] - gstart[ab.y]);
+  valid[j] = 1;
+  best[ab.x] = 0ull;   // (every lane that writes one writes 0)
+  best[ab.y] = 0ull;
+}
+
+// One lane per (face, pair) item, ioff[j] = the items before pair j: the face against D = A_a + A_b in fp64; a face
+// that fails clears its pair's flag.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_validity(const long long* __restrict__ ioff,
+                                                         const long long* __restrict__ ctr,
+                                                         const int2* __restrict__ gp,
+                                                         const int32_t* __restrict__ gstart,
+                                                         const int32_t* __restrict__ gend,
+                                                         const uint32_t* __restrict__ gf, const float* __restrict__ fn,
+                                                         const double* __restrict__ gA, double tt,
+                                                         int32_t* __restrict__ valid) {
+  const long long np = ctr[ACT_NP];
+  if (np <= 0) return;
+  const long long total = ioff[np];
+  for (long long it = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x; it < total;
+       it += (long long)gridDim.x * ATL_BLOCK) {
+    long long lo = 0, hi = np - 1;   // the last pair with ioff[j] <= it
+    while (lo < hi) {
+      const long long mid = lo + (hi - lo + 1) / 2;
+      if (ioff[mid] <= it) lo = mid;
+      else hi = mid - 1;
+    }
+    const int2 ab = gp[lo];
+    const long long k = it - ioff[lo], na = gend[ab.x] - gstart[ab.x];
+    const long long f = k < na ? gf[gstart[ab.x] + k] : gf[gstart[ab.y] + (k - na)];
+    const float fx = fn[3 * f], fy = fn[3 * f + 1], fz = fn[3 * f + 2];
+    if (fx == 0.f && fy == 0.f && fz == 0.f) continue;
+    const double nx = fx, ny = fy, nz = fz;
+    const double dx = gA[3 * (long long)ab.x] + gA[3 * (long long)ab.y];
+    const double dy = gA[3 * (long long)ab.x + 1] + gA[3 * (long long)ab.y + 1];
+    const double dz = gA[3 * (long long)ab.x + 2] + gA[3 * (long long)ab.y + 2];
+    const double c = (nx * dx + ny * dy) + nz * dz;
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    const double dd = (dx * dx + dy * dy) + dz * dz;
+    if (!(c > 0.0 && c * c >= (tt * nn) * dd)) atomicAnd(valid + lo, 0);
+  }
+}
+
+// A pick is (weight << 32 | ~neighbour): the maximum is the largest weight, ties to the smaller group id.
+__device__ __forceinline__ u64 atl_pick_key(int w, int g) { return (u64)(unsigned)w << 32 | (u64)(~(unsigned)g); }
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_pick(const int2* __restrict__ gp, long long E,
+                                                     const long long* __restrict__ ctr,
+                                                     const int32_t* __restrict__ pstart,
+                                                     const int32_t* __restrict__ pend,
+                                                     const int32_t* __restrict__ valid, u64* __restrict__ best,
+                                                     long long* __restrict__ nv) {
+  const long long j = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  const bool ok = j < E && j < ctr[ACT_NP] && valid[j];
+  if (ok) {
+    const int2 ab = gp[j];
+    const int w = pend[j] - pstart[j];
+    atomicMax((unsigned long long*)(best + ab.x), (unsigned long long)atl_pick_key(w, ab.y));
+    atomicMax((unsigned long long*)(best + ab.y), (unsigned long long)atl_pick_key(w, ab.x));
+  }
+  const u64 m = __ballot(ok);
+  if ((threadIdx.x & (VSA_WAVE - 1)) == 0 && m) atomicAdd((unsigned long long*)nv, (unsigned long long)__popcll(m));
+}
+
+// Two groups that picked each other merge under the smaller id a: par[b] = a, A_a = A_a + A_b, a is marked merged.  A
+// group is in at most one such pair, so no lane reads what another writes.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_merge(const int2* __restrict__ gp, long long E,
+                                                      const long long* __restrict__ ctr,
+                                                      const int32_t* __restrict__ pstart,
+                                                      const int32_t* __restrict__ pend,
+                                                      const int32_t* __restrict__ valid, const u64* __restrict__ best,
+                                                      int32_t* __restrict__ par, double* __restrict__ gA,
+                                                      int32_t* __restrict__ merged, long long* __restrict__ nm) {
+  const long long j = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (j >= E || j >= ctr[ACT_NP] || !valid[j]) return;
+  const int2 ab = gp[j];
+  const int w = pend[j] - pstart[j];
+  if (best[ab.x] != atl_pick_key(w, ab.y) || best[ab.y] != atl_pick_key(w, ab.x)) return;
+  const long long a = ab.x, b = ab.y;
+  par[b] = ab.x;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) gA[3 * a + k] = gA[3 * a + k] + gA[3 * b + k];
+  merged[a] = 1;
+  atomicAdd((unsigned long long*)nm, 1ull);
+}
+
+__global__ __launch_bounds__(ATL_BLOCK) void atl_relabel(const int32_t* __restrict__ par, long long F,
+                                                        int32_t* __restrict__ grp) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f < F) grp[f] = par[grp[f]];
+}
+
+// Frame of a merged group (par[g] = g: it is one still), D = A_g: k the smallest |D_k| (ties to the earlier), t = e_k x
+// D, b = D x t, each over the square root of its own squared length, in fp64.  fr[6 g ..] = (t, b).
+__global__ __launch_bounds__(ATL_BLOCK) void atl_frames(const int32_t* __restrict__ par,
+                                                       const int32_t* __restrict__ merged,
+                                                       const double* __restrict__ gA, long long F,
+                                                       double* __restrict__ fr) {
+  const long long g = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (g >= F || par[g] != g || !merged[g]) return;
+  const double dx = gA[3 * g], dy = gA[3 * g + 1], dz = gA[3 * g + 2];
+  const double ax = fabs(dx), ay = fabs(dy), az = fabs(dz);
+  const int k = (ax <= ay && ax <= az) ? 0 : (ay <= az ? 1 : 2);
+  const double tx = k == 0 ? 0.0 : (k == 1 ? dz : -dy);
+  const double ty = k == 0 ? -dz : (k == 1 ? 0.0 : dx);
+  const double tz = k == 0 ? dy : (k == 1 ? -dx : 0.0);
+  const double bx = dy * tz - dz * ty, by = dz * tx - dx * tz, bz = dx * ty - dy * tx;
+  const double tl = sqrt((tx * tx + ty * ty) + tz * tz), bl = sqrt((bx * bx + by * by) + bz * bz);
+  fr[6 * g] = tx / tl;
+  fr[6 * g + 1] = ty / tl;
+  fr[6 * g + 2] = tz / tl;
+  fr[6 * g + 3] = bx / bl;
+  fr[6 * g + 4] = by / bl;
+  fr[6 * g + 5] = bz / bl;
+}
+
+// pc[f, c] = corner c's plane coordinates: the label's pick for a face of an unmerged group, (P . t, P . b) in fp64
+// rounded once to fp32 for one of a merged group.
+__global__ __launch_bounds__(ATL_BLOCK) void atl_plane_coords(const float* __restrict__ P,
+                                                             const int32_t* __restrict__ faces, long long F,
+                                                             const int32_t* __restrict__ label,
+                                                             const int32_t* __restrict__ grp,
+                                                             const int32_t* __restrict__ merged,
+                                                             const double* __restrict__ fr, float* __restrict__ pc) {
+  const long long f = (long long)blockIdx.x * ATL_BLOCK + threadIdx.x;
+  if (f >= F) return;
+  const long long g = grp[f];
+  if (!merged[g]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float2 q = atl_corner<false>(P, faces, label, nullptr, f, c);
+      pc[6 * f + 2 * c] = q.x;
+      pc[6 * f + 2 * c + 1] = q.y;
+    }
+    return;
+  }
+  const double tx = fr[6 * g], ty = fr[6 * g + 1], tz = fr[6 * g + 2];
+  const double bx = fr[6 * g + 3], by = fr[6 * g + 4], bz = fr[6 * g + 5];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const long long v = faces[3 * f + c];
+    const double x = P[3 * v], y = P[3 * v + 1], z = P[3 * v + 2];
+    pc[6 * f + 2 * c] = (float)((x * tx + y * ty) + z * tz);
+    pc[6 * f + 2 * c + 1] = (float)((x * bx + y * by) + z * bz);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host
 
 struct AtlLayout {
   size_t fn, nv, vstart, vend, label, code, par, cidx, flags, rank, A, B, va, vb, pairs, box, off, flag, pre, wid,
       sh_start, sh_y, toff, ntile, count, ctr, tmp, tmp_bytes, total;
+  // vsa_atlas_merged
+  size_t grp, sg, gf, fiota, gstart, gend, glist, merged, gA, fr, best, pc, gp, pstart, pend, valid, cnt, ioff;
 };
 
 static int atl_check(long long V, long long F, int R) {
@@ -451,16 +747,17 @@ static int atl_check(long long V, long long F, int R) {
   return mt::check_vf(V, F);
 }
 
-// V = 0: the rasterize-only layout (toff, ntile, count unused, ctr, tmp).
-static int atl_layout(long long V, long long F, int R, AtlLayout* l) {
-  const size_t v = (size_t)V, f = (size_t)F, n3 = 3 * f, rr = (size_t)R * (size_t)R;
+// V = 0: the rasterize-only layout (toff, ntile, count unused, ctr, tmp).  merged: vsa_atlas_merged's buffers after
+// vsa_atlas's, e = the most eligible edges (3F / 2) + 1.
+static int atl_layout(long long V, long long F, int R, AtlLayout* l, bool merged = false) {
+  const size_t v = (size_t)V, f = (size_t)F, n3 = 3 * f, rr = (size_t)R * (size_t)R, e = n3 / 2 + 1;
   const bool full = V > 0;
   mt::TmpCounts cnt = {};
-  cnt.iscan64 = f;
+  cnt.iscan64 = merged ? e : f;
   if (full) {
     cnt.pairs64 = n3;
     cnt.pairs32 = n3;
-    cnt.keys64 = f;
+    cnt.keys64 = merged ? e : f;
     cnt.xscan32 = n3;
   }
   MT_TRY(mt::tmp_bytes(cnt, &l->tmp_bytes));
@@ -492,6 +789,26 @@ static int atl_layout(long long V, long long F, int R, AtlLayout* l) {
   l->sh_y = b.take(full ? 4 * f : 0);
   l->count = b.take(full ? 4 * rr : 0);
   l->tmp = b.take(l->tmp_bytes);
+  if (merged) {
+    l->grp = b.take(4 * f);
+    l->sg = b.take(4 * f);
+    l->gf = b.take(4 * f);
+    l->fiota = b.take(4 * f);
+    l->gstart = b.take(4 * f);
+    l->gend = b.take(4 * f);
+    l->glist = b.take(4 * f);
+    l->merged = b.take(4 * f);
+    l->gA = b.take(24 * f);
+    l->fr = b.take(48 * f);
+    l->best = b.take(8 * f);
+    l->pc = b.take(24 * f);
+    l->gp = b.take(8 * e);
+    l->pstart = b.take(4 * e);
+    l->pend = b.take(4 * e);
+    l->valid = b.take(4 * e);
+    l->cnt = b.take(8 * e);
+    l->ioff = b.take(8 * (e + 1));
+  }
   l->total = b.o;
   return VSA_OK;
 }
@@ -500,6 +817,13 @@ extern "C" long long vsa_atlas_workspace_bytes(long long nr_verts, long long nr_
   AtlLayout l;
   int rc = atl_check(nr_verts, nr_faces, resolution);
   if (rc == VSA_OK) rc = mt::abi_status(atl_layout(nr_verts, nr_faces, resolution, &l));
+  return rc != VSA_OK ? rc : (long long)l.total;
+}
+
+extern "C" long long vsa_atlas_merged_workspace_bytes(long long nr_verts, long long nr_faces, int resolution) {
+  AtlLayout l;
+  int rc = atl_check(nr_verts, nr_faces, resolution);
+  if (rc == VSA_OK) rc = mt::abi_status(atl_layout(nr_verts, nr_faces, resolution, &l, true));
   return rc != VSA_OK ? rc : (long long)l.total;
 }
 
@@ -524,6 +848,11 @@ struct Atl {
   const int32_t* faces;
   long long* ctr;
   mt::StageTimer timer;
+  // vsa_atlas_merged: charts are built inside groups and laid out from plane coordinates
+  bool merged;
+  double min_cos;
+  int merge_rounds;
+  long long mstats[4];   // box charts, groups, merge rounds run, valid pairs left
 };
 
 // Rasterization of F faces' UVs: tile counts, their scan and the item passes (mode 0 counts, then mode 1 flags when
@@ -579,7 +908,8 @@ int label_stage(Atl& m) {
   MT_TRY(mt::sorted_edges(m.faces, F, m.s_bits, ek, es, vin, slot, m.tmp, m.st));
   int32_t* flags = at<int32_t>(ws, l.flags);
   int32_t* rank = at<int32_t>(ws, l.rank);
-  hipLaunchKernelGGL(atl_join_flags, mt::grid(n3), dim3(ATL_BLOCK), 0, m.st, es, slot, m.faces, label, n3, flags);
+  hipLaunchKernelGGL(atl_join_flags, mt::grid(n3), dim3(ATL_BLOCK), 0, m.st, es, slot, m.faces,
+                     m.merged ? nullptr : label, n3, flags);
   MT_LAUNCHED();
   MT_TRY(mt::exclusive_scan(m.tmp, flags, rank, (size_t)n3, m.st));
   hipLaunchKernelGGL(atl_join_compact, mt::grid(n3), dim3(ATL_BLOCK), 0, m.st, slot, flags, rank, n3,
@@ -598,7 +928,7 @@ int chart_stage(Atl& m) {
   MT_TRY(mt::iota(par, F, m.st));
   // J <= 3F / 2: the grid covers every pair, the kernel reads J on the device
   hipLaunchKernelGGL(atl_hook, mt::grid(3 * F / 2 + 1), dim3(ATL_BLOCK), 0, m.st, at<int2>(ws, l.pairs), m.ctr,
-                     at<uint32_t>(ws, l.code), par);
+                     at<uint32_t>(ws, l.code), m.merged ? at<int32_t>(ws, l.grp) : nullptr, par);
   MT_LAUNCHED();
   int32_t* cidx = at<int32_t>(ws, l.cidx);
   MT_TRY(mt::roots(par, F, cidx, flags, m.st));
@@ -610,8 +940,12 @@ int chart_stage(Atl& m) {
   unsigned* box = at<unsigned>(ws, l.box);
   hipLaunchKernelGGL(atl_box_init, mt::grid(4 * m.C), dim3(ATL_BLOCK), 0, m.st, box, 4 * m.C);
   MT_LAUNCHED();
-  hipLaunchKernelGGL(atl_boxes, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
-                     box);
+  if (m.merged)
+    hipLaunchKernelGGL(atl_boxes<true>, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F,
+                       at<int32_t>(ws, l.label), at<float>(ws, l.pc), cidx, box);
+  else
+    hipLaunchKernelGGL(atl_boxes<false>, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F,
+                       at<int32_t>(ws, l.label), nullptr, cidx, box);
   MT_LAUNCHED();
   return VSA_OK;
 }
@@ -678,6 +1012,121 @@ int pack_stage(Atl& m, uint32_t* s_out, long long* minres) {
   return VSA_OK;
 }
 
+// The faces sorted by group (ascending face within a group) and every group's run in them.
+int group_faces(Atl& m) {
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  uint32_t* sg = at<uint32_t>(ws, l.sg);
+  MT_TRY(mt::sort_pairs(m.tmp, at<uint32_t>(ws, l.grp), sg, at<uint32_t>(ws, l.fiota), at<uint32_t>(ws, l.gf),
+                        (size_t)m.F, 0, mt::bits_of(m.F), m.st));
+  hipLaunchKernelGGL(atl_group_runs, mt::grid(m.F), dim3(ATL_BLOCK), 0, m.st, sg, m.F, at<int32_t>(ws, l.gstart),
+                     at<int32_t>(ws, l.gend));
+  MT_LAUNCHED();
+  return VSA_OK;
+}
+
+// The box charts as groups, then merge rounds (header rules 1 - 5) and the plane coordinates of every corner.  The
+// host reads the edge and box-chart counts once, the valid-pair count once per round, and the merge count at the end.
+int merge_stage(Atl& m) {
+  const long long F = m.F;
+  char* ws = m.ws;
+  const AtlLayout& l = m.l;
+  int32_t* par = at<int32_t>(ws, l.par);
+  int32_t* grp = at<int32_t>(ws, l.grp);
+  int32_t* flags = at<int32_t>(ws, l.flags);
+  int32_t* rank = at<int32_t>(ws, l.rank);
+  int32_t* label = at<int32_t>(ws, l.label);
+  int32_t* merged = at<int32_t>(ws, l.merged);
+  int32_t* gstart = at<int32_t>(ws, l.gstart);
+  int32_t* gend = at<int32_t>(ws, l.gend);
+  uint32_t* gf = at<uint32_t>(ws, l.gf);
+  float* fn = at<float>(ws, l.fn);
+  double* gA = at<double>(ws, l.gA);
+  int2* pairs = at<int2>(ws, l.pairs);
+  // groups = the box charts: the eligible edges between faces of one label
+  MT_TRY(mt::iota(par, F, m.st));
+  hipLaunchKernelGGL(atl_hook, mt::grid(3 * F / 2 + 1), dim3(ATL_BLOCK), 0, m.st, pairs, m.ctr, at<uint32_t>(ws, l.code),
+                     label, par);
+  MT_LAUNCHED();
+  MT_TRY(mt::roots(par, F, grp, flags, m.st));
+  MT_TRY(mt::exclusive_scan(m.tmp, flags, rank, (size_t)F, m.st));
+  hipLaunchKernelGGL(atl_group_list, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, flags, rank, F, at<int32_t>(ws, l.glist),
+                     m.ctr);
+  MT_LAUNCHED();
+  MT_TRY(mt::iota(at<int32_t>(ws, l.fiota), F, m.st));
+  VSA_HIP_TRY(hipMemsetAsync(merged, 0, 4 * (size_t)F, m.st));
+  MT_TRY(group_faces(m));
+  long long ctr[ACT_N];
+  MT_TRY(mt::read_counters(m.st, m.ctr, ctr, ACT_N));
+  const long long E = ctr[ACT_J], box = ctr[ACT_BOX];
+  if (E < 0 || E > 3 * F / 2 || box < 1 || box > F) return VSA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(atl_group_area, dim3((unsigned)box), dim3(VSA_WAVE), 0, m.st, fn, gf, gstart, gend,
+                     at<int32_t>(ws, l.glist), gA);
+  MT_LAUNCHED();
+  const int s = mt::bits_of(F);
+  const double tt = m.min_cos * m.min_cos;
+  u64* keys = at<u64>(ws, l.A);
+  u64* sk = at<u64>(ws, l.B);
+  int2* gp = at<int2>(ws, l.gp);
+  int32_t* pstart = at<int32_t>(ws, l.pstart);
+  int32_t* pend = at<int32_t>(ws, l.pend);
+  int32_t* valid = at<int32_t>(ws, l.valid);
+  long long* cnt = at<long long>(ws, l.cnt);
+  long long* ioff = at<long long>(ws, l.ioff);
+  u64* best = at<u64>(ws, l.best);
+  long long rounds = 0, nv = 0;
+  // item lanes: enough to fill the device, each walking its share of the (face, pair) items
+  const long long vb = (8 * F + ATL_BLOCK - 1) / ATL_BLOCK;
+  const dim3 vgrid((unsigned)(vb < 64 ? 64 : (vb > 65536 ? 65536 : vb)));
+  while (E > 0) {
+    hipLaunchKernelGGL(atl_pair_keys, mt::grid(E), dim3(ATL_BLOCK), 0, m.st, pairs, E, grp, s, keys);
+    MT_LAUNCHED();
+    MT_TRY(mt::sort_keys(m.tmp, keys, sk, (size_t)E, 0, 2 * s, m.st));
+    hipLaunchKernelGGL(atl_pair_heads, mt::grid(E), dim3(ATL_BLOCK), 0, m.st, sk, E, s, flags);
+    MT_LAUNCHED();
+    MT_TRY(mt::exclusive_scan(m.tmp, flags, rank, (size_t)E, m.st));
+    hipLaunchKernelGGL(atl_pair_runs, mt::grid(E), dim3(ATL_BLOCK), 0, m.st, sk, flags, rank, E, s, gp, pstart, pend,
+                       m.ctr);
+    MT_LAUNCHED();
+    hipLaunchKernelGGL(atl_pair_items, mt::grid(E), dim3(ATL_BLOCK), 0, m.st, gp, E, m.ctr, gstart, gend, cnt, valid,
+                       best);
+    MT_LAUNCHED();
+    VSA_HIP_TRY(hipMemsetAsync(ioff, 0, 8, m.st));
+    MT_TRY(mt::inclusive_scan(m.tmp, cnt, ioff + 1, (size_t)E, m.st));
+    hipLaunchKernelGGL(atl_validity, vgrid, dim3(ATL_BLOCK), 0, m.st, ioff, m.ctr, gp, gstart, gend, gf, fn, gA, tt,
+                       valid);
+    MT_LAUNCHED();
+    VSA_HIP_TRY(hipMemsetAsync(m.ctr + ACT_NV, 0, 8, m.st));
+    hipLaunchKernelGGL(atl_pick, mt::grid(E), dim3(ATL_BLOCK), 0, m.st, gp, E, m.ctr, pstart, pend, valid, best,
+                       m.ctr + ACT_NV);
+    MT_LAUNCHED();
+    MT_TRY(mt::read_counters(m.st, m.ctr + ACT_NV, &nv));
+    if (rounds == m.merge_rounds) break;
+    ++rounds;   // (the round that finds no valid pair counts)
+    if (nv == 0) break;
+    hipLaunchKernelGGL(atl_merge, mt::grid(E), dim3(ATL_BLOCK), 0, m.st, gp, E, m.ctr, pstart, pend, valid, best, par,
+                       gA, merged, m.ctr + ACT_MERGES);
+    MT_LAUNCHED();
+    hipLaunchKernelGGL(atl_relabel, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, par, F, grp);
+    MT_LAUNCHED();
+    MT_TRY(group_faces(m));
+  }
+  if (E == 0 && m.merge_rounds > 0) rounds = 1;   // no pair at all: the one round that finds none
+  long long merges = 0;
+  MT_TRY(mt::read_counters(m.st, m.ctr + ACT_MERGES, &merges));
+  if (merges < 0 || merges >= box) return VSA_ERR_UNSUPPORTED;
+  m.mstats[0] = box;
+  m.mstats[1] = box - merges;
+  m.mstats[2] = rounds;
+  m.mstats[3] = nv;
+  hipLaunchKernelGGL(atl_frames, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, par, merged, gA, F, at<double>(ws, l.fr));
+  MT_LAUNCHED();
+  hipLaunchKernelGGL(atl_plane_coords, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, label, grp, merged,
+                     at<double>(ws, l.fr), at<float>(ws, l.pc));
+  MT_LAUNCHED();
+  return VSA_OK;
+}
+
 int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
   char* ws = m.ws;
   const AtlLayout& l = m.l;
@@ -686,6 +1135,11 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
   MT_TRY(m.timer.open());
   MT_TRY(label_stage(m));
   MT_TRY(m.timer.close(0));
+  if (m.merged) {
+    MT_TRY(m.timer.open());
+    MT_TRY(merge_stage(m));
+    MT_TRY(m.timer.close(5));
+  }
   int32_t* count = at<int32_t>(ws, l.count);
   int32_t* flag = at<int32_t>(ws, l.flag);
   int32_t* cidx = at<int32_t>(ws, l.cidx);
@@ -703,14 +1157,21 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
       stats[1] = splits;
       stats[2] = 0;
       stats[3] = minres;
+      if (m.merged) memcpy(stats + 4, m.mstats, sizeof(m.mstats));
     }
     if (rc != VSA_OK) return rc;
     MT_TRY(m.timer.close(2));
     MT_TRY(m.timer.open());
     float s;
     memcpy(&s, &sb, 4);
-    hipLaunchKernelGGL(atl_emit, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
-                       at<unsigned>(ws, l.box), at<int2>(ws, l.off), s, m.R, m.p, uv);
+    if (m.merged)
+      hipLaunchKernelGGL(atl_emit<true>, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F,
+                         at<int32_t>(ws, l.label), at<float>(ws, l.pc), cidx, at<unsigned>(ws, l.box),
+                         at<int2>(ws, l.off), s, m.R, m.p, uv);
+    else
+      hipLaunchKernelGGL(atl_emit<false>, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F,
+                         at<int32_t>(ws, l.label), nullptr, cidx, at<unsigned>(ws, l.box), at<int2>(ws, l.off), s, m.R,
+                         m.p, uv);
     MT_LAUNCHED();
     MT_TRY(m.timer.close(3));
     MT_TRY(m.timer.open());
@@ -734,14 +1195,21 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
       stats[1] = splits;
       stats[2] = cov;
       stats[3] = 0;
+      if (m.merged) memcpy(stats + 4, m.mstats, sizeof(m.mstats));
       memcpy(scale, &sb, 4);
       return VSA_OK;
     }
     // a texel counted twice across two charts, or one-face charts flagged, would repeat the round unchanged
     if (splits + 1 >= ATL_MAX_ROUNDS) return VSA_ERR_UNSUPPORTED;
     VSA_HIP_TRY(hipMemsetAsync(m.ctr + ACT_PROG, 0, 8, m.st));
-    hipLaunchKernelGGL(atl_split, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F, at<int32_t>(ws, l.label), cidx,
-                       at<unsigned>(ws, l.box), flag, at<uint32_t>(ws, l.code), m.ctr);
+    if (m.merged)
+      hipLaunchKernelGGL(atl_split<true>, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F,
+                         at<int32_t>(ws, l.label), at<float>(ws, l.pc), cidx, at<unsigned>(ws, l.box), flag,
+                         at<uint32_t>(ws, l.code), m.ctr);
+    else
+      hipLaunchKernelGGL(atl_split<false>, mt::grid(F), dim3(ATL_BLOCK), 0, m.st, m.P, m.faces, F,
+                         at<int32_t>(ws, l.label), nullptr, cidx, at<unsigned>(ws, l.box), flag,
+                         at<uint32_t>(ws, l.code), m.ctr);
     MT_LAUNCHED();
     long long changed = 0;
     MT_TRY(mt::read_counters(m.st, m.ctr + ACT_PROG, &changed));
@@ -751,16 +1219,18 @@ int run(Atl& m, float* uv, int32_t* out_chart, long long* stats, float* scale) {
   }
 }
 
-}  // namespace
-
-extern "C" int vsa_atlas(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
-                         int resolution, int padding, void* workspace, long long workspace_bytes, float* out_faces_uvs,
-                         int32_t* out_chart, long long* stats, float* scale, float* stage_ms, void* stream) {
+// The body of both entries: merged = vsa_atlas_merged's groups and plane coordinates.
+int atlas(bool merged, double min_cos, int merge_rounds, const float* verts, long long nr_verts, const int32_t* faces,
+          long long nr_faces, int resolution, int padding, void* workspace, long long workspace_bytes,
+          float* out_faces_uvs, int32_t* out_chart, long long* stats, float* scale, float* stage_ms, void* stream) {
   if (!verts || !faces || !workspace || !out_faces_uvs || !out_chart || !stats || !scale) return VSA_ERR_ARG;
   MT_TRY(atl_check(nr_verts, nr_faces, resolution));
   if (padding < 0 || 2 * padding >= resolution) return VSA_ERR_ARG;
   Atl m;
-  MT_TRY(mt::abi_status(atl_layout(nr_verts, nr_faces, resolution, &m.l)));
+  MT_TRY(mt::abi_status(atl_layout(nr_verts, nr_faces, resolution, &m.l, merged)));
+  m.merged = merged;
+  m.min_cos = min_cos;
+  m.merge_rounds = merge_rounds;
   if (workspace_bytes < (long long)m.l.total) return VSA_ERR_ARG;
   m.st = (hipStream_t)stream;
   m.ws = static_cast<char*>(workspace);
@@ -774,10 +1244,28 @@ extern "C" int vsa_atlas(const float* verts, long long nr_verts, const int32_t* 
   m.faces = faces;
   m.s_bits = mt::bits_of(nr_verts);
   m.ctr = at<long long>(m.ws, m.l.ctr);
-  MT_TRY(m.timer.create(stage_ms, 5, m.st));
+  MT_TRY(m.timer.create(stage_ms, merged ? 6 : 5, m.st));
   const int rc = run(m, out_faces_uvs, out_chart, stats, scale);
   m.timer.destroy();
   return rc;
+}
+
+}  // namespace
+
+extern "C" int vsa_atlas(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                         int resolution, int padding, void* workspace, long long workspace_bytes, float* out_faces_uvs,
+                         int32_t* out_chart, long long* stats, float* scale, float* stage_ms, void* stream) {
+  return atlas(false, 0.0, 0, verts, nr_verts, faces, nr_faces, resolution, padding, workspace, workspace_bytes,
+               out_faces_uvs, out_chart, stats, scale, stage_ms, stream);
+}
+
+extern "C" int vsa_atlas_merged(const float* verts, long long nr_verts, const int32_t* faces, long long nr_faces,
+                                int resolution, int padding, double min_cos, int merge_rounds, void* workspace,
+                                long long workspace_bytes, float* out_faces_uvs, int32_t* out_chart, long long* stats,
+                                float* scale, float* stage_ms, void* stream) {
+  if (!(min_cos > 0.0 && min_cos <= 1.0) || merge_rounds < 0) return VSA_ERR_ARG;   // (a NaN fails the first test)
+  return atlas(true, min_cos, merge_rounds, verts, nr_verts, faces, nr_faces, resolution, padding, workspace,
+               workspace_bytes, out_faces_uvs, out_chart, stats, scale, stage_ms, stream);
 }
 
 extern "C" int vsa_atlas_rasterize(const float* faces_uvs, long long nr_faces, int resolution, void* workspace,

@@ -222,14 +222,16 @@ def transfer_scene(src, dst_meshes, textures_res=None, samples=1, reach=1.5, max
 
 @torch.no_grad()
 def make_lod(src, ratio, textures_res=None, padding=4, samples=1, anchor_shell=None, builder="device", reach=1.5,
-             max_distance=math.inf, refit=None):
+             max_distance=math.inf, refit=None, charts="box", min_cos=0.5):
     """(scene, report): a lighter copy of a baked scene.  `simplify_shells` of the source's meshes to `ratio` of their
     faces (guarded: a nested stack stays nested; a single shell goes through `simplify_mesh`), `compute_atlas` of every
     result at the finest destination resolution with `padding`, then `transfer_scene`.
     report: {"simplify": the ShellSimplifyReports (None for one shell), "atlas": [stats per shell], "transfer":
     {(shell, degree): ...}, "faces": [faces per shell]}.
     refit: None, or a dict of `texture_fit.refit_lod`'s arguments: the transferred textures are then fitted to renders
-    of the source (the returned scene is the fitted one) and the report gains "refit", the `FitReport`."""
+    of the source (the returned scene is the fitted one) and the report gains "refit", the `FitReport`.
+    charts, min_cos: `compute_atlas`'s chart mode ("merged": fewer, plane-projected charts; the atlas stats then carry
+    `groups`)."""
     from .atlas import compute_atlas
     from .simplify import simplify_mesh, simplify_shells
     from .texture_export import baked_bank_of
@@ -243,7 +245,7 @@ def make_lod(src, ratio, textures_res=None, padding=4, samples=1, anchor_shell=N
         simple, simplify_reports = [simplify_mesh(bare[0], ratio)], None
     atlased, atlas_stats = [], []
     for m in simple:
-        out, st = compute_atlas(m, max(res), padding, return_stats=True)
+        out, st = compute_atlas(m, max(res), padding, return_stats=True, charts=charts, min_cos=min_cos)
         atlased.append(out)
         atlas_stats.append(st)
     scene, reports = transfer_scene(src, atlased, res, samples, reach, max_distance, builder, return_reports=True)
@@ -257,16 +259,17 @@ def make_lod(src, ratio, textures_res=None, padding=4, samples=1, anchor_shell=N
 
 @torch.no_grad()
 def lod_chain(src, ratios, out_dir, textures_res=None, padding=4, samples=1, anchor_shell=None, builder="device",
-              cameras=None, compress_level=6, refit=None):
+              cameras=None, compress_level=6, refit=None, charts="box", min_cos=0.5):
     """Writes <out_dir>/lod_0/ as the source itself and <out_dir>/lod_i/ for ratios[i - 1] (`write_scene`'s layout,
     read by `load_scene` and `VolsurfsRenderer.from_scene`).  Every level is made from the SOURCE, not from the level
-    before it, so that resampling errors do not compound.  refit: as `make_lod`'s, for every level.  Returns the list of
-    `make_lod`'s reports (None for lod_0)."""
+    before it, so that resampling errors do not compound.  refit, charts, min_cos: as `make_lod`'s, for every level.
+    Returns the list of `make_lod`'s reports (None for lod_0)."""
     from .texture_export import write_scene
     write_scene(src, os.path.join(out_dir, "lod_0"), cameras=cameras, compress_level=compress_level)
     reports = [None]
     for i, ratio in enumerate(ratios, 1):
-        scene, report = make_lod(src, ratio, textures_res, padding, samples, anchor_shell, builder, refit=refit)
+        scene, report = make_lod(src, ratio, textures_res, padding, samples, anchor_shell, builder, refit=refit,
+                                 charts=charts, min_cos=min_cos)
         write_scene(scene, os.path.join(out_dir, f"lod_{i}"), cameras=cameras, compress_level=compress_level)
         reports.append(report)
     return reports
