@@ -131,6 +131,73 @@ __device__ __forceinline__ void cell_indices(const LevelGeom& g, unsigned cx, un
   }
 }
 
+// The same cell arithmetic split into a ROW part (everything that depends on y alone) and a COLUMN part, for
+// the encode backward (nt_encode.hip, vsa_nt_encode_row_terms): a lane walks consecutive slots, which are texels
+// of one texture row except where the run crosses a row's end, and the y of a row's texels is one float bit for
+// bit — the row part is then computed once per run.  Every operation is the one cell_ref / cell_indices perform,
+// on the same operands: same bits.  (The forward keeps cell_ref_s per slot: the split bought it nothing.)
+struct CellRow {
+  unsigned cy;
+  float fy, gy;        // fract(py), 1 - fract(py)
+  unsigned h0, h1;     // hashed: cy * PRIME_Y, (cy + 1) * PRIME_Y; dense: h0 = cy * res, h1 unused
+};
+
+template <bool HASHED>
+__device__ __forceinline__ CellRow cell_row(const LevelGeom& g, float y) {
+  const float py = y * g.scale + 0.5f;
+  CellRow r;
+  r.fy = enc_fract(py);
+  r.gy = 1.0f - r.fy;
+  r.cy = (unsigned)enc_floor_i(py);
+  if (HASHED) {
+    r.h0 = r.cy * PRIME_Y, r.h1 = (r.cy + 1u) * PRIME_Y;
+  } else {
+    r.h0 = r.cy * g.res, r.h1 = 0u;
+  }
+  return r;
+}
+
+// column part: cell_ref with the y half taken from the row
+__device__ __forceinline__ CellRef cell_col(const LevelGeom& g, float x, const CellRow& r) {
+  const float px = x * g.scale + 0.5f;
+  const float fx = enc_fract(px);
+  const f32x2 ax = {1.0f - fx, fx};
+  CellRef c;
+  c.cx = (unsigned)enc_floor_i(px);
+  c.cy = r.cy;
+  c.w01 = ax * r.gy;
+  c.w23 = ax * r.fy;
+  return c;
+}
+
+// cell_indices with the row's terms
+template <bool HASHED>
+__device__ __forceinline__ void cell_col_indices(const LevelGeom& g, unsigned cx, const CellRow& r,
+                                                 unsigned idx[4]) {
+  if (HASHED) {
+    idx[0] = (cx ^ r.h0) & g.mask;
+    idx[1] = ((cx + 1u) ^ r.h0) & g.mask;
+    idx[2] = (cx ^ r.h1) & g.mask;
+    idx[3] = ((cx + 1u) ^ r.h1) & g.mask;
+  } else {
+    const unsigned r0 = cx + r.h0;
+    idx[0] = r0;
+    idx[1] = r0 + 1u;
+    idx[2] = r0 + g.res;
+    idx[3] = r0 + g.res + 1u;
+    if (idx[3] >= g.size || idx[0] > idx[3]) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) idx[k] %= g.size;
+    }
+  }
+}
+
+// does any active lane of the wave hold a y whose bits differ from the one its row terms were made from?
+// (wave-uniform: the caller's recompute sits behind a scalar branch that only waves with a row break take)
+__device__ __forceinline__ bool enc_row_break(float y, float y_prev) {
+  return __builtin_amdgcn_ballot_w64(__builtin_bit_cast(unsigned, y) != __builtin_bit_cast(unsigned, y_prev)) != 0;
+}
+
 template <bool HASHED>
 __device__ __forceinline__ CellCorners cell_corners(const LevelGeom& g, float x, float y) {
   const CellRef r = cell_ref(g, x, y);

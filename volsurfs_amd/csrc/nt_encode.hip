@@ -30,6 +30,12 @@ namespace {
 // Measured (800x800, K = 5; profiles/NOTEBOOK.md "Encode kernels"): backward 2.79 -> 1.50 GB fetched, 0.538 -> 0.507 ms;
 // forward 1.11 -> 0.92 GB fetched but 0.299 -> 0.316 ms, so the forward keeps the plain walk.
 #define NT_ENC_SIBLING_GROUPS 2
+// defaults of vsa_nt_encode_row_terms: 1 = a lane's texel-row terms once per run of slots.  Measured (800x800, K = 5;
+// profiles/NOTEBOOK.md "Encode kernels", profiles/r08/): backward 0.490 -> 0.463 ms, the step +1.5 %.  The forward has
+// no such walk: with the row terms NEVER remade (a timing-only build) its launch was not shorter (0.302 -> 0.302-0.309 ms),
+// and the exact form neither (0.302), so its path left the source and its value here is stored and ignored.
+#define NT_ENC_ROW_TERMS_FWD 0
+#define NT_ENC_ROW_TERMS_BWD 1
 #define NT_ENC_PAIR_W 22       /* cost of a (colour, alpha) pair unit in 1/16 of a single texture's (forward, dense) */
 constexpr int ENC_BLOCK = 1024;     // 16 waves: a 128 KiB level pins one workgroup per CU
 constexpr int ENC_UNROLL = 8;       // slots in flight per lane (backward)
@@ -249,7 +255,9 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_fwd_both_kernel(
 // features in one pass over the slots (two planes; levels of <= 16384 entries), which
 // shares the loads, the cell arithmetic and the indices between the features.
 #define NT_ENC_FLUSH_BATCH 8     /* table entries per thread whose flush is in flight together */
-template <bool HASHED, int NF, bool MERGE>
+// ROW (vsa_nt_encode_row_terms): the texel-row terms of a lane's 8 slots are made once per run instead of once per
+// slot (nt_enc_common.h: cell_row / cell_col / cell_col_indices); the integer sums are the same either way.
+template <bool HASHED, int NF, bool MERGE, bool ROW>
 __device__ __forceinline__ void enc_bwd_piece(
     const vsa_nt_plan& plan, int* s_g, int level, int feat, int tex, int first, int last,
     bool store, const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
@@ -339,11 +347,25 @@ __device__ __forceinline__ void enc_bwd_piece(
     // dense levels take this path at any scale, and every contribution of such a texel was dropped.)
     constexpr unsigned NO_CELL = 0x80000000u;
     unsigned cur_cx = NO_CELL, cur_cy = 0u;
+    // ROW: the row terms are made from the first slot's y and again only where some lane of the wave crosses
+    // a row's end (a scalar branch in front of the per-slot guard; every lane then takes its own slot's y).
+    // The pending cell is then (cur_cx, the row): a lane whose row index changed forgets cur_cx's match
+    // (match_cx), which leaves the same-cell test with the cx comparison alone.
+    CellRow row = {};
+    float y_row = 0.f;
+    unsigned match_cx = NO_CELL;
 #pragma unroll
     for (int u = 0; u < ENC_UNROLL; ++u) {
       const int slot = s0 + u;
       const float x = (u & 1) ? xyv[u >> 1].z : xyv[u >> 1].x;
       const float y = (u & 1) ? xyv[u >> 1].w : xyv[u >> 1].y;
+      if constexpr (ROW) {
+        if (u == 0 || enc_row_break(y, y_row)) {
+          const CellRow r = cell_row<HASHED>(g, y);
+          if (MERGE && u > 0 && r.cy != row.cy) match_cx = NO_CELL;
+          row = r, y_row = y;
+        }
+      }
       float gv[NF];
       bool nz = false;
 #pragma unroll
@@ -355,7 +377,7 @@ __device__ __forceinline__ void enc_bwd_piece(
         nz |= gv[f] != 0.f;
       }
       if (slot >= first && slot < last && nz) {
-        const CellRef cr = cell_ref(g, x, y);
+        const CellRef cr = ROW ? cell_col(g, x, row) : cell_ref(g, x, y);
         int v[NF][4];
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -365,12 +387,13 @@ __device__ __forceinline__ void enc_bwd_piece(
         }
         if (!MERGE) {   // cells are finer than texels: every slot has its own cell
           unsigned idx[4];
-          cell_indices<HASHED>(g, cr.cx, cr.cy, idx);
+          if constexpr (ROW) cell_col_indices<HASHED>(g, cr.cx, row, idx);
+          else cell_indices<HASHED>(g, cr.cx, cr.cy, idx);
 #pragma unroll
           for (int f = 0; f < NF; ++f)
 #pragma unroll
             for (int k = 0; k < 4; ++k) atomicAdd(&my_g[f * plane + idx[k]], v[f][k]);
-        } else if (cr.cx == cur_cx && cr.cy == cur_cy) {
+        } else if (ROW ? cr.cx == match_cx : (cr.cx == cur_cx && cr.cy == cur_cy)) {
 #pragma unroll
           for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -383,7 +406,12 @@ __device__ __forceinline__ void enc_bwd_piece(
               for (int k = 0; k < 4; ++k) atomicAdd(&my_g[f * plane + cur_idx[k]], acc[f][k]);
           }
           cur_cx = cr.cx, cur_cy = cr.cy;
-          cell_indices<HASHED>(g, cr.cx, cr.cy, cur_idx);
+          if constexpr (ROW) {
+            match_cx = cr.cx;
+            cell_col_indices<HASHED>(g, cr.cx, row, cur_idx);
+          } else {
+            cell_indices<HASHED>(g, cr.cx, cr.cy, cur_idx);
+          }
 #pragma unroll
           for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -473,7 +501,7 @@ __device__ __host__ inline bool enc_both_features(const vsa_nt_plan& p, int leve
   return !hashed && (long long)p.level_size[level] * 2 <= LDS_ENTRIES;
 }
 
-template <bool HASHED, bool SIB = false>
+template <bool HASHED, bool SIB = false, bool ROW = false>
 __device__ __forceinline__ void nt_encode_bwd_body(
     const vsa_nt_plan& plan, int level0, int n_levels, int n_planes,
     const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
@@ -504,13 +532,13 @@ __device__ __forceinline__ void nt_encode_bwd_body(
     // in-register merging of same-cell slots cannot fire and its bookkeeping is skipped
     const bool merge = plan.level_scale[level] < (float)plan.tex_res[tex % VSA_NT_MAX_DEG];
     if (both)
-      enc_bwd_piece<HASHED, 2, true>(plan, s_g, level, 0, tex, first, last, store, dfeatures,
+      enc_bwd_piece<HASHED, 2, true, ROW>(plan, s_g, level, 0, tex, first, last, store, dfeatures,
                                      dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
     else if (merge)
-      enc_bwd_piece<HASHED, 1, true>(plan, s_g, level, r, tex, first, last, store, dfeatures,
+      enc_bwd_piece<HASHED, 1, true, ROW>(plan, s_g, level, r, tex, first, last, store, dfeatures,
                                      dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
     else
-      enc_bwd_piece<HASHED, 1, false>(plan, s_g, level, r, tex, first, last, store, dfeatures,
+      enc_bwd_piece<HASHED, 1, false, ROW>(plan, s_g, level, r, tex, first, last, store, dfeatures,
                                       dfeat_abs_sum, dscale_inv, slot_xy, grad_tables);
   };
   // SIB (hashed levels, the whole texture range; the host's choice): groups of four workgroups of one XCD walk a
@@ -526,30 +554,30 @@ __device__ __forceinline__ void nt_encode_bwd_body(
   if (full_range) { NT_BAL_END(HASHED ? NT_BAL_ENC_BWD_H : NT_BAL_ENC_BWD_D); }
 }
 
-template <bool HASHED>
+template <bool HASHED, bool ROW>
 __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_kernel(
     vsa_nt_plan plan, int level0, int n_levels, int n_planes,
     const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
     float dscale_inv, const float2* __restrict__ slot_xy, const int* __restrict__ seg_start,
     float* __restrict__ grad_tables, int tex_begin, int tex_end) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  nt_encode_bwd_body<HASHED>(plan, level0, n_levels, n_planes, dfeatures, dfeat_abs_sum, dscale_inv, slot_xy,
-                             seg_start, grad_tables, tex_begin, tex_end, s_raw);
+  nt_encode_bwd_body<HASHED, false, ROW>(plan, level0, n_levels, n_planes, dfeatures, dfeat_abs_sum, dscale_inv,
+                                         slot_xy, seg_start, grad_tables, tex_begin, tex_end, s_raw);
 }
 
 // dense planes, then hashed planes, in one launch (as nt_encode_fwd_both_kernel)
-template <bool SIB>
+template <bool SIB, bool ROW>
 __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_both_kernel(
     vsa_nt_plan plan, int lh, int n_planes_dense,
     const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
     float dscale_inv, const float2* __restrict__ slot_xy, const int* __restrict__ seg_start,
     float* __restrict__ grad_tables, int tex_begin, int tex_end) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  nt_encode_bwd_body<false>(plan, 0, lh, n_planes_dense, dfeatures, dfeat_abs_sum, dscale_inv, slot_xy,
-                            seg_start, grad_tables, tex_begin, tex_end, s_raw);
+  nt_encode_bwd_body<false, false, ROW>(plan, 0, lh, n_planes_dense, dfeatures, dfeat_abs_sum, dscale_inv, slot_xy,
+                                        seg_start, grad_tables, tex_begin, tex_end, s_raw);
   __syncthreads();
-  nt_encode_bwd_body<true, SIB>(plan, lh, plan.n_levels - lh, 2 * (plan.n_levels - lh), dfeatures, dfeat_abs_sum,
-                                dscale_inv, slot_xy, seg_start, grad_tables, tex_begin, tex_end, s_raw);
+  nt_encode_bwd_body<true, SIB, ROW>(plan, lh, plan.n_levels - lh, 2 * (plan.n_levels - lh), dfeatures, dfeat_abs_sum,
+                                     dscale_inv, slot_xy, seg_start, grad_tables, tex_begin, tex_end, s_raw);
 }
 
 // The data-parallel form (vsa_nt_encode_bwd_phased): every workgroup first walks its share of the dense
@@ -568,6 +596,7 @@ struct EncPhases {
   unsigned* flag[VSA_MAX_SHELLS];      // one word per phase (each its own signal allocation: vsa_dp_flags)
 };
 
+template <bool ROW>
 __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_phased_kernel(
     vsa_nt_plan plan, int lh, int n_planes_dense,
     const half2_t* __restrict__ dfeatures, const float* __restrict__ dfeat_abs_sum,
@@ -578,16 +607,17 @@ __global__ __launch_bounds__(ENC_BLOCK) void nt_encode_bwd_phased_kernel(
   // the dense (coarse) planes of ALL shells first, un-phased: they are a quarter of the work in many small
   // pieces, and a phase is final once its hashed planes are — the dense ones are long done by then
   if (lh > 0)
-    nt_encode_bwd_body<false>(plan, 0, lh, n_planes_dense, dfeatures, dfeat_abs_sum, dscale_inv, slot_xy,
-                              seg_start, grad_tables, 0, 1 << 30, s_raw);
+    nt_encode_bwd_body<false, false, ROW>(plan, 0, lh, n_planes_dense, dfeatures, dfeat_abs_sum, dscale_inv, slot_xy,
+                                          seg_start, grad_tables, 0, 1 << 30, s_raw);
   __syncthreads();
   int shell0 = 0;
   for (int p = 0; p < ph.n; ++p) {
     const int tex_begin = shell0 * 2 * VSA_NT_MAX_DEG, tex_end = ph.shell_end[p] * 2 * VSA_NT_MAX_DEG;
     shell0 = ph.shell_end[p];
     if (lh < plan.n_levels)
-      nt_encode_bwd_body<true>(plan, lh, plan.n_levels - lh, 2 * (plan.n_levels - lh), dfeatures, dfeat_abs_sum,
-                               dscale_inv, slot_xy, seg_start, grad_tables, tex_begin, tex_end, s_raw);
+      nt_encode_bwd_body<true, false, ROW>(plan, lh, plan.n_levels - lh, 2 * (plan.n_levels - lh), dfeatures,
+                                           dfeat_abs_sum, dscale_inv, slot_xy, seg_start, grad_tables, tex_begin,
+                                           tex_end, s_raw);
     // every wave's flush atomics have been acknowledged (vmcnt 0) before the workgroup counts itself in; ONE
     // wave then issues the agent-scope release (as a fence in all 16 waves it cost 0.16 ms per phase:
     // 4 096 L2 write-back requests per phase chip-wide, profiles/r05/dp_schedule_one_gpu.txt)
@@ -664,6 +694,19 @@ static EncConfig& enc_config() {
 extern "C" int vsa_nt_encode_config(int sibling_groups, int grid_override) {
   if (sibling_groups < 0 || sibling_groups > 3 || grid_override < 0 || grid_override > 4096) return VSA_ERR_ARG;
   enc_config() = EncConfig{sibling_groups, grid_override};
+  return VSA_OK;
+}
+// process-wide switch of the row-terms walk, per direction (vsa_nt_encode_row_terms; only the backward has one)
+struct EncRowTerms {
+  int forward, backward;
+};
+static EncRowTerms& enc_row_terms() {
+  static EncRowTerms cfg{NT_ENC_ROW_TERMS_FWD, NT_ENC_ROW_TERMS_BWD};
+  return cfg;
+}
+extern "C" int vsa_nt_encode_row_terms(int forward, int backward) {
+  if (forward < 0 || forward > 1 || backward < 0 || backward > 1) return VSA_ERR_ARG;
+  enc_row_terms() = EncRowTerms{forward, backward};
   return VSA_OK;
 }
 // workgroups of an encode launch, and whether its hashed levels walk in sibling groups of G
@@ -753,10 +796,14 @@ extern "C" int vsa_nt_encode_bwd_range(const vsa_nt_plan* plan, const void* dfea
   if (rc) return rc;
   static bool attr_set = false;
   if (!attr_set) {
-    if ((rc = set_lds_attr(nt_encode_bwd_kernel<false>))) return rc;
-    if ((rc = set_lds_attr(nt_encode_bwd_kernel<true>))) return rc;
-    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<false>))) return rc;
-    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<true>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_kernel<false, false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_kernel<true, false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<false, false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<true, false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_kernel<false, true>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_kernel<true, true>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<false, true>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_both_kernel<true, true>))) return rc;
     attr_set = true;
   }
   const int lh = first_hashed_level(plan);
@@ -764,30 +811,31 @@ extern "C" int vsa_nt_encode_bwd_range(const vsa_nt_plan* plan, const void* dfea
   const float2* xy = reinterpret_cast<const float2*>(slot_xy);
   int nr_cus = 0;
   if ((rc = enc_grid(&nr_cus))) return rc;
+  const bool row = enc_row_terms().backward != 0;
   if (lh > 0 && lh < plan->n_levels) {
     int n_planes = 0;
     for (int l = 0; l < lh; ++l) n_planes += enc_both_features(*plan, l, false) ? 1 : 2;
     // (a launch over some of the shells keeps the plain walk)
-    if (shell_begin == 0 && shell_end == plan->nr_shells && enc_siblings(plan, nr_cus, 4))
-      hipLaunchKernelGGL(nt_encode_bwd_both_kernel<true>, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
-                         (hipStream_t)stream, *plan, lh, n_planes, dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
-                         seg_start, grad_tables, tex_begin, tex_end);
-    else
-      hipLaunchKernelGGL(nt_encode_bwd_both_kernel<false>, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
-                         (hipStream_t)stream, *plan, lh, n_planes, dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
-                         seg_start, grad_tables, tex_begin, tex_end);
+    const bool sib = shell_begin == 0 && shell_end == plan->nr_shells && enc_siblings(plan, nr_cus, 4);
+    auto kernel = sib ? (row ? nt_encode_bwd_both_kernel<true, true> : nt_encode_bwd_both_kernel<true, false>)
+                      : (row ? nt_encode_bwd_both_kernel<false, true> : nt_encode_bwd_both_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
+                       (hipStream_t)stream, *plan, lh, n_planes, dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
+                       seg_start, grad_tables, tex_begin, tex_end);
     VSA_RETURN_LAUNCH_STATUS();
   }
+  auto dense = row ? nt_encode_bwd_kernel<false, true> : nt_encode_bwd_kernel<false, false>;
+  auto hashed = row ? nt_encode_bwd_kernel<true, true> : nt_encode_bwd_kernel<true, false>;
   if (lh > 0) {
     int n_planes = 0;
     for (int l = 0; l < lh; ++l) n_planes += enc_both_features(*plan, l, false) ? 1 : 2;
-    hipLaunchKernelGGL(nt_encode_bwd_kernel<false>, dim3(nr_cus), dim3(ENC_BLOCK),
+    hipLaunchKernelGGL(dense, dim3(nr_cus), dim3(ENC_BLOCK),
                        (size_t)LDS_ENTRIES * 4, (hipStream_t)stream, *plan, 0, lh, n_planes, dF,
                        dfeat_abs_sum, 1.0f / grad_scale, xy, seg_start, grad_tables, tex_begin,
                        tex_end);
   }
   if (lh < plan->n_levels)
-    hipLaunchKernelGGL(nt_encode_bwd_kernel<true>, dim3(nr_cus), dim3(ENC_BLOCK),
+    hipLaunchKernelGGL(hashed, dim3(nr_cus), dim3(ENC_BLOCK),
                        (size_t)LDS_ENTRIES * 4, (hipStream_t)stream, *plan, lh, plan->n_levels - lh,
                        2 * (plan->n_levels - lh), dF, dfeat_abs_sum, 1.0f / grad_scale, xy,
                        seg_start, grad_tables, tex_begin, tex_end);
@@ -866,7 +914,8 @@ extern "C" int vsa_nt_encode_bwd_phased(const vsa_nt_plan* plan, const void* dfe
   if (rc) return rc;
   static bool attr_set = false;
   if (!attr_set) {
-    if ((rc = set_lds_attr(nt_encode_bwd_phased_kernel))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_phased_kernel<false>))) return rc;
+    if ((rc = set_lds_attr(nt_encode_bwd_phased_kernel<true>))) return rc;
     attr_set = true;
   }
   const int lh = first_hashed_level(plan);
@@ -876,7 +925,8 @@ extern "C" int vsa_nt_encode_bwd_phased(const vsa_nt_plan* plan, const void* dfe
   if ((rc = vsa_cu_count(&nr_cus))) return rc;
   if (reserve_cus < 0 || reserve_cus >= nr_cus) return VSA_ERR_ARG;
   nr_cus -= reserve_cus;       // workgroups = compute units left to this launch (the rest: the collectives' kernels)
-  hipLaunchKernelGGL(nt_encode_bwd_phased_kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
+  auto kernel = enc_row_terms().backward != 0 ? nt_encode_bwd_phased_kernel<true> : nt_encode_bwd_phased_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(nr_cus), dim3(ENC_BLOCK), (size_t)LDS_ENTRIES * 4,
                      (hipStream_t)stream, *plan, lh, n_planes, reinterpret_cast<const half2_t*>(dfeatures),
                      dfeat_abs_sum, 1.0f / grad_scale, reinterpret_cast<const float2*>(slot_xy), seg_start,
                      grad_tables, ph, counters, epoch);

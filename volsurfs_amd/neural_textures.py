@@ -365,6 +365,13 @@ class NeuralTextureBank(torch.nn.Module):
         and a forced number of workgroups (0: one per compute unit)."""
         _lib.call("vsa_nt_encode_config", int(sibling_groups), int(grid_override))
 
+    @staticmethod
+    def encode_row_terms(forward, backward):
+        """Process-wide switch of the encode kernels' row terms (vsa_nt_encode_row_terms), 0 / 1 per direction: what
+        the cell arithmetic derives from a texel row's y once per lane run instead of once per slot.  Same bits.
+        Only the backward has such a walk (default on); `forward` is accepted and ignored."""
+        _lib.call("vsa_nt_encode_row_terms", int(forward), int(backward))
+
     def encode(self):
         self.wait_params()
         _lib.call("vsa_nt_encode_fwd", ctypes.byref(self.plan), self.tables_h, self.slot_xy,
